@@ -330,6 +330,31 @@ def write_detail(out):
         return 'not written (%s)' % e.__class__.__name__
 
 
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs writes at most this much
+DUMP_SAMPLE = 1 << 22        # elements kept of a larger output: a fixed, seeded sample, stored as <name>_sample.npy
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of ``arrays`` (name -> tensor / host array) as <path>/<name>.npy, float32 (float64 for
+    integers and float64 data).  An output of more than DUMP_SAMPLE elements is flattened and only the elements at
+    DUMP_SAMPLE sorted indices drawn with a fixed seed are kept, so two runs with the same arguments compare element by element."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        if isinstance(a, torch.Tensor):
+            a = a.detach()
+            if a.numel() > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(0).choice(a.numel(), DUMP_SAMPLE, replace=False))
+                a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+                name += '_sample'
+            a = a.cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.kind in 'biu' or a.dtype == np.float64 else np.float32)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, 'the dumped outputs exceed %d bytes' % DUMP_LIMIT_BYTES
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 def _r(x, n=4):
     return None if x is None else (float('%.*g' % (n, x)) if isinstance(x, float) else x)
 
@@ -395,7 +420,12 @@ def parse_args(argv=None):
     ap.add_argument('--frame-ids', default=None, help='comma-separated synthetic frame ids of THIS process (default: rank + world * j)')
     ap.add_argument('--timed-only', action='store_true',
                     help='only warm-up + the timed steps (no alt / isolated / CPU passes): what profiles/ is made from')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (gradients, parameters after the optimizer step, voxel counts and '
+                         'the mode\'s own outputs) to DIR/<name>.npy')
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.timed_only:
         args.no_alt = args.no_cpu_baseline = True
     return args
@@ -467,7 +497,7 @@ def _run(args, rank, world, dev):
     imsize = [float(v) for v in cfg.imsize]            # host list: no device read-back inside the step
     frames_total = args.frames * world
     pending_status = []
-    state = {'ready': None}
+    state = {'ready': None, 'keep': None}        # keep: list that the step appends its outputs to (--dump-outputs, last step)
 
     def fence():
         torch.cuda.synchronize()
@@ -480,7 +510,7 @@ def _run(args, rank, world, dev):
         b = batch if b is None else b
         bucket.zero()
         fn = pl.train_step_frame_set if pl.BATCHED else pl.train_step_frames
-        nv, statuses, state['ready'] = fn(model, b, grad_mid, imsize, ready=state['ready'], prepare_next=b)
+        nv, statuses, state['ready'] = fn(model, b, grad_mid, imsize, ready=state['ready'], prepare_next=b, keep_mid=state['keep'])
         bucket.all_reduce_mean(frames_total)
         opt.step()
         pending_status.extend(statuses)
@@ -575,6 +605,8 @@ def _run(args, rank, world, dev):
                 reg = reg.squeeze(0).permute(1, 2, 0)
                 cls_loss, reg_loss = drop['crit'](pi, ni, gi, drop['gt_dev'], score, reg, drop['anchors'], 2)
                 loss = cls_loss if reg_loss is None else cls_loss + reg_loss
+                if state['keep'] is not None:
+                    state['keep'].append((score.detach(), reg.detach(), cls_loss.detach(), reg_loss))
                 loss.backward()
                 opt.step()
         finally:
@@ -608,8 +640,11 @@ def _run(args, rank, world, dev):
             ready, targets = None, full_targets()
         else:
             ready, targets = state['ready']
+        kd = None if state['keep'] is None else {}
         out = pl.train_step_full(model, batch, targets, d['crit'], d['anchors'], imsize, ready=ready,
-                                 prepare_next=(batch, full_targets), read=False)
+                                 prepare_next=(batch, full_targets), read=False, keep=kd)
+        if kd is not None:
+            state['keep'].append(kd)
         state['ready'] = out.pop('next')
         bucket.all_reduce_mean(frames_total)
         opt.step()
@@ -646,7 +681,8 @@ def _run(args, rank, world, dev):
                    'vfe': ('hbm:voxelize',)}
     ROOF_TIMERS['full'] = ROOF_TIMERS['dropin'] = ROOF_TIMERS['hot']
 
-    def timed_run(warmup, steps, fn=None, names=None):
+    def timed_run(warmup, steps, fn=None, names=None, keep=None):
+        """``keep``: a list handed to the LAST timed step, which appends its outputs to it (--dump-outputs)."""
         fn = step if fn is None else fn
         nv = None
         _hip.TIMER_NAMES = frozenset(names) if names is not None else None
@@ -666,9 +702,12 @@ def _run(args, rank, world, dev):
             prof = cProfile.Profile()
             prof.enable()
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for i in range(steps):
+            if keep is not None and i == steps - 1:
+                state['keep'] = keep
             nv = fn()
         host_dt = time.perf_counter() - t0
+        state['keep'] = None
         if prof is not None:
             import io
             import pstats
@@ -740,14 +779,39 @@ def _run(args, rank, world, dev):
                                  'frac_of_8TBps': tb / (tms * 1e-3) / 8e12 if tms > 0 and tb > 0 else None}
         return out
 
+    def last_step_outputs(kept, nvox):
+        """What the last timed step computed, as a caller of the step receives it: the exchanged gradient bucket, the parameters
+        after the optimizer step, the voxels of every frame, and the mode's own outputs -- the middle maps (hot), the RPN heads and
+        per-frame (cls, reg) losses (full), every frame's score and box regression maps and losses (dropin)."""
+        torch.cuda.synchronize()
+        o = {'voxels_per_frame': np.asarray(nvox, np.float64), 'grad_bucket': bucket.flat,
+             'params': torch.cat([p.detach().reshape(-1) for p in hot])}
+        if args.mode == 'hot' and kept:
+            o['middle'] = torch.cat(kept)
+        elif args.mode == 'full':
+            if kept and 'heads' in kept[0]:
+                o['heads'] = kept[0]['heads']
+            if 'losses_dev' in full['pending']:
+                o['losses'] = full['pending']['losses_dev']
+        elif args.mode == 'dropin':
+            o['score'] = torch.stack([k[0] for k in kept])
+            o['reg'] = torch.stack([k[1] for k in kept])
+            o['losses'] = torch.stack([torch.stack([c.reshape(()), c.reshape(()) * 0 if r is None else r.detach().reshape(())])
+                                       for _, _, c, r in kept])
+        return o
+
     # ------------------------------------------------------------------------------------------------ the timed run
     vfe_check = None
     if args.mode == 'vfe' and rank == 0 and not args.timed_only:
         # BASELINE config 2: the voxel indices of every frame of the run are checked bit-exact against the C oracle (part
         # of the CPU-baseline leg: the only place the benchmark touches oracle/)
         vfe_check = voxel_index_check(batch, args.workload, frame_ids, args.points)
-    nvox, dt, timers = timed_run(args.warmup, args.steps, names=ROOF_TIMERS[args.mode])
+    kept = [] if args.dump_outputs else None
+    nvox, dt, timers = timed_run(args.warmup, args.steps, names=ROOF_TIMERS[args.mode], keep=kept)
     check_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(kept, nvox))
+    kept = None
     n_detail = min(args.steps, 10)
     _, dt_detail, timers_all = timed_run(2, n_detail)     # every timer on: other_kernels, hbm_stages
     check_status()
@@ -817,6 +881,7 @@ def _run(args, rank, world, dev):
             # short steps: enough of them to be out of the warm-up's shadow (allocator, clocks) at a few tenths of a second each
             a2.steps, a2.warmup = ((60, 15) if mode in ('vfe', 'fusion') else (ALT_STEPS, 4)) if args.steps >= 5 else (args.steps, 1)
             a2.no_alt = a2.no_cpu_baseline = True
+            a2.dump_outputs = None
             a2.timed_only = False
             state['ready'] = None
             o2 = run(a2, rank, world, dev)

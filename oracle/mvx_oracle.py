@@ -624,3 +624,33 @@ if _PKG not in _sys.path:
     _sys.path.insert(0, _PKG)
 from modules.data.Synthetic import (KITTI_CALIB, synth_fpn, synth_perm, synth_raw, synth_ring,  # noqa: E402,F401
                                     synth_uniform)
+
+
+# Inputs of the fixtures made from the reference's compiled extension (oracle/gen_ref_binary_golden.py ->
+# tests/golden/ref_*.npz, checked in tests/test_ref_extension.py)
+def ref_binary_frame(kind: str, fid: int, n: int = 20000):
+    """(points (n,4) f32 in shuffled order, their voxel indices (n,3) i32): the `_group` arguments of a synthetic frame."""
+    pc4 = synth_uniform(fid, n) if kind == 'uniform' else synth_ring(fid, n)
+    perm = synth_perm(fid, pc4.shape[0])
+    s = np.ascontiguousarray(pc4[perm][:, :4], np.float32)
+    idx = voxel_index(s[:, :3], VELORANGE, voxelsize())
+    return s, np.ascontiguousarray(idx, np.int32)
+
+
+def ref_binary_boxes(seed: int, n: int = 8) -> torch.Tensor:
+    """n random car boxes (xyzlwhr, f32) inside the range: the ground truth of the `_classifyAnchors` fixtures."""
+    g = np.random.default_rng(seed)
+    gt = np.stack([g.uniform(5, 65, n), g.uniform(-35, 35, n), g.uniform(-1.8, -0.6, n), g.uniform(3.4, 4.4, n),
+                   g.uniform(1.5, 1.8, n), g.uniform(1.4, 1.7, n), g.uniform(-1.6, 1.6, n)], 1).astype(np.float32)
+    return torch.from_numpy(gt)
+
+
+def array_digest(*arrays) -> str:
+    """SHA-256 over dtype, shape and bytes of each array: pins a regenerated input to the one a fixture was made from."""
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(('%s%s' % (a.dtype.str, a.shape)).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()

@@ -129,3 +129,22 @@ def test_bench_fusion_mode_runs_config_4():
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith('{')][0])
     assert d['config']['mode'] == 'fusion' and d['config']['frames_per_gpu'] == 2 and d['value'] > 0
     assert d['roofline']['bound'] == 'hbm' and d['roofline']['launches'] == 2 and 'feature_sample' in d['hbm_stages_frac_of_8TBps']
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the last timed step's middle maps (a fixed sample), exchanged gradients, parameters after AdamW and
+    voxel counts as float .npy files within 64 MiB; --steps is the number of timed steps and ms_per_step their mean time."""
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--timed-only', '--steps', '3', '--warmup', '1', '--frames',
+                          '2', '--points', '4000', '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith('{')][0])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and abs(d['value'] - 2 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    assert sorted(os.listdir(tmp_path)) == ['grad_bucket.npy', 'middle_sample.npy', 'params.npy', 'voxels_per_frame.npy']
+    import numpy as np
+    a = {n[:-4]: np.load(os.path.join(str(tmp_path), n)) for n in os.listdir(tmp_path)}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a['voxels_per_frame'].tolist() == [float(v) for v in d['config']['voxels_per_frame']]
+    assert a['middle_sample'].shape == (1 << 22,) and np.abs(a['middle_sample']).max() > 0
+    assert a['grad_bucket'].shape == a['params'].shape and np.abs(a['grad_bucket']).max() > 0

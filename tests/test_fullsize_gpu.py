@@ -3,8 +3,9 @@
 per layer for all frames of the step (modules/frames.py), restricted backward, side-stream weight gradients, exactly what
 bench.py times -- against the CPU oracle's forward + backward of the same frames.
 
-Asserted: voxel indices and payload bit-exact; the middle map within 1e-4 (max-norm relative) of the f32 oracle AND of a
-float64 run of the oracle (the yardstick; measured: HIP 6e-6, torch-CPU f32 4.6e-5 from it); element-wise, relative to
+Asserted: voxel indices and payload bit-exact; the middle map of every frame within 1e-4 (max-norm relative) of a float64
+run of the oracle (the yardstick; measured: HIP 6e-6 from it, torch-CPU f32 4.6e-5 .. 1.6e-2 depending on the host's thread
+count, which is why the f32 oracle is reported beside it but not asserted on); element-wise, relative to
 max(|value|, rms of the map), the HIP path stays below 1e-3 of the yardstick (the f32 oracle itself reaches 2.8e-3 on
 near-constant channels whose BatchNorm divides by a tiny deviation).  Parameter gradients: the upstream gradient of the
 benchmark is white noise, so every parameter gradient is the small residue of 1.4 M cancelling terms and fp32 -- torch-CPU's
@@ -161,18 +162,25 @@ def test_bench_path_matches_oracle_at_full_size():
                                  'mid_rms': rms, 'mid_abs_err_max': float(diff.max()),
                                  'mid_elementwise_rel_floor_rms': _percentiles(diff / np.maximum(mag, rms)),
                                  'mid_elementwise_rel_floor_1e-3rms': _percentiles(diff / np.maximum(mag, 1e-3 * rms))})
-        assert err < 1e-4, 'middle map differs from the oracle: %g' % err
-        if k != 0:
-            continue
-        # ---- float64 yardstick, frame 0: forward + backward (~30 s of host time).  The sampling positions
+        # ---- float64 yardstick: forward of every frame, backward of frame 0 (~30 s of host time).  The sampling positions
         # (trunc of proj / region - eps, imhead/Pipe.py:62-65) are part of the reference's f32 semantics -- in f64 a few
-        # points per frame fall into the neighbouring pixel -- so the yardstick samples in f32 and is exact from there on
-        P64 = {n: v.double().clone().requires_grad_(True) for n, v in P32.items()}
+        # points per frame fall into the neighbouring pixel -- so the yardstick samples in f32 and is exact from there on.
+        # The middle map is held to it rather than to the f32 oracle: torch-CPU's f32 BatchNorm statistics over the
+        # 1.4 M sites of a channel depend on the host's thread count (measured 1.6e-2 from the yardstick on 1 thread, 7e-4 on
+        # 8, 3.5e-4 on 16), so a bound against the f32 oracle measured the host, not the path
+        P64 = {n: v.double().clone().requires_grad_(k == 0) for n, v in P32.items()}
         vz = vox.clone()
         imf = O.feature_mapping(vz, fpn_cpu[k], torch.tensor(imsize))        # zeroes the padded rows of vz in place
-        imf64 = O.image_feature_fusion(imf.double(), P64, 'head.fusion.')
-        v23_64 = torch.cat([vz[..., :7].double(), imf64], dim=-1)
-        mid64 = O.voxelnet_middle(v23_64, idx, O.strip_prefix(P64, 'backbone.'))
+        with torch.set_grad_enabled(k == 0):
+            imf64 = O.image_feature_fusion(imf.double(), P64, 'head.fusion.')
+            v23_64 = torch.cat([vz[..., :7].double(), imf64], dim=-1)
+            mid64 = O.voxelnet_middle(v23_64, idx, O.strip_prefix(P64, 'backbone.'))
+        ref64 = mid64.detach().reshape(-1).numpy()
+        err64 = float(np.abs(got.reshape(-1).numpy() - ref64).max() / np.abs(ref64).max())
+        report['frames'][-1]['mid_rel_maxnorm_vs_float64'] = err64
+        assert err64 < 1e-4, 'middle map differs from the float64 oracle: %g' % err64
+        if k != 0:
+            continue
         # (a) the TIGHT gradient check -- float64 with the HIP forward's ReLU masks and max rows, 1e-4 per parameter in every
         # arithmetic, with the 1 % mutation check of the restricted backward's closed forms -- is
         # test_hot_path_gradients_tight_with_shared_kinks_at_full_size below.  (Rounds 3 and 4 held a plain float64 comparison
@@ -181,7 +189,6 @@ def test_bench_path_matches_oracle_at_full_size():
         # (b) the benchmark's white-noise upstream gradient: the reported worst case (every gradient the residue of 1.4 M
         # cancelling terms)
         mid64.backward(G.double())
-        ref64 = mid64.detach().reshape(-1).numpy()
         mag64 = np.maximum(np.abs(ref64), rms)
         e_hip = np.abs(got.reshape(-1).numpy().astype(np.float64) - ref64) / mag64
         e_ref = np.abs(ref.reshape(-1).numpy().astype(np.float64) - ref64) / mag64

@@ -2,9 +2,10 @@
 # usage: tools/isa.sh <file.hip>   -> /tmp/isa/<file>.s + resource table of its kernels (developer tool)
 set -e
 F="$1"; B=$(basename "$F" .hip)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p /tmp/isa
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -Wall -Wno-unused-function --cuda-device-only -S \
-    -o /tmp/isa/$B.s /root/repo/mvxnet-makise_amd/csrc/$B.hip -I/root/repo/mvxnet-makise_amd/csrc -I/root/repo/include 2>&1 | grep -v "hip-link" || true
+    -o /tmp/isa/$B.s "$ROOT/mvxnet-makise_amd/csrc/$B.hip" -I"$ROOT/mvxnet-makise_amd/csrc" -I"$ROOT/include" 2>&1 | grep -v "hip-link" || true
 python3 - "$B" <<'P'
 import re, sys
 s = open('/tmp/isa/%s.s' % sys.argv[1]).read()

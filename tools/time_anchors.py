@@ -1,6 +1,6 @@
 import os, sys, time
 sys.argv = sys.argv[:1]
-sys.path.insert(0, '/root/repo/mvxnet-makise_amd')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'mvxnet-makise_amd'))
 import numpy as np, torch
 import modules.config as cfg
 from modules import Calc, _hip
