@@ -883,6 +883,52 @@ int mvx_voxel_loss(const float *score, int64_t score_sl, int64_t score_sw, int64
                    int64_t dscore_sw, int64_t dscore_sa, float *dreg, int64_t dreg_sl, int64_t dreg_sw, int64_t dreg_sc,
                    float *losses, double *scratch, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Detection output (csrc/detect.hip): score selection, top-K, box decoding and rotated BEV NMS for the frames of a step.
+ * The reference has none of it (its Calc.decodeRegression is never called).
+ *
+ * mvx_detect_frames: per frame f < n_frames (1..MVX_MAX_FRAMES), on the raw head output read in place through element
+ *   strides (frame, x, y, channel):
+ *     cls  f32 logits of anchor a at cls[f*cls_sf + x*cls_sl + y*cls_sw + a*cls_sa];
+ *     reg  f32 regression k of anchor a at reg[f*reg_sf + x*reg_sl + y*reg_sw + (a*7 + k)*reg_sc] (voxelnet/Loss.py:42);
+ *   the frame-set heads (F*l*w, 16) = [cls (2) | reg (14)] of rpn_frames.rpn_forward are cls = heads, reg = heads + 2,
+ *   strides (l*w*16, w*16, 16, 1); NCHW maps (F,2,l,w) / (F,14,l,w) are (C*l*w, w, 1, l*w).
+ *   anchors f32 [l][w][anchors_per_loc][7] xyzlwhr (Preprocessing.createAnchors); anchor index n = (x*w + y)*A + a.
+ *   1. candidates: anchors with sigmoid(logit) >= score_thr (computed in the kernel), the first pre_max of them in the
+ *      order logit descending, then anchor index ascending (a total order: the result is deterministic);
+ *   2. decode (decode = MVX_DETECT_DECODE_LOSS): the exact inverse of VoxelLoss's targets (voxelnet/Loss.py:35-40),
+ *        d = sqrt(l_a^2 + w_a^2); x = r0*d + x_a, y = r1*d + y_a, z = r2*h_a + z_a, (l, w, h) = exp(r3..5) * (l_a, w_a, h_a),
+ *        yaw = r6 + yaw_a;
+ *      MVX_DETECT_DECODE_REFERENCE: Calc.decodeRegression as the reference wrote it, d = sqrt(x_a^2 + y_a^2) (anchor columns
+ *      0:2; a trained model does not match it).  BEV corners as Calc.bbox3d2bev.  A candidate with a non-finite decoded
+ *      component is dropped (status bit MVX_DETECT_NONFINITE);
+ *   3. greedy NMS in candidate order: j is suppressed by a kept i < j when IoU(i, j) > iou_thr (strict), IoU with
+ *      bboxOverlap's arithmetic (mvx_bbox_pairwise, boxes i against j); pairs whose bounding circles cannot touch count
+ *      as IoU 0 (the clipping there gives rounding noise of ~1e-6 only).  At most post_max boxes are kept.
+ *   Outputs (device): boxes f32 [n_frames][post_max][7] xyzlwhr, scores f32 [n_frames][post_max] = sigmoid(logit),
+ *   anchor_idx i32 [n_frames][post_max] (n), counts i32 [n_frames] kept boxes (the rest padded with 0 / index -1),
+ *   n_candidates i32 [n_frames] = anchors that passed score_thr, before the pre_max truncation, status i32 [n_frames]:
+ *   MVX_DETECT_TRUNCATED (informational) | MVX_DETECT_NONFINITE.  Optional debug outputs (all three or none):
+ *   dbg_idx i32 [n_frames][pre_max] the sorted candidates' anchor indices (-1 beyond min(n_candidates, pre_max)),
+ *   dbg_boxes f32 [n_frames][pre_max][7] their decoded boxes, dbg_corners f32 [n_frames][pre_max][4][2] their corners.
+ *   Limits (MVX_EINVAL before any launch): 1 <= pre_max <= MVX_DETECT_MAX_PRE, 1 <= post_max <= pre_max,
+ *   1e-3 <= iou_thr < 1, 0 <= score_thr < 1, non-NULL inputs / outputs, a 256-byte aligned workspace of
+ *   mvx_detect_workspace_bytes(n_frames, l*w*anchors_per_loc, pre_max) bytes.  Four launches for all frames, no float
+ *   atomics (bitwise reproducible), no host synchronisation.
+ */
+#define MVX_DETECT_MAX_PRE 4096
+#define MVX_DETECT_DECODE_LOSS 0
+#define MVX_DETECT_DECODE_REFERENCE 1
+#define MVX_DETECT_TRUNCATED 1
+#define MVX_DETECT_NONFINITE 2
+size_t mvx_detect_workspace_bytes(int32_t n_frames, int32_t n_anchors, int32_t pre_max);
+int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+                      int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *anchors, int32_t n_frames,
+                      int32_t l, int32_t w, int32_t anchors_per_loc, float score_thr, float iou_thr, int32_t pre_max,
+                      int32_t post_max, int32_t decode, float *boxes, float *scores, int32_t *anchor_idx, int32_t *counts,
+                      int32_t *n_candidates, int32_t *status, int32_t *dbg_idx, float *dbg_boxes, float *dbg_corners,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

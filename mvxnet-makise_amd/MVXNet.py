@@ -1,5 +1,6 @@
 """MVXNet top module with the reference's interface (MVXNet.py:13-27):
-``forward(voxels (1,N,T,9), imgs, idx (N,4), calibs, imsize) -> (score, reg)``."""
+``forward(voxels (1,N,T,9), imgs, idx (N,4), calibs, imsize) -> (score, reg)``, and ``detect`` (same inputs + the anchor
+grid) -> the frame's boxes after decoding and NMS (modules/detect.py; the reference has no detection output)."""
 import torch
 from torch import nn
 
@@ -71,3 +72,18 @@ class MVXNet(nn.Module):
         imfeat, cr, vox2d = self.head.forward_compact(imgs, voxels, calibs, imsize)
         rows = CompactInputFunction.apply(imfeat, vox2d, cr)
         return self.backbone(rows, idx, compact_rows=cr)
+
+    def detect(self, voxels, imgs, idx, calibs, imsize, anchors, **kw):
+        """Boxes of one frame, with forward's inputs (MVXNet.py:21-27) and the anchor grid (h1, w1, 14)
+        (Preprocessing.createAnchors): the forward on the single HIP node up to the raw head logits, then
+        ``modules.detect.postprocess`` (keyword arguments as there: score_thr, iou_thr, pre_max, post_max, decode).
+        Returns ``{boxes (n,7) xyzlwhr LiDAR frame, scores (n,), anchor_idx (n,), n_candidates, status}``."""
+        from modules import detect, whole
+        from modules import Extension as X
+        import modules.config as cfg
+        if not whole.supported(self, voxels, idx):
+            raise X.MvxHipError('MVXNet.detect runs on the single-node HIP path: f32 contiguous (1,N,T,9) voxels and (N,4) i64 '
+                                'indices on the GPU, the background rewrite and the HIP RPN on, map sides divisible by 8')
+        with torch.no_grad():
+            heads = whole.forward_heads(self, voxels, imgs, idx, imsize)
+            return detect.postprocess(heads, anchors, 1, cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2, **kw)[0]

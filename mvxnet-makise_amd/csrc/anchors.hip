@@ -12,115 +12,9 @@
 // (2R+1)^2 window around the centre in parallel into LDS, then one lane replays the reference's walk over the
 // window (rows up, rows down; inside a row right, then left) -- same visiting order, same break conditions -- and
 // a second single-workgroup launch concatenates the per-pair lists in (ground truth, orientation) order.
-#include "common.h"
+#include "bev_iou.h"
 
 namespace {
-
-struct P2 { float x, y; };
-
-// The polygons of the clipping live in LDS, one slot column per thread (element i of thread t at base[i * stride + t]:
-// consecutive lanes hit consecutive 8-byte words, no bank conflicts).  Thread-private arrays indexed by run-time counters
-// (q[m++]) are placed in scratch memory by the compiler: 336 B per thread and ~2,000 dependent scratch accesses per IoU
-// made one classifyAnchors call of 8 boxes take 0.5 ms.
-struct LP {
-    P2 *b;
-    int stride;
-    __device__ __forceinline__ P2 &operator[](int i) const { return b[i * stride]; }
-};
-constexpr int POLY_SLOTS = 40;          // per thread: p[10] | q[20] | quad 1 [5] | quad 2 [5]
-
-constexpr float TOL = 1e-6f;
-
-__device__ __forceinline__ int sgn(float d) { return (d > TOL) - (d < -TOL); }
-
-__device__ __forceinline__ float cross3(P2 o, P2 a, P2 b) { return (a.x - o.x) * (b.y - o.y) - (b.x - o.x) * (a.y - o.y); }
-
-__device__ __forceinline__ bool same_pt(P2 p, P2 q) { return sgn(p.x - q.x) == 0 && sgn(p.y - q.y) == 0; }
-
-// shoelace area of ps[0..n) (ps[n] is set to ps[0]); f32 accumulation, the halving in f64 (voxelutil.cpp:31-38)
-__device__ float shoelace(LP ps, int n) {
-    float acc = 0.f;
-    ps[n] = ps[0];
-    for (int i = 0; i < n; ++i) {
-        const P2 u = ps[i], v = ps[i + 1];
-        acc += u.x * v.y - u.y * v.x;
-    }
-    return (float)((double)acc / 2.0);
-}
-
-// polygon p[0..n) cut by the half plane left of (a, b) (voxelutil.cpp:50-63); q: 20 slots of scratch
-__device__ void cut(LP p, int &n, P2 a, P2 b, LP q) {
-    int m = 0;
-    p[n] = p[0];
-    for (int i = 0; i < n; ++i) {
-        const P2 pi = p[i], pj = p[i + 1];
-        const float s1 = cross3(a, b, pi), s2 = cross3(a, b, pj);
-        const int g1 = sgn(s1), g2 = sgn(s2);
-        if (g1 > 0) q[m++] = pi;
-        if (g1 != g2) {
-            // The reference consumes a slot even when |s2 - s1| <= 1e-6 makes it skip the crossing (voxelutil.cpp:44),
-            // leaving whatever an EARLIER call stored there; call history does not exist here, the slot takes p[i].
-            P2 c = pi;
-            if (sgn(s2 - s1) != 0) {
-                c.x = (pi.x * s2 - pj.x * s1) / (s2 - s1);
-                c.y = (pi.y * s2 - pj.y * s1) / (s2 - s1);
-            }
-            q[m++] = c;
-        }
-    }
-    n = 0;
-    for (int i = 0; i < m; ++i)
-        if (i == 0 || !same_pt(q[i], q[i - 1])) p[n++] = q[i];
-    while (n > 1 && same_pt(p[n - 1], p[0])) --n;
-}
-
-// signed intersection area of the origin triangles (o,a,b) and (o,c,d) (voxelutil.cpp:65-79); p: 10 slots, q: 20 slots
-__device__ float tri_pair(P2 a, P2 b, P2 c, P2 d, LP p, LP q) {
-    const P2 o = {0.f, 0.f};
-    const int s1 = sgn(cross3(o, a, b)), s2 = sgn(cross3(o, c, d));
-    if (s1 == 0 || s2 == 0) return 0.f;
-    if (s1 == -1) { const P2 t = a; a = b; b = t; }
-    if (s2 == -1) { const P2 t = c; c = d; d = t; }
-    p[0] = o; p[1] = a; p[2] = b;
-    int n = 3;
-    cut(p, n, o, c, q);
-    cut(p, n, c, d, q);
-    cut(p, n, d, o, q);
-    const float res = (float)fabs((double)shoelace(p, n));
-    return (s1 * s2 == -1) ? -res : res;
-}
-
-__device__ void orient_ccw(LP q) {      // voxelutil.cpp:82-83
-    if (shoelace(q, 4) < 0.f) {
-        P2 t = q[0]; q[0] = q[3]; q[3] = t;
-        t = q[1]; q[1] = q[2]; q[2] = t;
-    }
-    q[4] = q[0];
-}
-
-// q1, q2: 5 slots each, both already oriented (orient_ccw)
-__device__ float quad_intersection(LP q1, LP q2, LP p, LP q) {
-    float res = 0.f;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) res += tri_pair(q1[i], q1[i + 1], q2[j], q2[j + 1], p, q);
-    return res;
-}
-
-__device__ __forceinline__ void load_quad(LP q, const float *src) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { P2 v; v.x = src[2 * k]; v.y = src[2 * k + 1]; q[k] = v; }
-}
-
-// the four polygon areas of this thread inside a [POLY_SLOTS][threads] LDS block
-struct Polys { LP p, q, q1, q2; };
-__device__ __forceinline__ Polys polys_of(P2 *block, int threads, int t) {
-    Polys r;
-    r.p = LP{block + t, threads};
-    r.q = LP{block + 10 * threads + t, threads};
-    r.q1 = LP{block + 30 * threads + t, threads};
-    r.q2 = LP{block + 35 * threads + t, threads};
-    return r;
-}
 
 constexpr int PAIR_THREADS = 64;
 __global__ __launch_bounds__(PAIR_THREADS) void bbox_pairwise(const float *__restrict__ b1, int n, const float *__restrict__ b2, int m,
@@ -168,25 +62,18 @@ __global__ __launch_bounds__(256) void anchor_window_walk(const float *__restric
     // Bounding circles: boxes whose centres are further apart than the two half diagonals (+ 1 %) cannot touch.  Their
     // true IoU is 0 and the reference's origin-fan sum gives rounding noise of ~1e-6 there; either ends the walk
     // (iou < 0.1) the same way and neither value is ever output, so those cells skip the clipping.
-    P2 gc = {0.f, 0.f};
-    float gr = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const P2 v = gt[k]; gc.x += 0.25f * v.x; gc.y += 0.25f * v.y; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const P2 v = gt[k]; gr = fmaxf(gr, sqrtf((v.x - gc.x) * (v.x - gc.x) + (v.y - gc.y) * (v.y - gc.y))); }
+    P2 gc;
+    float gr;
+    quad_circle(gt, gc, gr);
     for (int c = threadIdx.x; c < Wn * Wn; c += blockDim.x) {
         const long long x = nl + c / Wn - R, y = nw + c % Wn - R;
         float iou = -1.f;                             // outside the grid: never visited (loop bounds of the reference)
         if (x >= 0 && x < L && y >= 0 && y < W) {
             load_quad(q, anchors + ((size_t)(x * W + y) * A + z) * 8);
-            P2 ac = {0.f, 0.f};
-            float ar = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const P2 v = q[k]; ac.x += 0.25f * v.x; ac.y += 0.25f * v.y; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const P2 v = q[k]; ar = fmaxf(ar, sqrtf((v.x - ac.x) * (v.x - ac.x) + (v.y - ac.y) * (v.y - ac.y))); }
-            const float dist = sqrtf((ac.x - gc.x) * (ac.x - gc.x) + (ac.y - gc.y) * (ac.y - gc.y));
-            if (dist > 1.01f * (gr + ar) + 1e-3f) {
+            P2 ac;
+            float ar;
+            quad_circle(q, ac, ar);
+            if (circles_apart(gc, gr, ac, ar)) {
                 iou = 0.f;
             } else {
                 orient_ccw(q);

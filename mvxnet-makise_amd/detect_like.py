@@ -1,0 +1,84 @@
+"""Detection counterpart of train_like.py: boxes for every frame of a KITTI split from a checkpoint, written as KITTI
+``label_2`` result files (one per frame) for the devkit.
+
+Frames are read with ``Load.createDataset``, grouped into frame sets with ``pipeline.batch_from_dataset`` and run through
+``detect.detect_frame_set`` (the training step's forward on this library's kernels, then decoding and rotated BEV NMS on the
+GPU).  The feature maps come from the same stand-in as train_like.py when torchvision is absent.
+
+    python detect_like.py <dataroot> --checkpoint checkpoints/epoch10.pkl [--split val] [--out results/data]
+    python detect_like.py /tmp/kitti --synthetic 8          # a synthetic tree, an untrained (seeded) model
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('dataroot')
+    ap.add_argument('--checkpoint', default=None, help='state dict written by train_like.py (default: the seeded, untrained model)')
+    ap.add_argument('--split', default='train', help='ImageSets/<split>.txt')
+    ap.add_argument('--out', default=None, help='result directory (default <dataroot>/results/data)')
+    ap.add_argument('--synthetic', type=int, default=0, help='write a synthetic KITTI tree with this many frames into dataroot first')
+    ap.add_argument('--points', type=int, default=20000)
+    ap.add_argument('--frames', type=int, default=4, help='frames per frame set')
+    ap.add_argument('--need-crop', action='store_true')
+    ap.add_argument('--score-thr', type=float, default=0.05)
+    ap.add_argument('--iou-thr', type=float, default=0.01)
+    ap.add_argument('--pre-max', type=int, default=1000)
+    ap.add_argument('--post-max', type=int, default=100)
+    ap.add_argument('--decode', choices=['loss', 'reference'], default='loss')
+    return ap.parse_args(argv)
+
+
+def main(args):
+    import modules.config as cfg
+    from modules import Extension as X
+    from modules import pipeline as pl
+    from modules.Calc import bbox3d2bev
+    from modules.data import Load as load, Preprocessing as pre
+    from modules.detect import detect_frame_set, write_kitti_results
+    from MVXNet import MVXNet
+    from train_like import fpn_maps_for
+
+    device = X.device()
+    torch.cuda.set_device(device)
+    if args.synthetic:
+        from modules.data import Synthetic
+        Synthetic.write_kitti_tree(args.dataroot, list(range(args.synthetic)), points=args.points)
+    with open(os.path.join(args.dataroot, 'ImageSets', args.split + '.txt'), 'r') as f:
+        names = [n for n in f.read().splitlines() if n]
+    data = load.createDataset(names, needCrop=args.need_crop, root=args.dataroot)
+    out_dir = args.out or os.path.join(args.dataroot, 'results', 'data')
+    os.makedirs(out_dir, exist_ok=True)
+
+    anchors = pre.createAnchors(cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2, cfg.velorange, cfg.carsize)
+    anchorBevs = bbox3d2bev(anchors.reshape(anchors.shape[:2] + (-1, 7))).to(device).contiguous()
+    anchors = anchors.to(device)
+    torch.manual_seed(0)
+    model = MVXNet().to(device)
+    if args.checkpoint:
+        model.load_state_dict(torch.load(args.checkpoint, map_location=device))
+    kw = dict(score_thr=args.score_thr, iou_thr=args.iou_thr, pre_max=args.pre_max, post_max=args.post_max, decode=args.decode)
+    cap = max(args.points, max(d[0].shape[0] for d in data))
+    t0, n_boxes = time.perf_counter(), 0
+    for lo in range(0, len(data), args.frames):
+        group, gnames = data[lo:lo + args.frames], names[lo:lo + args.frames]
+        batch, _ = pl.batch_from_dataset(group, gnames, device, anchorBevs, fpn_maps_for, cap_points=cap)
+        dets = detect_frame_set(model, batch, anchors, cfg.imsize, **kw)
+        for name, d, frame in zip(gnames, dets, group):
+            write_kitti_results(os.path.join(out_dir, name + '.txt'), d, frame[5], cfg.imsize)
+            n_boxes += d['boxes'].shape[0]
+    dt = time.perf_counter() - t0
+    print('%d frames, %d boxes -> %s (%.1f frames/s including file I/O)' % (len(data), n_boxes, out_dir, len(data) / max(dt, 1e-9)))
+
+
+if __name__ == '__main__':
+    a = parse_args()
+    sys.argv = sys.argv[:1]              # modules.config parses argv at import (reference modules/config/Parser.py:12)
+    main(a)

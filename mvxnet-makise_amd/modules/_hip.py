@@ -1641,3 +1641,41 @@ def voxel_loss(score, reg, pos_idx, neg_idx, gi, n_pos, n_neg, gts, anchors, A, 
                                  _vptr(dscore), ds[0], ds[1], ds[2], _vptr(dreg), dr[0], dr[1], dr[2],
                                  X.ptr(losses), X.ptr(scratch), X.stream()), 'mvx_voxel_loss')
     return losses, dscore, dreg
+
+
+# ---------------------------------------------------------------------------------------------
+# detection output (csrc/detect.hip)
+# ---------------------------------------------------------------------------------------------
+DECODE_MODES = {'loss': 0, 'reference': 1}
+
+
+def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, post_max, decode='loss', debug=False):
+    """Selection, decoding and rotated BEV NMS of F frames in four launches.  ``cls`` / ``reg``: f32 views (F, l, w, A) and
+    (F, l, w, 7A) with arbitrary element strides (the frame-set heads or NCHW maps, read in place); anchors f32 [l][w][A][7]
+    contiguous on the device.  Returns (boxes (F,post_max,7), scores (F,post_max), anchor_idx i32 (F,post_max), meta i32 (3,F) =
+    (kept count, candidates above score_thr, status)) on the device, plus (candidate anchor indices i32 (F,pre_max), decoded
+    boxes (F,pre_max,7), corners (F,pre_max,4,2)) with ``debug``."""
+    if decode not in DECODE_MODES:
+        raise X.MvxHipError("decode must be 'loss' or 'reference', not %r" % (decode,))
+    dev = cls.device
+    assert cls.shape == (F, l, w, A) and reg.shape == (F, l, w, 7 * A)
+    anchors = anchors.detach().float().contiguous()
+    assert anchors.is_cuda and anchors.numel() == l * w * A * 7
+    boxes = torch.empty((F, post_max, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((F, post_max), dtype=torch.float32, device=dev)
+    idx = torch.empty((F, post_max), dtype=torch.int32, device=dev)
+    meta = torch.empty((3, F), dtype=torch.int32, device=dev)          # counts, n_candidates, status
+    dbg = (None, None, None)
+    if debug:
+        dbg = (torch.empty((F, pre_max), dtype=torch.int32, device=dev), torch.empty((F, pre_max, 7), dtype=torch.float32, device=dev),
+               torch.empty((F, pre_max, 4, 2), dtype=torch.float32, device=dev))
+    nbytes = X.lib.mvx_detect_workspace_bytes(F, l * w * A, pre_max)
+    ws = workspace(nbytes, dev, 'detect')
+    cs, rs = cls.stride(), reg.stride()
+    X.check(X.lib.mvx_detect_frames(_vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3], X.ptr(anchors),
+                                    int(F), int(l), int(w), int(A), float(score_thr), float(iou_thr), int(pre_max), int(post_max),
+                                    DECODE_MODES[decode], X.ptr(boxes), X.ptr(scores), X.ptr(idx), X.ptr(meta[0]),
+                                    X.ptr(meta[1]), X.ptr(meta[2]), X.ptr(dbg[0]), X.ptr(dbg[1]), X.ptr(dbg[2]), X.ptr(ws),
+                                    ws.numel(), X.stream()), 'mvx_detect_frames')
+    out = (boxes, scores, idx, meta)
+    return out + dbg if debug else out

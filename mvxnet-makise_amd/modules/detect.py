@@ -1,0 +1,191 @@
+"""Detection output: the RPN's head output -> boxes per frame (csrc/detect.hip), and KITTI result files.
+
+The reference stops at the score / regression maps (its Calc.decodeRegression is never called; no NMS, no eval).  Here:
+  * ``postprocess``: score selection, top-K, box decoding and rotated BEV NMS of all frames of a step in four launches, one
+    host read of the counts;
+  * ``detect_frame_set``: the forward half of ``pipeline.train_step_full`` (frame sets through fusion / VFE / CML, the RPN on
+    this library's kernels) followed by ``postprocess`` -- no parameter, gradient or gradient bucket is touched;
+  * ``boxes_lidar_to_camera`` / ``write_kitti_results``: KITTI ``label_2`` lines for the devkit.
+"""
+import math
+
+import numpy as np
+import torch
+
+import modules.config as cfg
+from modules import _hip
+from modules import Extension as X
+
+DEFAULTS = dict(score_thr=0.05, iou_thr=0.01, pre_max=1000, post_max=100, decode='loss')
+
+
+def _anchors_dev(anchors, h1, w1, dev):
+    """[h1][w1][A][7] f32 contiguous on ``dev`` (the (l, w, 7A) grid of Preprocessing.createAnchors is the same memory)."""
+    from modules import Calc
+    a = anchors if anchors.is_cuda else Calc._anchors_on(anchors, dev)
+    a = a.detach().float().contiguous()
+    return a.view(h1, w1, -1, 7)
+
+
+def _views(heads_or_maps, F, h1, w1):
+    """(cls (F,h1,w1,A), reg (F,h1,w1,7A)) views of the channels-last heads (F*h1*w1, 16) or of NCHW maps (cls, reg)."""
+    if isinstance(heads_or_maps, (tuple, list)):
+        cls, reg = heads_or_maps
+        assert cls.dim() == 4 and cls.shape[0] == F and cls.shape[2:] == (h1, w1), tuple(cls.shape)
+        assert reg.shape == (F, 7 * cls.shape[1], h1, w1), tuple(reg.shape)
+        return cls.permute(0, 2, 3, 1), reg.permute(0, 2, 3, 1)
+    v = heads_or_maps.view(F, h1, w1, -1)
+    A = v.shape[-1] // 8
+    assert v.shape[-1] == 8 * A, tuple(heads_or_maps.shape)
+    return v[..., :A], v[..., A:]
+
+
+def postprocess(heads_or_maps, anchors, F, h1, w1, *, score_thr=0.05, iou_thr=0.01, pre_max=1000, post_max=100, decode='loss',
+                read=True, debug=False):
+    """Boxes of F frames from the raw head output, read in place: the frame-set heads (F*h1*w1, 16) = [cls logits | reg] of
+    ``rpn_frames.rpn_forward``, or NCHW maps ``(cls logits (F,2,h1,w1), reg (F,14,h1,w1))``.  ``anchors`` (h1, w1, 14) =
+    [l][w][A][7] (Preprocessing.createAnchors), on the host or the device.
+
+    Per frame: anchors with sigmoid(logit) >= score_thr, the best ``pre_max`` of them (logit descending, then anchor index
+    ascending), decoded (``decode='loss'``: the inverse of VoxelLoss's targets; ``'reference'``: Calc.decodeRegression as the
+    reference wrote it, diagonal from anchor columns 0:2), greedy NMS at BEV IoU > iou_thr, at most ``post_max`` kept.
+
+    Returns a list of F dicts ``{boxes (n,7) xyzlwhr, scores (n,), anchor_idx (n,) i32, n_candidates, status}`` (device
+    tensors) after ONE device->host read; ``read=False`` returns the padded device tensors instead
+    ``{boxes (F,post_max,7), scores, anchor_idx, meta i32 (3,F) = (counts, n_candidates, status)}`` for a caller that
+    pipelines (``unpack`` reads them later).  ``debug`` adds the sorted candidates ('cand_idx', 'cand_boxes',
+    'cand_corners', padded to pre_max) to the device dict."""
+    cls, reg = _views(heads_or_maps, F, h1, w1)
+    if cls.dtype != torch.float32 or reg.dtype != torch.float32:
+        raise X.MvxHipError('postprocess reads f32 head outputs')
+    A = cls.shape[-1]
+    anc = _anchors_dev(anchors, h1, w1, cls.device)
+    if anc.shape[2] != A:
+        raise X.MvxHipError('anchors hold %d orientations per cell, the heads %d' % (anc.shape[2], A))
+    res = _hip.detect_frames(cls, reg, anc, F, h1, w1, A, score_thr, iou_thr, pre_max, post_max, decode, debug=debug)
+    out = dict(boxes=res[0], scores=res[1], anchor_idx=res[2], meta=res[3])
+    if debug:
+        out.update(cand_idx=res[4], cand_boxes=res[5], cand_corners=res[6])
+    return unpack(out) if read else out
+
+
+def unpack(dev_out):
+    """The device dict of ``postprocess(read=False)`` -> per-frame dicts (one host read)."""
+    counts, n_cand, status = dev_out['meta'].tolist()
+    return [dict(boxes=dev_out['boxes'][f, :n], scores=dev_out['scores'][f, :n], anchor_idx=dev_out['anchor_idx'][f, :n],
+                 n_candidates=n_cand[f], status=status[f]) for f, n in enumerate(counts)]
+
+
+def _empty(dev):
+    return dict(boxes=torch.zeros((0, 7), device=dev), scores=torch.zeros((0,), device=dev),
+                anchor_idx=torch.zeros((0,), dtype=torch.int32, device=dev), n_candidates=0, status=0)
+
+
+def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw):
+    """Detections for every frame of ``batch`` (pipeline.FrameBatch): the forward of ``pipeline.train_step_full`` -- the frame
+    set through fusion / VFE / CML and the RPN on this library's kernels, per-frame BatchNorm statistics -- then
+    ``postprocess`` (keyword arguments as there).  ``ready``: a prepared frame set as train_step_full takes it (or None).
+    Returns one dict per batch frame; frames without voxels get empty results.  Reads no gradient and writes none; the
+    data-dependent status words are checked like ``pipeline.read_losses``.  ``keep`` (tests): receives 'heads'."""
+    from modules import frames as fr
+    from modules import pipeline as pl
+    from modules import rpn_frames as rf
+    opts = dict(DEFAULTS, **kw)
+    dev = batch.device
+    ev_ready = None
+    if ready is None:
+        ready = pl.prepare_frame_set(batch)
+    elif len(ready) == 5:
+        ready, ev_ready = ready[:4], ready[4]
+    fs, live, counts, status = ready
+    if ev_ready is not None:
+        main = torch.cuda.current_stream(dev)
+        main.wait_event(ev_ready)
+        status.record_stream(main)
+        if fs is not None:
+            fs.hand_over(main, fenced=pl.PREP_FENCE)
+    hw = [float(imsize[0]), float(imsize[1])]
+    statuses = [status]
+    dets = None
+    try:
+        if fs is not None:
+            model.prepack()
+            _hip.arena_begin(dev, doubles=1 << 22)
+            F = len(live)
+            with torch.no_grad():
+                feat, saved = fr.rows_forward(model, fs, [batch.fpn_levels[f] for f in live], hw, statuses)
+                fr.cml_forward(model, fs, feat, saved, statuses, want_bev=False)
+                heads, rs = rf.rpn_forward(model.backbone.rpn, saved.x3, F, saved.D3, saved.H, saved.W, saved.C3)
+                dets = postprocess(heads, anchors, F, rs['h1'], rs['w1'], read=False, **opts)
+            if keep is not None:
+                keep.update(heads=heads, geom=(F, rs['h1'], rs['w1']))
+    finally:
+        _hip.arena_end()
+        pl._fence_record(dev)
+    bad = int(torch.stack([s.reshape(()) for s in statuses]).max())
+    if bad:
+        raise X.MvxHipError('a kernel reported a data-dependent error (status %d)' % bad)
+    out = [_empty(dev) for _ in range(batch.n_frames)]
+    if dets is not None:
+        for f, d in zip(live, unpack(dets)):
+            out[f] = d
+    return out
+
+
+# ---- KITTI result files ----------------------------------------------------------------------------------------------
+def _tensor(m):
+    return m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m))
+
+
+def boxes_lidar_to_camera(boxes, calib):
+    """(N,7) LiDAR-frame xyzlwhr -> camera-frame 'hwlxyzr' (KITTI label order): the exact inverse of ``Calc.bboxCam2Lidar``
+    as ``Load.createDataset`` applies it.  Like the reference's loader this uses ``Tr_velo_to_cam`` only, WITHOUT
+    ``R0_rect``: the written boxes are in the frame the training labels were read in, so a model's output goes back to the
+    file it would have been trained from.  Float64 arithmetic on the host; returns a float64 tensor."""
+    b = _tensor(boxes).detach().to('cpu', torch.float64).reshape(-1, 7)
+    v2c = _tensor(calib['Tr_velo_to_cam']).to('cpu', torch.float64)
+    xyz1 = torch.cat([b[:, :3], torch.ones((b.shape[0], 1), dtype=torch.float64)], 1)
+    cam = torch.empty_like(b)
+    cam[:, 0:3] = b[:, [5, 4, 3]]
+    cam[:, 3:6] = (xyz1 @ v2c.T)[:, :3]
+    cam[:, 6] = b[:, 6] + 0.5 * math.pi
+    return cam
+
+
+def kitti_lines(dets, calib, imsize):
+    """KITTI ``label_2`` lines of one frame's detections (dict with 'boxes' (n,7) LiDAR xyzlwhr and 'scores' (n,)):
+    ``Car -1 -1 alpha x1 y1 x2 y2 h w l x y z ry score`` with alpha = ry - atan2(x, z) and the 2-D box spanned by the eight
+    corners (Calc.bbox3d2corner) taken to the camera frame like the box (Tr_velo_to_cam), projected through P2 and clipped
+    to the image ``imsize`` = (height, width)."""
+    from modules import Calc
+    boxes = _tensor(dets['boxes']).detach().to('cpu', torch.float64).reshape(-1, 7)
+    scores = _tensor(dets['scores']).detach().to('cpu', torch.float64).reshape(-1)
+    if boxes.shape[0] == 0:
+        return []
+    cam = boxes_lidar_to_camera(boxes, calib)
+    v2c = _tensor(calib['Tr_velo_to_cam']).to('cpu', torch.float64)
+    p2 = _tensor(calib['P2']).to('cpu', torch.float64)
+    corners = Calc.bbox3d2corner(boxes)                                           # (n, 8, 3) LiDAR frame
+    hom = torch.cat([corners, torch.ones(corners.shape[:2] + (1,), dtype=torch.float64)], 2)
+    uvw = hom @ (p2 @ v2c).T                                                      # (n, 8, 4)
+    depth = uvw[..., 2].clamp_min(1e-6)
+    u, v = uvw[..., 0] / depth, uvw[..., 1] / depth
+    h_img, w_img = float(imsize[0]), float(imsize[1])
+    x1 = u.min(1).values.clamp(0, w_img - 1)
+    x2 = u.max(1).values.clamp(0, w_img - 1)
+    y1 = v.min(1).values.clamp(0, h_img - 1)
+    y2 = v.max(1).values.clamp(0, h_img - 1)
+    lines = []
+    for k in range(boxes.shape[0]):
+        h, w, l, x, y, z, ry = cam[k].tolist()
+        alpha = ry - math.atan2(x, z)
+        lines.append('Car -1 -1 %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.4f'
+                     % (alpha, x1[k], y1[k], x2[k], y2[k], h, w, l, x, y, z, ry, float(scores[k])))
+    return lines
+
+
+def write_kitti_results(path, dets, calib, imsize):
+    """One frame's detections as a KITTI result file (``kitti_lines``); an empty file when there are none."""
+    lines = kitti_lines(dets, calib, imsize)
+    with open(path, 'w') as f:
+        f.write(''.join(ln + '\n' for ln in lines))

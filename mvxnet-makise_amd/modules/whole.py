@@ -140,16 +140,22 @@ def _all_params(model):
     return hit[1]
 
 
-def forward(model, voxels, imgs, idx, imsize):
-    """MVXNet.forward on the single node: (score (1,2,H/2,W/2), reg (1,14,H/2,W/2)).  The data-dependent status words of the
-    sampling / scatter kernels stand for the reference's assert (imhead/Pipe.py:71); they are collected on the model and
-    read without stalling the training stream (take_status), at once for a no-grad call."""
+def forward_heads(model, voxels, imgs, idx, imsize):
+    """The single node's raw output: heads (H/2 * W/2, 16) = [cls logits (2) | reg (14)] per BEV cell.  The data-dependent
+    status words of the sampling / scatter kernels stand for the reference's assert (imhead/Pipe.py:71); they are collected
+    on the model and read without stalling the training stream (take_status), at once for a no-grad call."""
     hw = _imsize_hw(imsize)
     params = [p for p in _all_params(model) if p.requires_grad]
     heads = WholeModelFunction.apply(voxels, idx, model, imgs, hw, *params)
     # no backward will follow (inference): the reference's assert, now; training: at most every MAX_PENDING_STATUS words
     if not heads.requires_grad or len(model.__dict__.get('_mvx_status', ())) > MAX_PENDING_STATUS:
         _check(take_status(model))
+    return heads
+
+
+def forward(model, voxels, imgs, idx, imsize):
+    """MVXNet.forward on the single node: (score (1,2,H/2,W/2) = sigmoid of the logits, reg (1,14,H/2,W/2))."""
+    heads = forward_heads(model, voxels, imgs, idx, imsize)
     h1, w1 = cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2
     v = heads.view(1, h1, w1, 16)
     return torch.sigmoid(v[..., :2]).permute(0, 3, 1, 2), v[..., 2:].permute(0, 3, 1, 2)
