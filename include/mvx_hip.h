@@ -929,6 +929,55 @@ int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t 
                       int32_t *n_candidates, int32_t *status, int32_t *dbg_idx, float *dbg_boxes, float *dbg_corners,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * KITTI object evaluation (csrc/kitti_eval.hip): AP for 2D bbox, BEV and 3D, plus AOS, in the semantics of the widely used
+ * kitti-object-eval-python tool as DESIGN.md section 3.17 states them.  The reference has no evaluation.
+ *
+ * All frames of an evaluation in one flat layout (F = n_frames >= 1, no MVX_MAX_FRAMES limit):
+ *   off_host (host) / off (device) i32 [3][F+1]: offsets of the detection, GT and don't-care rows of every frame (each
+ *     starting at 0); per frame at most MVX_DETECT_MAX_PRE detections and MVX_KITTI_MAX_GT GT plus don't-care rows;
+ *   pair_off i64 [3][F+1] (device): prefix sums over the frames of nd*ng, nd*nc and min(nd, ng) (TP score slots);
+ *   det_rows / gt_rows f64 [n][8] = x1 y1 x2 y2 l w h y (2-D box; camera-frame size and bottom y), dc_rows f64 [n][4];
+ *   det_quads / gt_quads f32 [n][4][2]: BEV corner quads in the (x, z) plane; scores / det_alpha / gt_alpha f64 [n];
+ *   curves: curve_host (host) i32 [n_curves][2] = (metric 0 = 2D / 1 = BEV / 2 = 3D, flag set), min_overlap_host (host)
+ *     f64 [n_curves] in [0, 1), 1 <= n_curves <= MVX_KITTI_MAX_CURVES;
+ *   ignored_gt / ignored_det i8 [n_sets][n_gt] / [n_sets][n_det]: the cleaning flags (-1 / 0 / 1) of every flag set.
+ * mvx_kitti_eval_overlaps: overlaps f64 [3][n_pairs], frame f's pair (GT g, detection d) at pair_off[0][f] + g*nd + d;
+ *   2D IoU, BEV IoU = I / (l_d w_d + l_g w_g - I) with I the f32 rotated intersection of the quads (bev_iou.h, 0 when the
+ *   bounding circles cannot touch), 3D IoU over the vertical extents [y - h, y]; dc_overlaps f64 at pair_off[1][f] + k*nd + d:
+ *   2-D intersection over the detection's area.
+ * mvx_kitti_eval_tp_scores: the threshold pass (compute_fp = false) of every (frame, curve): tp_scores f64
+ *   [n_curves][pair_off[2][F]] holds the TP scores of frame f from pair_off[2][f] on, -inf in the unused slots;
+ *   n_valid_gt i32 [n_curves][F].  The caller sorts every curve's row in descending order for:
+ * mvx_kitti_eval_thresholds: get_thresholds of every curve: thresholds f64 [n_curves][MVX_KITTI_THRESHOLDS] (0-padded),
+ *   n_thresholds i32 [n_curves], n_gt i32 [n_curves] = valid GTs summed over the frames.
+ * mvx_kitti_eval_counts: compute_fp = true for every (frame, curve, threshold), per-frame results in a 256-byte aligned
+ *   workspace of mvx_kitti_eval_workspace_bytes(n_frames, n_curves) bytes, summed over the frames in a fixed order:
+ *   totals i32 [n_curves][MVX_KITTI_THRESHOLDS][3] = (tp, fp, fn), similarity f64 [n_curves][MVX_KITTI_THRESHOLDS] (AOS,
+ *   2D curves only; 0 elsewhere); thresholds beyond n_thresholds give zeros.
+ * Argument errors, a frame over the limits included, return MVX_EINVAL before any launch.  No atomics (bitwise
+ * reproducible), no host synchronisation.
+ */
+#define MVX_KITTI_MAX_GT 1024
+#define MVX_KITTI_MAX_CURVES 72
+#define MVX_KITTI_THRESHOLDS 41
+size_t mvx_kitti_eval_workspace_bytes(int32_t n_frames, int32_t n_curves);
+int mvx_kitti_eval_overlaps(int32_t n_frames, const int32_t *off_host, const int32_t *off, const int64_t *pair_off,
+                            const double *det_rows, const float *det_quads, const double *gt_rows, const float *gt_quads,
+                            const double *dc_rows, double *overlaps, double *dc_overlaps, void *stream);
+int mvx_kitti_eval_tp_scores(int32_t n_frames, const int32_t *off_host, const int32_t *off, const int64_t *pair_off,
+                             int32_t n_curves, const int32_t *curve_host, const double *min_overlap_host, int32_t n_sets,
+                             const int8_t *ignored_gt, const int8_t *ignored_det, const double *scores, const double *overlaps,
+                             double *tp_scores, int32_t *n_valid_gt, void *stream);
+int mvx_kitti_eval_thresholds(int32_t n_frames, int32_t n_curves, int64_t n_slots, const double *sorted_scores,
+                              const int32_t *n_valid_gt, double *thresholds, int32_t *n_thresholds, int32_t *n_gt, void *stream);
+int mvx_kitti_eval_counts(int32_t n_frames, const int32_t *off_host, const int32_t *off, const int64_t *pair_off,
+                          int32_t n_curves, const int32_t *curve_host, const double *min_overlap_host, int32_t n_sets,
+                          const int8_t *ignored_gt, const int8_t *ignored_det, const double *scores, const double *det_alpha,
+                          const double *gt_alpha, const double *overlaps, const double *dc_overlaps, const double *thresholds,
+                          const int32_t *n_thresholds, int32_t *totals, double *similarity, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

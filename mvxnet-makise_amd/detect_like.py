@@ -7,6 +7,7 @@ GPU).  The feature maps come from the same stand-in as train_like.py when torchv
 
     python detect_like.py <dataroot> --checkpoint checkpoints/epoch10.pkl [--split val] [--out results/data]
     python detect_like.py /tmp/kitti --synthetic 8          # a synthetic tree, an untrained (seeded) model
+    python detect_like.py <dataroot> --split val --eval     # then score the files against the split's label_2 (eval_like.py)
 """
 import argparse
 import os
@@ -33,6 +34,8 @@ def parse_args(argv=None):
     ap.add_argument('--pre-max', type=int, default=1000)
     ap.add_argument('--post-max', type=int, default=100)
     ap.add_argument('--decode', choices=['loss', 'reference'], default='loss')
+    ap.add_argument('--eval', action='store_true', help='score the written files against the split\'s label_2 (KITTI AP on the GPU)')
+    ap.add_argument('--classes', nargs='+', default=['Car'], help='classes scored by --eval')
     return ap.parse_args(argv)
 
 
@@ -76,6 +79,10 @@ def main(args):
             n_boxes += d['boxes'].shape[0]
     dt = time.perf_counter() - t0
     print('%d frames, %d boxes -> %s (%.1f frames/s including file I/O)' % (len(data), n_boxes, out_dir, len(data) / max(dt, 1e-9)))
+    if args.eval:
+        import json
+        from eval_like import run
+        print(json.dumps(run(args.dataroot, out_dir, names, args.classes)))
 
 
 if __name__ == '__main__':

@@ -180,6 +180,12 @@ PROTOTYPES = {
     'mvx_detect_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'mvx_detect_frames': (_i32, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _i32, _i32, _i32, _i32, _f32, _f32, _i32,
                                  _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'mvx_kitti_eval_workspace_bytes': (_sz, [_i32, _i32]),
+    'mvx_kitti_eval_overlaps': (_i32, [_i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'mvx_kitti_eval_tp_scores': (_i32, [_i32, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    'mvx_kitti_eval_thresholds': (_i32, [_i32, _i32, _i64, _p, _p, _p, _p, _p, _p]),
+    'mvx_kitti_eval_counts': (_i32, [_i32, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                     _sz, _p]),
 }
 
 

@@ -1,6 +1,6 @@
 """Typed torch-tensor wrappers over the C ABI (plumbing only: allocation, pointers, stream)."""
 import collections
-
+import ctypes
 import os
 
 import torch
@@ -1679,3 +1679,61 @@ def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, po
                                     ws.numel(), X.stream()), 'mvx_detect_frames')
     out = (boxes, scores, idx, meta)
     return out + dbg if debug else out
+
+
+# ---------------------------------------------------------------------------------------------
+# KITTI object evaluation (csrc/kitti_eval.hip); ``inp`` is a kitti_eval.EvalInput, ``t`` its device copies
+# ---------------------------------------------------------------------------------------------
+def _host_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def kitti_eval_overlaps(inp, t):
+    """(overlaps f64 (3, n_pairs) = 2D | BEV | 3D, dc_overlaps f64 (n_dc_pairs,)) of every frame."""
+    dev = t['off'].device
+    ov = torch.empty((3, inp.n_pairs), dtype=torch.float64, device=dev)
+    dco = torch.empty((inp.n_dc_pairs,), dtype=torch.float64, device=dev)
+    X.check(X.lib.mvx_kitti_eval_overlaps(inp.F, _host_ptr(inp.off), X.ptr(t['off']), X.ptr(t['pair_off']), X.ptr(t['det_rows']),
+                                          X.ptr(t['det_quads']), X.ptr(t['gt_rows']), X.ptr(t['gt_quads']), X.ptr(t['dc_rows']),
+                                          X.ptr(ov), X.ptr(dco), X.stream()), 'mvx_kitti_eval_overlaps')
+    return ov, dco
+
+
+def kitti_eval_tp_scores(inp, t, ov):
+    """Threshold pass: (TP scores f64 (C, n_slots), -inf in unused slots; valid GTs i32 (C, F))."""
+    dev = ov.device
+    C = len(inp.keys)
+    tp = torch.empty((C, inp.n_slots), dtype=torch.float64, device=dev)
+    n_valid = torch.empty((C, inp.F), dtype=torch.int32, device=dev)
+    X.check(X.lib.mvx_kitti_eval_tp_scores(inp.F, _host_ptr(inp.off), X.ptr(t['off']), X.ptr(t['pair_off']), C, _host_ptr(inp.curves),
+                                           _host_ptr(inp.min_overlaps), inp.ignored_gt.shape[0], X.ptr(t['ignored_gt']),
+                                           X.ptr(t['ignored_det']), X.ptr(t['scores']), X.ptr(ov), X.ptr(tp), X.ptr(n_valid),
+                                           X.stream()), 'mvx_kitti_eval_tp_scores')
+    return tp, n_valid
+
+
+def kitti_eval_thresholds(inp, tp_sorted, n_valid):
+    """get_thresholds of every curve from its descending TP scores: (thresholds f64 (C, 41), count i32 (C,), n_gt i32 (C,))."""
+    dev = n_valid.device
+    C = len(inp.keys)
+    thr = torch.empty((C, 41), dtype=torch.float64, device=dev)
+    n_thr = torch.empty((C,), dtype=torch.int32, device=dev)
+    n_gt = torch.empty((C,), dtype=torch.int32, device=dev)
+    X.check(X.lib.mvx_kitti_eval_thresholds(inp.F, C, inp.n_slots, X.ptr(tp_sorted.contiguous()), X.ptr(n_valid), X.ptr(thr),
+                                            X.ptr(n_thr), X.ptr(n_gt), X.stream()), 'mvx_kitti_eval_thresholds')
+    return thr, n_thr, n_gt
+
+
+def kitti_eval_counts(inp, t, ov, dco, thr, n_thr):
+    """Counting pass summed over the frames: (tp / fp / fn i32 (C, 41, 3), AOS similarity f64 (C, 41))."""
+    dev = ov.device
+    C = len(inp.keys)
+    totals = torch.empty((C, 41, 3), dtype=torch.int32, device=dev)
+    sim = torch.empty((C, 41), dtype=torch.float64, device=dev)
+    ws = workspace(X.lib.mvx_kitti_eval_workspace_bytes(inp.F, C), dev, 'kitti_eval')
+    X.check(X.lib.mvx_kitti_eval_counts(inp.F, _host_ptr(inp.off), X.ptr(t['off']), X.ptr(t['pair_off']), C, _host_ptr(inp.curves),
+                                        _host_ptr(inp.min_overlaps), inp.ignored_gt.shape[0], X.ptr(t['ignored_gt']),
+                                        X.ptr(t['ignored_det']), X.ptr(t['scores']), X.ptr(t['det_alpha']), X.ptr(t['gt_alpha']),
+                                        X.ptr(ov), X.ptr(dco), X.ptr(thr), X.ptr(n_thr), X.ptr(totals), X.ptr(sim), X.ptr(ws),
+                                        ws.numel(), X.stream()), 'mvx_kitti_eval_counts')
+    return totals, sim
