@@ -13,12 +13,17 @@ One step (--mode hot, the headline) = one batch of `--frames` synthetic frames P
   one flat gradient all-reduce over RCCL -> one AdamW step.
 Other modes (BASELINE.json configs): --mode fusion (config 4: FPN feature sampling + fusion MLP + VFE, 2 frames),
 --mode vfe (config 2: voxelize + VFE stack forward/backward, 16 frames, voxel
-indices asserted bit-exact against the C oracle inside the run), --mode dropin (the nn.Module API: MVXNet.forward +
+indices asserted bit-exact against the C oracle inside a --full run), --mode dropin (the nn.Module API: MVXNet.forward +
 VoxelLoss + autograd + AdamW, one frame at a time like train.py:110-164: compact rows, RPN as one HIP node), --mode full (the WHOLE model
 of train.py:110-164 for B frames per step on this library's kernels: classifyAnchors, frame sets through fusion / VFE /
 CML, the RPN on the same gather kernels, VoxelLoss, whole backward).
 --workload S1|S2: uniform worst case (V ~ 19.9 k voxels per frame) or the KITTI-like ring model (V ~ 5 k, default).
 Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the --steps steps, writes --dump-outputs and prints the line (the headline figure and
+the roofline of its own timed steps).  --full adds everything else the benchmark measures or checks: a second pass with every
+kernel timer on (other_kernels, hbm_stages), the host enqueue probe, the isolated roofline, the other workload / arithmetics /
+BASELINE configs (alt_modes), the CPU baseline, the --mode vfe voxel check against the C oracle, and the detail file.
 """
 import argparse
 import gc
@@ -372,7 +377,7 @@ def _roof(r):
 
 def compact_line(out, detail_path):
     """The printed line: the bench contract's keys, `roofline` and `cpu_baseline` in full, and for every other mode measured in the
-    same run only what identifies it and its result.  Everything else is in the detail file."""
+    same run only what identifies it and its result.  Everything else is in the detail file, which only --full writes."""
     line = {k: out[k] for k in ('metric', 'value', 'unit', 'summary', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better',
                                 'scaling', 'vs_baseline', 'dtype', 'data') if k in out}
     c = out['config']
@@ -387,10 +392,12 @@ def compact_line(out, detail_path):
               'gradient_fingerprint'):
         if k in out:
             line[k] = out[k]
-    line['other_kernels'] = {n: {'frac': _r(v.get('frac')), 'avg_launch_ms': _r(v['avg_launch_ms']), 'launches': v['launches'],
-                                 'arithmetic': v.get('arithmetic')} for n, v in out.get('other_kernels', {}).items()}
-    line['hbm_stages_frac_of_8TBps'] = {n: _r(v['frac_of_8TBps'], 3) for n, v in out.get('hbm_stages', {}).items()
-                                        if v.get('frac_of_8TBps') is not None}
+    if 'other_kernels' in out:                            # --full: the pass with every timer on
+        line['other_kernels'] = {n: {'frac': _r(v.get('frac')), 'avg_launch_ms': _r(v['avg_launch_ms']), 'launches': v['launches'],
+                                     'arithmetic': v.get('arithmetic')} for n, v in out['other_kernels'].items()}
+    if 'hbm_stages' in out:
+        line['hbm_stages_frac_of_8TBps'] = {n: _r(v['frac_of_8TBps'], 3) for n, v in out['hbm_stages'].items()
+                                            if v.get('frac_of_8TBps') is not None}
     alts = []
     for a in out.get('alt_modes', []):
         alts.append({'config': a.get('baseline_config', 'headline path'), 'mode': a.get('mode', out['config']['mode']),
@@ -399,7 +406,8 @@ def compact_line(out, detail_path):
                      'roofline_kernel': str(a['roofline'].get('kernel', '')).split(' (')[0]})
     if alts:
         line['alt_modes'] = alts
-    line['detail'] = detail_path
+    if detail_path is not None:
+        line['detail'] = detail_path
     if 'summary_tail' in out:
         line['summary_tail'] = out['summary_tail']
     return line
@@ -414,19 +422,22 @@ def parse_args(argv=None):
     ap.add_argument('--workload', choices=['S1', 'S2'], default='S2')
     ap.add_argument('--frames', type=int, default=None, help='frames per GPU per step (default 4; 16 in --mode vfe, 2 in --mode fusion)')
     ap.add_argument('--points', type=int, default=20000)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline (module docstring); a plain run only times the steps')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--convmath', choices=['fp16x3', 'bf16x6', 'bf16x3', 'f32'], default=None, help='override config.yml convmath')
-    ap.add_argument('--no-alt', action='store_true', help='skip the extra runs (other workload, bf16x3 arithmetic, the other BASELINE configs)')
+    ap.add_argument('--no-alt', action='store_true',
+                    help='with --full: skip the extra runs (other workload, bf16x3 arithmetic, the other BASELINE configs)')
     ap.add_argument('--frame-ids', default=None, help='comma-separated synthetic frame ids of THIS process (default: rank + world * j)')
     ap.add_argument('--timed-only', action='store_true',
-                    help='only warm-up + the timed steps (no alt / isolated / CPU passes): what profiles/ is made from')
+                    help='with --full: no alt / isolated / CPU passes (a plain run never makes them)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the last timed step computed (gradients, parameters after the optimizer step, voxel counts and '
                          'the mode\'s own outputs) to DIR/<name>.npy')
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
-    if args.timed_only:
+    if args.timed_only or not args.full:
         args.no_alt = args.no_cpu_baseline = True
     return args
 
@@ -440,7 +451,7 @@ def main():
     torch.cuda.set_device(dev)
     out = run(args, rank, world, dev)
     if rank == 0:
-        line = compact_line(out, write_detail(out))
+        line = compact_line(out, write_detail(out) if args.full else None)
         text = json.dumps(line)
         assert len(text) < LINE_LIMIT, 'bench line grew to %d bytes' % len(text)
         print(text)
@@ -802,7 +813,7 @@ def _run(args, rank, world, dev):
 
     # ------------------------------------------------------------------------------------------------ the timed run
     vfe_check = None
-    if args.mode == 'vfe' and rank == 0 and not args.timed_only:
+    if args.mode == 'vfe' and rank == 0 and args.full and not args.timed_only:
         # BASELINE config 2: the voxel indices of every frame of the run are checked bit-exact against the C oracle (part
         # of the CPU-baseline leg: the only place the benchmark touches oracle/)
         vfe_check = voxel_index_check(batch, args.workload, frame_ids, args.points)
@@ -812,9 +823,10 @@ def _run(args, rank, world, dev):
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, last_step_outputs(kept, nvox))
     kept = None
-    n_detail = min(args.steps, 10)
-    _, dt_detail, timers_all = timed_run(2, n_detail)     # every timer on: other_kernels, hbm_stages
-    check_status()
+    if args.full:
+        n_detail = min(args.steps, 10)
+        _, dt_detail, timers_all = timed_run(2, n_detail)     # every timer on: other_kernels, hbm_stages
+        check_status()
 
     def host_probe(n=3):
         """Host time to enqueue one step when the launch queues are empty (`n` steps from an idle GPU, no sync inside): what
@@ -830,8 +842,9 @@ def _run(args, rank, world, dev):
         d = (time.perf_counter() - t0 - full.get('read_s', 0.0)) / n * 1e3
         fence()
         return d
-    host_probe_ms = host_probe()
-    check_status()
+    if args.full:
+        host_probe_ms = host_probe()
+        check_status()
 
     alt = []
     if not args.no_alt and args.mode == 'hot':
@@ -904,7 +917,7 @@ def _run(args, rank, world, dev):
                         'voxelize, fusion sampling+MLP, VFE, reindex+CML fwd+bwd, all-reduce, AdamW; convmath=%s'
                         % (wl, RAW_POINTS, args.points, args.frames, main_math))
             roof = conv_roofline(timers, 0)
-            if not args.timed_only:
+            if args.full and not args.timed_only:
                 roof['isolated'] = isolated_conv_roofline(dev, main_math)
             # HBM bytes per launch from the PMC passes (profiles/traffic.json, written by tools/pmc_summary.py): printed only when
             # the file was measured on the SAME kernel sources and arithmetic that ran here (hash of the .hip files)
@@ -941,7 +954,7 @@ def _run(args, rank, world, dev):
         elif args.mode == 'vfe':
             workload = ('%s, %d raw pts -> %d pts, T=35, %d frames/GPU/step: crop+cropToSight+lidar2Img, voxelize, VFE stack '
                         '(SVFE + FCN + max) fwd+bwd, AdamW; voxel indices bit-exact vs the C oracle (checked in this run: %s)'
-                        % (wl, RAW_POINTS, args.points, args.frames, vfe_check))
+                        % (wl, RAW_POINTS, args.points, args.frames, vfe_check or 'no'))
             ev = timers.get('hbm:voxelize', [])
             ms = sum(s.elapsed_time(e) for s, e, _ in ev)
             tb = sum(_hip.timer_value(b) for _, _, b in ev)
@@ -974,7 +987,6 @@ def _run(args, rank, world, dev):
             'steps': args.steps,
             'warmup': args.warmup,
             'ms_per_step': dt / args.steps * 1e3,
-            'host_enqueue_ms_per_step': host_probe_ms,
             'host_in_timed_region_ms_per_step': host_ms[0],
             'library_launches_per_step': launches[0],
             'library_launches_per_frame': launches[0] / args.frames,
@@ -986,39 +998,42 @@ def _run(args, rank, world, dev):
             'config': {'workload': workload, 'mode': args.mode, 'frames_per_gpu': args.frames, 'voxels_per_frame': nvox,
                        'parallelism': 'dp%d' % world, 'frame_sets': bool(pl.BATCHED and args.mode != 'dropin')},
             'roofline': roof,
-            'hbm_stages': hbm_stages(timers_all),
-            'ms_per_step_all_timers': dt_detail / n_detail * 1e3,
-            'timers': 'value / ms_per_step / roofline: HIP events around the roofline kernel only; other_kernels / hbm_stages: a second '
-                      'pass of %d steps with events around every library call (ms_per_step_all_timers)' % n_detail,
+            'timers': 'value / ms_per_step / roofline: HIP events around the roofline kernel only',
         }
+        if args.full:
+            out.update(host_enqueue_ms_per_step=host_probe_ms, hbm_stages=hbm_stages(timers_all),
+                       ms_per_step_all_timers=dt_detail / n_detail * 1e3)
+            out['timers'] += ('; other_kernels / hbm_stages: a second pass of %d steps with events around every library call '
+                              '(ms_per_step_all_timers)' % n_detail)
         from modules import frames as _fr
         if _fr.KNOCKOUT:
             out['INVALID_diagnostic_knockout'] = sorted(_fr.KNOCKOUT)       # kernels were skipped: timing experiment, not a result
-        # the other MFMA kernels of the step, each with EXECUTED FLOPs / event time inside the timed region (they share the
-        # chip with the kernels of the other streams: side-stream weight gradients run beside main-stream convolutions)
-        other = {}
-        for name in ('conv3d_wgrad_bg', 'linear_fwd', 'linear_dgrad', 'linear_wgrad', 'rpn_conv', 'rpn_wgrad'):
-            evs = timers_all.get(name, [])
-            if evs:
-                tms = sum(s.elapsed_time(e) for s, e, _ in evs)
-                other[name] = {'launches': len(evs), 'avg_launch_ms': tms / len(evs)}
-                fl = sum(_hip.timer_value(f) for _, _, f in evs)
-                if fl > 0:
-                    # algorithmic = one multiply-add per product; in a split arithmetic the matrix pipes execute 3 (bf16x3) or 6
-                    # (bf16x6) bf16 MFMA products per algorithmic one.  The convolution kernels run split as a whole; of the row
-                    # GEMMs the wide layers (n > 64: 99 % of the FLOPs) do, the narrow ones stay on the exact-f32 kernel -- their
-                    # figure is therefore an upper bound by < 1 %
-                    split_k = main_math != 'f32'
-                    if main_math == 'bf16x3' and name == 'linear_fwd':
-                        split_k = False                      # forward rows stay exact f32 in that mode (modules/_hip.py row_split)
-                    alg = fl / (tms * 1e-3) / 1e12
-                    mult, peak = (MATH_MFMAS[main_math], BF16_MFMA_PEAK_TFLOPS) if split_k else (1.0, FP32_MFMA_PEAK_TFLOPS)
-                    other[name]['algorithmic_tflops'] = alg
-                    other[name]['executed_tflops'] = mult * alg
-                    other[name]['peak_tflops'] = peak
-                    other[name]['frac'] = other[name]['executed_tflops'] / peak
-                    other[name]['arithmetic'] = main_math if split_k else 'f32'
-        out['other_kernels'] = other
+        if args.full:
+            # the other MFMA kernels of the step, each with EXECUTED FLOPs / event time inside the timed region (they share the
+            # chip with the kernels of the other streams: side-stream weight gradients run beside main-stream convolutions)
+            other = {}
+            for name in ('conv3d_wgrad_bg', 'linear_fwd', 'linear_dgrad', 'linear_wgrad', 'rpn_conv', 'rpn_wgrad'):
+                evs = timers_all.get(name, [])
+                if evs:
+                    tms = sum(s.elapsed_time(e) for s, e, _ in evs)
+                    other[name] = {'launches': len(evs), 'avg_launch_ms': tms / len(evs)}
+                    fl = sum(_hip.timer_value(f) for _, _, f in evs)
+                    if fl > 0:
+                        # algorithmic = one multiply-add per product; in a split arithmetic the matrix pipes execute 3 (bf16x3) or 6
+                        # (bf16x6) bf16 MFMA products per algorithmic one.  The convolution kernels run split as a whole; of the row
+                        # GEMMs the wide layers (n > 64: 99 % of the FLOPs) do, the narrow ones stay on the exact-f32 kernel -- their
+                        # figure is therefore an upper bound by < 1 %
+                        split_k = main_math != 'f32'
+                        if main_math == 'bf16x3' and name == 'linear_fwd':
+                            split_k = False                      # forward rows stay exact f32 in that mode (modules/_hip.py row_split)
+                        alg = fl / (tms * 1e-3) / 1e12
+                        mult, peak = (MATH_MFMAS[main_math], BF16_MFMA_PEAK_TFLOPS) if split_k else (1.0, FP32_MFMA_PEAK_TFLOPS)
+                        other[name]['algorithmic_tflops'] = alg
+                        other[name]['executed_tflops'] = mult * alg
+                        other[name]['peak_tflops'] = peak
+                        other[name]['frac'] = other[name]['executed_tflops'] / peak
+                        other[name]['arithmetic'] = main_math if split_k else 'f32'
+            out['other_kernels'] = other
         if world > 1 and bucket.times:
             # the gradient exchange's own duration (events on its streams): 'early' = everything but the step's last weight
             # gradient, on the communication stream while that kernel still runs; 'late' = the rest (modules/parallel.py)

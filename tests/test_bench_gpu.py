@@ -12,7 +12,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
     env = dict(os.environ)
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--frames', '2',
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--steps', '2', '--warmup', '1', '--frames', '2',
                           '--points', '4000', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith('{')]
@@ -37,14 +37,40 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_the_steps_and_nothing_else(tmp_path):
+    """Without --full a run warms up, times its steps and prints the line: the contract's fields and the roofline of its own timed
+    steps, but no alternative modes, CPU baseline, second timer pass, host probe, isolated roofline or detail file."""
+    detail = tmp_path / 'detail.json'
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '2', '--warmup', '1', '--frames', '2', '--points',
+                          '4000'], capture_output=True, text=True, timeout=600, cwd=REPO,
+                         env=dict(os.environ, MVX_BENCH_DETAIL=str(detail)))
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
+              'dtype', 'data', 'config', 'roofline'):
+        assert k in d, k
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['higher_is_better'] is True
+    assert abs(d['value'] - 2 * 1e3 / d['ms_per_step']) < 1e-6 * d['value']
+    r = d['roofline']
+    assert r['bound'] == 'mfma' and 0 < r['frac'] < 1 and r['launches'] > 0 and 'isolated_frac' not in r
+    for k in ('alt_modes', 'cpu_baseline', 'other_kernels', 'hbm_stages_frac_of_8TBps', 'host_enqueue_ms_per_step',
+              'ms_per_step_all_timers', 'detail'):
+        assert k not in d, k
+    assert not detail.exists()
+
+
+@pytest.mark.gpu
 def test_default_invocation_prints_a_short_parsable_line_in_the_reference_arithmetic():
-    """`python bench.py` exactly as the driver runs it (the r04 line was 27 KB and the driver could not parse it).  The
-    line is < 12 KB, one JSON object, carries roofline + cpu_baseline, its headline arithmetic is operand-exact (bf16x6 or exact f32,
+    """`python bench.py --full`, every other argument at its default (the r04 line was 27 KB and the driver could not
+    parse it).  The line is < 12 KB, one JSON object, with roofline + cpu_baseline; its headline arithmetic is operand-exact (bf16x6 or f32,
     /root/reference/config.yml:2 `half: False`) with fp16x3 as the first alternative, and every alternative mode was timed over >= 20
     steps."""
     env = dict(os.environ)
     env.pop('MVX_CONVMATH', None)
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py')], capture_output=True, text=True, timeout=1500, env=env, cwd=REPO)
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full'], capture_output=True, text=True, timeout=1500, env=env,
+                         cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -64,8 +90,8 @@ def test_default_invocation_prints_a_short_parsable_line_in_the_reference_arithm
 
 @pytest.mark.gpu
 def test_bench_vfe_mode_checks_voxel_indices_against_the_oracle():
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--mode', 'vfe', '--steps', '2', '--warmup', '1', '--frames',
-                          '3', '--points', '4000'], capture_output=True, text=True, timeout=600, cwd=REPO)
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--mode', 'vfe', '--steps', '2', '--warmup', '1',
+                          '--frames', '3', '--points', '4000'], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith('{')][0])
     assert d['roofline']['bound'] == 'hbm' and d['value'] > 0
@@ -75,8 +101,8 @@ def test_bench_vfe_mode_checks_voxel_indices_against_the_oracle():
 @pytest.mark.gpu
 def test_bench_full_mode_runs_the_whole_model_and_reports_losses():
     """--mode full (BASELINE config 3): classifyAnchors + frame sets + HIP RPN + VoxelLoss + whole backward inside the step."""
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--mode', 'full', '--steps', '3', '--warmup', '1', '--frames',
-                          '2', '--points', '4000', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=REPO)
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--mode', 'full', '--steps', '3', '--warmup', '1',
+                          '--frames', '2', '--points', '4000', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith('{')][0])
     assert d['config']['mode'] == 'full' and d['value'] > 0 and 'rpn_conv' in d['other_kernels']
@@ -123,8 +149,8 @@ def test_bench_two_ranks_share_the_frames_and_print_one_line():
 @pytest.mark.gpu
 def test_bench_fusion_mode_runs_config_4():
     """--mode fusion (BASELINE config 4): FPN feature sampling + fusion MLP + VFE, 2 frames per step, HBM roofline of the sampler."""
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--mode', 'fusion', '--steps', '2', '--warmup', '1', '--points',
-                          '4000', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=REPO)
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--mode', 'fusion', '--steps', '2', '--warmup', '1',
+                          '--points', '4000', '--no-cpu-baseline'], capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith('{')][0])
     assert d['config']['mode'] == 'fusion' and d['config']['frames_per_gpu'] == 2 and d['value'] > 0

@@ -16,6 +16,15 @@ def test_steps_must_be_positive():
         bench.parse_args(['--warmup', '-1'])
 
 
+def test_only_full_makes_the_extra_runs():
+    plain = bench.parse_args([])
+    assert not plain.full and plain.no_alt and plain.no_cpu_baseline
+    full = bench.parse_args(['--full'])
+    assert full.full and not full.no_alt and not full.no_cpu_baseline
+    assert bench.parse_args(['--full', '--timed-only']).no_alt
+    assert bench.parse_args(['--full', '--no-cpu-baseline']).no_cpu_baseline
+
+
 def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_large_ones(tmp_path, monkeypatch):
     monkeypatch.setattr(bench, 'DUMP_SAMPLE', 1000)
     big = torch.arange(6000, dtype=torch.float32).reshape(2, 3000)

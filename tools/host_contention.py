@@ -1,4 +1,4 @@
-"""Host cost of the training step when several ranks share one host: N concurrent `bench.py --timed-only` processes (each
+"""Host cost of the training step when several ranks share one host: N concurrent `bench.py --full --timed-only` processes (each
 a fresh process, as torchrun would start them) on the one leased GPU.  The GPU is shared N ways, so ms_per_step is
 meaningless here; what is measured is the per-process host time to enqueue a step (bench.py's host probe) under
 contention for the host's threads.  At most 6 processes may use the GPU at once on this pool.  Developer tool."""
@@ -23,7 +23,7 @@ def pin(k):
 
 
 t0 = time.time()
-procs = [subprocess.Popen([sys.executable, os.path.join(REPO, 'bench.py'), '--timed-only', '--steps', '12', '--warmup', '4', '--mode', mode,
+procs = [subprocess.Popen([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--timed-only', '--steps', '12', '--warmup', '4', '--mode', mode,
                            '--points', str(points)], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, cwd=REPO, preexec_fn=pin(k),
                           env=dict(os.environ, MVX_CPU_THREADS=str(threads_per_proc or 64), OMP_NUM_THREADS=str(threads_per_proc or 16)))
          for k in range(n)]
