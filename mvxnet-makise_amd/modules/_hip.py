@@ -202,16 +202,11 @@ _SIDE = {}
 def side_stream(device):
     st = _SIDE.get(device.index)
     if st is None:
-        st = torch.cuda.Stream(device=device, priority=int(os.environ.get('MVX_SIDE_PRIORITY', '0')))
+        st = torch.cuda.Stream(device=device, priority=0)
         _SIDE[device.index] = st
     return st
 
 
-if os.environ.get('MVX_SPLIT16_MIN_UNITS'):        # developer knob: launch-shape threshold of the split gather (csrc/conv3d_split.hip)
-    X.check(X.lib.mvx_tuning_set(1, int(os.environ['MVX_SPLIT16_MIN_UNITS'])), 'mvx_tuning_set')
-if os.environ.get('MVX_K128'):                     # developer knob (A/B runs): 0 = 128-deep row layers on linear_fwd_split again
-    X.check(X.lib.mvx_tuning_set(3, int(os.environ['MVX_K128'])), 'mvx_tuning_set')
-SIDE_KEEP = os.environ.get('MVX_SIDE_KEEP', '1') != '0'
 _KEEP = {}          # device index -> tensors read by side-stream kernels since the last join
 _COMM = {}
 _TAIL = {}          # device index -> [event on the side stream before the step's last weight gradient, event at the end of the main stream's backward]
@@ -271,7 +266,7 @@ def join_side_stream(device=None):
 
 class _SideStream:
     """Run the enclosed launches on the side stream, ordered after everything already enqueued on the
-    current stream; the tensors they read are kept alive for the side stream (record_stream)."""
+    current stream; the tensors they read are kept alive until the owning stream joins the side stream."""
 
     def __init__(self, *tensors):
         self.tensors = [t for t in tensors if t is not None]
@@ -282,15 +277,11 @@ class _SideStream:
         dev = self.tensors[0].device
         self.side = side_stream(dev)
         self.side.wait_stream(torch.cuda.current_stream(dev))
-        if SIDE_KEEP:
-            # keep the tensors alive until the owning stream has JOINED the side stream (join_side_stream drops the list after
-            # its wait): their blocks then return to the owning stream's pool in stream order.  record_stream instead parks a
-            # block until an event of the side stream has been seen to complete, which is timing dependent: the hot loop held
-            # 40 GB reserved for 8 GB allocated and its peak crept 6.6 % over 1,500 identical steps (profiles/r03_soak.txt)
-            _KEEP.setdefault(dev.index, []).extend(self.tensors)
-        else:
-            for t in self.tensors:
-                t.record_stream(self.side)
+        # keep the tensors alive until the owning stream has JOINED the side stream (join_side_stream drops the list after
+        # its wait): their blocks then return to the owning stream's pool in stream order.  record_stream instead parks a
+        # block until an event of the side stream has been seen to complete, which is timing dependent: the hot loop held
+        # 40 GB reserved for 8 GB allocated and its peak crept 6.6 % over 1,500 identical steps (profiles/r03_soak.txt)
+        _KEEP.setdefault(dev.index, []).extend(self.tensors)
         self.ctx = torch.cuda.stream(self.side)
         self.ctx.__enter__()
         return self
@@ -966,9 +957,7 @@ def _work_counter(device):
     return torch.zeros((1,), dtype=torch.float64, device=device)
 
 
-ROW_SPLIT = tuple(k for k in os.environ.get('MVX_ROW_SPLIT', 'dgrad,wgrad,rpn').split(',') if k)
-# ... and under convmath: bf16x6 (fp32-grade arithmetic: every wide row GEMM may use it)
-ROW_SPLIT6 = tuple(k for k in os.environ.get('MVX_ROW_SPLIT6', 'fusion,vfe,conv1,rpn,dgrad,wgrad').split(',') if k)
+ROW_SPLIT = ('dgrad', 'wgrad', 'rpn')
 
 
 def row_split(tag):
@@ -980,7 +969,7 @@ def row_split(tag):
     Default: the input and weight gradients and the RPN's forward GEMMs only.  A forward layer in split arithmetic carries ~5e-6 relative
     error (exact-f32 MFMA: ~8e-7) and the BatchNorm chain behind the FIRST layers of the network amplifies it 5-7x on the
     way to the BEV map.  Measured on one full-size frame against the float64 oracle and on bench.py --convmath bf16x3
-    (tools/split_accuracy.py, tools/split_speed.sh -> profiles/r03_split_accuracy.json, r03_split_speed.txt):
+    (tools/split_accuracy.py -> profiles/r03_split_accuracy.json; profiles/r03_split_speed.txt):
 
         forward rows in bf16x3          BEV map   cls logits  hot frames/s  full frames/s   (input gradients split, weight gradients f32)
         none (convolutions only)        7.6e-6    1.36e-4     443           200
@@ -992,17 +981,16 @@ def row_split(tag):
         fusion,vfe,conv1,rpn            4.8e-5    6.3e-4      472           208
 
     i.e. the 768 -> 768 layer, the only one whose speed matters (81 % of the row-GEMM flops of a step, +5 % frames/s), is
-    also the one that costs a factor 3-4 in accuracy of every later map: it stays on the exact-f32 kernel unless
-    MVX_ROW_SPLIT asks otherwise.  The weight-gradient GEMMs ('wgrad', linear_wgrad_split: 0.955 -> 0.517 ms for the
+    also the one that costs a factor 3-4 in accuracy of every later map: it stays on the exact-f32 kernel.  The weight-gradient GEMMs ('wgrad', linear_wgrad_split: 0.955 -> 0.517 ms for the
     768 x 768 layer over 80 k rows) touch no forward map and are split by default: hot 443 -> 470, full 200 -> 210 frames/s.
 
     Returns the number of bf16 pieces (0 = exact-f32 kernel, 2 = bf16x3, 3 = bf16x6).  Under ``convmath: bf16x6`` the split is
-    fp32-grade (three pieces = the whole f32 mantissa), so every tag of ROW_SPLIT6 -- by default all of them -- uses it."""
+    fp32-grade (three pieces = the whole f32 mantissa), so every tag uses it."""
     np_ = split_pieces()
     if np_ == 2:
         return 2 if any(tag.startswith(k) for k in ROW_SPLIT) else 0
     if np_ in (3, 4):
-        return np_ if any(tag.startswith(k) for k in ROW_SPLIT6) else 0
+        return np_
     return 0
 
 
@@ -1044,26 +1032,18 @@ def padded_weight(w2, k):
 # Row GEMMs on pre-cut operands (csrc/rowgemm_pre.hip): the operands are PLANES of 16-bit pieces, int16 (pieces, rows, k),
 # written by their producers; the GEMM moves them global -> LDS by DMA.  Used for the wide layers whose shape fills its
 # 256 x 256 tiles (n a multiple of 256: the 768 -> 768 fusion layer, 70 % of the row-GEMM work of a step) in the bf16x6
-# arithmetic; every other call keeps the in-kernel-cut kernels.  MVX_PRECUT=0 switches it off (A/B runs).
-# ---------------------------------------------------------------------------------------------
-PRECUT = os.environ.get('MVX_PRECUT', '1') != '0'
+# arithmetic; every other call keeps the in-kernel-cut kernels.
 # The FORWARD on pre-cut operands: its products and their accumulation order are those of linear_fwd_split (y is bit-identical)
 # and its BatchNorm sums are formed term by term in f64 from an LDS copy of the tile (csrc/rowgemm_pre.hip), equal to that
 # kernel's to f64 rounding -- the four-term f32 partial sums of its first form (1e-9 off: enough to move a mean by an ulp between
-# executors that tile the rows differently) are gone, and with them the reason it was opt-in.  MVX_PRECUT_FWD=0: linear_fwd_split.
-PRECUT_FWD = os.environ.get('MVX_PRECUT_FWD', '1') != '0'
-# Row ranges in which the step's last BatchNorm backward + weight gradient are enqueued (frames.rows_backward): the product of
-# range p runs on the side stream beside the apply pass of range p + 1.  1 = one pass, one product: the default, because the
-# ranges measured SLOWER (same box, bf16x6, 40 steps: 463.7 / 463.1 frames/s in one part, 460.7 / 460.9 in two, 455.4 / 455.3 in
-# four): the main queue's idle end of the step is not an idle chip, the HBM-bound apply pass and the MFMA-bound product slow each
-# other down by more than the overlap hides.
-TAIL_PARTS = max(1, int(os.environ.get('MVX_TAIL_PARTS', '1')))
+# executors that tile the rows differently) are gone, and with them the reason it was opt-in.
+# ---------------------------------------------------------------------------------------------
 # MVX_FLAG_PRE_XCD_STRIPS of mvx_linear_wgrad_pre: every block of a row strip on the same XCD (developer knob, A/B runs)
 PRE_XCD_STRIPS = 4096 if os.environ.get('MVX_PRE_XCD', '0') != '0' else 0
 
 
 def precut_ok(split, rows, K, N):
-    return bool(PRECUT and split and int(split) == 3 and N % 256 == 0 and K % 16 == 0 and rows >= 2048 and
+    return bool(split and int(split) == 3 and N % 256 == 0 and K % 16 == 0 and rows >= 2048 and
                 3 * rows * max(K, N) * 2 < (1 << 32))
 
 

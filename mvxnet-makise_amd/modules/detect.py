@@ -92,22 +92,11 @@ def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw)
     from modules import rpn_frames as rf
     opts = dict(DEFAULTS, **kw)
     dev = batch.device
-    ev_ready = None
-    if ready is None:
-        ready = pl.prepare_frame_set(batch)
-    elif len(ready) == 5:
-        ready, ev_ready = ready[:4], ready[4]
-    fs, live, counts, status = ready
-    if ev_ready is not None:
-        main = torch.cuda.current_stream(dev)
-        main.wait_event(ev_ready)
-        status.record_stream(main)
-        if fs is not None:
-            fs.hand_over(main, fenced=pl.PREP_FENCE)
+    fs, live, counts, status = pl._take_ready(batch, ready, torch.cuda.current_stream(dev))
     hw = [float(imsize[0]), float(imsize[1])]
     statuses = [status]
     dets = None
-    try:
+    with pl._step_scope(dev, train=False):
         if fs is not None:
             model.prepack()
             _hip.arena_begin(dev, doubles=1 << 22)
@@ -119,12 +108,7 @@ def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw)
                 dets = postprocess(heads, anchors, F, rs['h1'], rs['w1'], read=False, **opts)
             if keep is not None:
                 keep.update(heads=heads, geom=(F, rs['h1'], rs['w1']))
-    finally:
-        _hip.arena_end()
-        pl._fence_record(dev)
-    bad = int(torch.stack([s.reshape(()) for s in statuses]).max())
-    if bad:
-        raise X.MvxHipError('a kernel reported a data-dependent error (status %d)' % bad)
+    pl._check_statuses(statuses)
     out = [_empty(dev) for _ in range(batch.n_frames)]
     if dets is not None:
         for f, d in zip(live, unpack(dets)):

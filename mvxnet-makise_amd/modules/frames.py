@@ -103,12 +103,7 @@ def _stats(F, C, dev):
     return buf, fz
 
 
-SAMPLE_PLANES = os.environ.get('MVX_SAMPLE_PLANES', '1') != '0'   # the FPN sampler writes the operand planes of its rows itself (A/B: 0)
-TAPS_ON_SIDE = os.environ.get('MVX_TAPS_ON_SIDE', '1') != '0'   # the layers' tap sums in front of their weight gradient on the side stream (A/B: 0)
-ROW_PITCH4 = os.environ.get('MVX_ROW_PITCH4', '1') != '0'   # the VFE input rows with a pitch that is a multiple of 4 floats (A/B: 0)
-BG_READ_SET = os.environ.get('MVX_BG_READ_SET', '1') != '0'   # background tiles of x1 / x2 that the next layer does not read stay unwritten (A/B: 0)
-BEV_FUSED = os.environ.get('MVX_BEV_FUSED', '1') != '0'   # conv3's BatchNorm apply writes the (F, C * D, H, W) map itself (A/B: 0)
-TAP_SKIP = os.environ.get('MVX_TAP_SKIP', '1') != '0'     # conv2 / conv3 forward: skip depth taps with a background-only source halo
+BEV_FUSED = True      # conv3's BatchNorm apply writes the (F, C * D, H, W) map itself (tests set False to compare)
 # DIAGNOSTIC ONLY (tools/knockout.sh): comma-separated kernel classes that are NOT launched, to measure what each class costs
 # on the critical path of a step (step time with the class removed).  Results are garbage; bench.py marks such a run invalid.
 KNOCKOUT = frozenset(k for k in os.environ.get('MVX_KNOCKOUT', '').split(',') if k)
@@ -130,7 +125,7 @@ def linear_bn(x, w, b, fs, kind, row_w, eps, tag='fusion', foreign=False):
         return y, mi
     sp, xfl = _hip.row_split(tag), 0                     # convmath bf16x3 / bf16x6 / fp16x3: the wide layers on the split-MFMA row GEMM
     xp = getattr(x, '_mvx_planes', None)                 # the producer of x wrote it as planes of bf16 pieces too (sample_rows)
-    if xp is not None and _hip.PRECUT_FWD and _hip.precut_ok(sp, Rr, K, N):
+    if xp is not None and _hip.precut_ok(sp, Rr, K, N):
         # the row GEMM on pre-cut operands (csrc/rowgemm_pre.hip): same products, same accumulation order -- bit-identical y
         _hip.linear_forward_pre(xp, _hip.weight_planes(w2, sp), b, y, stats, row_w, _hip.FLAG_RELU | fz | _hip.split_flags(sp, True),
                                 counter, eps, mi, fs.desc, kind)
@@ -280,22 +275,22 @@ def sample_rows(head, fs, fpn_levels, imsize):
     # fp16x3: the image features come from outside this library -- their range (max |value|) is formed by the sampler while it
     # writes them, so that the first fusion layer can scale them (forward: the coarse scale, _hip.foreign_split)
     amax = torch.zeros((1,), dtype=torch.float32, device=dev) if _hip.split_pieces() == 4 else None
-    # the first fusion layer's weight gradient (and, opt-in, the layer itself) reads its input as planes of bf16 pieces
+    # the first fusion layer and its weight gradient read their input as planes of bf16 pieces
     # (csrc/rowgemm_pre.hip): the sampler writes them beside the f32 rows while the values are in registers
     w0 = head.fusion._layers()[0][0]
     planes = None
     want_planes = _hip.precut_ok(_hip.split_pieces(), Rt + F, L * C, w0.shape[0]) and _hip.split_pieces() == 3
-    if want_planes and SAMPLE_PLANES:
+    if want_planes:
         planes = torch.empty((3, Rt + F, L * C), dtype=torch.int16, device=dev)
         planes[:, Rt:].zero_()
     with _hip._timed_bytes('feature_sample', Rt * L * C * 4 * 5 + Rt * 9 * 4 + (Rt * L * C * 6 if planes is not None else 0)):
       if 'sample' not in KNOCKOUT:
         if planes is not None:
-            # with the first fusion layer on planes too (_hip.PRECUT_FWD) nobody reads the f32 rows: they are not written (245 MB per
+            # with the first fusion layer on planes too nobody reads the f32 rows: they are not written (245 MB per
             # 4-frame step); `compact` stays as the rows' handle (shape, planes, range tag).  MVX_POISON_BG=1 (tests) fills it with
             # NaN instead, which any read would carry into the results
             K0, N0 = L * C, w0.shape[0]
-            planes_only = bool(_hip.PRECUT_FWD and not KNOCKOUT and
+            planes_only = bool(not KNOCKOUT and
                                _hip.precut_ok(_hip.row_split('fusion_%dx%d' % (N0, K0)), Rt + F, K0, N0) and
                                _hip.precut_ok(_hip.row_split('wgrad'), Rt + F, K0, N0))       # both readers take the planes
             if planes_only and os.environ.get('MVX_POISON_BG'):
@@ -313,8 +308,6 @@ def sample_rows(head, fs, fpn_levels, imsize):
     _hip.tag_amax(compact, amax)
     if planes is not None:
         compact._mvx_planes = planes
-    elif want_planes:
-        compact._mvx_planes = _hip.split_rows(compact, 3)           # the two-pass form (MVX_SAMPLE_PLANES=0)
     return compact, status
 
 
@@ -360,7 +353,7 @@ def _vfe_forward(bb, fs, x, S, eps):
     # rows of 7 + Fc = 23 floats are written with a pitch of 24 (one zero column): the first VFE layer and its weight gradient then
     # read them with 16-byte loads (k = 24 against a weight padded with a zero column: the same sums) instead of falling to the
     # scalar-load forms of their kernels (config 2: 106 / 170 us for 11 / 50 MB)
-    ldr = (7 + Fc + 3) & ~3 if ROW_PITCH4 else 7 + Fc
+    ldr = (7 + Fc + 3) & ~3
     rows23 = torch.empty((Rt + Vt, ldr), dtype=torch.float32, device=dev)
     X.check(X.lib.mvx_vfe_compact_input_pitch_frames(X.ptr(fs.vox2d), fs.vox2d.shape[1], X.ptr(fs.rows_sel), X.ptr(x), Fc, Rt, Vt,
                                                      X.ptr(rows23), ldr, fs.desc.ref(), X.stream()), 'mvx_vfe_compact_input_pitch_frames')
@@ -499,8 +492,6 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
         (grid_activity): the background tiles outside that set are not written (MVX_POISON_BG=1, tests: they hold NaN)."""
         if 'bn_apply_cml' in KNOCKOUT:
             return y
-        if read is not None and not BG_READ_SET:
-            read = None
         out = torch.full_like(y, float('nan')) if (read is not None and os.environ.get('MVX_POISON_BG')) else torch.empty_like(y)
         Cn = y.shape[-1]
         # algorithmic bytes (timing runs only): flagged tiles are read and written, the others only written
@@ -535,7 +526,7 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
         dout = _hip.conv_out_depth(din, sd, pd)
         wpk = m._packer(False, split)
         # background constants of this layer: [planes][co] totals, followed by the per-depth-tap ones the exact-f32 gather
-        # uses to skip the depth taps whose source halo holds no active site (TAP_SKIP)
+        # uses to skip the depth taps whose source halo holds no active site (FLAG_BG_TAPS)
         bg_all = torch.empty((F * dout * 13, co), dtype=torch.float32, device=dev)      # totals | 3 depth taps | 9 border classes
         bg_pre = bg_all[:F * dout]
         X.check(X.lib.mvx_conv3d_background_taps_frames(X.ptr(w), X.ptr(c_in), din, dout, ci, co, sd, pd, X.ptr(bg_all), F,
@@ -556,7 +547,7 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
             with _hip._Timed('conv3d_gather_bg', F * _hip.conv_flops(dout, din, H, W, ci, co, sd, pd) if _hip.KERNEL_TIMERS is not None else 0):
                 X.check(X.lib.mvx_conv3d_forward_bg_split_frames(X.ptr(x_in), X.ptr(wpk), X.ptr(b), X.ptr(y), X.ptr(stats), din, dout,
                                                                  H, W, ci, co, sd, pd,
-                                                                 _hip.FLAG_RELU | fz | (_hip.FLAG_BG_TAPS if TAP_SKIP else 0) | _hip.split_flags(split),
+                                                                 _hip.FLAG_RELU | fz | _hip.FLAG_BG_TAPS | _hip.split_flags(split),
                                                                  X.ptr(hflag_in), X.ptr(mask_o), X.ptr(bg_pre), 1, X.ptr(counter), F,
                                                                  X.stream()),
                         'mvx_conv3d_forward_bg_split_frames')
@@ -565,7 +556,7 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
         elif 'gather_fwd' not in KNOCKOUT:
           with _hip._Timed('conv3d_gather_bg', F * _hip.conv_flops(dout, din, H, W, ci, co, sd, pd) if _hip.KERNEL_TIMERS is not None else 0):
             X.check(X.lib.mvx_conv3d_forward_bg_frames(X.ptr(x_in), X.ptr(wpk), X.ptr(b), X.ptr(y), X.ptr(stats), din, dout, H, W,
-                                                       ci, co, sd, pd, _hip.FLAG_RELU | fz | (_hip.FLAG_BG_TAPS if TAP_SKIP else 0),
+                                                       ci, co, sd, pd, _hip.FLAG_RELU | fz | _hip.FLAG_BG_TAPS,
                                                        X.ptr(hflag_in), X.ptr(mask_o),
                                                        X.ptr(bg_pre), 1, X.ptr(counter), X.ptr(fin), float(dout * H * W),
                                                        float(eps), X.ptr(mi), X.ptr(_hip._work_counter(dev)), F, X.stream()),
@@ -701,7 +692,7 @@ def cml_backward(model, S, grad_mid, g_cl=None):
         """The tap sums of a layer on the SIDE stream, in front of their first reader (the layer's weight gradient); returns
         (T, event): the main stream goes straight from the BatchNorm backward to the input-gradient gather and waits for the
         event only in front of input_grad_sums.  (T, None): computed inline."""
-        if not (TAPS_ON_SIDE and _hip.ASYNC_WGRAD) or 'tap_sums' in KNOCKOUT:
+        if not _hip.ASYNC_WGRAD or 'tap_sums' in KNOCKOUT:
             return _mut(name, tap_sums(dz, planes, Cn, tile_flags, inactive)), None
         main = torch.cuda.current_stream(dev)
         with _hip._SideStream(dz, tile_flags, inactive):
@@ -792,7 +783,7 @@ def cml_backward(model, S, grad_mid, g_cl=None):
     _hip.tag_amax(G, _hip.amax_of(dz1))                                    # G's rows are rows of dz1
     # conv1's weight gradient ((27 * cout, cin) = G^T feat, then reordered into the parameter's layout): off the main stream like
     # the other weight gradients -- the main stream goes on to the input gradient
-    with (_hip._SideStream(c1['feat'], G) if TAPS_ON_SIDE else _hip._Inline()):
+    with _hip._SideStream(c1['feat'], G):
         dw_all = _hip.linear_wgrad(c1['feat'], G)
     with _hip._SideStream(dw_all):
         _grad_of(w1).add_(dw_all.reshape(3, 3, 3, cout, cin).permute(3, 4, 0, 1, 2))
@@ -856,14 +847,11 @@ def rows_backward(model, S, dfeat):
         if i == 0 and xp is not None and _hip.precut_ok(_hip.row_split('wgrad'), x.shape[0], x.shape[1], w.shape[0]):
             # the step's last and largest weight gradient on pre-cut operands: the BatchNorm backward writes dz as planes (no other
             # reader: the sampled features carry no gradient), the weight gradient moves both operands by DMA (rowgemm_pre.hip)
-            # ... and in TAIL_PARTS row ranges: the weight gradient of a range runs on the side stream beside the apply pass of
-            # the next one, so that what is left after the main stream's last kernel is the last range's product only
-            first = True
-            for dzp, lo, hi in bn_relu_backward_planes_parts(gx, y, mi, fs, X.ROWS_FUSION, fs.fusion_row_w, _grad_of(b),
-                                                             _hip.TAIL_PARTS):
-                if first:
-                    _hip.mark_tail(dev)
-                    first = False
+            # in ONE row range: more ranges, each weight gradient on the side stream beside the apply pass of the next range, measured
+            # slower (463.7 / 463.1 frames/s in one part, 460.7 / 460.9 in two, 455.4 / 455.3 in four; bf16x6, 40 steps): the
+            # HBM-bound apply pass and the MFMA-bound product slow each other down by more than the overlap hides
+            for dzp, lo, hi in bn_relu_backward_planes_parts(gx, y, mi, fs, X.ROWS_FUSION, fs.fusion_row_w, _grad_of(b), 1):
+                _hip.mark_tail(dev)
                 if 'lin_wgrad' not in KNOCKOUT:
                     _hip.linear_wgrad_pre(xp, dzp, accumulate_into=_grad_of(w).view(w.shape[0], -1), rows=(lo, hi))
             break

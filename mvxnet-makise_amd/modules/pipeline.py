@@ -5,6 +5,9 @@ This reproduces the per-frame call sequence of the reference's training loop (tr
 CPU preprocessing, :113-131 forward, :161 backward) for a batch of independent frames: the
 reference is strictly batch-1 (config.yml:18), so a batch of B frames is B forwards with
 per-frame BatchNorm statistics and summed gradients."""
+import contextlib
+import os as _os
+
 import torch
 
 import modules.config as cfg
@@ -12,19 +15,17 @@ from modules import _hip
 from modules import tape
 
 
-import os as _os
-ASYNC_WGRAD = _os.environ.get('MVX_ASYNC_WGRAD', '1') != '0'    # weight-gradient kernels on a second stream (see modules/_hip.py)
-LANES = int(_os.environ.get('MVX_LANES', '2'))   # frames in flight: frame f runs on lane stream f % LANES (needs ASYNC_WGRAD for the
-                        # single-writer gradient accumulation); 1 = all frames on the caller's stream
-TAPE = _os.environ.get('MVX_TAPE', '1') != '0'     # frames run through modules/tape.py (no autograd engine); 0 = autograd
-LANE_PRIORITY = int(_os.environ.get('MVX_LANE_PRIORITY', '0'))      # -1 = above the side (weight-gradient) stream
+ASYNC_WGRAD = True      # weight-gradient kernels on a second stream (see modules/_hip.py)
+LANES = 2               # frames in flight: frame f runs on lane stream f % LANES (needs ASYNC_WGRAD for the single-writer
+                        # gradient accumulation); 1 = all frames on the caller's stream
+TAPE = True             # frames run through modules/tape.py (no autograd engine); False = autograd
 _LANE_STREAMS = {}
 
 
 def lane_streams(device, n):
     key = device.index
     if key not in _LANE_STREAMS or len(_LANE_STREAMS[key]) < n:
-        _LANE_STREAMS[key] = [torch.cuda.Stream(device=device, priority=LANE_PRIORITY) for _ in range(n)]
+        _LANE_STREAMS[key] = [torch.cuda.Stream(device=device, priority=0) for _ in range(n)]
     return _LANE_STREAMS[key][:n]
 
 
@@ -137,7 +138,7 @@ def _prep_stream(device):
     if device.index not in _PREP_STREAMS:
         # high priority: the few small preparation kernels should not queue behind the step's long ones (the host
         # waits for their two results)
-        _PREP_STREAMS[device.index] = torch.cuda.Stream(device=device, priority=int(_os.environ.get('MVX_PREP_PRIORITY', '-1')))
+        _PREP_STREAMS[device.index] = torch.cuda.Stream(device=device, priority=-1)
     return _PREP_STREAMS[device.index]
 
 
@@ -145,22 +146,87 @@ def _prep_stream(device):
 # function records an event on the training stream once everything that reads the prepared tensors is enqueued (after it joined
 # the side stream), the tensors stay referenced until the step function returns, and every preparation first waits for the
 # latest fence -- so a block of the preparation stream's pool is never rewritten before its last reader has run, without
-# `record_stream`.  MVX_PREP_FENCE=0: the record_stream hand-over of rounds 2-4.
-PREP_FENCE = _os.environ.get('MVX_PREP_FENCE', '1') != '0'
+# `record_stream`.
 _FENCE = {}
 
 
 def _fence_record(device):
-    if PREP_FENCE and PREP_STREAM:
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(device))
-        _FENCE[device.index] = ev
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(device))
+    _FENCE[device.index] = ev
 
 
 def _fence_wait(prep, device):
     ev = _FENCE.get(device.index)
-    if PREP_FENCE and ev is not None:
+    if ev is not None:
         prep.wait_event(ev)
+
+
+def _prepare_next(dev, nxt, make):
+    """Enqueue the preparation of the next batch ``nxt`` on the preparation stream, after its creation and the latest fence:
+    ``make()`` runs with that stream current.  Returns make()'s tuple with the event its consumer waits for appended."""
+    prep = _prep_stream(dev)
+    _wait_created(prep, nxt)
+    _fence_wait(prep, dev)
+    with torch.cuda.stream(prep):
+        out = make()
+        ev = torch.cuda.Event()
+        ev.record(prep)
+    return out + (ev,)
+
+
+def _wait_ready(ready, main):
+    """``ready`` as a step function takes it: a preparation result, or one of _prepare_next with its event appended, which
+    ``main`` then waits for.  Returns (the preparation result, the event or None)."""
+    if len(ready) != 5:
+        return ready, None
+    ready, ev = ready[:4], ready[4]
+    main.wait_event(ev)
+    ready[3].record_stream(main)                    # the status word
+    return ready, ev
+
+
+def _take_ready(batch, ready, main, also=()):
+    """(frame set, live frame ids, voxel counts, status) of a step: prepared here when ``ready`` is None, else taken over from
+    the preparation stream (_wait_ready) -- the set fenced (FrameSet.hand_over), the tensors of ``also`` by record_stream."""
+    if ready is None:
+        return prepare_frame_set(batch)
+    ready, ev = _wait_ready(ready, main)
+    if ev is not None:
+        if ready[0] is not None:
+            ready[0].hand_over(main, fenced=True)
+        for t in also:
+            t.record_stream(main)
+    return ready
+
+
+@contextlib.contextmanager
+def _step_scope(dev, async_wgrad=None, train=True, fence=True):
+    """Global state of one step function.  ``train``: gradients go straight into .grad (_hip.GRAD_SINK) and the side stream is
+    joined at the end; ``async_wgrad``: the value of _hip.ASYNC_WGRAD in the step (None: left alone).  On exit the two are
+    restored, the arena is released and, with ``fence``, the end-of-step fence is recorded."""
+    old_sink, old_async = _hip.GRAD_SINK, _hip.ASYNC_WGRAD
+    if train:
+        _hip.GRAD_SINK = True
+    if async_wgrad is not None:
+        _hip.ASYNC_WGRAD = async_wgrad
+    try:
+        yield
+    finally:
+        _hip.GRAD_SINK = old_sink
+        _hip.ASYNC_WGRAD = old_async
+        _hip.arena_end()
+        if train:
+            _hip.join_side_stream()          # the gradients are complete for whoever comes next on this stream
+        if fence:
+            _fence_record(dev)
+
+
+def _check_statuses(statuses):
+    """One host read of the step's device status words; raises on any data-dependent error a kernel reported."""
+    bad = int(torch.stack([s.reshape(()) for s in statuses]).max())
+    if bad:
+        raise _hip.X.MvxHipError('a kernel reported a data-dependent error (status %d)' % bad)
 
 
 _PINNED = {}
@@ -311,16 +377,19 @@ def train_step_frames(model, batch, grad_mid, imsize, ready=None, prepare_next=N
 
 # ---- frame sets: every layer ONCE for all frames of the step (modules/frames.py) --------------------------------------
 BATCHED = _os.environ.get('MVX_FRAME_SETS', '1') != '0'
-
-
-PREGRID = _os.environ.get('MVX_PREGRID', '1') != '0'          # ... and the coordinate-only bookkeeping of the CML (frames.grid_activity)
+# Facts of the execution mode, not switches: a batch handed to a step as ``prepare_next`` is always prepared on the preparation
+# stream (_prepare_next), and the frame-set steps always sample its FPN features there too.  Tests assert them to pin the
+# benchmarked mode.
+PREP_STREAM = True
+PRESAMPLE = True
 
 
 def prepare_frame_set(batch, T=None, sample=None, grid=None):
     """Voxelize the batch and build the frame set (voxels of all non-empty frames back to back + compact-row maps) with TWO
     host reads: the voxel counts, then the real-row offsets.  Returns (frame set or None, frame ids in it, voxel counts of
     every frame of the batch, status word).  ``sample`` = (fusion head, imsize): also sample the FPN features of the real
-    rows here (frames.sample_rows) -- input preparation like the rest, no parameter involved."""
+    rows here (frames.sample_rows) -- input preparation like the rest, no parameter involved.  ``grid`` = the model: also the
+    coordinate-only bookkeeping of the CML (frames.grid_activity).  A step prepared ahead (_prepare_next) passes both."""
     from modules import frames as fr
     T = cfg.samplenum if T is None else T
     points6, n_points = batch.prepared()
@@ -346,18 +415,11 @@ def prepare_frame_set(batch, T=None, sample=None, grid=None):
     return fs, live, counts, status_v
 
 
-# ... enqueued between this step's forward and backward instead of after the backward.  OFF: +0.6 % of the step (484.4 -> 487.5
-# frames/s, the preparation no longer runs beside the step's last weight gradient), but the host is so far ahead that the
-# preparation then lands beside conv2's forward gather, which goes from 0.58 to 0.90 ms (profiles/r05b_prep_early_*): the
-# convolution -- the kernel the roofline is quoted on -- loses more than the tail gains once a step is not host-paced
-PREP_EARLY = _os.environ.get('MVX_PREP_EARLY', '0') != '0'
-PREP_STREAM = _os.environ.get('MVX_PREP_STREAM', '1') != '0'    # next batch prepared on its own stream (host reads return early)
-PRESAMPLE = _os.environ.get('MVX_PRESAMPLE', '1') != '0'        # ... including the FPN feature sampling of its real rows (frames.sample_rows)
 # Frame-set lanes: the frames of a step split into this many frame sets that run on their own streams, so that the small
 # latency-bound kernels of one set (BatchNorm passes, VFE, list builders) execute beside the MFMA-bound kernels of the other.
 # Every set keeps per-frame BatchNorm statistics, so the result per frame is unchanged; lane k > 0 accumulates its parameter
 # gradients in a buffer of its own that is added to the bucket once per step (no two streams ever write one address).
-SET_LANES = int(_os.environ.get('MVX_SET_LANES', '1'))
+SET_LANES = 1
 _LANE_FLAT = {}
 
 
@@ -405,89 +467,69 @@ def _train_step_frame_set_lanes(model, batch, grad_mid, imsize, ready, prepare_n
     from modules import frames as fr
     dev = batch.device
     main = torch.cuda.current_stream(dev)
-    ev_ready = None
     if ready is None:
-        ready = prepare_frame_sets(batch, SET_LANES)
-    elif len(ready) == 5:
-        ready, ev_ready = ready[:4], ready[4]
+        ready, ev_ready = prepare_frame_sets(batch, SET_LANES), None
+    else:
+        ready, ev_ready = _wait_ready(ready, main)
     sets, live, counts, status = ready
-    if ev_ready is not None:
-        main.wait_event(ev_ready)
-        status.record_stream(main)
     statuses = [status]
-    old_sink, _hip.GRAD_SINK = _hip.GRAD_SINK, True
-    old_async, _hip.ASYNC_WGRAD = _hip.ASYNC_WGRAD, True
     next_ready = None
     streams = [main] + lane_streams(dev, max(0, len(sets) - 1))
-    flat, done = None, False
-    try:
-        if sets:
-            model.prepack()
-            params = [p for p in model.parameters() if p.requires_grad and p.grad is not None]
-            flat = params[0].grad._base
-            if flat is None:
-                raise _hip.X.MvxHipError('frame-set lanes need the flat gradient bucket (modules/parallel.py GradBucket)')
-            lane_state = []
-            for k, (fs, ids) in enumerate(sets):
-                st = streams[k]
-                if st is not main:
-                    st.wait_stream(main)                        # packed weights, zeroed bucket, the preparation event
-                    fs.hand_over(st)
-                elif ev_ready is not None:
-                    fs.hand_over(main)
-                targets = None
-                if k > 0:
-                    lf = _lane_flat(flat, k)
-                    targets = {}
-                    for p in params:
-                        o = (p.grad.data_ptr() - flat.data_ptr()) // 4
-                        targets[id(p)] = lf[o:o + p.numel()].view_as(p)
-                gm = grad_mid if grad_mid.shape[0] == 1 else grad_mid[ids]
-                lane_state.append([st, fs, ids, targets, gm, None, None])
-            with torch.no_grad():
-                for ls in lane_state:                           # forward of every lane, then the backward of every lane
-                    st, fs, ids, targets, gm, _, _ = ls
-                    with torch.cuda.stream(st):
-                        if targets is not None:
-                            _lane_flat(flat, lane_state.index(ls)).zero_()
-                        _hip.arena_begin(dev, doubles=1 << 21)
-                        ls[5], ls[6] = fr.middle_forward(model, fs, [batch.fpn_levels[f] for f in ids], imsize, statuses)
-                for ls in lane_state:
-                    st, fs, ids, targets, gm, mid, saved = ls
-                    with torch.cuda.stream(st), fr.grad_targets(targets):
-                        if gm.device == dev and st is not main:
-                            gm.record_stream(st)
-                        fr.middle_backward(model, saved, gm)
-                    ls[6] = None
-            if keep_mid is not None:
-                for ls in lane_state:
-                    ls[5].record_stream(main)
-                    for k in range(len(ls[2])):
-                        keep_mid.append(ls[5][k:k + 1])
-        if prepare_next is not None:
-            if PREP_STREAM:
-                prep = _prep_stream(dev)
-                _wait_created(prep, prepare_next)
-                with torch.cuda.stream(prep):
-                    nr = prepare_frame_sets(prepare_next, SET_LANES)
-                    ev = torch.cuda.Event()
-                    ev.record(prep)
-                next_ready = nr + (ev,)
-            else:
-                next_ready = prepare_frame_sets(prepare_next, SET_LANES)
-        done = True
-    finally:
-        _hip.GRAD_SINK = old_sink
-        _hip.ASYNC_WGRAD = old_async
-        _hip.arena_end()
-        for st in streams[1:]:
-            main.wait_stream(st)
-        _hip.join_side_stream()
-        if done and sets and flat is not None:                  # success only: partial lane gradients never reach the bucket
-            for k in range(1, len(sets)):                       # the other lanes' gradients join the bucket (main stream)
-                flat.add_(_lane_flat(flat, k))
-            if len(sets) > 1:
-                _hip.drop_tail(dev)                             # written after the join: the early exchange waits for the main stream
+    with _step_scope(dev, async_wgrad=True, fence=False):
+        try:
+            if sets:
+                model.prepack()
+                params = [p for p in model.parameters() if p.requires_grad and p.grad is not None]
+                flat = params[0].grad._base
+                if flat is None:
+                    raise _hip.X.MvxHipError('frame-set lanes need the flat gradient bucket (modules/parallel.py GradBucket)')
+                lane_state = []
+                for k, (fs, ids) in enumerate(sets):
+                    st = streams[k]
+                    if st is not main:
+                        st.wait_stream(main)                        # packed weights, zeroed bucket, the preparation event
+                        fs.hand_over(st)
+                    elif ev_ready is not None:
+                        fs.hand_over(main)
+                    targets = None
+                    if k > 0:
+                        lf = _lane_flat(flat, k)
+                        targets = {}
+                        for p in params:
+                            o = (p.grad.data_ptr() - flat.data_ptr()) // 4
+                            targets[id(p)] = lf[o:o + p.numel()].view_as(p)
+                    gm = grad_mid if grad_mid.shape[0] == 1 else grad_mid[ids]
+                    lane_state.append([st, fs, ids, targets, gm, None, None])
+                with torch.no_grad():
+                    for ls in lane_state:                           # forward of every lane, then the backward of every lane
+                        st, fs, ids, targets, gm, _, _ = ls
+                        with torch.cuda.stream(st):
+                            if targets is not None:
+                                _lane_flat(flat, lane_state.index(ls)).zero_()
+                            _hip.arena_begin(dev, doubles=1 << 21)
+                            ls[5], ls[6] = fr.middle_forward(model, fs, [batch.fpn_levels[f] for f in ids], imsize, statuses)
+                    for ls in lane_state:
+                        st, fs, ids, targets, gm, mid, saved = ls
+                        with torch.cuda.stream(st), fr.grad_targets(targets):
+                            if gm.device == dev and st is not main:
+                                gm.record_stream(st)
+                            fr.middle_backward(model, saved, gm)
+                        ls[6] = None
+                if keep_mid is not None:
+                    for ls in lane_state:
+                        ls[5].record_stream(main)
+                        for k in range(len(ls[2])):
+                            keep_mid.append(ls[5][k:k + 1])
+            if prepare_next is not None:
+                next_ready = _prepare_next(dev, prepare_next, lambda: prepare_frame_sets(prepare_next, SET_LANES))
+        finally:
+            for st in streams[1:]:
+                main.wait_stream(st)
+    if sets:                                                    # success only: partial lane gradients never reach the bucket
+        for k in range(1, len(sets)):                           # the other lanes' gradients join the bucket (main stream)
+            flat.add_(_lane_flat(flat, k))
+        if len(sets) > 1:
+            _hip.drop_tail(dev)                                 # written after the join: the early exchange waits for the main stream
     if prepare_next is not None:
         return counts, statuses, next_ready
     return counts, statuses
@@ -496,69 +538,32 @@ def _train_step_frame_set_lanes(model, batch, grad_mid, imsize, ready, prepare_n
 def train_step_frame_set(model, batch, grad_mid, imsize, ready=None, prepare_next=None, keep_mid=None):
     """Same contract as train_step_frames, executed through modules/frames.py: ONE launch per layer for all frames of the
     batch, weight-gradient kernels on the side stream.  ``grad_mid``: (1,128,H,W) for every frame or (B,128,H,W).
-    ``prepare_next`` is voxelized and mapped on the preparation stream right after this step has been enqueued: its two
-    host reads only wait for those few small kernels (which share the GPU with the step), so the host stays a step ahead
-    of the GPU."""
+    ``prepare_next`` is voxelized, mapped and sampled on the preparation stream right after this step has been enqueued: its
+    two host reads only wait for those few small kernels (which share the GPU with the step), so the host stays a step ahead
+    of the GPU.  (Enqueued between the forward and the backward instead -- a removed switch -- the step was 0.6 % faster, 484.4
+    -> 487.5 frames/s, but the preparation then landed beside conv2's forward gather, 0.58 -> 0.90 ms,
+    profiles/r05b_prep_early_*: the convolution the roofline is quoted on lost more than the tail gained.)"""
     from modules import frames as fr
     if SET_LANES > 1:
         return _train_step_frame_set_lanes(model, batch, grad_mid, imsize, ready, prepare_next, keep_mid)
     dev = batch.device
-    main = torch.cuda.current_stream(dev)
-    ev_ready = None
-    if ready is None:
-        ready = prepare_frame_set(batch)
-    elif len(ready) == 5:
-        ready, ev_ready = ready[:4], ready[4]
-    fs, live, counts, status = ready
-    if ev_ready is not None:
-        main.wait_event(ev_ready)
-        status.record_stream(main)
-        if fs is not None:
-            fs.hand_over(main, fenced=PREP_FENCE)
+    fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev))
     statuses = [status]
-    old_sink, _hip.GRAD_SINK = _hip.GRAD_SINK, True
     next_ready = None
-    try:
+    with _step_scope(dev):
         if fs is not None:
             model.prepack()
             _hip.arena_begin(dev, doubles=1 << 21)
             gm = grad_mid if grad_mid.shape[0] == 1 or len(live) == batch.n_frames else grad_mid[live]
             with torch.no_grad():
                 mid, saved = fr.middle_forward(model, fs, [batch.fpn_levels[f] for f in live], imsize, statuses)
-                if prepare_next is not None and PREP_STREAM and PREP_EARLY:
-                    # the next batch's preparation is enqueued BEFORE this step's backward: its HBM-bound kernels then run beside
-                    # the backward's first convolutions instead of beside the step's last weight gradient, which nothing else
-                    # hides (the step ended when the preparation did, 0.17 ms after the last gradient kernel)
-                    prep = _prep_stream(dev)
-                    _wait_created(prep, prepare_next)
-                    _fence_wait(prep, dev)
-                    with torch.cuda.stream(prep):
-                        nr = prepare_frame_set(prepare_next, sample=(model.head, imsize) if PRESAMPLE else None,
-                                               grid=model if PREGRID else None)
-                        ev = torch.cuda.Event()
-                        ev.record(prep)
-                    next_ready = nr + (ev,)
                 fr.middle_backward(model, saved, gm)
             if keep_mid is not None:
                 for k in range(len(live)):
                     keep_mid.append(mid[k:k + 1])
-        if prepare_next is not None and next_ready is None:
-            if PREP_STREAM:
-                prep = _prep_stream(dev)
-                _wait_created(prep, prepare_next)
-                _fence_wait(prep, dev)
-                with torch.cuda.stream(prep):
-                    nr = prepare_frame_set(prepare_next, sample=(model.head, imsize) if PRESAMPLE else None, grid=model if PREGRID else None)
-                    ev = torch.cuda.Event()
-                    ev.record(prep)
-                next_ready = nr + (ev,)
-            else:
-                next_ready = prepare_frame_set(prepare_next)
-    finally:
-        _hip.GRAD_SINK = old_sink
-        _hip.arena_end()
-        _hip.join_side_stream()
-        _fence_record(dev)
+        if prepare_next is not None:
+            next_ready = _prepare_next(dev, prepare_next,
+                                       lambda: prepare_frame_set(prepare_next, sample=(model.head, imsize), grid=model))
     if prepare_next is not None:
         return counts, statuses, next_ready
     return counts, statuses
@@ -573,22 +578,9 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
     the frames' FPN maps at the projected points + the fusion MLP (imhead/Pipe.py:23-104), forward and backward."""
     from modules import frames as fr
     dev = batch.device
-    main = torch.cuda.current_stream(dev)
-    ev_ready = None
-    if ready is None:
-        ready = prepare_frame_set(batch)
-    elif len(ready) == 5:
-        ready, ev_ready = ready[:4], ready[4]
-    fs, live, counts, status = ready
-    if ev_ready is not None:
-        main.wait_event(ev_ready)
-        status.record_stream(main)
-        if fs is not None:
-            fs.hand_over(main, fenced=PREP_FENCE)
-    old_sink, _hip.GRAD_SINK = _hip.GRAD_SINK, True
-    old_async, _hip.ASYNC_WGRAD = _hip.ASYNC_WGRAD, True
+    fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev))
     next_ready = None
-    try:
+    with _step_scope(dev, async_wgrad=True):
         if fs is not None:
             cap_rows = batch.n_frames * (batch.cap_points + 1)
             if 'imfeat' not in state or state['imfeat'].shape[0] < cap_rows:
@@ -605,23 +597,7 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
                     feat, saved = fr.rows_forward(model, fs, None, None, [], imfeat=state['imfeat'][:fs.Rt + fs.F])
                 fr.rows_backward(model, saved, state['dfeat'][:fs.Vt])
         if prepare_next is not None:
-            if PREP_STREAM:
-                prep = _prep_stream(dev)
-                _wait_created(prep, prepare_next)
-                _fence_wait(prep, dev)
-                with torch.cuda.stream(prep):
-                    nr = prepare_frame_set(prepare_next)
-                    ev = torch.cuda.Event()
-                    ev.record(prep)
-                next_ready = nr + (ev,)
-            else:
-                next_ready = prepare_frame_set(prepare_next)
-    finally:
-        _hip.GRAD_SINK = old_sink
-        _hip.ASYNC_WGRAD = old_async
-        _hip.arena_end()
-        _hip.join_side_stream()
-        _fence_record(dev)
+            next_ready = _prepare_next(dev, prepare_next, lambda: prepare_frame_set(prepare_next))
     st_out = state.pop('statuses', [status])
     if prepare_next is not None:
         return counts, st_out, next_ready
@@ -660,9 +636,6 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points):
     return batch, targets
 
 
-RPN_HIP = _os.environ.get('MVX_RPN_HIP', '1') != '0'       # RPN frame sets on this library's kernels (modules/rpn_frames.py); 0 = torch modules (MIOpen)
-
-
 def heads_loss(heads, F, h1, w1, targets, criterion, anchors):
     """VoxelLoss (voxelnet/Loss.py:15-45) of every frame on the channels-last head output (F*h1*w1, 16) = [cls logits | reg]
     and its gradient, without the autograd engine: score = sigmoid(logits) (voxelnet/Pipe.py:74), one loss call per frame
@@ -696,7 +669,7 @@ def heads_loss(heads, F, h1, w1, targets, criterion, anchors):
     return torch.stack(losses), has_reg, d.view(F * h1 * w1, 16)
 
 
-def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=None, prepare_next=None, rpn_hip=None, read=True,
+def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=None, prepare_next=None, rpn_hip=True, read=True,
                     keep=None):
     """One optimizer step's worth of forward + backward of the WHOLE model for the frames of ``batch``: frame sets up to
     the CML output (modules/frames.py), the RPN of all frames on this library's kernels (modules/rpn_frames.py; per-frame
@@ -711,31 +684,14 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     [F*D3][H][W][C3] (BEV channel c*D3 + d, VoxelNet.py:36), 'heads' (F*h1*w1, 16) = [cls logits | reg], 'geom'."""
     from modules import frames as fr
     from modules import rpn_frames as rf
-    rpn_hip = RPN_HIP if rpn_hip is None else rpn_hip
     dev = batch.device
-    main = torch.cuda.current_stream(dev)
-    ev_ready = None
-    if ready is None:
-        ready = prepare_frame_set(batch)
-    elif len(ready) == 5:
-        ready, ev_ready = ready[:4], ready[4]
-    fs, live, counts, status = ready
-    if ev_ready is not None:
-        main.wait_event(ev_ready)
-        status.record_stream(main)
-        if fs is not None:
-            fs.hand_over(main, fenced=PREP_FENCE)
-        for t in targets:
-            if t is not None:
-                for x in tuple(t[0]) + tuple(t[1]) + (t[2], t[3]):
-                    if isinstance(x, torch.Tensor) and x.is_cuda:
-                        x.record_stream(main)
+    target_tensors = (x for t in targets if t is not None for x in tuple(t[0]) + tuple(t[1]) + (t[2], t[3])
+                      if isinstance(x, torch.Tensor) and x.is_cuda)      # written on the preparation stream too (target_fn)
+    fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev), also=target_tensors)
     out = {'loss': [], 'cls': [], 'reg': [], 'voxels': counts, 'live': live}
     hw = [float(imsize[0]), float(imsize[1])]
-    old_sink, _hip.GRAD_SINK = _hip.GRAD_SINK, True
-    old_async, _hip.ASYNC_WGRAD = _hip.ASYNC_WGRAD, True
     statuses = [status]
-    try:
+    with _step_scope(dev, async_wgrad=True):
         if fs is not None:
             model.prepack()
             _hip.arena_begin(dev, doubles=1 << 22)
@@ -777,27 +733,11 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
             out['losses_dev'], out['has_reg'] = losses, has_reg
         if prepare_next is not None:
             nb, target_fn = prepare_next
-            if PREP_STREAM:
-                prep = _prep_stream(dev)
-                _wait_created(prep, nb)
-                _fence_wait(prep, dev)
-                with torch.cuda.stream(prep):
-                    nr = prepare_frame_set(nb, sample=(model.head, hw) if PRESAMPLE else None, grid=model if PREGRID else None)
-                    nt = target_fn()
-                    ev = torch.cuda.Event()
-                    ev.record(prep)
-                out['next'] = (nr + (ev,), nt)
-            else:
-                out['next'] = (prepare_frame_set(nb), target_fn())
+            nr, nt, ev = _prepare_next(dev, nb, lambda: (prepare_frame_set(nb, sample=(model.head, hw), grid=model), target_fn()))
+            out['next'] = (nr + (ev,), nt)
         out['statuses'] = statuses
         if read and fs is not None:
             read_losses(out)
-    finally:
-        _hip.GRAD_SINK = old_sink
-        _hip.ASYNC_WGRAD = old_async
-        _hip.arena_end()
-        _hip.join_side_stream()
-        _fence_record(dev)
     return out
 
 
@@ -805,9 +745,7 @@ def read_losses(out):
     """Host side of a step enqueued with read=False: the status words and the per-frame losses (ONE device read each)."""
     if 'losses_dev' not in out:
         return out
-    bad = int(torch.stack([s.reshape(()) for s in out['statuses']]).max())
-    if bad:
-        raise _hip.X.MvxHipError('a kernel reported a data-dependent error (status %d)' % bad)
+    _check_statuses(out['statuses'])
     vals = out['losses_dev'].tolist()
     for (c, r), hr in zip(vals, out['has_reg']):
         out['cls'].append(c)

@@ -29,9 +29,6 @@ R = _hip.STATS_REPLICAS
 TAPS2 = 16          # MVX_FLAG_TAPS2
 
 
-ROW_WGRAD_SIDE = __import__('os').environ.get('MVX_RPN_ROW_WGRAD_SIDE', '1') != '0'   # heads / deconv2 / deconv3 weight gradients on the side stream (A/B: 0)
-
-
 def _split():
     """convmath: bf16x3 / bf16x6 -> the 3x3 convolutions run on the split-MFMA kernels (csrc/conv3d_split.hip): the number of
     bf16 pieces per operand (0 = exact-f32 kernels)."""
@@ -329,7 +326,7 @@ def rpn_backward(rpn, S, d_heads):
     # heads
     # (the row-GEMM weight gradients of the heads and of deconv2 / deconv3 run on the side stream like the convolutions': they
     # were 0.41 ms of main-queue time per --mode full step)
-    with (_hip._SideStream(up, d_heads) if ROW_WGRAD_SIDE else _hip._Inline()):
+    with _hip._SideStream(up, d_heads):
         dwh = _hip.linear_wgrad(up, d_heads)                               # (16, 768)
     with _hip._SideStream(dwh, d_heads):
         _grad_of(rpn.cls.weight).view(2, 768).add_(dwh[:2])
@@ -348,7 +345,7 @@ def rpn_backward(rpn, S, d_heads):
                 'mvx_d2s_bn_apply_frames')
         dz0 = _bn_bwd(gt.view(-1, cout), rec['t'].view(-1, cout), rec['mi'], F, m.deconv.bias)
         dz = _retag(dz0.view(rec['t'].shape), dz0)
-        with (_hip._SideStream(rec['x'], dz) if ROW_WGRAD_SIDE else _hip._Inline()):
+        with _hip._SideStream(rec['x'], dz):
             dw_all = _hip.linear_wgrad(rec['x'], dz)                       # (s*s*cout, cin)
         with _hip._SideStream(dw_all):
             _grad_of(m.deconv.weight).add_(dw_all.view(s, s, cout, cin).permute(3, 2, 0, 1))

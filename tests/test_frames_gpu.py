@@ -152,7 +152,7 @@ def test_frame_set_bf16x3_matches_per_frame_bf16x3_and_f32(golden, small_cfg):
 
 @pytest.mark.parametrize('B,with_empty', [(4, False), (4, True), (3, False)])
 def test_frame_set_lanes_equal_one_frame_set(golden, small_cfg, B, with_empty):
-    """MVX_SET_LANES = 2: the frames of a step as TWO frame sets on two streams (modules/pipeline.py) -- per-frame BatchNorm
+    """pl.SET_LANES = 2: the frames of a step as TWO frame sets on two streams (modules/pipeline.py) -- per-frame BatchNorm
     statistics, so every frame's map is that of the single frame set; the parameter gradients (second lane accumulated in
     its own buffer, added once) equal the single set's up to the order of the sums over the frames.  Repeated with the next
     batch prepared on the preparation stream, as bench.py runs it."""
