@@ -467,6 +467,11 @@ def conv_flops(d_out_planes, d_src_planes, H, W, cin, cout, sd, pd, dgrad=False)
     return 2.0 * taps * 9 * H * W * cin * cout
 
 
+def _per_frame(F, *shape):
+    """Shape of a per-frame quantity: ``F=None`` is ONE frame without the frame axis, an int a frame set with it in front."""
+    return shape if F is None else (F,) + shape
+
+
 def workspace(nbytes, dev, tag):
     """Grow-only scratch buffer per (device, tag); stream-ordered reuse on the current stream."""
     key = (dev.index, tag, X.raw_stream(dev.index))    # one buffer per (tag, stream): no cross-stream reuse
@@ -572,20 +577,32 @@ def gather_voxels(grid, coords, V):
     return feat
 
 
-def cl_to_bev(cl):
-    """channels-last (D,H,W,C) -> (C*D,H,W) contiguous, channel = c*D + d."""
-    D, H, W, C = cl.shape
-    bev = torch.empty((C * D, H, W), dtype=torch.float32, device=cl.device)
+def cl_to_bev(cl, F=None):
+    """channels-last (D,H,W,C) -> (C*D,H,W) contiguous, channel = c*D + d; a frame set (F*D,H,W,C) -> (F,C*D,H,W)."""
+    FD, H, W, C = cl.shape
+    D = FD // (F or 1)
+    bev = torch.empty(_per_frame(F, C * D, H, W), dtype=torch.float32, device=cl.device)
     with _timed_bytes('cl_bev_transpose', 2 * cl.numel() * 4):
-        X.check(X.lib.mvx_cl_to_bev(X.ptr(cl), X.ptr(bev), D, H, W, C, 0, X.stream()), 'mvx_cl_to_bev')
+        X.check(X.lib.mvx_cl_to_bev_frames(X.ptr(cl), X.ptr(bev), D, H, W, C, 0, F or 1, X.stream()), 'mvx_cl_to_bev_frames')
     return bev
 
 
 def bev_to_cl(bev, D):
-    CD, H, W = bev.shape
+    """(C*D,H,W) -> channels-last (D,H,W,C); a frame set (F,C*D,H,W) -> (F*D,H,W,C)."""
+    F = bev.shape[0] if bev.dim() == 4 else 1
+    CD, H, W = bev.shape[-3:]
     C = CD // D
-    cl = torch.empty((D, H, W, C), dtype=torch.float32, device=bev.device)
-    X.check(X.lib.mvx_cl_to_bev(X.ptr(cl), X.ptr(bev), D, H, W, C, 1, X.stream()), 'mvx_cl_to_bev')
+    cl = torch.empty((F * D, H, W, C), dtype=torch.float32, device=bev.device)
+    X.check(X.lib.mvx_cl_to_bev_frames(X.ptr(cl), X.ptr(bev), D, H, W, C, 1, F, X.stream()), 'mvx_cl_to_bev_frames')
+    return cl
+
+
+def bev_to_cl_broadcast(bev, D, F):
+    """ONE map (1,C*D,H,W) -> channels-last (F*D,H,W,C): transposed once, written F times."""
+    CD, H, W = bev.shape[-3:]
+    C = CD // D
+    cl = torch.empty((F * D, H, W, C), dtype=torch.float32, device=bev.device)
+    X.check(X.lib.mvx_bev_to_cl_broadcast(X.ptr(bev), X.ptr(cl), D, H, W, C, F, X.stream()), 'mvx_bev_to_cl_broadcast')
     return cl
 
 
@@ -599,27 +616,66 @@ def row_stats(y2d):
     return stats
 
 
-def bn_finalize(stats, count, eps):
+def row_stats_frames(y, C, F):
+    """BatchNorm sums f64 (F,R,2,C) of a frame set: y holds its rows of C channels frame after frame."""
+    stats = torch.empty((F, STATS_REPLICAS, 2, C), dtype=torch.float64, device=y.device)
+    X.check(X.lib.mvx_row_stats_frames(X.ptr(y), X.ptr(stats), y.numel() // C, C, F, X.stream()), 'mvx_row_stats_frames')
+    return stats
+
+
+def bn_finalize(stats, count, eps, F=None):
+    """(mean, 1/sqrt(var + eps)) f32 (2,C) from the sums of one frame; (F,2,C) from those of a frame set."""
     C = stats.shape[-1]
-    mi = torch.empty((2, C), dtype=torch.float32, device=stats.device)
-    X.check(X.lib.mvx_bn_finalize(X.ptr(stats), float(count), float(eps), X.ptr(mi), C, X.stream()),
-            'mvx_bn_finalize')
+    mi = torch.empty(_per_frame(F, 2, C), dtype=torch.float32, device=stats.device)
+    X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(count), float(eps), X.ptr(mi), C, F or 1, X.stream()),
+            'mvx_bn_finalize_frames')
     return mi
 
 
-def bn_apply(y, mi, out=None):
-    C = mi.shape[1]
+def _desc_ref(desc):
+    return desc.ref() if desc is not None else None
+
+
+def bn_apply(y, mi, out=None, desc=None, kind=X.ROWS_SINGLE, timed=True):
+    """``desc`` / ``kind``: the frames of a frame set and its row layout (X.FramesDesc, X.ROWS_*), mi (F,2,C) then."""
+    C = mi.shape[-1]
     rows = y.numel() // C
     if out is None:
         out = torch.empty_like(y)
-    with _timed_bytes('bn_apply', 2 * y.numel() * 4):
-        X.check(X.lib.mvx_bn_apply(X.ptr(y), X.ptr(mi), X.ptr(out), rows, C, X.stream()), 'mvx_bn_apply')
+    with _timed_bytes('bn_apply', 2 * y.numel() * 4) if timed else _Inline():
+        X.check(X.lib.mvx_bn_apply_frames(X.ptr(y), X.ptr(mi), X.ptr(out), rows, C, _desc_ref(desc), kind, X.stream()),
+                'mvx_bn_apply_frames')
     return out
 
 
-def bn_relu_backward(dyhat, y, mi, count, want_dbias=True, dz=None, row_w=None, dbias_out=None):
-    """dbias_out: existing gradient buffer to ADD the bias gradient to (returns None for dbias then)."""
-    C = mi.shape[1]
+def bn_apply_strided(x, mi, buf, rows, C, ld, off, F, reverse=False):
+    """x (rows,C) normalised per frame into columns off..off+C of the (rows,ld) buffer ``buf``; ``reverse``: that column slice of
+    buf copied out into x (mi unused: the gradient of the concat)."""
+    X.check(X.lib.mvx_bn_apply_strided_frames(X.ptr(x), X.ptr(mi), X.ptr(buf), rows, C, ld, off, F, int(reverse), X.stream()),
+            'mvx_bn_apply_strided_frames')
+
+
+def d2s_bn_apply(t, mi, buf, F, h, w, s, cout, ld, off, reverse=False):
+    """t (F*h*w, s*s*cout) normalised per frame and pixel-shuffled into columns off..off+cout of the (F*h*s*w*s, ld) buffer
+    ``buf``; ``reverse``: the inverse shuffle of that slice of buf into t (mi unused)."""
+    X.check(X.lib.mvx_d2s_bn_apply_frames(X.ptr(t), X.ptr(mi), X.ptr(buf), F, h, w, s, cout, ld, off, int(reverse), X.stream()),
+            'mvx_d2s_bn_apply_frames')
+
+
+def space_to_depth(x, F, planes, h, w, C, reverse=False):
+    """[F*planes][h][w][C] -> [F][h/2][w/2][4*planes*C] (2x2 parity blocks side by side); ``reverse``: the way back."""
+    shape = (F * planes, h, w, C) if reverse else (F, h // 2, w // 2, 4 * planes * C)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    X.check(X.lib.mvx_space_to_depth_frames(X.ptr(x), X.ptr(out), F, planes, h, w, C, int(reverse), X.stream()),
+            'mvx_space_to_depth_frames')
+    return out
+
+
+def bn_relu_backward(dyhat, y, mi, count, want_dbias=True, dz=None, row_w=None, dbias_out=None, desc=None, kind=X.ROWS_SINGLE,
+                     timed=True):
+    """dbias_out: existing gradient buffer to ADD the bias gradient to (returns None for dbias then).  ``desc`` / ``kind``: a frame
+    set (per-frame counts come from its descriptor; dbias is summed over the frames)."""
+    C = mi.shape[-1]
     rows = y.numel() // C
     if dz is None:
         dz = torch.empty_like(y)
@@ -628,14 +684,52 @@ def bn_relu_backward(dyhat, y, mi, count, want_dbias=True, dz=None, row_w=None, 
         dbias, flags = dbias_out, FLAG_ACCUMULATE
     else:
         dbias = torch.empty((C,), dtype=torch.float32, device=y.device) if want_dbias else None
-    scratch, fz = _acc_f64((X.lib.mvx_bn_backward_scratch_bytes(C) // 8,), y.device)
+    scratch, fz = _bn_backward_scratch(C, desc, y.device)
     amax = new_amax(y.device)
-    with _timed_bytes('bn_relu_backward', 5 * y.numel() * 4):      # reduce reads 2 tensors, apply reads 2 + writes 1
+    with _timed_bytes('bn_relu_backward', 5 * y.numel() * 4) if timed else _Inline():      # reduce reads 2 tensors, apply reads 2 + writes 1
         X.check(X.lib.mvx_bn_relu_backward_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), float(count), X.ptr(dz),
-                                                  X.ptr(dbias), X.ptr(scratch), X.ptr(row_w), rows, C, flags | fz, None,
-                                                  X.ROWS_SINGLE, X.ptr(amax), X.stream()), 'mvx_bn_relu_backward_frames')
+                                                  X.ptr(dbias), X.ptr(scratch), X.ptr(row_w), rows, C, flags | fz, _desc_ref(desc),
+                                                  kind, X.ptr(amax), X.stream()), 'mvx_bn_relu_backward_frames')
     tag_amax(dz, amax)                                   # max |dz|: the range the fp16x3 kernels scale dz by
     return dz, (None if dbias_out is not None else dbias)
+
+
+def _bn_backward_scratch(C, desc, device):
+    return _acc_f64((X.lib.mvx_bn_backward_scratch_bytes_frames(C, desc.n_frames if desc is not None else 1) // 8,), device)
+
+
+def bn_relu_backward_planes(dyhat, y, mi, dbias_out, row_w, desc, kind):
+    """bn_relu_backward of a frame set with dz written as three planes of bf16 pieces, int16 (3, rows, C), instead of f32 (a
+    layer whose dz only feeds its own weight gradient on pre-cut operands: linear_wgrad_pre)."""
+    C = mi.shape[-1]
+    rows = y.numel() // C
+    dzp = torch.empty((3, rows, C), dtype=torch.int16, device=y.device)
+    scratch, fz = _bn_backward_scratch(C, desc, y.device)
+    with _timed_bytes('bn_relu_backward', 5.5 * y.numel() * 4):
+        X.check(X.lib.mvx_bn_relu_backward_planes_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dzp), X.ptr(dbias_out),
+                                                         X.ptr(scratch), X.ptr(row_w), rows, C, FLAG_ACCUMULATE | fz,
+                                                         desc.ref(), kind, None, X.stream()), 'mvx_bn_relu_backward_planes_frames')
+    return dzp
+
+
+def bn_relu_backward_planes_parts(dyhat, y, mi, dbias_out, row_w, desc, kind, nparts):
+    """Generator form of bn_relu_backward_planes: the apply pass is enqueued range by range; every iteration enqueues one part
+    and yields ``(planes, row_lo, row_hi)`` -- the rows whose planes that part writes -- so the caller can put the weight gradient
+    of those rows on the side stream before the next part is enqueued (mvx_bn_relu_backward_planes_part_frames).  The bias
+    gradient is complete after the last part."""
+    C = mi.shape[-1]
+    rows = y.numel() // C
+    dzp = torch.empty((3, rows, C), dtype=torch.int16, device=y.device)
+    scratch, fz = _bn_backward_scratch(C, desc, y.device)
+    rng = (ctypes.c_int64 * 2)()
+    for part in range(nparts):
+        with _timed_bytes('bn_relu_backward', 5.5 * y.numel() * 4 / nparts):
+            X.check(X.lib.mvx_bn_relu_backward_planes_part_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dzp),
+                                                                  X.ptr(dbias_out), X.ptr(scratch), X.ptr(row_w), rows, C,
+                                                                  FLAG_ACCUMULATE | fz, desc.ref(), kind, part, nparts, rng,
+                                                                  X.stream()), 'mvx_bn_relu_backward_planes_part_frames')
+        if rng[1] > rng[0]:
+            yield dzp, int(rng[0]), int(rng[1])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -730,6 +824,72 @@ def conv3d_wgrad(x, dz, sd, pd, split=False, accumulate_into=None, two_d=False):
 
 
 # ---------------------------------------------------------------------------------------------
+# 3x3 2-D convolutions of a frame set on the same kernels: maps channels-last [F][h][w][c], one plane per frame; ``flags``:
+# FLAG_TAPS2 = a 2x2 tap window (the stride-2 layers on the space-to-depth image); wpk from conv3d_pack
+# ---------------------------------------------------------------------------------------------
+FLAG_TAPS2 = 16          # MVX_FLAG_TAPS2
+
+
+def _conv2d_flops(F, h, w, cin, cout, flags):
+    if KERNEL_TIMERS is None:
+        return 0
+    return 2.0 * F * h * w * cin * cout * (2.25 if flags & FLAG_TAPS2 else 9)     # 2x2 window: 9 of the 16 (tap, parity) blocks run
+
+
+def conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, split=False):
+    """y = ReLU(conv(x) + b) -> (y, mean_inv (F,2,cout)): per-frame statistics finalised in the launch (split kernels: behind it)."""
+    dev = x.device
+    y = torch.empty((F, h, w, cout), dtype=torch.float32, device=dev)
+    stats, fz = _acc_f64((F, STATS_REPLICAS, 2, cout), dev)
+    fin = _fin_slot(dev, fz)
+    if fin is None:
+        fin = torch.zeros((1,), dtype=torch.float64, device=dev)
+    mi = torch.empty((F, 2, cout), dtype=torch.float32, device=dev)
+    with _Timed('rpn_conv', _conv2d_flops(F, h, w, cin, cout, flags)):
+        if split:                              # split arithmetic (bf16x3 / bf16x6), same window / structural-zero skipping
+            X.check(X.lib.mvx_conv2d_forward_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), X.ptr(stats), h, w, cin, cout,
+                                                          FLAG_RELU | fz | flags | split_flags(split), F, X.stream()),
+                    'mvx_conv2d_forward_split_frames')
+        else:
+            X.check(X.lib.mvx_conv2d_forward_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), X.ptr(stats), h, w, cin, cout,
+                                                    FLAG_RELU | fz | flags, X.ptr(fin), float(eps), X.ptr(mi),
+                                                    X.ptr(_work_counter(dev)), F, X.stream()), 'mvx_conv2d_forward_frames')
+    if split:
+        X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(h * w), float(eps), X.ptr(mi), cout, F, X.stream()),
+                'mvx_bn_finalize_frames')
+    return y, mi
+
+
+def conv2d_dgrad(dz, wpk_d, F, h, w, cin, cout, flags, split=False):
+    dx = torch.empty((F, h, w, cin), dtype=torch.float32, device=dz.device)
+    with _Timed('rpn_conv', _conv2d_flops(F, h, w, cin, cout, flags)):
+        if split:
+            bind_amax(split, dz)
+            X.check(X.lib.mvx_conv2d_dgrad_split_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), h, w, cin, cout,
+                                                        flags | split_flags(split), F, X.stream()), 'mvx_conv2d_dgrad_split_frames')
+        else:
+            X.check(X.lib.mvx_conv2d_dgrad_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), h, w, cin, cout, flags,
+                                                  X.ptr(_work_counter(dz.device)), F, X.stream()), 'mvx_conv2d_dgrad_frames')
+    return dx
+
+
+def conv2d_wgrad(x, dz, F, h, w, cin, cout, flags, accumulate_into=None, split=False):
+    """dW (cout, cin, 3, 3) summed over the frames, on the side stream; ADDED into ``accumulate_into`` or returned."""
+    dev = x.device
+    # split arithmetic: the same entry point and workgroup decomposition (conv3d_wgrad4s, csrc/conv3d.hip) -- MVX_FLAG_SPLIT[3]
+    sp = split_flags(split, True)
+    nbytes = X.lib.mvx_conv2d_wgrad_workspace_bytes_frames(h, w, cin, cout, F)
+    dw = accumulate_into if accumulate_into is not None else torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev)
+    with _SideStream(x, dz, dw), _Timed('rpn_wgrad', _conv2d_flops(F, h, w, cin, cout, flags)):
+        ws = workspace(nbytes, dev, 'rpn_wgrad_side')
+        bind_amax(split, None, dz)
+        X.check(X.lib.mvx_conv2d_wgrad_frames(X.ptr(x), X.ptr(dz), X.ptr(dw), h, w, cin, cout,
+                                              flags | sp | (FLAG_ACCUMULATE if accumulate_into is not None else 0), X.ptr(ws),
+                                              ws.numel(), F, X.stream()), 'mvx_conv2d_wgrad_frames')
+    return dw
+
+
+# ---------------------------------------------------------------------------------------------
 # background rewrite of the CML stack (csrc/activity.hip)
 # ---------------------------------------------------------------------------------------------
 class Background:
@@ -754,15 +914,27 @@ def n_tiles(H, W):
     return ((H + 7) // 8) * ((W + 15) // 16)
 
 
-def activity_dilate(src, src_is_index, din, H, W, sd, pd, mark_border, want_tile_flags=False):
+def _exec_stages(device):
+    """The EXEC_STAGES counter while KERNEL_TIMERS is on (created on first use), else None."""
+    global EXEC_STAGES
+    if KERNEL_TIMERS is None:
+        return None
+    if EXEC_STAGES is None:
+        EXEC_STAGES = torch.zeros((1,), dtype=torch.int64, device=device)
+    return EXEC_STAGES
+
+
+# The wrappers of this section serve one frame and a frame set: ``F`` frames stacked along the depth axis ((F*D,H,W,C) where one
+# frame is (D,H,W,C)); ``din`` / ``planes`` arguments stay PER FRAME.
+def activity_dilate(src, src_is_index, din, H, W, sd, pd, mark_border, want_tile_flags=False, F=1):
     """(mask u8 (dout,H,W), halo flags i32 (dout,tiles)[, tile flags]) of a layer output from its input's activity."""
     dout = conv_out_depth(din, sd, pd)
-    mask = torch.empty((dout, H, W), dtype=torch.uint8, device=src.device)
-    hflag = torch.empty((dout, n_tiles(H, W)), dtype=torch.int32, device=src.device)
+    mask = torch.empty((F * dout, H, W), dtype=torch.uint8, device=src.device)
+    hflag = torch.empty((F * dout, n_tiles(H, W)), dtype=torch.int32, device=src.device)
     tflag = torch.empty_like(hflag) if want_tile_flags else None
-    X.check(X.lib.mvx_activity_dilate(X.ptr(src), 1 if src_is_index else 0, din, dout, H, W, sd, pd,
-                                      1 if mark_border else 0, X.ptr(mask), X.ptr(hflag), X.ptr(tflag), X.stream()),
-            'mvx_activity_dilate')
+    X.check(X.lib.mvx_activity_dilate_frames(X.ptr(src), 1 if src_is_index else 0, din, dout, H, W, sd, pd,
+                                             1 if mark_border else 0, X.ptr(mask), X.ptr(hflag), X.ptr(tflag), F, X.stream()),
+            'mvx_activity_dilate_frames')
     return (mask, hflag, tflag) if want_tile_flags else (mask, hflag)
 
 
@@ -775,12 +947,55 @@ def conv3d_background(w, c_in, din, sd, pd):
     return bg_pre
 
 
-def bn_background(bg_pre, bias, mi, planes, channels, relu=True, want_y=False):
-    c_out = torch.empty((planes, channels), dtype=torch.float32, device=mi.device)
+def conv3d_background_taps(w, c_in, din, sd, pd, F=1):
+    """Background constants of a layer, f32 (F*dout*13, cout): the [planes][cout] totals of conv3d_background, followed by the
+    per-depth-tap ones (3) and the border classes (9) that the gather kernels use under FLAG_BG_TAPS."""
+    cout, cin = w.shape[0], w.shape[1]
+    dout = conv_out_depth(din, sd, pd)
+    bg_all = torch.empty((F * dout * 13, cout), dtype=torch.float32, device=w.device)
+    X.check(X.lib.mvx_conv3d_background_taps_frames(X.ptr(w), X.ptr(c_in), din, dout, cin, cout, sd, pd, X.ptr(bg_all), F,
+                                                    X.stream()), 'mvx_conv3d_background_taps_frames')
+    return bg_all
+
+
+def bn_background(bg_pre, bias, mi, planes, channels, relu=True, want_y=False, F=1):
+    c_out = torch.empty((F * planes, channels), dtype=torch.float32, device=mi.device)
     y_bg = torch.empty_like(c_out) if want_y else None
-    X.check(X.lib.mvx_bn_background(X.ptr(bg_pre), X.ptr(bias), X.ptr(mi), planes, channels, FLAG_RELU if relu else 0,
-                                    X.ptr(y_bg), X.ptr(c_out), X.stream()), 'mvx_bn_background')
+    X.check(X.lib.mvx_bn_background_frames(X.ptr(bg_pre), X.ptr(bias), X.ptr(mi), planes, channels, FLAG_RELU if relu else 0,
+                                           X.ptr(y_bg), X.ptr(c_out), F, X.stream()), 'mvx_bn_background_frames')
     return (c_out, y_bg) if want_y else c_out
+
+
+def bn_apply_tiles(y, mi, c_bg, tflag, F=1, read=None, out=None):
+    """BatchNorm apply of a layer output with a background: tiles without a non-background site (``tflag`` 0) take the normalised
+    constant ``c_bg`` without being read (bit-identical to bn_apply).  ``read``: tile flags of what the consuming layer reads
+    (tile_read_flags): the background tiles outside that set are not written.  ``out``: written into (default: a new tensor)."""
+    FD, H, W, C = y.shape
+    if out is None:
+        out = torch.empty_like(y)
+    # algorithmic bytes (timing runs only): flagged tiles are read and written, the others only written
+    nbytes = (lambda: (tflag.ne(0).sum() + (torch.logical_or(tflag.ne(0), read.ne(0)).sum() if read is not None else tflag.numel()))
+              * (128 * C * 4)) if KERNEL_TIMERS is not None else 0
+    with _timed_bytes('bn_apply', nbytes):
+        if read is not None:
+            X.check(X.lib.mvx_bn_apply_tiles_read_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(read), X.ptr(out),
+                                                         FD // F, H, W, C, F, X.stream()), 'mvx_bn_apply_tiles_read_frames')
+        else:
+            X.check(X.lib.mvx_bn_apply_tiles_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(out), FD // F, H, W, C,
+                                                    F, X.stream()), 'mvx_bn_apply_tiles_frames')
+    return out
+
+
+def bn_apply_tiles_bev(y, mi, c_bg, tflag, F=1):
+    """bn_apply_tiles + cl_to_bev in one pass: the normalised (F*D,H,W,C) output written as the (F, C*D, H, W) map."""
+    FD, H, W, C = y.shape
+    D = FD // F
+    bev = torch.empty((F, C * D, H, W), dtype=torch.float32, device=y.device)
+    nbytes = (lambda: (tflag.ne(0).sum() + tflag.numel()) * (128 * C * 4)) if KERNEL_TIMERS is not None else 0
+    with _timed_bytes('bn_apply', nbytes):
+        X.check(X.lib.mvx_bn_apply_tiles_bev_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(bev), D, H, W, C,
+                                                    F, X.stream()), 'mvx_bn_apply_tiles_bev_frames')
+    return bev
 
 
 def plane_tap_sums(dz, tile_flags=None, inactive_sums=None):
@@ -794,127 +1009,136 @@ def plane_tap_sums(dz, tile_flags=None, inactive_sums=None):
     return T
 
 
-def tile_dilate_flags(in_tflag, self_tflag, din, H, W, sd, pd):
+def tile_dilate_flags(in_tflag, self_tflag, din, H, W, sd, pd, F=1):
     dout = conv_out_depth(din, sd, pd)
-    out = torch.empty((dout, n_tiles(H, W)), dtype=torch.int32, device=in_tflag.device)
-    X.check(X.lib.mvx_tile_dilate_flags(X.ptr(in_tflag), X.ptr(self_tflag), din, dout, H, W, sd, pd, X.ptr(out), X.stream()),
-            'mvx_tile_dilate_flags')
+    out = torch.empty((F * dout, n_tiles(H, W)), dtype=torch.int32, device=in_tflag.device)
+    X.check(X.lib.mvx_tile_dilate_flags_frames(X.ptr(in_tflag), X.ptr(self_tflag), din, dout, H, W, sd, pd, X.ptr(out), F,
+                                               X.stream()), 'mvx_tile_dilate_flags_frames')
     return out
 
 
-def conv3d_input_grad_sums(w, T, din, sd, pd):
+def tile_read_flags(hflag, din, H, W, sd, pd, F=1):
+    """Which tiles of a layer's normalised INPUT the layer reads (its forward gather and weight gradient: the 3 x 3 tile
+    neighbourhoods of the output tiles it computes), from the input's halo flags i32 (F*din, tiles)."""
+    dout = conv_out_depth(din, sd, pd)
+    out = torch.empty_like(hflag)
+    X.check(X.lib.mvx_tile_read_flags_frames(X.ptr(hflag), din, dout, H, W, sd, pd, X.ptr(out), F, X.stream()),
+            'mvx_tile_read_flags_frames')
+    return out
+
+
+def conv3d_input_grad_sums(w, T, din, sd, pd, F=1):
     cout, cin = w.shape[0], w.shape[1]
-    A = torch.empty((din, cin), dtype=torch.float32, device=w.device)
-    X.check(X.lib.mvx_conv3d_input_grad_sums(X.ptr(w.contiguous()), X.ptr(T), din, T.shape[0], cin, cout, sd, pd, X.ptr(A),
-                                             X.stream()), 'mvx_conv3d_input_grad_sums')
+    A = torch.empty((F * din, cin), dtype=torch.float32, device=w.device)
+    X.check(X.lib.mvx_conv3d_input_grad_sums_frames(X.ptr(w.contiguous()), X.ptr(T), din, T.shape[0] // F, cin, cout, sd, pd,
+                                                    X.ptr(A), F, X.stream()), 'mvx_conv3d_input_grad_sums_frames')
     return A
 
 
-def conv3d_dgrad_tiles(dz, wpk_d, din, cin, sd, pd, tflag, split=False):
+def conv3d_dgrad_tiles(dz, wpk_d, din, cin, sd, pd, tflag, split=False, F=1):
     """Input gradient on the flagged tiles only; the rest of the returned tensor is NOT initialised."""
-    dout, H, W, cout = dz.shape
-    dx = torch.empty((din, H, W, cin), dtype=torch.float32, device=dz.device)
-    if split:
-        with _Timed('conv3d_gather_split', 0):
+    FD, H, W, cout = dz.shape
+    dout = FD // F
+    dx = torch.empty((F * din, H, W, cin), dtype=torch.float32, device=dz.device)
+    counter = _exec_stages(dz.device)
+    with _Timed('conv3d_gather_tiles', F * conv_flops(din, dout, H, W, cout, cin, sd, pd, True) if KERNEL_TIMERS is not None else 0):   # dense-equivalent
+        if split:
             bind_amax(split, dz)
-            X.check(X.lib.mvx_conv3d_dgrad_tiles_split(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd, pd,
-                                                       split_flags(split), X.ptr(tflag), X.stream()), 'mvx_conv3d_dgrad_tiles_split')
-        return dx
-    global EXEC_STAGES
-    counter = None
-    if KERNEL_TIMERS is not None:
-        if EXEC_STAGES is None:
-            EXEC_STAGES = torch.zeros((1,), dtype=torch.int64, device=dz.device)
-        counter = EXEC_STAGES
-    with _Timed('conv3d_gather_tiles', conv_flops(din, dout, H, W, cout, cin, sd, pd, True) if KERNEL_TIMERS is not None else 0):   # dense-equivalent
-        X.check(X.lib.mvx_conv3d_dgrad_tiles(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd, pd,
-                                             X.ptr(tflag), X.ptr(counter), X.ptr(_work_counter(dz.device)), X.stream()),
-                'mvx_conv3d_dgrad_tiles')
+            X.check(X.lib.mvx_conv3d_dgrad_tiles_split_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd,
+                                                              pd, split_flags(split), X.ptr(tflag), X.ptr(counter), F, X.stream()),
+                    'mvx_conv3d_dgrad_tiles_split_frames')
+        else:
+            X.check(X.lib.mvx_conv3d_dgrad_tiles_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd, pd,
+                                                        X.ptr(tflag), X.ptr(counter), X.ptr(_work_counter(dz.device)), F,
+                                                        X.stream()), 'mvx_conv3d_dgrad_tiles_frames')
     return dx
 
 
-def bn_relu_backward_tiles(dyhat, y, mi, bg, plane_grad_sums, dbias_out=None, want_inactive_sums=False):
-    """BatchNorm+ReLU backward of a layer output with Background ``bg``; dyhat valid on bg.bflag tiles only.
-    Returns (dz valid on those tiles only, dbias[, sums of dz over the other tiles (planes, C)])."""
-    D, H, W, C = y.shape
+def bn_relu_backward_tiles(dyhat, y, mi, bg, plane_grad_sums, dbias_out=None, want_inactive_sums=False, F=1):
+    """BatchNorm+ReLU backward of a layer output with Background ``bg`` (its c, y_bg and bflag are read); dyhat valid on bg.bflag
+    tiles only.  Returns (dz valid on those tiles only, dbias[, sums of dz over the other tiles (planes, C)])."""
+    FD, H, W, C = y.shape
     dz = torch.empty_like(y)
     if dbias_out is not None:
         db, flags = dbias_out, FLAG_ACCUMULATE
     else:
         db, flags = torch.empty((C,), dtype=torch.float32, device=y.device), 0
-    ws = workspace(X.lib.mvx_bn_relu_backward_tiles_workspace_bytes(D, H, W, C), y.device, 'bn_tiles')
-    inact = torch.empty((D, C), dtype=torch.float32, device=y.device) if want_inactive_sums else None
+    ws = workspace(X.lib.mvx_bn_relu_backward_tiles_workspace_bytes_frames(FD // F, H, W, C, F), y.device, 'bn_tiles')
+    inact = torch.empty((FD, C), dtype=torch.float32, device=y.device) if want_inactive_sums else None
     amax = new_amax(y.device)                            # max |dz| over the written tiles (zeroed by the call)
-    with _timed_bytes('bn_relu_backward_tiles', 0):
+    # algorithmic bytes (timing runs only): the flagged 8x16 tiles, two passes reading dyhat and y, the second writing dz
+    bflag = bg.bflag
+    nbytes = (lambda: bflag.ne(0).sum() * (128 * C * 4 * 5)) if KERNEL_TIMERS is not None else 0
+    with _timed_bytes('bn_relu_backward_tiles', nbytes):
         X.check(X.lib.mvx_bn_relu_backward_tiles_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), X.ptr(bg.c), X.ptr(bg.y_bg),
-                                                        X.ptr(plane_grad_sums), X.ptr(bg.bflag), D, H, W, C, X.ptr(dz), X.ptr(db),
-                                                        X.ptr(inact), X.ptr(amax), flags, X.ptr(ws), ws.numel(), 1, X.stream()),
-                'mvx_bn_relu_backward_tiles_frames')
+                                                        X.ptr(plane_grad_sums), X.ptr(bflag), FD // F, H, W, C, X.ptr(dz),
+                                                        X.ptr(db), X.ptr(inact), X.ptr(amax), flags, X.ptr(ws), ws.numel(), F,
+                                                        X.stream()), 'mvx_bn_relu_backward_tiles_frames')
     tag_amax(dz, amax)
     db = None if dbias_out is not None else db
     return (dz, db, inact) if want_inactive_sums else (dz, db)
 
 
 def conv3d_forward_bg(x, wpk, bias, cout, sd, pd, bg_in, out_mask, bg_pre, relu=True, want_stats=True, finalize_eps=None,
-                      split=False):
-    """finalize_eps: also form the BatchNorm mean / inverse std in the kernel (returns (y, mean_inv) then).
-    split=True: bf16x3 kernel (wpk from conv3d_pack(..., split=True)); the statistics are finalised separately."""
-    global EXEC_STAGES
-    din, H, W, cin = x.shape
+                      split=False, F=None, bg_taps=False):
+    """finalize_eps: also form the BatchNorm mean / inverse std (returns (y, mean_inv) then): in the kernel, or with the split
+    kernels (wpk from conv3d_pack(..., split=...)) by a launch of bn_finalize behind it.  Of ``bg_in`` the halo flags are read.
+    ``F``: a frame set (statistics per frame: (F,R,2,cout) / (F,2,cout)); ``bg_taps``: bg_pre is the head of a
+    conv3d_background_taps table (FLAG_BG_TAPS)."""
+    nf = F or 1
+    FD, H, W, cin = x.shape
+    din = FD // nf
     dout = conv_out_depth(din, sd, pd)
-    out = torch.empty((dout, H, W, cout), dtype=torch.float32, device=x.device)
-    stats, fz = _acc_f64((STATS_REPLICAS, 2, cout), x.device) if want_stats else (None, 0)
-    flags = (FLAG_RELU if relu else 0) | fz | split_flags(split)
-    if split:
-        with _Timed('conv3d_gather_split', conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):
-            X.check(X.lib.mvx_conv3d_forward_bg_split(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
-                                                      H, W, cin, cout, sd, pd, flags, X.ptr(bg_in.hflag), X.ptr(out_mask),
-                                                      X.ptr(bg_pre), 1, X.stream()), 'mvx_conv3d_forward_bg_split')
-        if finalize_eps is not None and want_stats:
-            return out, bn_finalize(stats, float(dout * H * W), finalize_eps)
-        return out, stats
-    counter = None
-    if KERNEL_TIMERS is not None:
-        if EXEC_STAGES is None:
-            EXEC_STAGES = torch.zeros((1,), dtype=torch.int64, device=x.device)
-        counter = EXEC_STAGES
+    out = torch.empty((nf * dout, H, W, cout), dtype=torch.float32, device=x.device)
+    stats, fz = _acc_f64(_per_frame(F, STATS_REPLICAS, 2, cout), x.device) if want_stats else (None, 0)
+    flags = (FLAG_RELU if relu else 0) | fz | split_flags(split) | (FLAG_BG_TAPS if bg_taps else 0)
     fin, mi, npos = None, None, float(dout * H * W)
     if finalize_eps is not None and want_stats:
         fin = _fin_slot(x.device, fz)
         if fin is None:
             fin = torch.zeros((1,), dtype=torch.float64, device=x.device)
-        mi = torch.empty((2, cout), dtype=torch.float32, device=x.device)
-    with _Timed('conv3d_gather_bg', conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):   # dense-equivalent
-        X.check(X.lib.mvx_conv3d_forward_bg(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout, H, W,
-                                            cin, cout, sd, pd, flags, X.ptr(bg_in.hflag), X.ptr(out_mask), X.ptr(bg_pre),
-                                            1, X.ptr(counter), X.ptr(fin), npos, float(finalize_eps or 0.0), X.ptr(mi),
-                                            X.ptr(_work_counter(x.device)), X.stream()), 'mvx_conv3d_forward_bg')
+        mi = torch.empty(_per_frame(F, 2, cout), dtype=torch.float32, device=x.device)
+    counter = _exec_stages(x.device)
+    with _Timed('conv3d_gather_bg', nf * conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):   # dense-equivalent
+        if split:
+            X.check(X.lib.mvx_conv3d_forward_bg_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
+                                                             H, W, cin, cout, sd, pd, flags, X.ptr(bg_in.hflag), X.ptr(out_mask),
+                                                             X.ptr(bg_pre), 1, X.ptr(counter), nf, X.stream()),
+                    'mvx_conv3d_forward_bg_split_frames')
+        else:
+            X.check(X.lib.mvx_conv3d_forward_bg_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout, H, W,
+                                                       cin, cout, sd, pd, flags, X.ptr(bg_in.hflag), X.ptr(out_mask), X.ptr(bg_pre),
+                                                       1, X.ptr(counter), X.ptr(fin), npos, float(finalize_eps or 0.0), X.ptr(mi),
+                                                       X.ptr(_work_counter(x.device)), nf, X.stream()), 'mvx_conv3d_forward_bg_frames')
+    if split and mi is not None:
+        X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), npos, float(finalize_eps), X.ptr(mi), cout, nf, X.stream()),
+                'mvx_bn_finalize_frames')
     return (out, mi) if mi is not None else (out, stats)
 
 
-def conv3d_wgrad_bg(x, dz, sd, pd, bg_in, tap_sums=None, accumulate_into=None, split=False):
-    din, H, W, cin = x.shape
-    dout, _, _, cout = dz.shape
+def conv3d_wgrad_bg(x, dz, sd, pd, bg_in, tap_sums=None, accumulate_into=None, split=False, F=1, flops=0):
+    """Of ``bg_in`` the constants c and the halo flags are read.  ``flops``: the figure of the timer (a number, or a callable
+    evaluated after the timed region: the executed steps depend on the flags)."""
+    FD, H, W, cin = x.shape
+    din = FD // F
+    dout, cout = dz.shape[0] // F, dz.shape[3]
     if accumulate_into is not None:
         dw, flags = accumulate_into, FLAG_ACCUMULATE
     else:
         dw, flags = torch.empty((cout, cin, 3, 3, 3), dtype=torch.float32, device=x.device), 0
     flags |= split_flags(split, True)              # split arithmetic: conv3d_wgrad4s behind the same entry point
-    fn_bytes = X.lib.mvx_conv3d_wgrad_bg_workspace_bytes
-    fn = X.lib.mvx_conv3d_wgrad_bg
-    nbytes = fn_bytes(dout, H, W, cin, cout)
+    nbytes = X.lib.mvx_conv3d_wgrad_bg_workspace_bytes_frames(dout, H, W, cin, cout, F)
     if tap_sums is None:
         tap_sums = plane_tap_sums(dz)
-    # every tensor the side-stream kernels read must be kept alive for that stream (record_stream), not only x and dz:
-    # the tap sums and the background description are temporaries of the frame's own stream
+    # every tensor the side-stream kernels read must be kept alive until that stream is joined (_SideStream), not only x and
+    # dz: the tap sums and the background description are temporaries of the frame's own stream
     with _wgrad_scope(accumulate_into, x, dz, tap_sums, bg_in.c, bg_in.hflag) as scope:
         ws = workspace(nbytes, x.device, 'wgrad_bg_side' if isinstance(scope, _SideStream) else 'wgrad_bg')
-        with _Timed('conv3d_wgrad_bg', 0):
+        with _Timed('conv3d_wgrad_bg', flops):
             bind_amax(split, None, dz)
-            X.check(fn(X.ptr(x), X.ptr(dz), X.ptr(dw), din, dout, H, W, cin, cout, sd, pd, flags,
-                                              X.ptr(bg_in.hflag), X.ptr(bg_in.c), X.ptr(tap_sums), X.ptr(ws), ws.numel(),
-                                              X.stream()),
-                    'mvx_conv3d_wgrad_bg')
+            X.check(X.lib.mvx_conv3d_wgrad_bg_frames(X.ptr(x), X.ptr(dz), X.ptr(dw), din, dout, H, W, cin, cout, sd, pd, flags,
+                                                     X.ptr(bg_in.hflag), X.ptr(bg_in.c), X.ptr(tap_sums), X.ptr(ws), ws.numel(),
+                                                     F, X.stream()), 'mvx_conv3d_wgrad_bg_frames')
     return None if accumulate_into is not None else dw
 
 
@@ -1155,6 +1379,39 @@ def linear_forward(x, w, bias, relu=True, want_stats=True, w_transposed=False, r
     return out, stats
 
 
+def linear_forward_bn_frames(x, w2, bias, desc, kind, row_w, eps, split=False, foreign=False):
+    """Rows of a frame set -> (y = ReLU(x w2^T + b), mean_inv (F,2,N)) with per-frame BatchNorm statistics formed and finalised
+    inside the launch (mvx_linear_forward_bn_frames); ``desc`` / ``kind``: the frames and their row layout (X.ROWS_*).  When the
+    producer of x wrote it as planes of bf16 pieces too (``x._mvx_planes``) and the shape qualifies (precut_ok), the row GEMM on
+    pre-cut operands runs instead: same products, same accumulation order -- bit-identical y.  ``foreign``: x was not produced
+    by this library (the sampled image features): foreign_split."""
+    Rr, K = x.shape
+    N = w2.shape[0]
+    y = torch.empty((Rr, N), dtype=torch.float32, device=x.device)
+    stats, fz = _acc_f64((desc.n_frames, STATS_REPLICAS, 2, N), x.device)
+    counter = _fin_slot(x.device, fz)              # arena slot when the statistics came from the (pre-zeroed) arena
+    if counter is None:
+        counter = torch.zeros((1,), dtype=torch.float64, device=x.device)
+    mi = torch.empty((desc.n_frames, 2, N), dtype=torch.float32, device=x.device)
+    xp = getattr(x, '_mvx_planes', None)
+    if xp is not None and precut_ok(split, Rr, K, N):
+        linear_forward_pre(xp, weight_planes(w2, split), bias, y, stats, row_w, FLAG_RELU | fz | split_flags(split, True),
+                           counter, eps, mi, desc, kind)
+        return y, mi
+    xfl = 0
+    if foreign:
+        split, xfl = foreign_split(split, x)
+    if split and int(split) == 4:
+        guard_fp16_weight(w2)                          # fp16x3: |w| < 255.9 (device-side status bit, checked once per step)
+    with _Timed('linear_fwd', 2.0 * Rr * K * N if KERNEL_TIMERS is not None else 0):
+        bind_amax(split, x)                            # fp16x3: the range tag of a foreign input (the sampled image features)
+        X.check(X.lib.mvx_linear_forward_bn_frames(_vptr(x), _ld(x), _vptr(w2), _ld(w2), 0, X.ptr(bias), _vptr(y), _ld(y),
+                                                   X.ptr(stats), X.ptr(row_w), Rr, K, N,
+                                                   FLAG_RELU | fz | split_flags(split, True) | xfl, X.ptr(counter), float(eps),
+                                                   X.ptr(mi), desc.ref(), kind, X.stream()), 'mvx_linear_forward_bn_frames')
+    return y, mi
+
+
 def linear_wgrad(x, dz, accumulate_into=None, split=None, x_foreign=False):
     """dW (N,K) = dz^T x; accumulate_into: existing contiguous (N,K)-sized gradient buffer to ADD to.  ``split``: bf16x3
     arithmetic (MVX_FLAG_SPLIT, csrc/linear_split.hip linear_wgrad_split); None = as ``row_split('wgrad')`` says."""
@@ -1186,15 +1443,12 @@ class CompactRows:
     """Row layout of one frame in compact form: n_real real rows followed by one padded row per
     voxel (see include/mvx_hip.h, 'Compact rows')."""
 
+    desc = None                          # one frame (frames.FrameSet, the same layout for a frame set, carries its X.FramesDesc here)
+
     def __init__(self, row_map, rows_sel, n_real, V, T):
-        dev = row_map.device
         self.row_map, self.rows_sel = row_map, rows_sel
         self.n_real, self.V, self.T = int(n_real), int(V), int(T)
-        self.voff = torch.empty((V,), dtype=torch.int32, device=dev)
-        self.vcnt = torch.empty((V,), dtype=torch.int32, device=dev)
-        self.row_w = torch.empty((self.n_real + V,), dtype=torch.float32, device=dev)
-        X.check(X.lib.mvx_voxel_row_offsets(X.ptr(row_map), V, T, self.n_real, X.ptr(self.voff), X.ptr(self.vcnt),
-                                            X.ptr(self.row_w), X.stream()), 'mvx_voxel_row_offsets')
+        self.voff, self.vcnt, self.row_w = voxel_row_offsets(row_map, self.V, self.T, self.n_real)
 
     @property
     def rows(self):
@@ -1205,38 +1459,55 @@ class CompactRows:
         return self.V * self.T
 
 
+def voxel_row_offsets(row_map, V, T, n_real, desc=None):
+    """Per-voxel row offsets / counts i32 (V,) and the BatchNorm row weights f32 (n_real + V,) of a compact layout; with the
+    ``desc`` of a frame set also the row weights of its fusion layout f32 (n_real + F,)."""
+    dev = row_map.device
+    voff = torch.empty((V,), dtype=torch.int32, device=dev)
+    vcnt = torch.empty((V,), dtype=torch.int32, device=dev)
+    row_w = torch.empty((n_real + V,), dtype=torch.float32, device=dev)
+    fusion_row_w = torch.empty((n_real + desc.n_frames,), dtype=torch.float32, device=dev) if desc is not None else None
+    X.check(X.lib.mvx_voxel_row_offsets_frames(X.ptr(row_map), V, T, n_real, X.ptr(voff), X.ptr(vcnt), X.ptr(row_w),
+                                               X.ptr(fusion_row_w), _desc_ref(desc), X.stream()), 'mvx_voxel_row_offsets_frames')
+    return (voff, vcnt, row_w) if desc is None else (voff, vcnt, row_w, fusion_row_w)
+
+
 def _rows_args(cr):
+    """``cr``: a CompactRows (one frame), a frames.FrameSet (a frame set: ``desc`` set), or None (dense rows)."""
     if cr is None:
-        return None, None, 0
-    return X.ptr(cr.voff), X.ptr(cr.vcnt), cr.n_real
+        return None, None, 0, None
+    return X.ptr(cr.voff), X.ptr(cr.vcnt), cr.n_real, _desc_ref(cr.desc)
 
 
 def vfe_bn_max_concat(y, mi, V, T, cr=None):
-    C = mi.shape[1]
+    C = mi.shape[-1]
     out = torch.empty((y.shape[0], 2 * C), dtype=torch.float32, device=y.device)
     am = torch.empty((V, C), dtype=torch.int32, device=y.device)
-    vo, vc, nr = _rows_args(cr)
-    X.check(X.lib.mvx_vfe_bn_max_concat(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), V, T, C, vo, vc, nr, X.stream()),
-            'mvx_vfe_bn_max_concat')
+    vo, vc, nr, d = _rows_args(cr)
+    with _timed_bytes('vfe_bn_max_concat', y.shape[0] * C * 4 * 3 + V * C * 4):      # read y, write [x | max] + argmax
+        X.check(X.lib.mvx_vfe_bn_max_concat_frames(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), V, T, C, vo, vc, nr, d, X.stream()),
+                'mvx_vfe_bn_max_concat_frames')
     return out, am
 
 
 def vfe_max_concat_backward(g, am, V, T, cr=None):
     C = am.shape[1]
     dyh = torch.empty((g.shape[0], C), dtype=torch.float32, device=g.device)
-    vo, vc, nr = _rows_args(cr)
-    X.check(X.lib.mvx_vfe_max_concat_backward(X.ptr(g), X.ptr(am), X.ptr(dyh), V, T, C, vo, vc, nr, X.stream()),
-            'mvx_vfe_max_concat_backward')
+    vo, vc, nr, _ = _rows_args(cr)
+    with _timed_bytes('vfe_max_concat_backward', g.shape[0] * C * 4 * 3 + V * C * 4):  # read [gx | gmax] + argmax, write dyhat
+        X.check(X.lib.mvx_vfe_max_concat_backward(X.ptr(g), X.ptr(am), X.ptr(dyh), V, T, C, vo, vc, nr, X.stream()),
+                'mvx_vfe_max_concat_backward')
     return dyh
 
 
 def bn_segment_max(y, mi, V, T, cr=None):
-    C = mi.shape[1]
+    C = mi.shape[-1]
     out = torch.empty((V, C), dtype=torch.float32, device=y.device)
     am = torch.empty((V, C), dtype=torch.int32, device=y.device)
-    vo, vc, nr = _rows_args(cr)
-    X.check(X.lib.mvx_bn_segment_max(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), V, T, C, vo, vc, nr, X.stream()),
-            'mvx_bn_segment_max')
+    vo, vc, nr, d = _rows_args(cr)
+    with _timed_bytes('vfe_bn_segment_max', y.shape[0] * C * 4 + V * C * 8):          # read y, write max + argmax
+        X.check(X.lib.mvx_bn_segment_max_frames(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), V, T, C, vo, vc, nr, d, X.stream()),
+                'mvx_bn_segment_max_frames')
     return out, am
 
 
@@ -1244,69 +1515,98 @@ def segment_max_backward(dfeat, am, V, T, cr=None):
     C = am.shape[1]
     rows = cr.rows if cr is not None else V * T
     dyh = torch.empty((rows, C), dtype=torch.float32, device=dfeat.device)
-    vo, vc, nr = _rows_args(cr)
+    vo, vc, nr, _ = _rows_args(cr)
     X.check(X.lib.mvx_segment_max_backward(X.ptr(dfeat), X.ptr(am), X.ptr(dyh), V, T, C, vo, vc, nr, X.stream()),
             'mvx_segment_max_backward')
     return dyh
 
 
-def vfe_compact_input(vox2d, imfeat_c, cr):
+def vfe_compact_input(vox2d, imfeat_c, cr, pitch=None):
+    """[7 geometric channels | image features] rows of the layout ``cr`` (see _rows_args); ``pitch``: floats per output row
+    (default 7 + F; more: zero columns behind)."""
     F = imfeat_c.shape[1]
-    out = torch.empty((cr.rows, 7 + F), dtype=torch.float32, device=vox2d.device)
-    X.check(X.lib.mvx_vfe_compact_input(X.ptr(vox2d), vox2d.shape[1], X.ptr(cr.rows_sel), X.ptr(imfeat_c), F,
-                                        cr.n_real, cr.V, X.ptr(out), X.stream()), 'mvx_vfe_compact_input')
+    pitch = 7 + F if pitch is None else pitch
+    out = torch.empty((cr.rows, pitch), dtype=torch.float32, device=vox2d.device)
+    X.check(X.lib.mvx_vfe_compact_input_pitch_frames(X.ptr(vox2d), vox2d.shape[1], X.ptr(cr.rows_sel), X.ptr(imfeat_c), F,
+                                                     cr.n_real, cr.V, X.ptr(out), pitch, _desc_ref(cr.desc), X.stream()),
+            'mvx_vfe_compact_input_pitch_frames')
     return out
 
 
 def vfe_compact_input_backward(g, F, cr):
-    d = torch.empty((cr.n_real + 1, F), dtype=torch.float32, device=g.device)
-    scratch = torch.empty((F,), dtype=torch.float64, device=g.device)
-    X.check(X.lib.mvx_vfe_compact_input_backward(X.ptr(g), F, cr.n_real, cr.V, X.ptr(d), X.ptr(scratch), X.stream()),
-            'mvx_vfe_compact_input_backward')
+    """Gradient of the image features f32 (real rows + one shared padded row per frame, F)."""
+    nf = cr.desc.n_frames if cr.desc is not None else 1
+    d = torch.empty((cr.n_real + nf, F), dtype=torch.float32, device=g.device)
+    scratch = torch.empty((nf * F,), dtype=torch.float64, device=g.device)
+    X.check(X.lib.mvx_vfe_compact_input_backward_frames(X.ptr(g), F, cr.n_real, cr.V, X.ptr(d), X.ptr(scratch),
+                                                        _desc_ref(cr.desc), X.stream()), 'mvx_vfe_compact_input_backward_frames')
     return d
 
 
 # ---------------------------------------------------------------------------------------------
 # point <-> image fusion
 # ---------------------------------------------------------------------------------------------
-def row_compact_map(vox2d):
-    """vox2d (R, vc) -> row_map i32 (R,), rows_sel i32 (R,), n_real i32 (1,) (all on the device)."""
+def row_compact_map(vox2d, desc=None):
+    """vox2d (R, vc) -> row_map i32 (R,), rows_sel i32 (R,), n_real i32 (1,) (all on the device); with the ``desc`` of a frame
+    set (its voxel offsets) also the real-row offsets of its frames i32 (F+1,)."""
     R, vc = vox2d.shape
     dev = vox2d.device
     row_map = torch.empty((R,), dtype=torch.int32, device=dev)
     rows_sel = torch.empty((R,), dtype=torch.int32, device=dev)
     n_real = torch.empty((1,), dtype=torch.int32, device=dev)
+    real_off = torch.empty((desc.n_frames + 1,), dtype=torch.int32, device=dev) if desc is not None else None
     nbytes = X.lib.mvx_row_compact_workspace_bytes(R)
     ws = workspace(nbytes, dev, 'compact')
-    X.check(X.lib.mvx_row_compact_map(X.ptr(vox2d), vc, R, X.ptr(row_map), X.ptr(rows_sel), X.ptr(n_real),
-                                      X.ptr(ws), ws.numel(), X.stream()), 'mvx_row_compact_map')
-    return row_map, rows_sel, n_real
+    X.check(X.lib.mvx_row_compact_map_frames(X.ptr(vox2d), vc, R, X.ptr(row_map), X.ptr(rows_sel), X.ptr(n_real), X.ptr(ws),
+                                             ws.numel(), _desc_ref(desc), X.ptr(real_off), X.stream()), 'mvx_row_compact_map_frames')
+    return (row_map, rows_sel, n_real) if desc is None else (row_map, rows_sel, n_real, real_off)
 
 
 def feature_sample(vox2d, feats_cl, imsize_hw, eps, out, row_map=None, rows_sel=None, n_real=None):
     """vox2d (R, vc) modified in place; feats_cl: list of channels-last (H, W, C) maps.  With ``rows_sel`` and
     ``n_real`` (from row_compact_map, which already zeroed the padding rows) only the real rows are visited."""
-    import ctypes
     R, vc = vox2d.shape
     L = len(feats_cl)
     C = feats_cl[0].shape[2]
+    for f in feats_cl:
+        assert f.is_contiguous() and f.dtype == torch.float32 and f.shape[2] == C
+    if rows_sel is not None and n_real is not None:
+        return feature_sample_rows(vox2d, rows_sel, int(n_real), feats_cl, imsize_hw, eps, out)
     ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in feats_cl])
     hw = (ctypes.c_int32 * (2 * L))(*[int(v) for f in feats_cl for v in f.shape[:2]])
     status = torch.zeros((1,), dtype=torch.int32, device=vox2d.device)
-    for f in feats_cl:
-        assert f.is_contiguous() and f.dtype == torch.float32 and f.shape[2] == C
     # algorithmic bytes: 4 taps x L levels x C floats gathered + L*C floats written per sampled row, + the voxel rows
     nrows = out.shape[0]
-    if rows_sel is not None and n_real is not None:
-        with _timed_bytes('feature_sample', nrows * L * C * 4 * 5 + int(n_real) * vc * 4):
-            X.check(X.lib.mvx_feature_sample_rows(X.ptr(vox2d), vc, X.ptr(rows_sel), int(n_real), ptrs, hw, L, C,
-                                                  float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
-                                                  X.ptr(status), X.stream()), 'mvx_feature_sample_rows')
-        return status
     with _timed_bytes('feature_sample', nrows * L * C * 4 * 5 + R * vc * 4):
         X.check(X.lib.mvx_feature_sample(X.ptr(vox2d), vc, R, X.ptr(row_map), ptrs, hw, L, C,
                                          float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
                                          X.ptr(status), X.stream()), 'mvx_feature_sample')
+    return status
+
+
+def feature_sample_rows(vox2d, rows_sel, n_real, feats_cl, imsize_hw, eps, out, desc=None, amax=None, planes=None):
+    """The ``n_real`` real rows ``rows_sel`` of vox2d (modified in place) sampled from channels-last (H, W, C) maps into the rows
+    of ``out`` (None: not written).  A frame set (``desc``): feats_cl holds the L levels of frame 0, then of frame 1, ...; every
+    row reads its own frame's maps.  ``amax`` f32 (1,), ZERO on entry: receives max |sample|.  ``planes`` int16 (3, rows, L*C):
+    the samples also as planes of bf16 pieces.  Returns the status word."""
+    vc = vox2d.shape[1]
+    L = len(feats_cl) // (desc.n_frames if desc is not None else 1)
+    C = feats_cl[0].shape[2]
+    ptrs = (ctypes.c_void_p * len(feats_cl))(*[f.data_ptr() for f in feats_cl])
+    hw = (ctypes.c_int32 * (2 * L))(*[int(v) for f in feats_cl[:L] for v in f.shape[:2]])
+    status = torch.zeros((1,), dtype=torch.int32, device=vox2d.device)
+    # algorithmic bytes: 4 taps x L levels x C floats gathered + L*C floats written per sampled row, + the voxel rows
+    with _timed_bytes('feature_sample', n_real * L * C * 4 * 5 + n_real * vc * 4 + (n_real * L * C * 6 if planes is not None else 0)):
+        if planes is not None:
+            X.check(X.lib.mvx_feature_sample_rows_planes_frames(X.ptr(vox2d), vc, X.ptr(rows_sel), n_real, ptrs, hw, L, C,
+                                                                float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
+                                                                X.ptr(status), _desc_ref(desc), X.ptr(amax), X.ptr(planes),
+                                                                planes.shape[1], X.stream()), 'mvx_feature_sample_rows_planes_frames')
+        else:
+            X.check(X.lib.mvx_feature_sample_rows_frames(X.ptr(vox2d), vc, X.ptr(rows_sel), n_real, ptrs, hw, L, C,
+                                                         float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
+                                                         X.ptr(status), _desc_ref(desc), X.ptr(amax), X.stream()),
+                    'mvx_feature_sample_rows_frames')
     return status
 
 
@@ -1395,12 +1695,14 @@ def lidar2img(pcd2d, cam_from_velo, p2, math_f32=True, out=None, col_offset=0, s
 # ---------------------------------------------------------------------------------------------
 # input-sparse convolution as voxel GEMMs + index-grid gathers
 # ---------------------------------------------------------------------------------------------
-def index_grid(coords, dhw):
+def index_grid(coords, dhw, desc=None):
+    """Voxel index grid of one frame; with the ``desc`` of a frame set (coords of its frames back to back) of every frame."""
     D, H, W = dhw
-    buf = torch.empty((X.lib.mvx_index_grid_bytes(D, H, W) // 4,), dtype=torch.int32, device=coords.device)
+    nf = desc.n_frames if desc is not None else 1
+    buf = torch.empty((X.lib.mvx_index_grid_bytes_frames(D, H, W, nf) // 4,), dtype=torch.int32, device=coords.device)
     status = torch.zeros((1,), dtype=torch.int32, device=coords.device)
-    X.check(X.lib.mvx_index_grid(X.ptr(coords), coords.shape[0], D, H, W, X.ptr(buf), X.ptr(status), X.stream()),
-            'mvx_index_grid')
+    X.check(X.lib.mvx_index_grid_frames(X.ptr(coords), coords.shape[0], D, H, W, X.ptr(buf), X.ptr(status), _desc_ref(desc),
+                                        X.stream()), 'mvx_index_grid_frames')
     return buf, status
 
 
@@ -1416,12 +1718,28 @@ def sparse_conv_output(P, idx_grid, dhw, bias, cout, sd, pd, relu=True, want_sta
     return out, stats
 
 
-def sparse_conv_gather_dz(dz, coords, din, sd, pd):
-    dout, H, W, cout = dz.shape
+def sparse_conv_output_tiles(P, idx_grid, dhw, bias, cout, sd, pd, tflag, F=1, out=None):
+    """sparse_conv_output of F frames, built only on the tiles ``tflag`` of the output that hold a site next to a voxel; the
+    voxel-free tiles are not written (MVX_FLAG_NO_BG_FILL).  ``out``: written into (default: a new tensor).  Statistics per frame."""
+    din, H, W = dhw
+    dout = conv_out_depth(din, sd, pd)
+    if out is None:
+        out = torch.empty((F * dout, H, W, cout), dtype=torch.float32, device=P.device)
+    stats, fz = _acc_f64((F, STATS_REPLICAS, 2, cout), P.device)
+    with _timed_bytes('sparse_conv_output', out.numel() * 4 + F * din * H * W * 4):     # dense output written + index grid read
+        X.check(X.lib.mvx_sparse_conv_output_tiles_frames(X.ptr(P), X.ptr(idx_grid), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
+                                                          H, W, cout, sd, pd, FLAG_RELU | FLAG_NO_BG_FILL | fz, F, X.ptr(tflag),
+                                                          X.stream()), 'mvx_sparse_conv_output_tiles_frames')
+    return out, stats
+
+
+def sparse_conv_gather_dz(dz, coords, din, sd, pd, desc=None):
+    FD, H, W, cout = dz.shape
+    dout = FD // (desc.n_frames if desc is not None else 1)
     V = coords.shape[0]
     G = torch.empty((V, 27 * cout), dtype=torch.float32, device=dz.device)
-    X.check(X.lib.mvx_sparse_conv_gather_dz(X.ptr(dz), X.ptr(coords), V, X.ptr(G), din, dout, H, W, cout, sd, pd,
-                                            X.stream()), 'mvx_sparse_conv_gather_dz')
+    X.check(X.lib.mvx_sparse_conv_gather_dz_frames(X.ptr(dz), X.ptr(coords), V, X.ptr(G), din, dout, H, W, cout, sd, pd,
+                                                   _desc_ref(desc), X.stream()), 'mvx_sparse_conv_gather_dz_frames')
     return tag_amax(G, amax_of(dz))                     # G's rows are rows of dz
 
 

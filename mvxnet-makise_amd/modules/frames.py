@@ -12,7 +12,6 @@ the reductions themselves.
 
 Weight-gradient kernels go to the side stream (modules/_hip.py), everything else stays on the caller's stream.
 """
-import ctypes
 import os
 
 import torch
@@ -42,36 +41,26 @@ class FrameSet:
 
     # -- step 1 (enqueue only): dense-row -> compact-row map of all frames, real-row offsets stay on the device
     def enqueue_map(self):
-        dev = self.voxels.device
         rows = self.Vt * self.T
         vox2d = self.voxels.view(rows, self.voxels.shape[-1])
         self.vox2d = vox2d
-        self.row_map = torch.empty((rows,), dtype=torch.int32, device=dev)
-        self.rows_sel = torch.empty((rows,), dtype=torch.int32, device=dev)
-        self.n_real_dev = torch.empty((1,), dtype=torch.int32, device=dev)
-        self.real_off_dev = torch.empty((self.F + 1,), dtype=torch.int32, device=dev)
         d0 = X.FramesDesc.make(self.vox_off, [0] * (self.F + 1), self.T)
-        ws = _hip.workspace(X.lib.mvx_row_compact_workspace_bytes(rows), dev, 'compact')
-        X.check(X.lib.mvx_row_compact_map_frames(X.ptr(vox2d), vox2d.shape[1], rows, X.ptr(self.row_map), X.ptr(self.rows_sel),
-                                                 X.ptr(self.n_real_dev), X.ptr(ws), ws.numel(), d0.ref(),
-                                                 X.ptr(self.real_off_dev), X.stream()), 'mvx_row_compact_map_frames')
+        self.row_map, self.rows_sel, self.n_real_dev, self.real_off_dev = _hip.row_compact_map(vox2d, d0)
         return self.real_off_dev
 
     # -- step 2 (after ONE host read of real_off_dev): the descriptor and the per-voxel offsets
     def finish_map(self, real_off):
-        dev = self.voxels.device
         self.real_off = [int(v) for v in real_off]
         self.Rt = self.real_off[-1]
+        self.n_real, self.V = self.Rt, self.Vt             # the names of _hip.CompactRows: the wrappers take either
         self.desc = X.FramesDesc.make(self.vox_off, self.real_off, self.T)
-        self.voff = torch.empty((self.Vt,), dtype=torch.int32, device=dev)
-        self.vcnt = torch.empty((self.Vt,), dtype=torch.int32, device=dev)
-        self.row_w = torch.empty((self.Rt + self.Vt,), dtype=torch.float32, device=dev)          # MVX_ROWS_VFE layout
-        self.fusion_row_w = torch.empty((self.Rt + self.F,), dtype=torch.float32, device=dev)    # MVX_ROWS_FUSION layout
-        X.check(X.lib.mvx_voxel_row_offsets_frames(X.ptr(self.row_map), self.Vt, self.T, self.Rt, X.ptr(self.voff),
-                                                   X.ptr(self.vcnt), X.ptr(self.row_w), X.ptr(self.fusion_row_w),
-                                                   self.desc.ref(), X.stream()), 'mvx_voxel_row_offsets_frames')
+        # row_w: MVX_ROWS_VFE layout (Rt + Vt,); fusion_row_w: MVX_ROWS_FUSION layout (Rt + F,)
+        self.voff, self.vcnt, self.row_w, self.fusion_row_w = _hip.voxel_row_offsets(self.row_map, self.Vt, self.T, self.Rt, self.desc)
         return self
 
+    @property
+    def rows(self):
+        return self.Rt + self.Vt
 
     def hand_over(self, stream, fenced=False):
         """The set was built on another stream (input preparation): keep its tensors alive for ``stream`` too.
@@ -95,118 +84,53 @@ class FrameSet:
         self._kept = kept                                            # sampled / grid are dropped mid-step: their tensors stay here
 
 
-# ---------------------------------------------------------------------------------------------------------
-# thin wrappers over the frame-set entry points (allocation + pointers only)
-# ---------------------------------------------------------------------------------------------------------
-def _stats(F, C, dev):
-    buf, fz = _hip._acc_f64((F, R, 2, C), dev)
-    return buf, fz
-
-
 BEV_FUSED = True      # conv3's BatchNorm apply writes the (F, C * D, H, W) map itself (tests set False to compare)
 # DIAGNOSTIC ONLY (tools/knockout.sh): comma-separated kernel classes that are NOT launched, to measure what each class costs
 # on the critical path of a step (step time with the class removed).  Results are garbage; bench.py marks such a run invalid.
+# A knocked-out call hands back an uninitialised tensor of the shape the kernel would have written (_knocked).
 KNOCKOUT = frozenset(k for k in os.environ.get('MVX_KNOCKOUT', '').split(',') if k)
 
 
+def _knocked(like=None, shape=None, dtype=torch.float32):
+    return torch.empty_like(like) if shape is None else torch.empty(shape, dtype=dtype, device=like.device)
+
+
 def linear_bn(x, w, b, fs, kind, row_w, eps, tag='fusion', foreign=False):
-    """rows -> (y = ReLU(x w^T + b), mean_inv (F,2,N)) with per-frame statistics formed inside the launch.  ``foreign``: x was not
-    produced by this library (the sampled image features): _hip.foreign_split."""
-    Rr, K = x.shape
+    """rows -> (y = ReLU(x w^T + b), mean_inv (F,2,N)) with per-frame statistics formed inside the launch, in the arithmetic of
+    _hip.row_split(tag).  ``foreign``: x was not produced by this library (the sampled image features): _hip.foreign_split."""
     N = w.shape[0]
-    w2 = w.reshape(N, -1)
-    y = torch.empty((Rr, N), dtype=torch.float32, device=x.device)
-    stats, fz = _stats(fs.F, N, x.device)
-    counter = _hip._fin_slot(x.device, fz)              # arena slot when the statistics came from the (pre-zeroed) arena
-    if counter is None:
-        counter = torch.zeros((1,), dtype=torch.float64, device=x.device)
-    mi = torch.empty((fs.F, 2, N), dtype=torch.float32, device=x.device)
     if 'lin_fwd' in KNOCKOUT:
-        return y, mi
-    sp, xfl = _hip.row_split(tag), 0                     # convmath bf16x3 / bf16x6 / fp16x3: the wide layers on the split-MFMA row GEMM
-    xp = getattr(x, '_mvx_planes', None)                 # the producer of x wrote it as planes of bf16 pieces too (sample_rows)
-    if xp is not None and _hip.precut_ok(sp, Rr, K, N):
-        # the row GEMM on pre-cut operands (csrc/rowgemm_pre.hip): same products, same accumulation order -- bit-identical y
-        _hip.linear_forward_pre(xp, _hip.weight_planes(w2, sp), b, y, stats, row_w, _hip.FLAG_RELU | fz | _hip.split_flags(sp, True),
-                                counter, eps, mi, fs.desc, kind)
-        return y, mi
-    if foreign:
-        sp, xfl = _hip.foreign_split(sp, x)
-    if sp and int(sp) == 4:
-        _hip.guard_fp16_weight(w2)                          # fp16x3: |w| < 255.9 (device-side status bit, checked once per step)
-    code, sp = sp, _hip.split_flags(sp, True) | xfl
-    with _hip._Timed('linear_fwd', 2.0 * Rr * K * N if _hip.KERNEL_TIMERS is not None else 0):
-        _hip.bind_amax(code, x)                             # fp16x3: the range tag of a foreign input (the sampled image features)
-        X.check(X.lib.mvx_linear_forward_bn_frames(_hip._vptr(x), _hip._ld(x), _hip._vptr(w2), _hip._ld(w2), 0, X.ptr(b),
-                                                   _hip._vptr(y), _hip._ld(y), X.ptr(stats), X.ptr(row_w), Rr, K, N,
-                                                   _hip.FLAG_RELU | fz | sp, X.ptr(counter), float(eps), X.ptr(mi), fs.desc.ref(),
-                                                   kind, X.stream()), 'mvx_linear_forward_bn_frames')
-    return y, mi
+        return _knocked(x, (x.shape[0], N)), _knocked(x, (fs.F, 2, N))
+    return _hip.linear_forward_bn_frames(x, w.reshape(N, -1), b, fs.desc, kind, row_w, eps, _hip.row_split(tag), foreign)
 
 
 def bn_apply(y, mi, fs, kind):
-    C = mi.shape[-1]
-    rows = y.numel() // C
     if 'bn_apply_rows' in KNOCKOUT:
         return y
-    out = torch.empty_like(y)
-    with _hip._timed_bytes('bn_apply', 2 * y.numel() * 4):
-        X.check(X.lib.mvx_bn_apply_frames(X.ptr(y), X.ptr(mi), X.ptr(out), rows, C, fs.desc.ref(), kind, X.stream()),
-                'mvx_bn_apply_frames')
-    return out
+    return _hip.bn_apply(y, mi, desc=fs.desc, kind=kind)
 
 
 def bn_relu_backward(dyhat, y, mi, fs, kind, row_w, dbias_into, dz=None, planes=False):
     """dz (may alias dyhat); the bias gradient is ADDED to ``dbias_into`` (summed over the frames).  ``planes``: dz is
     written as three planes of bf16 pieces, int16 (3, rows, C), instead of f32 (a layer whose dz only feeds its own weight
     gradient on pre-cut operands: _hip.linear_wgrad_pre)."""
-    C = mi.shape[-1]
-    rows = y.numel() // C
     if planes:
-        dzp = torch.empty((3, rows, C), dtype=torch.int16, device=y.device)
         if 'bn_bwd_rows' in KNOCKOUT:
-            return dzp
-        scratch, fz = _hip._acc_f64((X.lib.mvx_bn_backward_scratch_bytes_frames(C, fs.F) // 8,), y.device)
-        with _hip._timed_bytes('bn_relu_backward', 5.5 * y.numel() * 4):
-            X.check(X.lib.mvx_bn_relu_backward_planes_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dzp), X.ptr(dbias_into),
-                                                             X.ptr(scratch), X.ptr(row_w), rows, C, _hip.FLAG_ACCUMULATE | fz,
-                                                             fs.desc.ref(), kind, None, X.stream()), 'mvx_bn_relu_backward_planes_frames')
-        return dzp
-    if dz is None:
-        dz = torch.empty_like(y)
+            return _knocked(y, (3, y.numel() // mi.shape[-1], mi.shape[-1]), torch.int16)
+        return _hip.bn_relu_backward_planes(dyhat, y, mi, dbias_into, row_w, fs.desc, kind)
     if ('bn_bwd_rows' if kind != X.ROWS_GRID else 'bn_bwd_grid') in KNOCKOUT:
-        return dz
-    scratch, fz = _hip._acc_f64((X.lib.mvx_bn_backward_scratch_bytes_frames(C, fs.F) // 8,), y.device)
-    amax = _hip.new_amax(y.device)
-    with _hip._timed_bytes('bn_relu_backward', 5 * y.numel() * 4):
-        X.check(X.lib.mvx_bn_relu_backward_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dz), X.ptr(dbias_into),
-                                                  X.ptr(scratch), X.ptr(row_w), rows, C, _hip.FLAG_ACCUMULATE | fz,
-                                                  fs.desc.ref(), kind, X.ptr(amax), X.stream()), 'mvx_bn_relu_backward_frames')
-    return _hip.tag_amax(dz, amax)                      # max |dz|: the range the fp16x3 kernels scale dz by
+        return dz if dz is not None else _knocked(y)
+    return _hip.bn_relu_backward(dyhat, y, mi, 1.0, dz=dz, row_w=row_w, dbias_out=dbias_into, desc=fs.desc, kind=kind)[0]
 
 
 def bn_relu_backward_planes_parts(dyhat, y, mi, fs, kind, row_w, dbias_into, nparts):
-    """Generator form of ``bn_relu_backward(..., planes=True)``: the apply pass is enqueued range by range; every iteration
-    enqueues one part and yields ``(planes, row_lo, row_hi)`` -- the rows whose planes that part writes -- so the caller can
-    put the weight gradient of those rows on the side stream before the next part is enqueued
-    (mvx_bn_relu_backward_planes_part_frames).  The bias gradient is complete after the last part."""
-    import ctypes
-    C = mi.shape[-1]
-    rows = y.numel() // C
-    dzp = torch.empty((3, rows, C), dtype=torch.int16, device=y.device)
+    """``bn_relu_backward(..., planes=True)`` enqueued range by range: yields ``(planes, row_lo, row_hi)`` per part
+    (_hip.bn_relu_backward_planes_parts)."""
     if 'bn_bwd_rows' in KNOCKOUT:
-        yield dzp, 0, rows
+        rows = y.numel() // mi.shape[-1]
+        yield _knocked(y, (3, rows, mi.shape[-1]), torch.int16), 0, rows
         return
-    scratch, fz = _hip._acc_f64((X.lib.mvx_bn_backward_scratch_bytes_frames(C, fs.F) // 8,), y.device)
-    rng = (ctypes.c_int64 * 2)()
-    for part in range(nparts):
-        with _hip._timed_bytes('bn_relu_backward', 5.5 * y.numel() * 4 / nparts):
-            X.check(X.lib.mvx_bn_relu_backward_planes_part_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dzp),
-                                                                  X.ptr(dbias_into), X.ptr(scratch), X.ptr(row_w), rows, C,
-                                                                  _hip.FLAG_ACCUMULATE | fz, fs.desc.ref(), kind, part, nparts, rng,
-                                                                  X.stream()), 'mvx_bn_relu_backward_planes_part_frames')
-        if rng[1] > rng[0]:
-            yield dzp, int(rng[0]), int(rng[1])
+    yield from _hip.bn_relu_backward_planes_parts(dyhat, y, mi, dbias_into, row_w, fs.desc, kind, nparts)
 
 
 # (The BatchNorm-backward reduction folded into the epilogue of the producing input-gradient kernel -- VERDICT r03 #1a, built and
@@ -267,11 +191,8 @@ def sample_rows(head, fs, fpn_levels, imsize):
     levels = [f[0].permute(1, 2, 0).contiguous() for lv in fpn_levels for f in head.extractor(lv)]
     L = len(levels) // F
     C = levels[0].shape[2]
-    ptrs = (ctypes.c_void_p * (F * L))(*[t.data_ptr() for t in levels])
-    hw = (ctypes.c_int32 * (2 * L))(*[int(v) for t in levels[:L] for v in t.shape[:2]])
     compact = torch.empty((Rt + F, L * C), dtype=torch.float32, device=dev)
     compact[Rt:].zero_()                                   # the shared padded rows (Pipe.py:80)
-    status = torch.zeros((1,), dtype=torch.int32, device=dev)
     # fp16x3: the image features come from outside this library -- their range (max |value|) is formed by the sampler while it
     # writes them, so that the first fusion layer can scale them (forward: the coarse scale, _hip.foreign_split)
     amax = torch.zeros((1,), dtype=torch.float32, device=dev) if _hip.split_pieces() == 4 else None
@@ -283,28 +204,23 @@ def sample_rows(head, fs, fpn_levels, imsize):
     if want_planes:
         planes = torch.empty((3, Rt + F, L * C), dtype=torch.int16, device=dev)
         planes[:, Rt:].zero_()
-    with _hip._timed_bytes('feature_sample', Rt * L * C * 4 * 5 + Rt * 9 * 4 + (Rt * L * C * 6 if planes is not None else 0)):
-      if 'sample' not in KNOCKOUT:
-        if planes is not None:
-            # with the first fusion layer on planes too nobody reads the f32 rows: they are not written (245 MB per
-            # 4-frame step); `compact` stays as the rows' handle (shape, planes, range tag).  MVX_POISON_BG=1 (tests) fills it with
-            # NaN instead, which any read would carry into the results
-            K0, N0 = L * C, w0.shape[0]
-            planes_only = bool(not KNOCKOUT and
-                               _hip.precut_ok(_hip.row_split('fusion_%dx%d' % (N0, K0)), Rt + F, K0, N0) and
-                               _hip.precut_ok(_hip.row_split('wgrad'), Rt + F, K0, N0))       # both readers take the planes
-            if planes_only and os.environ.get('MVX_POISON_BG'):
+    out = compact
+    if planes is not None:
+        # with the first fusion layer on planes too nobody reads the f32 rows: they are not written (245 MB per
+        # 4-frame step); `compact` stays as the rows' handle (shape, planes, range tag).  MVX_POISON_BG=1 (tests) fills it with
+        # NaN instead, which any read would carry into the results
+        K0, N0 = L * C, w0.shape[0]
+        planes_only = bool(not KNOCKOUT and
+                           _hip.precut_ok(_hip.row_split('fusion_%dx%d' % (N0, K0)), Rt + F, K0, N0) and
+                           _hip.precut_ok(_hip.row_split('wgrad'), Rt + F, K0, N0))       # both readers take the planes
+        if planes_only:
+            out = None
+            if os.environ.get('MVX_POISON_BG'):
                 compact[:Rt].fill_(float('nan'))
-            X.check(X.lib.mvx_feature_sample_rows_planes_frames(X.ptr(fs.vox2d), fs.vox2d.shape[1], X.ptr(fs.rows_sel), Rt, ptrs, hw, L,
-                                                                C, float(imsize[0]), float(imsize[1]), float(cfg.eps),
-                                                                None if planes_only else X.ptr(compact),
-                                                                X.ptr(status), fs.desc.ref(), X.ptr(amax), X.ptr(planes), Rt + F,
-                                                                X.stream()), 'mvx_feature_sample_rows_planes_frames')
-        else:
-            X.check(X.lib.mvx_feature_sample_rows_frames(X.ptr(fs.vox2d), fs.vox2d.shape[1], X.ptr(fs.rows_sel), Rt, ptrs, hw, L, C,
-                                                         float(imsize[0]), float(imsize[1]), float(cfg.eps), X.ptr(compact),
-                                                         X.ptr(status), fs.desc.ref(), X.ptr(amax), X.stream()),
-                    'mvx_feature_sample_rows_frames')
+    if 'sample' in KNOCKOUT:
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    else:
+        status = _hip.feature_sample_rows(fs.vox2d, fs.rows_sel, Rt, levels, imsize, cfg.eps, out, fs.desc, amax, planes)
     _hip.tag_amax(compact, amax)
     if planes is not None:
         compact._mvx_planes = planes
@@ -354,9 +270,7 @@ def _vfe_forward(bb, fs, x, S, eps):
     # read them with 16-byte loads (k = 24 against a weight padded with a zero column: the same sums) instead of falling to the
     # scalar-load forms of their kernels (config 2: 106 / 170 us for 11 / 50 MB)
     ldr = (7 + Fc + 3) & ~3
-    rows23 = torch.empty((Rt + Vt, ldr), dtype=torch.float32, device=dev)
-    X.check(X.lib.mvx_vfe_compact_input_pitch_frames(X.ptr(fs.vox2d), fs.vox2d.shape[1], X.ptr(fs.rows_sel), X.ptr(x), Fc, Rt, Vt,
-                                                     X.ptr(rows23), ldr, fs.desc.ref(), X.stream()), 'mvx_vfe_compact_input_pitch_frames')
+    rows23 = _hip.vfe_compact_input(fs.vox2d, x, fs, pitch=ldr)
     S.fc = Fc
     # ---- SVFE (voxelnet/Pipe.py:5-29) and FCN + max (VoxelNet.py:27-33)
     S.vfe = []
@@ -364,21 +278,12 @@ def _vfe_forward(bb, fs, x, S, eps):
     for vfe in (bb.svfe.vfe1, bb.svfe.vfe2):
         w, b = vfe.fcn.fc.weight, vfe.fcn.fc.bias
         y, mi = linear_bn(x, _hip.padded_weight(w.reshape(w.shape[0], -1), x.shape[1]), b, fs, X.ROWS_VFE, fs.row_w, eps, 'vfe')
-        Cn = w.shape[0]
-        out = torch.empty((Rt + Vt, 2 * Cn), dtype=torch.float32, device=dev)
-        am = torch.empty((Vt, Cn), dtype=torch.int32, device=dev)
-        with _hip._timed_bytes('vfe_bn_max_concat', (Rt + Vt) * Cn * 4 * 3 + Vt * Cn * 4):      # read y, write [x | max] + argmax
-            X.check(X.lib.mvx_vfe_bn_max_concat_frames(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), Vt, T, Cn, X.ptr(fs.voff),
-                                                       X.ptr(fs.vcnt), Rt, fs.desc.ref(), X.stream()), 'mvx_vfe_bn_max_concat_frames')
+        out, am = _hip.vfe_bn_max_concat(y, mi, Vt, T, fs)
         S.vfe.append((x, w, b, y, mi, am))
         x = out
     w, b = bb.fcn.fc.weight, bb.fcn.fc.bias
     y, mi = linear_bn(x, w, b, fs, X.ROWS_VFE, fs.row_w, eps, 'vfe')
-    feat = torch.empty((Vt, w.shape[0]), dtype=torch.float32, device=dev)
-    am = torch.empty((Vt, w.shape[0]), dtype=torch.int32, device=dev)
-    with _hip._timed_bytes('vfe_bn_segment_max', (Rt + Vt) * w.shape[0] * 4 + Vt * w.shape[0] * 8):   # read y, write max + argmax
-        X.check(X.lib.mvx_bn_segment_max_frames(X.ptr(y), X.ptr(mi), X.ptr(feat), X.ptr(am), Vt, T, w.shape[0], X.ptr(fs.voff),
-                                                X.ptr(fs.vcnt), Rt, fs.desc.ref(), X.stream()), 'mvx_bn_segment_max_frames')
+    feat, am = _hip.bn_segment_max(y, mi, Vt, T, fs)
     S.head = (x, w, b, y, mi, am)
     return feat, S
 
@@ -393,44 +298,27 @@ def grid_activity(model, fs):
     dev = fs.voxels.device
     F, Vt = fs.F, fs.Vt
     D0, H, W = cfg.voxelshape[2], cfg.voxelshape[0], cfg.voxelshape[1]
-    ntl = _hip.n_tiles(H, W)
-    idx_grid = torch.empty((X.lib.mvx_index_grid_bytes_frames(D0, H, W, F) // 4,), dtype=torch.int32, device=dev)
-    st2 = torch.zeros((1,), dtype=torch.int32, device=dev)
-    X.check(X.lib.mvx_index_grid_frames(X.ptr(fs.coords), Vt, D0, H, W, X.ptr(idx_grid), X.ptr(st2), fs.desc.ref(), X.stream()),
-            'mvx_index_grid_frames')
+    idx_grid, st2 = _hip.index_grid(fs.coords, (D0, H, W), fs.desc)
     tensors = [idx_grid, st2]
     layers = []
     src, is_index, din = idx_grid, True, D0
     for li, m in enumerate((bb.cml.conv1, bb.cml.conv2, bb.cml.conv3)):
-        sd, pd = m._sd, m._pd
-        dout = _hip.conv_out_depth(din, sd, pd)
-        mask = torch.empty((F * dout, H, W), dtype=torch.uint8, device=dev)
-        hflag = torch.empty((F * dout, ntl), dtype=torch.int32, device=dev)
-        tflag = torch.empty_like(hflag)
-        X.check(X.lib.mvx_activity_dilate_frames(X.ptr(src), 1 if is_index else 0, din, dout, H, W, sd, pd, 0 if li == 0 else 1,
-                                                 X.ptr(mask), X.ptr(hflag), X.ptr(tflag), F, X.stream()), 'mvx_activity_dilate_frames')
-        layers.append((mask, hflag, tflag))
-        tensors += [mask, hflag, tflag]
-        src, is_index, din = mask, False, dout
+        lay = _hip.activity_dilate(src, is_index, din, H, W, m._sd, m._pd, li > 0, want_tile_flags=True, F=F)      # (mask, hflag, tflag)
+        layers.append(lay)
+        tensors += lay
+        src, is_index, din = lay[0], False, _hip.conv_out_depth(din, m._sd, m._pd)
     # the tiles layer 2's own restricted backward touches (from layer 1's and layer 2's tile flags)
     c2 = bb.cml.conv2
     d1 = _hip.conv_out_depth(D0, bb.cml.conv1._sd, bb.cml.conv1._pd)
-    d2 = _hip.conv_out_depth(d1, c2._sd, c2._pd)
-    bflag2 = torch.empty((F * d2, ntl), dtype=torch.int32, device=dev)
-    X.check(X.lib.mvx_tile_dilate_flags_frames(X.ptr(layers[0][2]), X.ptr(layers[1][2]), d1, d2, H, W, c2._sd, c2._pd, X.ptr(bflag2), F,
-                                               X.stream()), 'mvx_tile_dilate_flags_frames')
+    bflag2 = _hip.tile_dilate_flags(layers[0][2], layers[1][2], d1, H, W, c2._sd, c2._pd, F=F)
     tensors.append(bflag2)
     # which tiles of conv1's / conv2's normalised OUTPUT the next layer reads (its forward gather and weight gradient: the 3 x 3
     # tile neighbourhoods of the output tiles it computes): bn_apply_bg leaves the other background tiles unwritten
     reads = []
     din = d1
     for li, m in enumerate((bb.cml.conv2, bb.cml.conv3)):
-        dout = _hip.conv_out_depth(din, m._sd, m._pd)
-        R = torch.empty_like(layers[li][1])
-        X.check(X.lib.mvx_tile_read_flags_frames(X.ptr(layers[li][1]), din, dout, H, W, m._sd, m._pd, X.ptr(R), F, X.stream()),
-                'mvx_tile_read_flags_frames')
-        reads.append(R)
-        din = dout
+        reads.append(_hip.tile_read_flags(layers[li][1], din, H, W, m._sd, m._pd, F=F))
+        din = _hip.conv_out_depth(din, m._sd, m._pd)
     tensors += reads
     return dict(idx_grid=idx_grid, status=st2, layers=layers, bflag2=bflag2, reads=reads, tensors=tensors)
 
@@ -459,56 +347,31 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
     # voxel-free tiles of y1 are never read (bn_apply_bg / the tile-restricted BatchNorm backward walk the flagged tiles only):
     # they are not written either (MVX_FLAG_NO_BG_FILL: 742 -> ~300 MB of stores per 4-frame step).  MVX_POISON_BG=1 (tests)
     # fills them with NaN instead, which any read would carry into the results
-    if os.environ.get('MVX_POISON_BG'):
-        y1 = torch.full((F * D1, H, W, cout), float('nan'), dtype=torch.float32, device=dev)
+    y1 = torch.full((F * D1, H, W, cout), float('nan'), dtype=torch.float32, device=dev) if os.environ.get('MVX_POISON_BG') else None
+    if 'sparse_out' in KNOCKOUT:
+        y1, stats = _knocked(feat, (F * D1, H, W, cout)), torch.zeros((F, R, 2, cout), dtype=torch.float64, device=dev)
     else:
-        y1 = torch.empty((F * D1, H, W, cout), dtype=torch.float32, device=dev)
-    stats, fz = _stats(F, cout, dev)
-    with _hip._timed_bytes('sparse_conv_output', y1.numel() * 4 + F * D0 * H * W * 4):
-      if 'sparse_out' not in KNOCKOUT:
         # only the tiles of y1 that hold a site next to a voxel are built: the flags of this layer's output from grid_activity
-        X.check(X.lib.mvx_sparse_conv_output_tiles_frames(X.ptr(P), X.ptr(idx_grid), X.ptr(b1), X.ptr(y1), X.ptr(stats), D0, D1, H, W,
-                                                          cout, c1._sd, c1._pd, _hip.FLAG_RELU | _hip.FLAG_NO_BG_FILL | fz, F,
-                                                          X.ptr(ga['layers'][0][2]), X.stream()),
-                'mvx_sparse_conv_output_tiles_frames')
-    mi1 = torch.empty((F, 2, cout), dtype=torch.float32, device=dev)
-    X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(D1 * H * W), float(eps), X.ptr(mi1), cout, F, X.stream()),
-            'mvx_bn_finalize_frames')
-    ntl = _hip.n_tiles(H, W)
+        y1, stats = _hip.sparse_conv_output_tiles(P, idx_grid, (D0, H, W), b1, cout, c1._sd, c1._pd, ga['layers'][0][2], F, out=y1)
+    mi1 = _hip.bn_finalize(stats, D1 * H * W, eps, F)
 
     def dilate(li):
         return ga['layers'][li]
 
     def background(bg_pre, bias, mi, planes, C_):
-        c_out = torch.empty((F * planes, C_), dtype=torch.float32, device=dev)
-        y_bg = torch.empty_like(c_out)
-        X.check(X.lib.mvx_bn_background_frames(X.ptr(bg_pre), X.ptr(bias), X.ptr(mi), planes, C_, _hip.FLAG_RELU, X.ptr(y_bg),
-                                               X.ptr(c_out), F, X.stream()), 'mvx_bn_background_frames')
-        return c_out, y_bg
+        return _hip.bn_background(bg_pre, bias, mi, planes, C_, want_y=True, F=F)
 
-    def bn_apply_bg(y, mi, c_bg, tflag, planes, read=None):
-        """BatchNorm apply of a layer output with a background: tiles without a non-background site take the normalised
-        constant without being read (bit-identical to bn_apply).  ``read``: tile flags of what the consuming layer reads
-        (grid_activity): the background tiles outside that set are not written (MVX_POISON_BG=1, tests: they hold NaN)."""
+    def bn_apply_bg(y, mi, c_bg, tflag, read=None):
+        """BatchNorm apply of a layer output with a background (_hip.bn_apply_tiles).  ``read``: tile flags of what the consuming
+        layer reads (grid_activity): the background tiles outside that set are not written (MVX_POISON_BG=1, tests: they hold NaN)."""
         if 'bn_apply_cml' in KNOCKOUT:
             return y
-        out = torch.full_like(y, float('nan')) if (read is not None and os.environ.get('MVX_POISON_BG')) else torch.empty_like(y)
-        Cn = y.shape[-1]
-        # algorithmic bytes (timing runs only): flagged tiles are read and written, the others only written
-        nbytes = (lambda: (tflag.ne(0).sum() + (torch.logical_or(tflag.ne(0), read.ne(0)).sum() if read is not None else tflag.numel()))
-                  * (128 * Cn * 4)) if _hip.KERNEL_TIMERS is not None else 0
-        with _hip._timed_bytes('bn_apply', nbytes):
-            if read is not None:
-                X.check(X.lib.mvx_bn_apply_tiles_read_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(read), X.ptr(out),
-                                                             planes, H, W, Cn, F, X.stream()), 'mvx_bn_apply_tiles_read_frames')
-            else:
-                X.check(X.lib.mvx_bn_apply_tiles_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(out), planes, H, W, Cn,
-                                                        F, X.stream()), 'mvx_bn_apply_tiles_frames')
-        return out
+        out = torch.full_like(y, float('nan')) if (read is not None and os.environ.get('MVX_POISON_BG')) else None
+        return _hip.bn_apply_tiles(y, mi, c_bg, tflag, F, read, out)
 
     mask1, hflag1, tflag1 = dilate(0)
     cc1, ybg1 = background(None, b1, mi1, D1, cout)
-    x1 = bn_apply_bg(y1, mi1, cc1, tflag1, D1, ga['reads'][0])
+    x1 = bn_apply_bg(y1, mi1, cc1, tflag1, ga['reads'][0])
     S.conv1 = dict(feat=feat, w=w1, b=b1, w_all=w_all, y=y1, mi=mi1, c=cc1, ybg=ybg1, tflag=tflag1, D0=D0, D1=D1)
 
     # ---- conv2, conv3 on the MFMA gather kernel with the background rewrite (voxelnet/Pipe.py:37-42)
@@ -527,53 +390,22 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
         wpk = m._packer(False, split)
         # background constants of this layer: [planes][co] totals, followed by the per-depth-tap ones the exact-f32 gather
         # uses to skip the depth taps whose source halo holds no active site (FLAG_BG_TAPS)
-        bg_all = torch.empty((F * dout * 13, co), dtype=torch.float32, device=dev)      # totals | 3 depth taps | 9 border classes
-        bg_pre = bg_all[:F * dout]
-        X.check(X.lib.mvx_conv3d_background_taps_frames(X.ptr(w), X.ptr(c_in), din, dout, ci, co, sd, pd, X.ptr(bg_all), F,
-                                                        X.stream()), 'mvx_conv3d_background_taps_frames')
+        bg_pre = _hip.conv3d_background_taps(w, c_in, din, sd, pd, F)[:F * dout]      # totals | 3 depth taps | 9 border classes
         mask_o, hflag_o, tflag_o = dilate(li + 1)
-        y = torch.empty((F * dout, H, W, co), dtype=torch.float32, device=dev)
-        stats, fz = _stats(F, co, dev)
-        fin = _hip._fin_slot(dev, fz)
-        if fin is None:
-            fin = torch.zeros((1,), dtype=torch.float64, device=dev)
-        mi = torch.empty((F, 2, co), dtype=torch.float32, device=dev)
-        counter = None
-        if _hip.KERNEL_TIMERS is not None:
-            if _hip.EXEC_STAGES is None:
-                _hip.EXEC_STAGES = torch.zeros((1,), dtype=torch.int64, device=dev)
-            counter = _hip.EXEC_STAGES
-        if split:
-            with _hip._Timed('conv3d_gather_bg', F * _hip.conv_flops(dout, din, H, W, ci, co, sd, pd) if _hip.KERNEL_TIMERS is not None else 0):
-                X.check(X.lib.mvx_conv3d_forward_bg_split_frames(X.ptr(x_in), X.ptr(wpk), X.ptr(b), X.ptr(y), X.ptr(stats), din, dout,
-                                                                 H, W, ci, co, sd, pd,
-                                                                 _hip.FLAG_RELU | fz | _hip.FLAG_BG_TAPS | _hip.split_flags(split),
-                                                                 X.ptr(hflag_in), X.ptr(mask_o), X.ptr(bg_pre), 1, X.ptr(counter), F,
-                                                                 X.stream()),
-                        'mvx_conv3d_forward_bg_split_frames')
-            X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(dout * H * W), float(eps), X.ptr(mi), co, F, X.stream()),
-                    'mvx_bn_finalize_frames')
-        elif 'gather_fwd' not in KNOCKOUT:
-          with _hip._Timed('conv3d_gather_bg', F * _hip.conv_flops(dout, din, H, W, ci, co, sd, pd) if _hip.KERNEL_TIMERS is not None else 0):
-            X.check(X.lib.mvx_conv3d_forward_bg_frames(X.ptr(x_in), X.ptr(wpk), X.ptr(b), X.ptr(y), X.ptr(stats), din, dout, H, W,
-                                                       ci, co, sd, pd, _hip.FLAG_RELU | fz | _hip.FLAG_BG_TAPS,
-                                                       X.ptr(hflag_in), X.ptr(mask_o),
-                                                       X.ptr(bg_pre), 1, X.ptr(counter), X.ptr(fin), float(dout * H * W),
-                                                       float(eps), X.ptr(mi), X.ptr(_hip._work_counter(dev)), F, X.stream()),
-                    'mvx_conv3d_forward_bg_frames')
+        if 'gather_fwd' in KNOCKOUT and not split:
+            y, mi = _knocked(x_in, (F * dout, H, W, co)), _knocked(x_in, (F, 2, co))
+        else:
+            y, mi = _hip.conv3d_forward_bg(x_in, wpk, b, co, sd, pd, _hip.Background(c_in, mask_in, hflag_in), mask_o, bg_pre,
+                                           finalize_eps=eps, split=split, F=F, bg_taps=True)
         c_o, ybg_o = background(bg_pre, b, mi, dout, co)         # the background of this layer's output
         if want_bev and li == 1 and co <= 64 and 'bn_apply_cml' not in KNOCKOUT and BEV_FUSED:
             # the last layer's normalised output goes straight into the reference's (F, C * D, H, W) layout
             # (mvx_bn_apply_tiles_bev_frames): no channels-last copy of it, no transposition pass
-            mid = torch.empty((F, co * dout, H, W), dtype=torch.float32, device=dev)
-            nbytes = (lambda: (tflag_o.ne(0).sum() + tflag_o.numel()) * (128 * co * 4)) if _hip.KERNEL_TIMERS is not None else 0
-            with _hip._timed_bytes('bn_apply', nbytes):
-                X.check(X.lib.mvx_bn_apply_tiles_bev_frames(X.ptr(y), X.ptr(mi), X.ptr(c_o), X.ptr(tflag_o), X.ptr(mid), dout, H, W, co,
-                                                            F, X.stream()), 'mvx_bn_apply_tiles_bev_frames')
+            mid = _hip.bn_apply_tiles_bev(y, mi, c_o, tflag_o, F)
             x_out = None
         else:
             # conv2's output is read by conv3 only; conv3's (channels-last form: --mode full) by the RPN, everywhere
-            x_out = bn_apply_bg(y, mi, c_o, tflag_o, dout, ga['reads'][1] if li == 0 else None)
+            x_out = bn_apply_bg(y, mi, c_o, tflag_o, ga['reads'][1] if li == 0 else None)
         rec = dict(x=x_in, w=w, b=b, y=y, mi=mi, din=din, dout=dout, sd=sd, pd=pd, m=m, c_in=c_in, hflag_in=hflag_in,
                    bflag_in=bflag_in, split=split)
         if li == 0:
@@ -590,10 +422,7 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
         return None
     if x_in is None:
         return mid
-    mid = torch.empty((F, x_in.shape[-1] * D3, H, W), dtype=torch.float32, device=dev)
-    with _hip._timed_bytes('cl_bev_transpose', 2 * x_in.numel() * 4):
-        X.check(X.lib.mvx_cl_to_bev_frames(X.ptr(x_in), X.ptr(mid), D3, H, W, x_in.shape[-1], 0, F, X.stream()), 'mvx_cl_to_bev_frames')
-    return mid
+    return _hip.cl_to_bev(x_in, F)
 
 
 def _wgrad_bg_flops(rec, F):
@@ -619,21 +448,10 @@ def _wgrad_bg_flops(rec, F):
 def _wgrad_bg(rec, dz, tap_sums, F, H, W):
     if 'wgrad_bg' in KNOCKOUT:
         return
-    x, w = rec['x'], rec['w']
-    co, ci = w.shape[0], w.shape[1]
-    dw = _grad_of(w)
     fl = _wgrad_bg_flops(rec, F) if _hip.KERNEL_TIMERS is not None else 0      # a callable, evaluated after the timed region
-    nbytes = X.lib.mvx_conv3d_wgrad_bg_workspace_bytes_frames(rec['dout'], H, W, ci, co, F)
-    # split arithmetic (bf16x3 / bf16x6): the same entry point, conv3d_wgrad4s (csrc/conv3d.hip) under MVX_FLAG_SPLIT[3]
-    sp = _hip.split_flags(rec.get('split'), True)
-    with _hip._SideStream(x, dz, tap_sums, rec['c_in'], rec['hflag_in']):
-        ws = _hip.workspace(nbytes, x.device, 'wgrad_bg_side')
-        with _hip._Timed('conv3d_wgrad_bg', fl):
-            _hip.bind_amax(rec.get('split'), None, dz)
-            X.check(X.lib.mvx_conv3d_wgrad_bg_frames(X.ptr(x), X.ptr(dz), X.ptr(dw), rec['din'], rec['dout'], H, W, ci, co,
-                                                     rec['sd'], rec['pd'], _hip.FLAG_ACCUMULATE | sp, X.ptr(rec['hflag_in']),
-                                                     X.ptr(rec['c_in']), X.ptr(tap_sums), X.ptr(ws), ws.numel(), F, X.stream()),
-                    'mvx_conv3d_wgrad_bg_frames')
+    # on the side stream (_hip.ASYNC_WGRAD); split arithmetic: conv3d_wgrad4s (csrc/conv3d.hip) behind the same entry point
+    _hip.conv3d_wgrad_bg(rec['x'], dz, rec['sd'], rec['pd'], _hip.Background(rec['c_in'], None, rec['hflag_in']), tap_sums,
+                         accumulate_into=_grad_of(rec['w']), split=rec.get('split'), F=F, flops=fl)
 
 
 def _linear_wgrad_side(x, dz, w):
@@ -673,99 +491,59 @@ def cml_backward(model, S, grad_mid, g_cl=None):
         g = g_cl
     elif gm.shape[0] == 1 and F > 1:
         # one gradient map for every frame: transposed once, written F times (instead of a transposition and a repeat of it)
-        g = torch.empty((F * D3, H, W, C3), dtype=torch.float32, device=dev)
-        X.check(X.lib.mvx_bev_to_cl_broadcast(X.ptr(gm), X.ptr(g), D3, H, W, C3, F, X.stream()), 'mvx_bev_to_cl_broadcast')
+        g = _hip.bev_to_cl_broadcast(gm, D3, F)
     else:
-        g = torch.empty((F * D3, H, W, C3), dtype=torch.float32, device=dev)
-        X.check(X.lib.mvx_cl_to_bev_frames(X.ptr(g), X.ptr(gm), D3, H, W, C3, 1, F, X.stream()), 'mvx_cl_to_bev_frames')
+        g = _hip.bev_to_cl(gm, D3)
 
-    def tap_sums(dz, planes, Cn, tile_flags=None, inactive=None):
-        Tt = torch.empty((planes, 9, Cn), dtype=torch.float32, device=dev)
+    def tap_sums(dz, tile_flags=None, inactive=None):
         if 'tap_sums' in KNOCKOUT:
-            return Tt
-        ws = _hip.workspace(X.lib.mvx_plane_tap_sums_workspace_bytes(planes, Cn), dev, 'tap_sums')
-        X.check(X.lib.mvx_plane_tap_sums(X.ptr(dz), planes, H, W, Cn, X.ptr(tile_flags), X.ptr(inactive), X.ptr(Tt), X.ptr(ws),
-                                         ws.numel(), X.stream()), 'mvx_plane_tap_sums')
-        return Tt
+            return _knocked(dz, (dz.shape[0], 9, dz.shape[3]))
+        return _hip.plane_tap_sums(dz, tile_flags, inactive)
 
-    def tap_sums_side(name, dz, planes, Cn, tile_flags=None, inactive=None):
+    def tap_sums_side(name, dz, tile_flags=None, inactive=None):
         """The tap sums of a layer on the SIDE stream, in front of their first reader (the layer's weight gradient); returns
         (T, event): the main stream goes straight from the BatchNorm backward to the input-gradient gather and waits for the
         event only in front of input_grad_sums.  (T, None): computed inline."""
         if not _hip.ASYNC_WGRAD or 'tap_sums' in KNOCKOUT:
-            return _mut(name, tap_sums(dz, planes, Cn, tile_flags, inactive)), None
+            return _mut(name, tap_sums(dz, tile_flags, inactive)), None
         main = torch.cuda.current_stream(dev)
         with _hip._SideStream(dz, tile_flags, inactive):
-            Tt = _mut(name, tap_sums(dz, planes, Cn, tile_flags, inactive))
+            Tt = _mut(name, tap_sums(dz, tile_flags, inactive))
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
         Tt.record_stream(main)                  # allocated on the side stream's pool, read by input_grad_sums on the main stream
         return Tt, ev
 
     def dgrad_tiles(rec, dz, bflag):
-        w = rec['w']
-        co, ci = w.shape[0], w.shape[1]
-        dx = torch.empty((F * rec['din'], H, W, ci), dtype=torch.float32, device=dev)
-        wpd = rec['m']._packer(True, rec.get('split') or 0)
-        counter = None
-        if _hip.KERNEL_TIMERS is not None:
-            if _hip.EXEC_STAGES is None:
-                _hip.EXEC_STAGES = torch.zeros((1,), dtype=torch.int64, device=dev)
-            counter = _hip.EXEC_STAGES
-        if rec.get('split'):
-            with _hip._Timed('conv3d_gather_tiles', F * _hip.conv_flops(rec['din'], rec['dout'], H, W, co, ci, rec['sd'], rec['pd'], True)
-                             if _hip.KERNEL_TIMERS is not None else 0):
-                _hip.bind_amax(rec['split'], dz)
-                X.check(X.lib.mvx_conv3d_dgrad_tiles_split_frames(X.ptr(dz), X.ptr(wpd), X.ptr(dx), rec['din'], rec['dout'], H, W, ci,
-                                                                  co, rec['sd'], rec['pd'], _hip.split_flags(rec['split']), X.ptr(bflag),
-                                                                  X.ptr(counter), F, X.stream()), 'mvx_conv3d_dgrad_tiles_split_frames')
-            return dx
-        if 'gather_dgrad' in KNOCKOUT:
-            return dx
-        with _hip._Timed('conv3d_gather_tiles', F * _hip.conv_flops(rec['din'], rec['dout'], H, W, co, ci, rec['sd'], rec['pd'], True)
-                         if _hip.KERNEL_TIMERS is not None else 0):
-            X.check(X.lib.mvx_conv3d_dgrad_tiles_frames(X.ptr(dz), X.ptr(wpd), X.ptr(dx), rec['din'], rec['dout'], H, W, ci, co,
-                                                        rec['sd'], rec['pd'], X.ptr(bflag), X.ptr(counter),
-                                                        X.ptr(_hip._work_counter(dev)), F, X.stream()), 'mvx_conv3d_dgrad_tiles_frames')
-        return dx
+        split = rec.get('split') or 0
+        wpd = rec['m']._packer(True, split)
+        if 'gather_dgrad' in KNOCKOUT and not split:
+            return _knocked(dz, (F * rec['din'], H, W, rec['w'].shape[1]))
+        return _hip.conv3d_dgrad_tiles(dz, wpd, rec['din'], rec['w'].shape[1], rec['sd'], rec['pd'], bflag, split, F)
 
     def input_grad_sums(rec, Tt):
-        w = rec['w']
-        A = torch.empty((F * rec['din'], w.shape[1]), dtype=torch.float32, device=dev)
-        X.check(X.lib.mvx_conv3d_input_grad_sums_frames(X.ptr(w), X.ptr(Tt), rec['din'], rec['dout'], w.shape[1], w.shape[0],
-                                                        rec['sd'], rec['pd'], X.ptr(A), F, X.stream()), 'mvx_conv3d_input_grad_sums_frames')
-        return A
+        return _hip.conv3d_input_grad_sums(rec['w'], Tt, rec['din'], rec['sd'], rec['pd'], F)
 
-    def bn_bwd_tiles(gin, y, mi, c_bg, y_bg, A, bflag, planes, Cn, bias, want_inactive):
-        dz = torch.empty_like(y)
-        ws = _hip.workspace(X.lib.mvx_bn_relu_backward_tiles_workspace_bytes_frames(planes, H, W, Cn, F), dev, 'bn_tiles')
-        inact = torch.empty((F * planes, Cn), dtype=torch.float32, device=dev) if want_inactive else None
-        amax = _hip.new_amax(dev)                                             # max |dz| over the written tiles (zeroed by the call)
+    def bn_bwd_tiles(gin, y, mi, c_bg, y_bg, A, bflag, bias, want_inactive):
         if 'bn_bwd_tiles' in KNOCKOUT:
-            return dz, inact
-        # algorithmic bytes (timing runs only): the flagged 8x16 tiles, two passes reading dyhat and y, the second writing dz
-        nbytes = (lambda: bflag.ne(0).sum() * (128 * Cn * 4 * 5)) if _hip.KERNEL_TIMERS is not None else 0
-        with _hip._timed_bytes('bn_relu_backward_tiles', nbytes):
-            X.check(X.lib.mvx_bn_relu_backward_tiles_frames(X.ptr(gin), X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(y_bg), X.ptr(A),
-                                                            X.ptr(bflag), planes, H, W, Cn, X.ptr(dz), X.ptr(_grad_of(bias)),
-                                                            X.ptr(inact), X.ptr(amax), _hip.FLAG_ACCUMULATE, X.ptr(ws), ws.numel(), F,
-                                                            X.stream()), 'mvx_bn_relu_backward_tiles_frames')
-        return _hip.tag_amax(dz, amax), inact
+            return _knocked(y), (_knocked(y, (y.shape[0], y.shape[3])) if want_inactive else None)
+        bg = _hip.Background(c_bg, None, None, y_bg=y_bg, bflag=bflag)
+        out = _hip.bn_relu_backward_tiles(gin, y, mi, bg, A, _grad_of(bias), want_inactive, F)
+        return out[0], (out[2] if want_inactive else None)       # (dz, sums of dz over the other tiles)
 
     # ---- conv3: dense gradient in, restricted gradient + closed-form plane sums out
     r3, r2 = S.convs[1], S.convs[0]
     dz3 = bn_relu_backward(g, r3['y'], r3['mi'], fs, X.ROWS_GRID, None, _grad_of(r3['b']))
-    T3, ev3 = tap_sums_side('T3', dz3, F * r3['dout'], r3['w'].shape[0])
+    T3, ev3 = tap_sums_side('T3', dz3)
     _wgrad_bg(r3, dz3, T3, F, H, W)
     g2 = dgrad_tiles(r3, dz3, r3['bflag_in'])
     if ev3 is not None:
         torch.cuda.current_stream(dev).wait_event(ev3)
     A2 = _mut('A2', input_grad_sums(r3, T3))
     # ---- conv2
-    dz2, inact2 = bn_bwd_tiles(g2, r2['y'], r2['mi'], r2['c_out'], r2['ybg_out'], A2, r2['bflag_out'], r2['dout'],
-                               r2['w'].shape[0], r2['b'], True)
+    dz2, inact2 = bn_bwd_tiles(g2, r2['y'], r2['mi'], r2['c_out'], r2['ybg_out'], A2, r2['bflag_out'], r2['b'], True)
     inact2 = _mut('inact2', inact2)
-    T2, ev2 = tap_sums_side('T2', dz2, F * r2['dout'], r2['w'].shape[0], r2['bflag_out'], inact2)
+    T2, ev2 = tap_sums_side('T2', dz2, r2['bflag_out'], inact2)
     _wgrad_bg(r2, dz2, T2, F, H, W)
     g1 = dgrad_tiles(r2, dz2, r2['bflag_in'])
     if ev2 is not None:
@@ -775,12 +553,9 @@ def cml_backward(model, S, grad_mid, g_cl=None):
     c1 = S.conv1
     w1 = c1['w']
     cout, cin = w1.shape[0], w1.shape[1]
-    dz1, _ = bn_bwd_tiles(g1, c1['y'], c1['mi'], c1['c'], c1['ybg'], A1, c1['tflag'], c1['D1'], cout, c1['b'], False)
-    G = torch.empty((Vt, 27 * cout), dtype=torch.float32, device=dev)
+    dz1, _ = bn_bwd_tiles(g1, c1['y'], c1['mi'], c1['c'], c1['ybg'], A1, c1['tflag'], c1['b'], False)
     cm = model.backbone.cml.conv1
-    X.check(X.lib.mvx_sparse_conv_gather_dz_frames(X.ptr(dz1), X.ptr(fs.coords), Vt, X.ptr(G), c1['D0'], c1['D1'], H, W, cout,
-                                                   cm._sd, cm._pd, fs.desc.ref(), X.stream()), 'mvx_sparse_conv_gather_dz_frames')
-    _hip.tag_amax(G, _hip.amax_of(dz1))                                    # G's rows are rows of dz1
+    G = _hip.sparse_conv_gather_dz(dz1, fs.coords, c1['D0'], cm._sd, cm._pd, fs.desc)      # its rows are rows of dz1: keeps the range tag
     # conv1's weight gradient ((27 * cout, cin) = G^T feat, then reordered into the parameter's layout): off the main stream like
     # the other weight gradients -- the main stream goes on to the input gradient
     with _hip._SideStream(c1['feat'], G):
@@ -810,19 +585,14 @@ def rows_backward(model, S, dfeat):
     # ---- FCN + max
     x, w, b, y, mi, am = S.head
     Cn = w.shape[0]
-    dyh = torch.empty((Rt + Vt, Cn), dtype=torch.float32, device=dev)
-    X.check(X.lib.mvx_segment_max_backward(X.ptr(dfeat), X.ptr(am), X.ptr(dyh), Vt, T, Cn, X.ptr(fs.voff), X.ptr(fs.vcnt), Rt,
-                                           X.stream()), 'mvx_segment_max_backward')
+    dyh = _hip.segment_max_backward(dfeat, am, Vt, T, fs)
     dz = bn_relu_backward(dyh, y, mi, fs, X.ROWS_VFE, fs.row_w, _grad_of(b), dz=dyh)
     _linear_wgrad_side(x, dz, w)
     gx = _rows_dgrad(dz, w)
     # ---- VFE 2, VFE 1
     for x, w, b, y, mi, am in reversed(S.vfe):
         Cn = w.shape[0]
-        dyh = torch.empty((Rt + Vt, Cn), dtype=torch.float32, device=dev)
-        with _hip._timed_bytes('vfe_max_concat_backward', (Rt + Vt) * Cn * 4 * 3 + Vt * Cn * 4):  # read [gx | gmax] + argmax, write dyhat
-            X.check(X.lib.mvx_vfe_max_concat_backward(X.ptr(gx), X.ptr(am), X.ptr(dyh), Vt, T, Cn, X.ptr(fs.voff), X.ptr(fs.vcnt),
-                                                      Rt, X.stream()), 'mvx_vfe_max_concat_backward')
+        dyh = _hip.vfe_max_concat_backward(gx, am, Vt, T, fs)
         dz = bn_relu_backward(dyh, y, mi, fs, X.ROWS_VFE, fs.row_w, _grad_of(b), dz=dyh)
         w2 = w.reshape(w.shape[0], -1)
         if x.shape[1] != w2.shape[1] and 'lin_wgrad' not in KNOCKOUT:
@@ -835,10 +605,7 @@ def rows_backward(model, S, dfeat):
         gx = _rows_dgrad(dz, w)
     # ---- concat backward: gradient of the fused image features ([real rows | shared padded row per frame])
     Fc = S.fc
-    gim = torch.empty((Rt + F, Fc), dtype=torch.float32, device=dev)
-    scratch = torch.empty((F * Fc,), dtype=torch.float64, device=dev)
-    X.check(X.lib.mvx_vfe_compact_input_backward_frames(X.ptr(gx), Fc, Rt, Vt, X.ptr(gim), X.ptr(scratch), fs.desc.ref(),
-                                                        X.stream()), 'mvx_vfe_compact_input_backward_frames')
+    gim = _hip.vfe_compact_input_backward(gx, Fc, fs)
     # ---- fusion MLP, last layer first; the sampled features carry no gradient
     gx = gim
     for i in range(len(S.fusion) - 1, -1, -1):

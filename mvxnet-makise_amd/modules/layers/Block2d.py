@@ -16,10 +16,7 @@ import torch
 
 import modules.config as cfg
 from modules import _hip
-from modules import Extension as X
 from modules import rpn_frames as rf
-
-R = _hip.STATS_REPLICAS
 
 
 def kind_of(module_kind, k, s, p, cin, cout):
@@ -93,14 +90,9 @@ class Block2dFunction(torch.autograd.Function):
             xr = xc.view(h * wd, cin)
             t, _ = _hip.linear_forward(xr, w_all, b.repeat(s * s), relu=True, want_stats=False, split=_hip.row_split('rpn'),
                                        foreign=not getattr(x, '_mvx_lib', False))
-            stats = torch.empty((1, R, 2, cout), dtype=torch.float64, device=x.device)
-            X.check(X.lib.mvx_row_stats_frames(X.ptr(t), X.ptr(stats), t.numel() // cout, cout, 1, X.stream()), 'mvx_row_stats_frames')
-            mi = torch.empty((1, 2, cout), dtype=torch.float32, device=x.device)
-            X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(h * wd * s * s), float(eps), X.ptr(mi), cout, 1, X.stream()),
-                    'mvx_bn_finalize_frames')
+            mi = _hip.bn_finalize(_hip.row_stats_frames(t, cout, 1), h * wd * s * s, eps, 1)
             out = torch.empty((1, h * s, wd * s, cout), dtype=torch.float32, device=x.device)
-            X.check(X.lib.mvx_d2s_bn_apply_frames(X.ptr(t), X.ptr(mi), X.ptr(out), 1, h, wd, s, cout, cout, 0, 0, X.stream()),
-                    'mvx_d2s_bn_apply_frames')
+            _hip.d2s_bn_apply(t, mi, out, 1, h, wd, s, cout, cout, 0)
             y = t
             S.update(xr=xr, w_all=w_all, s=s)
         S.update(y=y, mi=mi, h=h, w=wd, cin=cin, cout=cout)
@@ -144,8 +136,7 @@ class Block2dFunction(torch.autograd.Function):
             else:
                 s = S['s']
                 gt = torch.empty_like(S['y'])
-                X.check(X.lib.mvx_d2s_bn_apply_frames(X.ptr(gt), None, X.ptr(gc), 1, h, wd, s, cout, cout, 0, 1, X.stream()),
-                        'mvx_d2s_bn_apply_frames')
+                _hip.d2s_bn_apply(gt, None, gc, 1, h, wd, s, cout, cout, 0, reverse=True)
                 dz0 = rf._bn_bwd(gt.view(-1, cout), S['y'].view(-1, cout), S['mi'], 1, b)
                 dz = rf._retag(dz0.view(S['y'].shape), dz0)
                 dw_all = _hip.linear_wgrad(S['xr'], dz)                           # (s*s*cout, cin)

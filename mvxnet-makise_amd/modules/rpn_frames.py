@@ -25,8 +25,7 @@ import modules.config as cfg
 from modules import _hip
 from modules import Extension as X
 
-R = _hip.STATS_REPLICAS
-TAPS2 = 16          # MVX_FLAG_TAPS2
+TAPS2 = _hip.FLAG_TAPS2
 
 
 def _split():
@@ -140,47 +139,18 @@ def _desc(F):
     return X.FramesDesc.make([0] * (F + 1), [0] * (F + 1), 1)
 
 
+# The convolution wrappers of _hip in this RPN's arithmetic (_split) and with its gradient targets (_grad_of).
 def _conv(x, wpk, bias, F, h, w, cin, cout, flags, eps):
     """y = ReLU(conv(x) + b) with per-frame statistics finalised in the launch -> (y, mean_inv (F,2,cout))."""
-    dev = x.device
-    y = torch.empty((F, h, w, cout), dtype=torch.float32, device=dev)
-    stats, fz = _hip._acc_f64((F, R, 2, cout), dev)
-    fin = _hip._fin_slot(dev, fz)
-    if fin is None:
-        fin = torch.zeros((1,), dtype=torch.float64, device=dev)
-    mi = torch.empty((F, 2, cout), dtype=torch.float32, device=dev)
-    if _split():                               # split arithmetic (bf16x3 / bf16x6), same window / structural-zero skipping
-        with _hip._Timed('rpn_conv', 2.0 * F * h * w * cin * cout * (2.25 if flags & TAPS2 else 9) if _hip.KERNEL_TIMERS is not None else 0):
-            X.check(X.lib.mvx_conv2d_forward_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), X.ptr(stats), h, w, cin, cout,
-                                                          _hip.FLAG_RELU | fz | flags | _hip.split_flags(_split()), F, X.stream()), 'mvx_conv2d_forward_split_frames')
-        X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(h * w), float(eps), X.ptr(mi), cout, F, X.stream()),
-                'mvx_bn_finalize_frames')
-        return y, mi
-    nt = 2.25 if flags & TAPS2 else 9          # space-to-depth form: 9 of the 16 (window tap, parity) blocks are executed
-    with _hip._Timed('rpn_conv', 2.0 * F * h * w * cin * cout * nt if _hip.KERNEL_TIMERS is not None else 0):
-        X.check(X.lib.mvx_conv2d_forward_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), X.ptr(stats), h, w, cin, cout,
-                                                _hip.FLAG_RELU | fz | flags, X.ptr(fin), float(eps), X.ptr(mi),
-                                                X.ptr(_hip._work_counter(dev)), F, X.stream()), 'mvx_conv2d_forward_frames')
-    return y, mi
+    return _hip.conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, _split())
 
 
 def _bn_apply(y, mi, F):
-    C = mi.shape[-1]
-    out = torch.empty_like(y)
-    X.check(X.lib.mvx_bn_apply_frames(X.ptr(y), X.ptr(mi), X.ptr(out), y.numel() // C, C, _desc(F).ref(), X.ROWS_GRID, X.stream()),
-            'mvx_bn_apply_frames')
-    return out
+    return _hip.bn_apply(y, mi, desc=_desc(F), kind=X.ROWS_GRID, timed=False)
 
 
 def _bn_bwd(g, y, mi, F, bias):
-    C = mi.shape[-1]
-    dz = torch.empty_like(y)
-    scratch, fz = _hip._acc_f64((X.lib.mvx_bn_backward_scratch_bytes_frames(C, F) // 8,), y.device)
-    amax = _hip.new_amax(y.device)
-    X.check(X.lib.mvx_bn_relu_backward_frames(X.ptr(g), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dz), X.ptr(_grad_of(bias)), X.ptr(scratch),
-                                              None, y.numel() // C, C, _hip.FLAG_ACCUMULATE | fz, _desc(F).ref(), X.ROWS_GRID,
-                                              X.ptr(amax), X.stream()), 'mvx_bn_relu_backward_frames')
-    return _hip.tag_amax(dz, amax)                      # max |dz|: the range the fp16x3 kernels scale dz by
+    return _hip.bn_relu_backward(g, y, mi, 1.0, dbias_out=_grad_of(bias), desc=_desc(F), kind=X.ROWS_GRID, timed=False)[0]
 
 
 def _retag(t, like):
@@ -189,47 +159,20 @@ def _retag(t, like):
 
 
 def _dgrad(dz, wpd, F, h, w, cin, cout, flags):
-    dx = torch.empty((F, h, w, cin), dtype=torch.float32, device=dz.device)
-    if _split():
-        with _hip._Timed('rpn_conv', 2.0 * F * h * w * cin * cout * (2.25 if flags & TAPS2 else 9) if _hip.KERNEL_TIMERS is not None else 0):
-            _hip.bind_amax(_split(), dz)
-            X.check(X.lib.mvx_conv2d_dgrad_split_frames(X.ptr(dz), X.ptr(wpd), X.ptr(dx), h, w, cin, cout, flags | _hip.split_flags(_split()), F, X.stream()),
-                    'mvx_conv2d_dgrad_split_frames')
-        return dx
-    nt = 2.25 if flags & TAPS2 else 9
-    with _hip._Timed('rpn_conv', 2.0 * F * h * w * cin * cout * nt if _hip.KERNEL_TIMERS is not None else 0):
-        X.check(X.lib.mvx_conv2d_dgrad_frames(X.ptr(dz), X.ptr(wpd), X.ptr(dx), h, w, cin, cout, flags,
-                                              X.ptr(_hip._work_counter(dz.device)), F, X.stream()), 'mvx_conv2d_dgrad_frames')
-    return dx
+    return _hip.conv2d_dgrad(dz, wpd, F, h, w, cin, cout, flags, _split())
 
 
 def _wgrad(x, dz, F, h, w, cin, cout, flags, into=None):
     """dW (cout, cin, 3, 3) over all frames, on the side stream; ADDED into ``into`` or returned."""
-    dev = x.device
-    # split arithmetic: the same entry point and workgroup decomposition (conv3d_wgrad4s, csrc/conv3d.hip) -- MVX_FLAG_SPLIT[3]
-    sp = _hip.split_flags(_split(), True)
-    nbytes = X.lib.mvx_conv2d_wgrad_workspace_bytes_frames(h, w, cin, cout, F)
-    dw = into if into is not None else torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev)
-    nt = 2.25 if flags & TAPS2 else 9
-    with _hip._SideStream(x, dz, dw), _hip._Timed('rpn_wgrad', 2.0 * F * h * w * cin * cout * nt if _hip.KERNEL_TIMERS is not None else 0):
-        ws = _hip.workspace(nbytes, dev, 'rpn_wgrad_side')
-        _hip.bind_amax(_split(), None, dz)
-        X.check(X.lib.mvx_conv2d_wgrad_frames(X.ptr(x), X.ptr(dz), X.ptr(dw), h, w, cin, cout,
-                                              flags | sp | (_hip.FLAG_ACCUMULATE if into is not None else 0), X.ptr(ws), ws.numel(), F,
-                                              X.stream()), 'mvx_conv2d_wgrad_frames')
-    return dw
+    return _hip.conv2d_wgrad(x, dz, F, h, w, cin, cout, flags, into, _split())
 
 
 def _s2d(x, F, planes, h, w, C):
-    out = torch.empty((F, h // 2, w // 2, 4 * planes * C), dtype=torch.float32, device=x.device)
-    X.check(X.lib.mvx_space_to_depth_frames(X.ptr(x), X.ptr(out), F, planes, h, w, C, 0, X.stream()), 'mvx_space_to_depth_frames')
-    return out
+    return _hip.space_to_depth(x, F, planes, h, w, C)
 
 
 def _d2s(xs, F, planes, h, w, C):
-    out = torch.empty((F * planes, h, w, C), dtype=torch.float32, device=xs.device)
-    X.check(X.lib.mvx_space_to_depth_frames(X.ptr(xs), X.ptr(out), F, planes, h, w, C, 1, X.stream()), 'mvx_space_to_depth_frames')
-    return out
+    return _hip.space_to_depth(xs, F, planes, h, w, C, reverse=True)
 
 
 def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
@@ -269,8 +212,7 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
     d1 = rpn.deconv1
     wc = pk.get(('d1',), d1.deconv.weight, lambda: d1.deconv.weight.flip(2, 3).transpose(0, 1).contiguous(), False)
     y, mi = _conv(x1, wc, d1.deconv.bias, F, h1, w1, 128, 256, 0, eps)
-    X.check(X.lib.mvx_bn_apply_strided_frames(X.ptr(y), X.ptr(mi), X.ptr(up), rows, 256, 768, 0, F, 0, X.stream()),
-            'mvx_bn_apply_strided_frames')
+    _hip.bn_apply_strided(y, mi, up, rows, 256, 768, 0, F)
     S['d1'] = dict(x=x1, y=y, mi=mi)
     # deconv2 / deconv3: kernel = stride -> row GEMM + normalising pixel shuffle into the concat slice
     S['dk'] = []
@@ -280,13 +222,8 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
         w_all = wt.permute(2, 3, 1, 0).reshape(s * s * cout, cin).contiguous()     # row (i*s+j)*Cout + co
         xr = xk.view(F * hk * wk, cin)
         t, _ = _hip.linear_forward(xr, w_all, b.repeat(s * s), relu=True, want_stats=False, split=_hip.row_split('rpn'))
-        stats = torch.empty((F, R, 2, cout), dtype=torch.float64, device=dev)
-        X.check(X.lib.mvx_row_stats_frames(X.ptr(t), X.ptr(stats), t.numel() // cout, cout, F, X.stream()), 'mvx_row_stats_frames')
-        mi = torch.empty((F, 2, cout), dtype=torch.float32, device=dev)
-        X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(hk * wk * s * s), float(eps), X.ptr(mi), cout, F, X.stream()),
-                'mvx_bn_finalize_frames')
-        X.check(X.lib.mvx_d2s_bn_apply_frames(X.ptr(t), X.ptr(mi), X.ptr(up), F, hk, wk, s, cout, 768, off, 0, X.stream()),
-                'mvx_d2s_bn_apply_frames')
+        mi = _hip.bn_finalize(_hip.row_stats_frames(t, cout, F), hk * wk * s * s, eps, F)
+        _hip.d2s_bn_apply(t, mi, up, F, hk, wk, s, cout, 768, off)
         S['dk'].append(dict(x=xr, t=t, mi=mi, m=m, s=s, off=off, h=hk, w=wk, w_all=w_all, cin=cin, cout=cout))
     # heads (Pipe.py:64-65,74): one GEMM, 16 columns
     w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768)]).contiguous()
@@ -341,8 +278,7 @@ def rpn_backward(rpn, S, d_heads):
     for rec in S['dk']:
         m, s, off, hk, wk, cin, cout = rec['m'], rec['s'], rec['off'], rec['h'], rec['w'], rec['cin'], rec['cout']
         gt = torch.empty_like(rec['t'])
-        X.check(X.lib.mvx_d2s_bn_apply_frames(X.ptr(gt), None, X.ptr(g_up), F, hk, wk, s, cout, 768, off, 1, X.stream()),
-                'mvx_d2s_bn_apply_frames')
+        _hip.d2s_bn_apply(gt, None, g_up, F, hk, wk, s, cout, 768, off, reverse=True)
         dz0 = _bn_bwd(gt.view(-1, cout), rec['t'].view(-1, cout), rec['mi'], F, m.deconv.bias)
         dz = _retag(dz0.view(rec['t'].shape), dz0)
         with _hip._SideStream(rec['x'], dz):
@@ -356,8 +292,7 @@ def rpn_backward(rpn, S, d_heads):
     # deconv1
     d1 = rpn.deconv1
     g1 = torch.empty((rows, 256), dtype=torch.float32, device=dev)
-    X.check(X.lib.mvx_bn_apply_strided_frames(X.ptr(g1), None, X.ptr(g_up), rows, 256, 768, 0, F, 1, X.stream()),
-            'mvx_bn_apply_strided_frames')
+    _hip.bn_apply_strided(g1, None, g_up, rows, 256, 768, 0, F, reverse=True)
     r1 = S['d1']
     dz = _bn_bwd(g1.view(F, h1, w1, 256), r1['y'], r1['mi'], F, d1.deconv.bias)
     dwc = _wgrad(r1['x'], dz, F, h1, w1, 128, 256, 0)                      # gradient of the flipped / transposed kernel

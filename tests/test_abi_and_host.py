@@ -68,6 +68,20 @@ def test_product_path_never_imports_the_oracle():
                 assert 'mvx_oracle' not in src and 'liboracle' not in src and 'oracle/' not in src, f
 
 
+def test_only_hip_py_names_the_c_entry_points():
+    """Every kernel call of the package has ONE Python wrapper, in modules/_hip.py (Extension.py loads the library): no other
+    file of the package names an ``X.lib.mvx_*`` function."""
+    import re as _re
+    pkg = os.path.join(REPO, 'mvxnet-makise_amd')
+    raw = []
+    for root, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith('.py') and f not in ('_hip.py', 'Extension.py'):
+                src = open(os.path.join(root, f)).read()
+                raw += ['%s: %s' % (os.path.relpath(os.path.join(root, f), pkg), m) for m in _re.findall(r'lib\.mvx_\w+', src)]
+    assert not raw, raw
+
+
 def test_config_surface():
     import modules.config as cfg
     assert cfg.voxelshape == [352, 400, 10] and cfg.samplenum == 35
