@@ -978,6 +978,68 @@ int mvx_kitti_eval_counts(int32_t n_frames, const int32_t *off_host, const int32
                           const int32_t *n_thresholds, int32_t *totals, double *similarity, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * GT-paste augmentation (csrc/augment.hip): the reference's modules/augment/Augment.py (check / locate / augment, called
+ * by train.py:28) plus the concatenation of train.py:37-42, for the frames of a step (1..MVX_MAX_FRAMES) in four launches.
+ * The host draws the random numbers (candidates and thresholds per slot, in the reference's order); the kernels decide.
+ *
+ * The object database is a set of device-resident flat tables over n_db objects (modules/augment/LoadGT.GTDatabase):
+ *   db_box2d f32 [n_db][4] x1 y1 x2 y2, db_box3d f32 [n_db][7] xyzlwhr, db_bev f32 [n_db][4][2] (Calc.bbox3d2bev of db_box3d),
+ *   db_points f32 [sum][6] = x y z r row col with pt_off i64 [n_db + 1] (row offsets),
+ *   patch u8 [sum_px][3], mask u8 [sum_px] (zero / non-zero) with px_off i64 [n_db + 1] (pixel offsets) and maskbbox i32
+ *   [n_db][4] = x1 y1 x2 y2 inclusive in image pixels: object k's patch is (y2-y1+1) rows of (x2-x1+1) pixels.
+ *
+ * mvx_gt_paste_ground_frames: zmax f32 [n_frames][grid_h][grid_w] (mvx_gt_paste_workspace_bytes bytes) = the largest z of
+ *   the scene points points6 f32 [n_frames][cap_points][6] (the first n_points[f] rows) of every cell, cells without a point
+ *   hold (float)(lo_z - 1).  Cell of a point: (int)(((double)x - lo_x) / ((hi_x - lo_x) / grid_h)), the same for y (Augment.py:16-17).
+ *   Points outside [lo, hi) in x or y, or with a NaN z, are skipped (the reference indexes out of bounds); -0 counts as +0.
+ *   A fill and ONE kernel; integer atomics on the f32 bit patterns (the maximum is exact and order-independent).
+ * mvx_gt_paste_place_frames: one workgroup per frame.  The frame's scene boxes box2d f32 [n_frames][cap][4], box3d
+ *   [n_frames][cap][7], bev [n_frames][cap][4][2] hold n_scene[f] rows on entry and n_out[f] rows on return (grown in place).
+ *   A frame with n_scene[f] > lim gets nothing; otherwise S = lim - n_scene[f] slots run in sequence (S <= s_max).  Slot s
+ *   tests its candidates cand i32 [n_frames][s_max][n_cand] (database indices, -1 = none) in order and takes the first that
+ *   passes:  test 0 (ground): cell (int)((x - lo_x) / cell), (int)((y - lo_y) / cell) in f32 (a true division); rejected when
+ *   the cell is outside the grid or zmax[cell] > z + z_margin;  with no scene box so far the candidate is accepted here;
+ *   test 1 (2-D): rejected when max_i inter(box2d_i, candidate) / area(box2d_i) > thr[f][s] (f32, utils/Bbox.py);
+ *   test 2 (BEV): rejected when max_i IoU(candidate bev, bev_i) > iou_thr, IoU as mvx_bbox_pairwise(candidate, box i);
+ *   pairs whose bounding circles cannot touch count as IoU 0.  The winner's three boxes are appended, so later slots test
+ *   against it.  picked i32 [n_frames][s_max] = its database index or -1.  Optional debug outputs (both or none):
+ *   dbg_fail i32 [n_frames][s_max][n_cand] = the first failing test 0..2, 3 = passes all, -1 = no candidate / slot not run;
+ *   dbg_val f32 [n_frames][s_max][n_cand][3] = (zmax of the cell, max 2-D ratio, max IoU).
+ * mvx_gt_paste_points_frames: appends the rows of every picked object, in slot order, behind the n_points[f] scene rows of
+ *   points6[f]; n_points_out[f] (a different array) = the new count.  An object that does not fit cap_points is dropped as
+ *   a whole and reported.  points6 and db_points 16-byte aligned.
+ * mvx_gt_paste_image_frames: img u8 [n_frames][h][w][3]: for every picked object in slot order img = mask ? patch : img over
+ *   its maskbbox, clipped to the image; a later slot overwrites an earlier one.  max_patch_px: the largest patch of the
+ *   database in pixels (sizes the grid).
+ * status i32 [n_frames] (OR-ed into, zero it first): MVX_GT_PASTE_POINTS_OVERFLOW, MVX_GT_PASTE_BAD_COUNT (n_scene outside
+ *   0..cap: frame untouched), MVX_GT_PASTE_SLOTS_SHORT (lim - n_scene > s_max: only s_max slots ran), MVX_GT_PASTE_BAD_INDEX
+ *   (a candidate index >= n_db, treated as none).  Argument errors return MVX_EINVAL before any launch.  No float atomics
+ *   (bitwise reproducible), no host synchronisation.
+ */
+#define MVX_GT_PASTE_MAX_BOXES 32
+#define MVX_GT_PASTE_MAX_CAND 32
+#define MVX_GT_PASTE_MAX_SLOTS 32
+#define MVX_GT_PASTE_POINTS_OVERFLOW 1
+#define MVX_GT_PASTE_BAD_COUNT 2
+#define MVX_GT_PASTE_SLOTS_SHORT 4
+#define MVX_GT_PASTE_BAD_INDEX 8
+size_t mvx_gt_paste_workspace_bytes(int32_t n_frames, int32_t grid_h, int32_t grid_w);
+int mvx_gt_paste_ground_frames(const float *points6, const int32_t *n_points, int32_t n_frames, int32_t cap_points, double lo_x,
+                               double lo_y, double lo_z, double hi_x, double hi_y, int32_t grid_h, int32_t grid_w, float *zmax,
+                               size_t zmax_bytes, void *stream);
+int mvx_gt_paste_place_frames(const float *zmax, int32_t grid_h, int32_t grid_w, float lo_x, float lo_y, float cell, float z_margin,
+                              float iou_thr, float *box2d, float *box3d, float *bev, const int32_t *n_scene, int32_t n_frames,
+                              int32_t cap, int32_t lim, const int32_t *cand, const float *thr, int32_t s_max, int32_t n_cand,
+                              const float *db_box2d, const float *db_box3d, const float *db_bev, int32_t n_db, int32_t *picked,
+                              int32_t *n_out, int32_t *status, int32_t *dbg_fail, float *dbg_val, void *stream);
+int mvx_gt_paste_points_frames(float *points6, const int32_t *n_points, int32_t *n_points_out, int32_t n_frames,
+                               int32_t cap_points, const int32_t *picked, int32_t s_max, const float *db_points,
+                               const int64_t *pt_off, int32_t n_db, int32_t *status, void *stream);
+int mvx_gt_paste_image_frames(uint8_t *img, int32_t n_frames, int32_t h, int32_t w, const int32_t *picked, int32_t s_max,
+                              const uint8_t *patch, const uint8_t *mask, const int64_t *px_off, const int32_t *maskbbox,
+                              int32_t n_db, int64_t max_patch_px, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

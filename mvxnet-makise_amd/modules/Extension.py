@@ -186,6 +186,12 @@ PROTOTYPES = {
     'mvx_kitti_eval_thresholds': (_i32, [_i32, _i32, _i64, _p, _p, _p, _p, _p, _p]),
     'mvx_kitti_eval_counts': (_i32, [_i32, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                      _sz, _p]),
+    'mvx_gt_paste_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'mvx_gt_paste_ground_frames': (_i32, [_p, _p, _i32, _i32, _f64, _f64, _f64, _f64, _f64, _i32, _i32, _p, _sz, _p]),
+    'mvx_gt_paste_place_frames': (_i32, [_p, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _i32,
+                                         _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p]),
+    'mvx_gt_paste_points_frames': (_i32, [_p, _p, _p, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p]),
+    'mvx_gt_paste_image_frames': (_i32, [_p, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i64, _p]),
 }
 
 

@@ -2035,3 +2035,70 @@ def kitti_eval_counts(inp, t, ov, dco, thr, n_thr):
                                         X.ptr(ov), X.ptr(dco), X.ptr(thr), X.ptr(n_thr), X.ptr(totals), X.ptr(sim), X.ptr(ws),
                                         ws.numel(), X.stream()), 'mvx_kitti_eval_counts')
     return totals, sim
+
+
+# ---------------------------------------------------------------------------------------------
+# GT-paste augmentation (csrc/augment.hip); ``db`` is a modules.augment.LoadGT.GTDatabase on the device
+# ---------------------------------------------------------------------------------------------
+GT_PASTE_MAX_BOXES, GT_PASTE_MAX_CAND, GT_PASTE_MAX_SLOTS = 32, 32, 32      # MVX_GT_PASTE_MAX_*
+GT_PASTE_POINTS_OVERFLOW, GT_PASTE_BAD_COUNT, GT_PASTE_SLOTS_SHORT, GT_PASTE_BAD_INDEX = 1, 2, 4, 8
+
+
+def gt_paste_ground(points6, n_points, range6, grid_shape=(704, 800)):
+    """zmax f32 (F, gh, gw): the largest z of the scene points of every x/y cell, (float)(range6[2] - 1) where there is none
+    (Augment.py check).  points6 f32 (F, cap, 6), n_points i32 (F,)."""
+    F, cap = points6.shape[0], points6.shape[1]
+    gh, gw = int(grid_shape[0]), int(grid_shape[1])
+    dev = points6.device
+    nbytes = X.lib.mvx_gt_paste_workspace_bytes(F, gh, gw)
+    zmax = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
+    X.check(X.lib.mvx_gt_paste_ground_frames(X.ptr(points6), X.ptr(n_points), F, cap, float(range6[0]), float(range6[1]),
+                                             float(range6[2]), float(range6[3]), float(range6[4]), gh, gw, X.ptr(zmax), nbytes,
+                                             X.stream()), 'mvx_gt_paste_ground_frames')
+    return zmax[:F * gh * gw].view(F, gh, gw)
+
+
+def gt_paste_place(zmax, range6, box2d, box3d, bev, n_scene, lim, cand, thr, db, status, cell=0.1, z_margin=0.1, iou_thr=0.05,
+                   debug=False):
+    """The placement of all frames in one launch.  zmax (F, gh, gw); the scene tables box2d (F, cap, 4), box3d (F, cap, 7),
+    bev (F, cap, 4, 2) grow in place; n_scene i32 (F,); cand i32 (F, S, C), thr f32 (F, S); status i32 (F,) is OR-ed into.
+    Returns (picked i32 (F, S), n_out i32 (F,)) plus (first failing test i32 (F, S, C), decision values f32 (F, S, C, 3))
+    with ``debug``."""
+    F, gh, gw = zmax.shape
+    cap = box2d.shape[1]
+    S, C = cand.shape[1], cand.shape[2]
+    dev = zmax.device
+    assert box2d.shape == (F, cap, 4) and box3d.shape == (F, cap, 7) and bev.shape == (F, cap, 4, 2)
+    assert cand.shape[0] == F and thr.shape == (F, S) and cand.dtype == torch.int32 and thr.dtype == torch.float32
+    picked = torch.empty((F, S), dtype=torch.int32, device=dev)
+    n_out = torch.empty((F,), dtype=torch.int32, device=dev)
+    dbg = (None, None)
+    if debug:
+        dbg = (torch.empty((F, S, C), dtype=torch.int32, device=dev), torch.empty((F, S, C, 3), dtype=torch.float32, device=dev))
+    X.check(X.lib.mvx_gt_paste_place_frames(X.ptr(zmax), gh, gw, float(range6[0]), float(range6[1]), float(cell), float(z_margin),
+                                            float(iou_thr), X.ptr(box2d), X.ptr(box3d), X.ptr(bev), X.ptr(n_scene), F, cap,
+                                            int(lim), X.ptr(cand), X.ptr(thr), S, C, X.ptr(db.box2d), X.ptr(db.box3d),
+                                            X.ptr(db.bev), db.n, X.ptr(picked), X.ptr(n_out), X.ptr(status), X.ptr(dbg[0]),
+                                            X.ptr(dbg[1]), X.stream()), 'mvx_gt_paste_place_frames')
+    out = (picked, n_out)
+    return out + dbg if debug else out
+
+
+def gt_paste_points(points6, n_points, picked, db, status):
+    """Appends the picked objects' rows behind the scene points of every frame (in place); returns the new counts i32 (F,)."""
+    F, cap = points6.shape[0], points6.shape[1]
+    n_new = torch.empty((F,), dtype=torch.int32, device=points6.device)
+    X.check(X.lib.mvx_gt_paste_points_frames(X.ptr(points6), X.ptr(n_points), X.ptr(n_new), F, cap, X.ptr(picked), picked.shape[1],
+                                             X.ptr(db.points), X.ptr(db.pt_off), db.n, X.ptr(status), X.stream()),
+            'mvx_gt_paste_points_frames')
+    return n_new
+
+
+def gt_paste_image(img, picked, db):
+    """img u8 (F, H, W, 3) in place: every picked object's patch under its mask, later slots over earlier ones."""
+    F, H, W = img.shape[0], img.shape[1], img.shape[2]
+    assert img.dtype == torch.uint8 and img.shape[3] == 3
+    X.check(X.lib.mvx_gt_paste_image_frames(X.ptr(img), F, H, W, X.ptr(picked), picked.shape[1], X.ptr(db.patch), X.ptr(db.mask),
+                                            X.ptr(db.px_off), X.ptr(db.maskbbox), db.n, int(db.max_patch_px), X.stream()),
+            'mvx_gt_paste_image_frames')
+    return img

@@ -1,0 +1,2 @@
+"""GT-paste augmentation (reference modules/augment): ``Augment`` places database objects into the frames of a step on the
+GPU (csrc/augment.hip), ``LoadGT`` reads the object database and packs it into device-resident tables."""

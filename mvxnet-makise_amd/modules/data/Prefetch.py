@@ -39,13 +39,14 @@ class _Staging:
 
 
 class PrefetchLoader:
-    def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1):
+    def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1, augment=None):
         """``groups``: iterable of lists of frames as ``modules.data.Load.createDataset`` returns them; ``names_of(frame)``:
         the frame's name (for ``fpn_fn``); ``fpn_fn(name, device)``: the frame's FPN maps (the frozen extractor or its
         stand-in); ``cap_points``: point capacity per frame of the resident batch."""
         self.groups = iter(groups)
         self.names_of, self.device, self.anchor_bevs, self.fpn_fn = names_of, device, anchor_bevs, fpn_fn
         self.cap = int(cap_points)
+        self.augment = augment          # pipeline.batch_from_dataset's ``augment``: the GT paste then runs on the training stream
         self.stream = torch.cuda.Stream(device=device, priority=priority)
         self.q = queue.Queue(maxsize=max(1, depth))
         self.slots = {}
@@ -89,9 +90,11 @@ class PrefetchLoader:
             n = st.n.to(dev, non_blocking=True)
             st.free = torch.cuda.Event()
             st.free.record(self.stream)
-            boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
-            lists = Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)      # one pass, one host read
-            targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
+            targets = [None] * B
+            if self.augment is None:          # with the GT paste the boxes are only known after it (__next__)
+                boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
+                lists = Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)      # one pass, one host read
+                targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
             ev = torch.cuda.Event()
             ev.record(self.stream)
         t2 = time.perf_counter()
@@ -157,4 +160,12 @@ class PrefetchLoader:
             m, p2 = _calib_products(d[5], True)
             _hip.lidar2img(pts6[k, :P], m, p2, math_f32=True, out=pts6[k, :P], col_offset=4, swap_rc=True)    # reads x y z, writes cols 4:6
             fpn.append(self.fpn_fn(self.names_of(d), self.device))
-        return FrameBatch(pts6, perms, n, fpn), targets
+        batch = FrameBatch(pts6, perms, n, fpn)
+        if self.augment is not None:
+            from modules.augment import Augment
+            a = self.augment
+            res = Augment.augmentFrames(batch, None, [None if d[3] is None else (d[2], d[3], d[4]) for d in group], a['db'],
+                                        lim=a.get('lim', 12), rng=a.get('rng'))
+            lists = Calc.classifyAnchorsFrames(res.boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)
+            targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, res.bbox3d)]
+        return batch, targets

@@ -216,3 +216,73 @@ def write_kitti_tree(root: str, frame_ids, points: int = 20000, raw_points: int 
     with open(os.path.join(root, 'ImageSets', 'train.txt'), 'w') as f:
         f.write('\n'.join(names) + '\n')
     return names
+
+
+def write_gt_database(root: str, n_objects: int, seed: int = 0, cls: str = 'Car', imsize_wh=(1224, 370), points=(40, 400),
+                      n_calib: int = 4):
+    """A synthetic ``training/gtdatabase/`` in the layout the reference's modules/augment/LoadGT.py reads, so that the GT-paste
+    augmentation runs without the dataset: ``gtinfo.pkl`` = {cls: [info, ...]} and per object ``<cls>/<k>.bin`` (its points
+    (n,4) f32, on the faces of its box), ``<k>.png`` (the image patch), ``<k>_mask.npy`` (u8 0/1, an ellipse) with
+    ``info`` = {'velo', 'image', 'mask' (file names), 'maskbbox' (x1 y1 x2 y2 inclusive), 'bbox2d' (the projected 3-D
+    corners' extent, clipped to the image), 'bbox3d' (xyzlwhr, LiDAR frame), 'id' (the source frame, whose
+    ``training/calib/<id>.txt`` is written when it is missing)}.  Returns the info list."""
+    import os
+    import pickle
+    import torch
+    from PIL import Image
+    g = np.random.default_rng(7000 + seed)
+    t = os.path.join(root, 'training')
+    odir = os.path.join(t, 'gtdatabase', cls)
+    os.makedirs(odir, exist_ok=True)
+    os.makedirs(os.path.join(t, 'calib'), exist_ok=True)
+    ids = ['%06d' % k for k in range(n_calib)]
+    for name in ids:
+        path = os.path.join(t, 'calib', name + '.txt')
+        if not os.path.exists(path):
+            with open(path, 'w') as f:
+                p2 = ' '.join('%.6e' % v for v in KITTI_CALIB['P2'][:3].reshape(-1))
+                r0 = ' '.join('%.6e' % v for v in KITTI_CALIB['R0_rect'][:3, :3].reshape(-1))
+                tr = ' '.join('%.6e' % v for v in KITTI_CALIB['Tr_velo_to_cam'][:3].reshape(-1))
+                f.write('P0: %s\nP1: %s\nP2: %s\nP3: %s\nR0_rect: %s\nTr_velo_to_cam: %s\nTr_imu_to_velo: %s\n' % (p2, p2, p2, p2, r0, tr, tr))
+    proj = KITTI_CALIB['P2'] @ KITTI_CALIB['R0_rect'] @ KITTI_CALIB['Tr_velo_to_cam']
+    W, H = imsize_wh
+    infos = []
+    for k in range(n_objects):
+        x = g.uniform(8, 62)
+        y = g.uniform(-min(20.0, 0.6 * x), min(20.0, 0.6 * x))
+        z = g.uniform(-1.8, -1.2)
+        l, w, h = g.uniform(3.4, 4.4), g.uniform(1.5, 1.8), g.uniform(1.4, 1.7)
+        yaw = g.choice([0.0, np.pi / 2]) + g.normal(0, 0.05)
+        box = np.array([x, y, z, l, w, h, yaw], np.float32)
+        # points on the four sides and the roof, box frame -> LiDAR frame with Calc.bbox3d2bev's rotation convention
+        n = int(g.integers(points[0], points[1]))
+        face = g.integers(0, 5, n)
+        u, v = g.uniform(-0.5, 0.5, n), g.uniform(0, 1, n)
+        px = np.where(face == 0, 0.5, np.where(face == 1, -0.5, u)) * l
+        py = np.where(face == 2, 0.5, np.where(face == 3, -0.5, np.where(face < 2, u, g.uniform(-0.5, 0.5, n)))) * w
+        pz = np.where(face == 4, 1.0, v) * h
+        c, s = np.cos(yaw), np.sin(yaw)
+        velo = np.stack([px * c + py * s + x, -px * s + py * c + y, pz + z, g.random(n)], 1).astype(np.float32)
+        cx = np.array([0.5, -0.5, -0.5, 0.5, 0.5, -0.5, -0.5, 0.5]) * l
+        cy = np.array([0.5, 0.5, -0.5, -0.5, 0.5, 0.5, -0.5, -0.5]) * w
+        cz = np.array([0, 0, 0, 0, 1, 1, 1, 1.0]) * h
+        corners = np.stack([cx * c + cy * s + x, -cx * s + cy * c + y, cz + z, np.ones(8)], 0)
+        im = proj @ corners
+        uu, vv = im[0] / im[2], im[1] / im[2]
+        b2 = np.array([np.clip(uu.min(), 0, W - 1), np.clip(vv.min(), 0, H - 1), np.clip(uu.max(), 0, W - 1),
+                       np.clip(vv.max(), 0, H - 1)], np.float32)
+        x1, y1, x2, y2 = int(np.floor(b2[0])), int(np.floor(b2[1])), int(np.ceil(b2[2])), int(np.ceil(b2[3]))
+        x2, y2 = min(max(x2, x1), W - 1), min(max(y2, y1), H - 1)
+        ph, pw = y2 - y1 + 1, x2 - x1 + 1
+        patch = g.integers(0, 256, (ph, pw, 3), dtype=np.uint8)
+        yy, xx = np.mgrid[0:ph, 0:pw]
+        mask = ((((xx + 0.5) / pw - 0.5) ** 2 + ((yy + 0.5) / ph - 0.5) ** 2) <= 0.25).astype(np.uint8)
+        velo.tofile(os.path.join(odir, '%d.bin' % k))
+        Image.fromarray(patch).save(os.path.join(odir, '%d.png' % k))
+        np.save(os.path.join(odir, '%d_mask.npy' % k), mask)
+        infos.append({'velo': '%d.bin' % k, 'image': '%d.png' % k, 'mask': '%d_mask.npy' % k,
+                      'maskbbox': np.array([x1, y1, x2, y2], np.int64), 'bbox2d': torch.from_numpy(b2),
+                      'bbox3d': torch.from_numpy(box), 'id': ids[k % n_calib]})
+    with open(os.path.join(t, 'gtdatabase', 'gtinfo.pkl'), 'wb') as f:
+        pickle.dump({cls: infos}, f)
+    return infos

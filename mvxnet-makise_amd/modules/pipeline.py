@@ -605,10 +605,14 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
 
 
 # ---- whole model on the fast path: frame sets up to the BEV map, RPN + VoxelLoss per frame ------------------------------
-def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points):
+def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None):
     """Frames of ``modules.data.Load.createDataset`` -> (FrameBatch resident on the GPU, per-frame targets).  Per frame, as
     train.py:26-49: lidar2Img on the torch path + (row, col) swap, the shuffle permutation drawn with np.random, and
-    classifyAnchors for the 'Car' boxes; (pi, ni, gi, gt) or None when the frame has no box."""
+    classifyAnchors for the 'Car' boxes; (pi, ni, gi, gt) or None when the frame has no box.
+    ``augment`` (default None: off): ``{'db': LoadGT.GTDatabase on ``device``, 'lim': 12}`` runs the GT-paste augmentation of
+    train.py:28 on all frames first (modules/augment/Augment.augmentFrames: four launches, one host read; optional keys
+    'rng', 'cand', 'thr' as there, 'images': True also pastes the camera images, kept as ``batch.images`` u8 (B,H,W,3),
+    'keep': a dict that receives the FramesResult); ``cap_points`` must leave room for the pasted points."""
     import numpy as np
     from modules import Calc
     from modules.data.Preprocessing import _calib_products
@@ -623,17 +627,32 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points):
         pts6[k, :P, :4] = src
         m, p2 = _calib_products(calib, True)
         _hip.lidar2img(src, m, p2, math_f32=True, out=pts6[k, :P], col_offset=4, swap_rc=True)
-        a = np.arange(P, dtype=np.int32)
-        np.random.shuffle(a)
-        perms[k, :P] = a
+        if augment is None:
+            a = np.arange(P, dtype=np.int32)
+            np.random.shuffle(a)
+            perms[k, :P] = a
         n[k] = P
         fpn.append(fpn_fn(names[k], device))
+    batch = FrameBatch(pts6, torch.from_numpy(perms).to(device), torch.from_numpy(n).to(device), fpn)
+    if augment is not None:
+        from modules.augment import Augment
+        images = None
+        if augment.get('images'):
+            images = torch.from_numpy(np.stack([np.ascontiguousarray(d[1], dtype=np.uint8) for d in group])).to(device)
+        res = Augment.augmentFrames(batch, images, [None if d[3] is None else (d[2], d[3], d[4]) for d in group], augment['db'],
+                                    lim=augment.get('lim', 12), cand=augment.get('cand'), thr=augment.get('thr'),
+                                    rng=augment.get('rng'))
+        batch.images = images
+        if augment.get('keep') is not None:
+            augment['keep']['result'] = res
+        boxes, gts = res.boxes, res.bbox3d
+    else:
+        boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
+        gts = [None if d[3] is None else d[3].to(device) for d in group]
     # target assignment of all frames in one kernel pass / one host read
-    boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
     lists = Calc.classifyAnchorsFrames(boxes, anchorBevs, cfg.velorange, 0.45, 0.6)
-    targets = [None if t is None else (t[0], t[1], t[2], d[3].to(device)) for t, d in zip(lists, group)]
-    batch = FrameBatch(pts6, torch.from_numpy(perms).to(device), torch.from_numpy(n).to(device), fpn).mark_created()
-    return batch, targets
+    targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, gts)]
+    return batch.mark_created(), targets
 
 
 def heads_loss(heads, F, h1, w1, targets, criterion, anchors):

@@ -2,13 +2,15 @@
 loop, checkpoints and resume), running on this package's HIP modules.
 
     python train_like.py <dataroot> [-n EPOCHS] [-r LAST] [--steps K] [--mode module|fast] [--frames B] [--synthetic N]
+                         [--augment [--gtdatabase DIR]]
 
 What is the same as train.py: createDataset -> createAnchors / bbox3d2bev -> MVXNet, VoxelLoss, AdamW(lr 1e-3, eps) ->
 per frame lidar2Img + (row, col) swap + group + classifyAnchors -> forward -> clsLoss (+ regLoss) -> backward -> step ->
 running loss statistics -> per-epoch ``checkpoints/epoch{n}.pkl`` / ``epoch{n}_opt.pkl`` and ``-r`` resume.
-What is not there: the GT-paste augmentation (modules/augment: needs the KINS-based gtdatabase, OpenCV and numba -- CPU
-label preparation outside the hot path) and the frozen torchvision extractor when torchvision is not installed (FPN maps
-are then deterministic synthetic tensors per frame; with torchvision the image goes through the real extractor).
+The GT-paste augmentation of train.py:28 is there with ``--augment`` (modules/augment, on the GPU; ``--synthetic`` also writes
+a synthetic gtdatabase; off by default).  What is not there: the frozen torchvision extractor when torchvision is not
+installed (FPN maps are then deterministic synthetic tensors per frame; with torchvision the image goes through the real
+extractor).
 
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
@@ -47,6 +49,9 @@ def parse_args(argv=None):
                          'the preparation on the GPU the loop already runs at the step time, and the thread costs more than it hides')
     ap.add_argument('--prefetch-depth', type=int, default=2)
     ap.add_argument('--prefetch-priority', type=int, default=-1, help='HIP stream priority of the loader stream (-1 high, 0 default)')
+    ap.add_argument('--augment', action='store_true', help='GT-paste augmentation (train.py:28: up to 12 cars per frame)')
+    ap.add_argument('--gtdatabase', default=None, help='root that holds training/gtdatabase (default: dataroot)')
+    ap.add_argument('--augment-objects', type=int, default=200, help='objects of the synthetic gtdatabase (--synthetic --augment)')
     return ap.parse_args(argv)
 
 
@@ -66,15 +71,26 @@ def have_torchvision():
         return False
 
 
-def cputask(data, anchorBevs, cfg):
-    """train.py:26-49 without the GT-paste augmentation: projection, (row, col) swap, voxelization, target assignment."""
+def cputask(data, anchorBevs, cfg, gtwithinfo=None):
+    """train.py:26-49: (GT-paste augmentation when ``gtwithinfo`` is given,) projection, (row, col) swap, voxelization,
+    target assignment."""
     from modules.Calc import classifyAnchors
     from modules.data import Preprocessing as pre
     from modules.utils import lidar2Img
     pcd, img, bbox2d, bbox3d, bev, calib = data
+    augpcd, augcalib = [], []
+    if gtwithinfo is not None:
+        from modules.augment.Augment import augmentTargetClasses
+        augpcd, augcalib, img, bbox3d, bev = augmentTargetClasses(pcd, img, bbox2d, bbox3d, bev, gtwithinfo, ['Car'], [12])
+        bbox3d, bev = bbox3d['Car'], bev['Car']
     pcd_t = torch.Tensor(pcd)
     proj = lidar2Img(pcd_t, calib, True)[:, [1, 0]]
     pcd6 = torch.concat([pcd_t, proj.cpu()], dim=1).numpy()
+    if augpcd:
+        pcdxy = [pcd6]
+        for ap_, ac in zip(augpcd, augcalib):
+            pcdxy.append(np.concatenate([ap_, lidar2Img(ap_, ac, True)[:, ::-1]], axis=1))
+        pcd6 = np.concatenate(pcdxy, axis=0).astype(np.float32)          # train.py:125 casts the voxels to float32
     voxel, idx = pre.group(pcd6, cfg.velorange, cfg.voxelsize, cfg.samplenum)
     if bev is not None and bev.shape[0] != 0:
         pi, ni, gi = classifyAnchors(bev, bbox3d[:, [0, 1]], anchorBevs, cfg.velorange, 0.45, 0.6)
@@ -106,6 +122,8 @@ def train(args):
         from modules.data import Synthetic
         if rank == 0:
             Synthetic.write_kitti_tree(args.dataroot, list(range(args.synthetic)), points=args.points)
+            if args.augment and args.gtdatabase is None:
+                Synthetic.write_gt_database(args.dataroot, args.augment_objects)
         if world > 1:
             torch.distributed.barrier()
     with open(os.path.join(args.dataroot, 'ImageSets/train.txt'), 'r') as f:
@@ -114,6 +132,14 @@ def train(args):
     trainDataSet = load.createDataset(trainSet, needCrop=args.need_crop, root=args.dataroot)
     dataset_s = time.perf_counter() - t_ds           # file I/O: the whole split is read into RAM first, like train.py:53-57
     names = {id(d): n for d, n in zip(trainDataSet, trainSet)}
+    gtwithinfo = aug = None
+    if args.augment:
+        from modules.augment.LoadGT import getAllGT, GTDatabase
+        gtwithinfo = getAllGT(['Car'], root=args.gtdatabase or args.dataroot)          # train.py:57
+        db = GTDatabase.from_gts(gtwithinfo['Car'], device)
+        # --mode fast draws with a Generator: the reference-order draw permutes the whole database once per slot
+        aug = {'db': db, 'lim': 12, 'rng': np.random.default_rng(rank)}
+        say('gtdatabase: %d objects, %.1f MB resident, %d points dropped at load' % (db.n, db.nbytes() / 1e6, db.dropped_points))
 
     anchors = pre.createAnchors(cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2, cfg.velorange, cfg.carsize)
     anchorBevs = bbox3d2bev(anchors.reshape(anchors.shape[:2] + (-1, 7))).to(device).contiguous()
@@ -141,7 +167,7 @@ def train(args):
         clsCnt = regCnt = 0
         if args.mode == 'module':
             for i, data in enumerate(mine):
-                voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg)
+                voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo)
                 calib = {k: torch.Tensor(calibCpu[k]).to(device) for k in calibCpu}
                 idx4 = np.concatenate([np.zeros((idx.shape[0], 1)), idx], axis=1)
                 opt.zero_grad()
@@ -189,20 +215,23 @@ def train(args):
             chunks = fast_chunks(len(trainDataSet), B, world)
             groups = [trainDataSet[lo + rank:hi:world] for lo, hi in chunks]
             cap = max(args.points, max(d[0].shape[0] for d in trainDataSet))
+            if aug is not None:
+                cap += aug['lim'] * aug['db'].max_points                 # room for the pasted objects
             if not args.prefetch:
                 def batches():
                     for group in groups:
                         if not group:
                             yield None, None
                         else:
-                            yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_maps_for, cap_points=cap)
+                            yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_maps_for, cap_points=cap,
+                                                        augment=aug)
                 loader = batches()
             else:
                 # batch k+1 is prepared by a worker thread on its own stream while step k runs (the reference overlaps its CPU
                 # preparation with a process pool, train.py:185-187)
                 from modules.data.Prefetch import PrefetchLoader
                 loader = PrefetchLoader(groups, lambda d: names[id(d)], device, anchorBevs, fpn_maps_for, cap,
-                                        depth=args.prefetch_depth, priority=args.prefetch_priority)
+                                        depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug)
             pending = None                        # the losses of a step are read one step later: the host never waits for
                                                   # the step it has just enqueued
 

@@ -12,6 +12,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, 'mvxnet-makise_amd'))
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+AUG = len(sys.argv) > 3 and sys.argv[3] == 'augment'
 sys.argv = sys.argv[:1]
 import numpy as np  # noqa: E402
 import train_like  # noqa: E402
@@ -19,8 +20,14 @@ import train_like  # noqa: E402
 root = tempfile.mkdtemp(prefix='mvx_kitti_')
 res = {'frames': n, 'frames_per_step': B, 'points': 20000}
 first = True
-for label, extra in (('prefetch', ['--prefetch']), ('prefetch_prio0', ['--prefetch', '--prefetch-priority', '0']),
-                     ('prefetch_depth4', ['--prefetch', '--prefetch-depth', '4']), ('no_prefetch', [])):
+runs = (('prefetch', ['--prefetch']), ('prefetch_prio0', ['--prefetch', '--prefetch-priority', '0']),
+        ('prefetch_depth4', ['--prefetch', '--prefetch-depth', '4']), ('no_prefetch', []))
+if AUG:
+    # a third argument ``augment``: batches prepared inside the step with and without the GT-paste augmentation (--augment, a
+    # synthetic gtdatabase), alternating, in one process instead;
+    # the first run writes the synthetic tree, and with --augment the synthetic gtdatabase too
+    runs = (('no_prefetch_augment', ['--augment']), ('no_prefetch', []), ('no_prefetch_augment_2', ['--augment']), ('no_prefetch_2', []))
+for label, extra in runs:
     args = train_like.parse_args([root, '-n', '2', '--mode', 'fast', '--frames', str(B), '--points', '20000', '--quiet',
                                   '--checkpoints', os.path.join(root, 'ck_' + label)] + extra + (['--synthetic', str(n)] if first else []))
     first = False
