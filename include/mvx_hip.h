@@ -1040,6 +1040,53 @@ int mvx_gt_paste_image_frames(uint8_t *img, int32_t n_frames, int32_t h, int32_t
                               const uint8_t *patch, const uint8_t *mask, const int64_t *px_off, const int32_t *maskbbox,
                               int32_t n_db, int64_t max_patch_px, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Builder of the GT-paste object database (csrc/gtdb.hip): the reference's create_gtdatabase.py for the frames of a call.
+ * The host parses (label files, the KINS annotation file, images, clouds) and prepares the label rows; the kernels match,
+ * rasterise and cut.  Tables, all on the device:
+ *   labels, n_labels rows in any order (the host sorts by class, frame, row so that a class is a contiguous range):
+ *     lab_box2d f32 [n][4] x1 y1 x2 y2, lab_box3d f32 [n][7] xyzlwhr (LiDAR), lab_cs f32 [n][2] = cos, sin of the yaw (the
+ *     entries of Calc.getRotationMatrices), lab_frame i32 [n], lab_group i32 [n] = the (frame, class) group of the row;
+ *   annotations sorted by group: ann_box f32 [n_ann][4] x1 y1 x2 y2, ann_off i32 [n_groups + 1]; their polygons as edges:
+ *     edges f64 [n_edges][4] = x0 y0 x1 y1 (every polygon closed), edge_poly i32 [n_edges] = the polygon of the edge inside
+ *     its instance (non-decreasing), edge_off i32 [n_ann + 1];
+ *   frames: images u8 [n_frames][h][w][3] BGR, im_hw i32 [n_frames][2] = the rows and columns that are really there (<= h, w);
+ *     points f32 [sum][4] x y z r with pts_off i64 [n_frames + 1], 16-byte aligned.
+ *
+ * mvx_gtdb_match: per label the IoU (torchvision box_iou arithmetic, f32) against the annotation boxes of its group:
+ *   best i32 [n] = the first annotation (global index) reaching the maximum, -1 for an empty group; iou f32 [n]; roi i32 [n][4]
+ *   = the annotation box truncated to int and clipped to the frame's image, x1 y1 x2 y2 inclusive; flag i32 [n]: bit 0 =
+ *   iou >= iou_thr, bit 1 = the ROI is not empty; a label is an OBJECT when flag == 3.  px_off i64 [n + 1] = the exclusive
+ *   scan of the objects' ROI pixel counts (0 for the other labels), by a second, single-workgroup kernel.
+ * mvx_gtdb_crop_count: pt_off i64 [n + 1] = the exclusive scan of the number of points of the label's frame inside its box
+ *   (objects only).  Inside, in f64 on the f32 values: dx = px - x, dy = py - y, u = dx * c - dy * s, v = dx * s + dy * c,
+ *   |u| <= l / 2, |v| <= w / 2, 0 <= pz - z <= h.  Counts per chunk of MVX_GTDB_CHUNK points go to the workspace
+ *   (mvx_gtdb_workspace_bytes) and become offsets there; mvx_gtdb_crop_write reads them.
+ * mvx_gtdb_crop_write: out_points f32 [out_rows][4]: the inside points of object k at rows pt_off[k] .. pt_off[k + 1], in file
+ *   order (count, scan, ordered write: no atomics; bitwise reproducible).  Same tables and workspace as the count call.
+ * mvx_gtdb_raster: for every object, mask u8 [n_px] (0 / 1) and patch u8 [n_px][3] at px_off: a pixel of the ROI is set when
+ *   its centre (x + 0.5, y + 0.5) is inside any polygon of annotation best[k] by the even-odd rule -- per edge, in f64:
+ *   (y0 > py) != (y1 > py) and px < (x1 - x0) * (py - y0) / (y1 - y0) + x0 --; patch = mask ? image : 0.  max_roi_rows sizes
+ *   the grid (the largest ROI height).  Every output byte has one writer.
+ * Argument errors return MVX_EINVAL before any launch.
+ */
+#define MVX_GTDB_CHUNK 1024
+size_t mvx_gtdb_workspace_bytes(int32_t n_labels, int32_t max_frame_points);
+int mvx_gtdb_match(const float *lab_box2d, const int32_t *lab_group, const int32_t *lab_frame, int32_t n_labels,
+                   const float *ann_box, const int32_t *ann_off, int32_t n_groups, const int32_t *im_hw, int32_t n_frames,
+                   float iou_thr, int32_t *best, float *iou, int32_t *flag, int32_t *roi, int64_t *px_off, void *stream);
+int mvx_gtdb_crop_count(const float *points, const int64_t *pts_off, int32_t n_frames, int32_t max_frame_points,
+                        const float *lab_box3d, const float *lab_cs, const int32_t *lab_frame, const int32_t *flag,
+                        int32_t n_labels, int64_t *pt_off, void *workspace, size_t workspace_bytes, void *stream);
+int mvx_gtdb_crop_write(const float *points, const int64_t *pts_off, int32_t n_frames, int32_t max_frame_points,
+                        const float *lab_box3d, const float *lab_cs, const int32_t *lab_frame, const int32_t *flag,
+                        int32_t n_labels, const int64_t *pt_off, const void *workspace, size_t workspace_bytes,
+                        float *out_points, int64_t out_rows, void *stream);
+int mvx_gtdb_raster(const uint8_t *images, int32_t n_frames, int32_t h, int32_t w, const int32_t *lab_frame,
+                    const int32_t *flag, const int32_t *best, const int32_t *roi, const int64_t *px_off, int32_t n_labels,
+                    const double *edges, const int32_t *edge_poly, const int32_t *edge_off, int32_t n_ann,
+                    int32_t max_roi_rows, uint8_t *mask, uint8_t *patch, int64_t n_px, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2102,3 +2102,68 @@ def gt_paste_image(img, picked, db):
                                             X.ptr(db.px_off), X.ptr(db.maskbbox), db.n, int(db.max_patch_px), X.stream()),
             'mvx_gt_paste_image_frames')
     return img
+
+
+# ---------------------------------------------------------------------------------------------
+# Builder of the GT-paste database (csrc/gtdb.hip); ``t`` holds the device tables of a call (modules.augment.BuildGT.pack):
+# lab_box2d / lab_box3d / lab_cs / lab_frame / lab_group, ann_box / ann_off, edges / edge_poly / edge_off, images / im_hw,
+# points / pts_off, and the host numbers n_labels, n_frames, max_frame_points
+# ---------------------------------------------------------------------------------------------
+GTDB_IOU_THR = 0.65
+GTDB_CHUNK = 1024           # MVX_GTDB_CHUNK
+
+
+def gtdb_match(t, iou_thr=GTDB_IOU_THR):
+    """Per label: (best i32 (n,), iou f32 (n,), flag i32 (n,), roi i32 (n, 4), px_off i64 (n + 1,)); an object has flag 3."""
+    n, dev = t.n_labels, t.lab_box2d.device
+    assert t.lab_box2d.shape == (n, 4) and t.lab_box2d.dtype == torch.float32 and t.ann_box.dtype == torch.float32
+    assert t.lab_group.dtype == torch.int32 and t.lab_frame.dtype == torch.int32 and t.ann_off.dtype == torch.int32
+    assert t.im_hw.shape == (t.n_frames, 2) and t.im_hw.dtype == torch.int32
+    best = torch.empty((n,), dtype=torch.int32, device=dev)
+    iou = torch.empty((n,), dtype=torch.float32, device=dev)
+    flag = torch.empty((n,), dtype=torch.int32, device=dev)
+    roi = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    px_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    X.check(X.lib.mvx_gtdb_match(X.ptr(t.lab_box2d), X.ptr(t.lab_group), X.ptr(t.lab_frame), n, X.ptr(t.ann_box), X.ptr(t.ann_off),
+                                 t.ann_off.numel() - 1, X.ptr(t.im_hw), t.n_frames, float(iou_thr), X.ptr(best), X.ptr(iou),
+                                 X.ptr(flag), X.ptr(roi), X.ptr(px_off), X.stream()), 'mvx_gtdb_match')
+    return best, iou, flag, roi, px_off
+
+
+def gtdb_crop_count(t, flag):
+    """(pt_off i64 (n + 1,), workspace): how many points of its frame every object's box holds, scanned; the workspace keeps
+    the chunk offsets for gtdb_crop_write."""
+    n, dev = t.n_labels, t.points.device
+    assert t.points.dtype == torch.float32 and t.points.shape[1] == 4 and t.pts_off.dtype == torch.int64
+    assert t.lab_box3d.shape == (n, 7) and t.lab_cs.shape == (n, 2)
+    nbytes = X.lib.mvx_gtdb_workspace_bytes(n, int(t.max_frame_points))
+    ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
+    pt_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+    X.check(X.lib.mvx_gtdb_crop_count(X.ptr(t.points), X.ptr(t.pts_off), t.n_frames, int(t.max_frame_points), X.ptr(t.lab_box3d),
+                                      X.ptr(t.lab_cs), X.ptr(t.lab_frame), X.ptr(flag), n, X.ptr(pt_off), X.ptr(ws), ws.numel(),
+                                      X.stream()), 'mvx_gtdb_crop_count')
+    return pt_off, ws
+
+
+def gtdb_crop_write(t, flag, pt_off, ws, n_rows):
+    """points f32 (max(n_rows, 1), 4): every object's inside points at pt_off, in file order."""
+    out = torch.zeros((max(int(n_rows), 1), 4), dtype=torch.float32, device=t.points.device)
+    X.check(X.lib.mvx_gtdb_crop_write(X.ptr(t.points), X.ptr(t.pts_off), t.n_frames, int(t.max_frame_points), X.ptr(t.lab_box3d),
+                                      X.ptr(t.lab_cs), X.ptr(t.lab_frame), X.ptr(flag), t.n_labels, X.ptr(pt_off), X.ptr(ws),
+                                      ws.numel(), X.ptr(out), out.shape[0], X.stream()), 'mvx_gtdb_crop_write')
+    return out
+
+
+def gtdb_raster(t, best, flag, roi, px_off, n_px, max_roi_rows):
+    """(mask u8 (max(n_px, 1),), patch u8 (max(n_px, 1), 3)) of every object at px_off."""
+    dev = t.images.device
+    F, H, W = t.images.shape[0], t.images.shape[1], t.images.shape[2]
+    assert t.images.dtype == torch.uint8 and t.images.shape[3] == 3 and F == t.n_frames
+    assert t.edges.dtype == torch.float64 and t.edge_poly.dtype == torch.int32 and t.edge_off.dtype == torch.int32
+    mask = torch.zeros((max(int(n_px), 1),), dtype=torch.uint8, device=dev)
+    patch = torch.zeros((max(int(n_px), 1), 3), dtype=torch.uint8, device=dev)
+    X.check(X.lib.mvx_gtdb_raster(X.ptr(t.images), F, H, W, X.ptr(t.lab_frame), X.ptr(flag), X.ptr(best), X.ptr(roi), X.ptr(px_off),
+                                  t.n_labels, X.ptr(t.edges), X.ptr(t.edge_poly), X.ptr(t.edge_off), t.edge_off.numel() - 1,
+                                  max(1, min(int(max_roi_rows), H)), X.ptr(mask), X.ptr(patch), mask.numel(), X.stream()),
+            'mvx_gtdb_raster')
+    return mask, patch

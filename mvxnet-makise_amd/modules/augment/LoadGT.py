@@ -117,6 +117,18 @@ class GTDatabase:
                    maskbbox=to(np.asarray(mbb, np.int32)), max_patch_px=max(1, int(px.max())),
                    max_points=int(np.diff(np.asarray(pt_off)).max()), dropped_points=dropped, velo_kept=[p[:, :4] for p in pts])
 
+    @classmethod
+    def from_built(cls, built, calibs, device, name='Car', velorange=None, imsize=None):
+        """The database of class ``name`` from what ``BuildGT.buildFrames`` returned (one result or a list of them, in order),
+        without going through the disk: the objects' tables are read back once and packed as ``from_gts`` packs loaded
+        objects (the row / col columns are the host projection with the object's own calibration, as there).  ``calibs``:
+        {frame id: calib dict as Load.readCalib returns it}."""
+        from modules.augment import BuildGT
+        gts = []
+        for b in (built if isinstance(built, (list, tuple)) else [built]):
+            gts += BuildGT.objectsOf(b[name], calibs)
+        return cls.from_gts(gts, device, velorange, imsize)
+
     def nbytes(self):
         """Resident size of the tables in bytes."""
         return sum(t.numel() * t.element_size() for t in self.__dict__.values() if isinstance(t, torch.Tensor))

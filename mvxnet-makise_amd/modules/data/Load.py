@@ -59,6 +59,19 @@ def _read_car_labels(path):
     return np.asarray(rows, dtype=np.float64).reshape(-1, 11)
 
 
+def _read_class_labels(path, classes=('Car', 'Pedestrian', 'Cyclist')):
+    """The rows of a label_2 file whose class is in ``classes``: (names, the 14 columns after the name as float64 (n, 14) =
+    truncated occluded alpha bbox2d (4) h w l x y z ry), in file order (create_gtdatabase.py:119-120)."""
+    names, rows = [], []
+    with open(path, 'r') as f:
+        for line in f:
+            tok = line.split(' ')
+            if tok and tok[0] in classes:
+                names.append(tok[0])
+                rows.append([float(v) for v in tok[1:15]])
+    return names, np.asarray(rows, dtype=np.float64).reshape(-1, 14)
+
+
 def createDataset(splitSet: List[str], needCrop=False, root=None) -> \
         List[Tuple[np.ndarray, np.ndarray, torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]]:
     """Read KITTI frames ``splitSet`` (e.g. ['000000', ...]) from ``root`` (reference Load.py:43-95)."""

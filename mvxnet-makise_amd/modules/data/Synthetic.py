@@ -286,3 +286,147 @@ def write_gt_database(root: str, n_objects: int, seed: int = 0, cls: str = 'Car'
     with open(os.path.join(t, 'gtdatabase', 'gtinfo.pkl'), 'wb') as f:
         pickle.dump({cls: infos}, f)
     return infos
+
+
+def _write_calib(path):
+    with open(path, 'w') as f:
+        p2 = ' '.join('%.6e' % v for v in KITTI_CALIB['P2'][:3].reshape(-1))
+        r0 = ' '.join('%.6e' % v for v in KITTI_CALIB['R0_rect'][:3, :3].reshape(-1))
+        tr = ' '.join('%.6e' % v for v in KITTI_CALIB['Tr_velo_to_cam'][:3].reshape(-1))
+        f.write('P0: %s\nP1: %s\nP2: %s\nP3: %s\nR0_rect: %s\nTr_velo_to_cam: %s\nTr_imu_to_velo: %s\n' % (p2, p2, p2, p2, r0, tr, tr))
+
+
+def _box_frame(box, xyz):
+    """(u, v, dz) of points in the frame of an xyzlwhr box (the inverse of Calc.bbox3d2bev's rotation)."""
+    c, s = np.cos(box[6]), np.sin(box[6])
+    dx, dy = xyz[:, 0] - box[0], xyz[:, 1] - box[1]
+    return dx * c - dy * s, dx * s + dy * c, xyz[:, 2] - box[2]
+
+
+_KINS_DIMS = {'Car': ((3.4, 4.4), (1.5, 1.8), (1.4, 1.7)), 'Pedestrian': ((0.6, 1.0), (0.5, 0.8), (1.6, 1.9)),
+              'Cyclist': ((1.5, 1.9), (0.5, 0.8), (1.6, 1.8))}
+_KINS_IDS = {'Car': 4, 'Pedestrian': 2, 'Cyclist': 1}
+
+
+def _kins_polygons(g, kind, ax, ay, aw, ah):
+    """Instance polygons inside the box (ax, ay, aw, ah), flat [x0 y0 x1 y1 ...] lists with three decimals: 0 = one convex
+    outline, 1 = one concave star, 2 = two overlapping parts, 3 = two parts with a gap."""
+    def ring(cx, cy, rx, ry, n, radii):
+        ang = np.linspace(0, 2 * np.pi, n, endpoint=False) + g.uniform(0, 0.3)
+        xs = ax + (cx + rx * radii * np.cos(ang)) * aw
+        ys = ay + (cy + ry * radii * np.sin(ang)) * ah
+        return [round(round(float(v), 2) + 0.003, 3) for xy in zip(xs, ys) for v in xy]      # never on a pixel centre
+    if kind == 0:
+        return [ring(0.5, 0.5, 0.5, 0.5, 14, g.uniform(0.85, 1.0, 14))]
+    if kind == 1:
+        return [ring(0.5, 0.5, 0.5, 0.5, 12, np.where(np.arange(12) % 2 == 0, 1.0, g.uniform(0.35, 0.55, 12)))]
+    if kind == 2:
+        return [ring(0.32, 0.5, 0.3, 0.48, 10, g.uniform(0.9, 1.0, 10)), ring(0.68, 0.5, 0.3, 0.45, 9, g.uniform(0.9, 1.0, 9))]
+    return [ring(0.22, 0.5, 0.2, 0.48, 8, g.uniform(0.9, 1.0, 8)), ring(0.78, 0.45, 0.2, 0.4, 11, g.uniform(0.6, 1.0, 11))]
+
+
+def write_kins_tree(root: str, frame_ids, seg_path=None, points: int = 6000, objects=(5, 9), seed: int = 0,
+                    imsize_wh=(1242, 375), rng=VELORANGE, no_annotation=(1,), out_of_range=(2,)):
+    """A KITTI tree (training/{velodyne_croped, label_2, calib, image_2}, ImageSets/train.txt) whose labels -- Car, Pedestrian
+    and Cyclist rows -- carry the projected 2-D boxes of their 3-D boxes (clipped to the image), plus a matching KINS-format
+    annotation file ``seg_path`` (default <root>/seglabel/update_train_2020.json): per label an instance with ``a_bbox`` = the
+    label's 2-D box jittered so that the IoUs lie on both sides of 0.65, and ``i_segm`` polygons of four kinds (convex,
+    concave, two overlapping parts, two separate parts).  Built in on purpose, per ordinary frame: object 0 is a car at the
+    right bottom corner of the image whose ROI touches the border, object 1 has no point inside its box, object 2 is
+    labelled twice (two labels match one instance); some labels have no instance, some instances no label or another
+    category.  The frames at positions ``no_annotation`` of ``frame_ids`` have no instance at all, those at ``out_of_range``
+    only labels beyond the crop range.  The clouds hold background points plus points around every box, about half of them
+    inside, in shuffled order.  The annotation file lists the frames in reversed order.  Returns the frame names."""
+    import json
+    import os
+    from PIL import Image
+    t = os.path.join(root, 'training')
+    for d in ('velodyne_croped', 'label_2', 'calib', 'image_2'):
+        os.makedirs(os.path.join(t, d), exist_ok=True)
+    os.makedirs(os.path.join(root, 'ImageSets'), exist_ok=True)
+    seg_path = os.path.join(root, 'seglabel', 'update_train_2020.json') if seg_path is None else seg_path
+    os.makedirs(os.path.dirname(os.path.abspath(seg_path)), exist_ok=True)
+    v2c = KITTI_CALIB['Tr_velo_to_cam']
+    proj = KITTI_CALIB['P2'] @ KITTI_CALIB['R0_rect'] @ v2c
+    W, H = imsize_wh
+    lo, hi = np.asarray(rng[:3], np.float64), np.asarray(rng[3:], np.float64)
+    names, images, anns = [], [], []
+    for pos, fid in enumerate(frame_ids):
+        name = '%06d' % fid
+        names.append(name)
+        g = np.random.default_rng(8000 + 1000 * seed + fid)
+        Image.fromarray(g.integers(0, 256, (H, W, 3), dtype=np.uint8)).save(os.path.join(t, 'image_2', name + '.png'))
+        _write_calib(os.path.join(t, 'calib', name + '.txt'))
+        far = pos in out_of_range
+        n_obj = int(g.integers(objects[0], objects[1]))
+        rows, boxes, frame_anns = [], [], []
+        for k in range(n_obj):
+            cls = 'Car' if k < 3 else str(g.choice(['Car', 'Pedestrian', 'Cyclist'], p=[0.5, 0.25, 0.25]))
+            dl, dw, dh = _KINS_DIMS[cls]
+            l, w, h = g.uniform(*dl), g.uniform(*dw), g.uniform(*dh)
+            x = g.uniform(71.5, 78.0) if far else g.uniform(9, 55)
+            y = g.uniform(-0.5 * x, 0.5 * x) * (0.3 if far else 1.0)
+            z, yaw = g.uniform(-1.8, -1.2), g.choice([0.0, np.pi / 2]) + g.normal(0, 0.08)
+            if k == 0 and not far:
+                x, y, z, yaw = g.uniform(7.2, 7.6), g.uniform(-5.6, -5.3), -1.75, g.normal(0, 0.05)
+            box = np.array([x, y, z, l, w, h, yaw])
+            boxes.append(box)
+            c, s = np.cos(yaw), np.sin(yaw)
+            cx = np.array([0.5, -0.5, -0.5, 0.5, 0.5, -0.5, -0.5, 0.5]) * l
+            cy = np.array([0.5, 0.5, -0.5, -0.5, 0.5, 0.5, -0.5, -0.5]) * w
+            cz = np.array([0, 0, 0, 0, 1, 1, 1, 1.0]) * h
+            im = proj @ np.stack([cx * c + cy * s + x, -cx * s + cy * c + y, cz + z, np.ones(8)], 0)
+            uu, vv = im[0] / im[2], im[1] / im[2]
+            b2 = np.array([np.clip(uu.min(), 0, W - 1), np.clip(vv.min(), 0, H - 1), np.clip(uu.max(), 0, W - 1),
+                           np.clip(vv.max(), 0, H - 1)])
+            cam = v2c @ np.array([x, y, z, 1.0])
+            occ = int(g.integers(0, 3))
+            rows.append('%s 0.00 %d 0.00 %.2f %.2f %.2f %.2f %.4f %.4f %.4f %.4f %.4f %.4f %.4f'
+                        % ((cls, occ) + tuple(b2) + (h, w, l, cam[0], cam[1], cam[2], yaw + 0.5 * np.pi)))
+            if k == 2:            # the same object labelled a second time, a little off
+                cam2 = v2c @ np.array([x + 0.05, y, z, 1.0])
+                rows.append('%s 0.00 %d 0.00 %.2f %.2f %.2f %.2f %.4f %.4f %.4f %.4f %.4f %.4f %.4f'
+                            % ((cls, occ) + tuple(b2 + np.array([1.0, 0.5, 1.5, 0.0])) + (h, w, l, cam2[0], cam2[1], cam2[2], yaw + 0.5 * np.pi)))
+            bw, bh = b2[2] - b2[0], b2[3] - b2[1]
+            if bw < 4 or bh < 4 or (k > 2 and g.random() < 0.15):
+                continue                                              # a label without an instance
+            if k == 0 and not far:
+                a = [b2[0], b2[1], bw + 8.0, bh + 8.0]                   # reaches over the image border
+            else:
+                a = [b2[0] + g.uniform(-0.2, 0.2) * bw, b2[1] + g.uniform(-0.12, 0.12) * bh, bw * g.uniform(0.85, 1.15),
+                     bh * g.uniform(0.85, 1.15)]
+            a = [round(float(v), 2) for v in a]
+            frame_anns.append({'category_id': _KINS_IDS[cls], 'a_bbox': a, 'i_bbox': a,
+                               'i_segm': _kins_polygons(g, k % 4, *a)})
+        for cat in (4, 3):        # instances without a label: one of a target class, one of another category
+            a = [round(float(v), 2) for v in (g.uniform(0, W - 80), g.uniform(0, H - 60), g.uniform(20, 80), g.uniform(20, 60))]
+            frame_anns.append({'category_id': cat, 'a_bbox': a, 'i_bbox': a, 'i_segm': _kins_polygons(g, 0, *a)})
+        with open(os.path.join(t, 'label_2', name + '.txt'), 'w') as f:
+            f.write('\n'.join(rows) + '\nDontCare -1 -1 -10 500.00 100.00 520.00 120.00 -1 -1 -1 -1000 -1000 -1000 -10\n')
+        # the cloud: background plus points around every box; none in or near box 1
+        pts = [g.uniform(lo, hi, (points, 3))]
+        for k, b in enumerate(boxes):
+            if k == 1:
+                continue
+            m = int(g.integers(30, 200))
+            u, v, dz = g.uniform(-0.7, 0.7, m) * b[3], g.uniform(-0.7, 0.7, m) * b[4], g.uniform(-0.3, b[5] + 0.3, m)
+            c, s = np.cos(b[6]), np.sin(b[6])
+            pts.append(np.stack([u * c + v * s + b[0], -u * s + v * c + b[1], dz + b[2]], 1))
+        xyz = np.concatenate(pts, 0)
+        if len(boxes) > 1:
+            u, v, dz = _box_frame(boxes[1], xyz)
+            xyz = xyz[~((np.abs(u) < boxes[1][3]) & (np.abs(v) < boxes[1][4]) & (dz > -1) & (dz < boxes[1][5] + 1))]
+        xyz = xyz[g.permutation(xyz.shape[0])]
+        pc = np.concatenate([xyz, g.random((xyz.shape[0], 1))], 1).astype(np.float32)
+        _crop(pc, rng).tofile(os.path.join(t, 'velodyne_croped', name + '.bin'))
+        images.append({'id': 1000 + fid, 'file_name': name + '.png', 'width': W, 'height': H})
+        if pos not in no_annotation:
+            anns.append([dict(a, image_id=1000 + fid) for a in frame_anns])
+    flat = [a for fa in reversed(anns) for a in fa]
+    for k, a in enumerate(flat):
+        a['id'] = k
+    with open(seg_path, 'w') as f:
+        json.dump({'images': images, 'annotations': flat, 'categories': [{'id': v, 'name': k} for k, v in _KINS_IDS.items()]}, f)
+    with open(os.path.join(root, 'ImageSets', 'train.txt'), 'w') as f:
+        f.write('\n'.join(names) + '\n')
+    return names
