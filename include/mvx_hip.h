@@ -1087,6 +1087,33 @@ int mvx_gtdb_raster(const uint8_t *images, int32_t n_frames, int32_t h, int32_t 
                     const double *edges, const int32_t *edge_poly, const int32_t *edge_off, int32_t n_ann,
                     int32_t max_roi_rows, uint8_t *mask, uint8_t *patch, int64_t n_px, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frozen ResNet50-FPN image extractor (csrc/extractor.hip; the reference's torchvision trunk, modules/imhead/Pipe.py:8-21):
+ * the glue between the row GEMMs (1x1 convolutions) and the mvx_conv2d_*_frames kernels (3x3).  Forward only; maps are
+ * channels-last frame sets [F][h][w][c] f32; every output element has one writer.
+ *   mvx_image_prepare_frames   torchvision's GeneralizedRCNNTransform (eval) in one launch.  img: u8 [F][h][w][3] (is_u8 != 0;
+ *                              values / 255 in f32) or f32 [F][3][h][w]; the channel order is kept.  (x - mean) / std with the
+ *                              ImageNet constants, bilinear resize to oh x ow (align_corners = False, coordinate scale h / oh and
+ *                              w / ow in f32), zeros from there to ph x pw.  out f32 [F][ph][pw][4], channel 3 is zero.
+ *   mvx_stem_conv7_frames      out [F][ch][cw][64] = ReLU(conv 7x7, stride 2, padding 3 of `in` [F][ph][pw][4] (channel 3 unread) +
+ *                              bias), ch = (ph - 1) / 2 + 1; wpk f32 [7][7][3][64] = W[co][ci][ky][kx] with BatchNorm folded in
+ *   mvx_maxpool3s2_frames      3x3, stride 2, padding 1: out [F][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c]
+ *   mvx_add_relu_frames        out = ReLU(a + b) over n floats (n % 4 == 0)
+ *   mvx_gather_stride2_frames  out [F][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c] = in at the even (y, x) sites
+ *   mvx_topdown_merge_frames   out [F][lat_h][lat_w][c] = lateral + top [F][top_h][top_w][c] at (y / 2, x / 2); the lateral map
+ *                              must be EXACTLY twice the top one (MVX_EINVAL otherwise)
+ * channels % 4 == 0 and 16-byte aligned pointers throughout.
+ */
+int mvx_image_prepare_frames(const void *img, int32_t is_u8, float *out, int32_t n_frames, int32_t h, int32_t w, int32_t oh,
+                             int32_t ow, int32_t ph, int32_t pw, void *stream);
+int mvx_stem_conv7_frames(const float *in, const float *wpk, const float *bias, float *out, int32_t n_frames, int32_t ph,
+                          int32_t pw, void *stream);
+int mvx_maxpool3s2_frames(const float *in, float *out, int32_t n_frames, int32_t h, int32_t w, int32_t channels, void *stream);
+int mvx_add_relu_frames(const float *a, const float *b, float *out, int64_t n, void *stream);
+int mvx_gather_stride2_frames(const float *in, float *out, int32_t n_frames, int32_t h, int32_t w, int32_t channels, void *stream);
+int mvx_topdown_merge_frames(const float *lateral, const float *top, float *out, int32_t n_frames, int32_t lat_h, int32_t lat_w,
+                             int32_t top_h, int32_t top_w, int32_t channels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,19 @@ class MVXNet(nn.Module):
         self.backbone = VoxelNet()
         self.backbone.apply(initWeights)
 
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """As nn.Module.load_state_dict; a checkpoint that carries the frozen extractor (``head.extractor.backbone.*``, what the
+        reference's train.py writes) also loads it (``ImageFeatureExtractor.load_weights``): the tensors the three FPN levels
+        read are kept, the rest of that subtree (RPN / ROI heads, unread FPN blocks) is dropped."""
+        pre = 'head.extractor.'
+        if any(k.startswith(pre + 'backbone.') for k in state_dict):
+            self.head.extractor.load_weights({k: v for k, v in state_dict.items() if k.startswith(pre + 'backbone.')})
+            dev = next(self.parameters()).device
+            self.head.extractor.to(dev)
+            kept = {pre + k for k in self.head.extractor.state_dict()}
+            state_dict = {k: v for k, v in state_dict.items() if not k.startswith(pre) or k in kept}
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
     def prepack(self):
         """Pack the dense-conv weights on the CURRENT stream for the arithmetic in use, so frames that
         run on other streams find them ready (modules/pipeline.py)."""

@@ -36,6 +36,8 @@ def parse_args(argv=None):
     ap.add_argument('--decode', choices=['loss', 'reference'], default='loss')
     ap.add_argument('--eval', action='store_true', help='score the written files against the split\'s label_2 (KITTI AP on the GPU)')
     ap.add_argument('--classes', nargs='+', default=['Car'], help='classes scored by --eval')
+    ap.add_argument('--extractor-weights', default=None,
+                    help='state dict of the frozen ResNet50-FPN extractor (torchvision key names): images go through the HIP extractor')
     return ap.parse_args(argv)
 
 
@@ -47,7 +49,7 @@ def main(args):
     from modules.data import Load as load, Preprocessing as pre
     from modules.detect import detect_frame_set, write_kitti_results
     from MVXNet import MVXNet
-    from train_like import fpn_maps_for
+    from train_like import extractor_fpn_fn, fpn_maps_for
 
     device = X.device()
     torch.cuda.set_device(device)
@@ -67,12 +69,16 @@ def main(args):
     model = MVXNet().to(device)
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location=device))
+    fpn_fn = fpn_maps_for
+    if args.extractor_weights:
+        model.head.extractor.load_weights(args.extractor_weights).to(device)
+        fpn_fn = extractor_fpn_fn(model.head.extractor, {n: d[1] for d, n in zip(data, names)})
     kw = dict(score_thr=args.score_thr, iou_thr=args.iou_thr, pre_max=args.pre_max, post_max=args.post_max, decode=args.decode)
     cap = max(args.points, max(d[0].shape[0] for d in data))
     t0, n_boxes = time.perf_counter(), 0
     for lo in range(0, len(data), args.frames):
         group, gnames = data[lo:lo + args.frames], names[lo:lo + args.frames]
-        batch, _ = pl.batch_from_dataset(group, gnames, device, anchorBevs, fpn_maps_for, cap_points=cap)
+        batch, _ = pl.batch_from_dataset(group, gnames, device, anchorBevs, fpn_fn, cap_points=cap)
         dets = detect_frame_set(model, batch, anchors, cfg.imsize, **kw)
         for name, d, frame in zip(gnames, dets, group):
             write_kitti_results(os.path.join(out_dir, name + '.txt'), d, frame[5], cfg.imsize)

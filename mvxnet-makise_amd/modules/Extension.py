@@ -197,6 +197,12 @@ PROTOTYPES = {
     'mvx_gtdb_crop_count': (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _sz, _p]),
     'mvx_gtdb_crop_write': (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _sz, _p, _i64, _p]),
     'mvx_gtdb_raster': (_i32, [_p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _p, _p, _i64, _p]),
+    'mvx_image_prepare_frames': (_i32, [_p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
+    'mvx_stem_conv7_frames': (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _p]),
+    'mvx_maxpool3s2_frames': (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p]),
+    'mvx_add_relu_frames': (_i32, [_p, _p, _p, _i64, _p]),
+    'mvx_gather_stride2_frames': (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p]),
+    'mvx_topdown_merge_frames': (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
 }
 
 

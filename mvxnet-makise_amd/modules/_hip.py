@@ -2167,3 +2167,97 @@ def gtdb_raster(t, best, flag, roi, px_off, n_px, max_roi_rows):
                                   max(1, min(int(max_roi_rows), H)), X.ptr(mask), X.ptr(patch), mask.numel(), X.stream()),
             'mvx_gtdb_raster')
     return mask, patch
+
+
+# ---------------------------------------------------------------------------------------------
+# Frozen ResNet50-FPN image extractor (csrc/extractor.hip; modules/imhead/Extractor.py chains these with the row GEMMs and the
+# conv2d kernels above).  Forward only, channels-last frame sets (F, h, w, C).
+# ---------------------------------------------------------------------------------------------
+def prepared_size(h, w, min_size=800, max_size=1333, divisor=32):
+    """(oh, ow, ph, pw) of torchvision's GeneralizedRCNNTransform in eval mode: the resized size floor(dim * s) with
+    s = min(min_size / min(h, w), max_size / max(h, w)) held in float32 (torchvision forms it from float32 tensors and hands
+    interpolate its ``.item()``), and that size padded up to multiples of ``divisor``."""
+    import numpy as np
+    s = float(min(np.float32(min_size) / np.float32(min(h, w)), np.float32(max_size) / np.float32(max(h, w))))
+    oh, ow = int(np.floor(float(h) * s)), int(np.floor(float(w) * s))
+    up = lambda v: -(-v // divisor) * divisor
+    return oh, ow, up(oh), up(ow)
+
+
+def image_prepare(img, min_size=800, max_size=1333):
+    """u8 (F, H, W, 3) or f32 (F, 3, H, W) images -> (normalised, resized, zero-padded f32 (F, ph, pw, 4) with channel 3 zero,
+    (oh, ow)) in one launch (mvx_image_prepare_frames)."""
+    u8 = img.dtype == torch.uint8
+    if u8:
+        assert img.dim() == 4 and img.shape[3] == 3
+        F, H, W = img.shape[0], img.shape[1], img.shape[2]
+    else:
+        assert img.dtype == torch.float32 and img.dim() == 4 and img.shape[1] == 3
+        F, H, W = img.shape[0], img.shape[2], img.shape[3]
+    oh, ow, ph, pw = prepared_size(H, W, min_size, max_size)
+    out = torch.empty((F, ph, pw, 4), dtype=torch.float32, device=img.device)
+    with _timed_bytes('image_prepare', out.numel() * 4 + img.numel() * img.element_size()):
+        X.check(X.lib.mvx_image_prepare_frames(X.ptr(img), int(u8), X.ptr(out), F, H, W, oh, ow, ph, pw, X.stream()),
+                'mvx_image_prepare_frames')
+    return out, (oh, ow)
+
+
+def stem_conv7(x4, wpk, bias):
+    """ReLU(conv 7x7 / 2 / 3 (3 -> 64) + bias) of the prepared image (F, ph, pw, 4) -> (F, ch, cw, 64); wpk f32 (7, 7, 3, 64)."""
+    F, ph, pw = x4.shape[0], x4.shape[1], x4.shape[2]
+    assert x4.shape[3] == 4 and wpk.numel() == 49 * 3 * 64 and bias.numel() == 64
+    out = torch.empty((F, (ph - 1) // 2 + 1, (pw - 1) // 2 + 1, 64), dtype=torch.float32, device=x4.device)
+    with _Timed('stem_conv7', 2.0 * out.numel() * 147 if KERNEL_TIMERS is not None else 0):
+        X.check(X.lib.mvx_stem_conv7_frames(X.ptr(x4), X.ptr(wpk), X.ptr(bias), X.ptr(out), F, ph, pw, X.stream()),
+                'mvx_stem_conv7_frames')
+    return out
+
+
+def maxpool3s2(x):
+    """Max pool 3x3 / 2 / 1 of (F, h, w, C)."""
+    F, h, w, C = x.shape
+    out = torch.empty((F, (h - 1) // 2 + 1, (w - 1) // 2 + 1, C), dtype=torch.float32, device=x.device)
+    X.check(X.lib.mvx_maxpool3s2_frames(X.ptr(x), X.ptr(out), F, h, w, C, X.stream()), 'mvx_maxpool3s2_frames')
+    return out
+
+
+def add_relu(a, b):
+    """ReLU(a + b) of two tensors of the same shape (the bottleneck's skip)."""
+    assert a.shape == b.shape
+    out = torch.empty_like(a)
+    X.check(X.lib.mvx_add_relu_frames(X.ptr(a), X.ptr(b), X.ptr(out), a.numel(), X.stream()), 'mvx_add_relu_frames')
+    return out
+
+
+def gather_stride2(x):
+    """(F, h, w, C) -> its even (y, x) sites (F, ceil(h / 2), ceil(w / 2), C): the rows a 1x1 stride-2 convolution reads."""
+    F, h, w, C = x.shape
+    out = torch.empty((F, (h - 1) // 2 + 1, (w - 1) // 2 + 1, C), dtype=torch.float32, device=x.device)
+    X.check(X.lib.mvx_gather_stride2_frames(X.ptr(x), X.ptr(out), F, h, w, C, X.stream()), 'mvx_gather_stride2_frames')
+    return out
+
+
+def topdown_merge(lateral, top):
+    """lateral (F, 2h, 2w, C) + nearest_upsample(top (F, h, w, C)); any other size relation is an error."""
+    F, lh, lw, C = lateral.shape
+    if top.shape != (F, lh // 2, lw // 2, C) or lh % 2 or lw % 2:
+        raise X.MvxHipError('topdown_merge: the lateral map %s is not exactly twice the top map %s' % (tuple(lateral.shape), tuple(top.shape)))
+    out = torch.empty_like(lateral)
+    X.check(X.lib.mvx_topdown_merge_frames(X.ptr(lateral), X.ptr(top), X.ptr(out), F, lh, lw, top.shape[1], top.shape[2], C,
+                                           X.stream()), 'mvx_topdown_merge_frames')
+    return out
+
+
+def conv2d_forward_plain(x, wpk, bias, F, h, w, cin, cout, flags, relu, split=False):
+    """[ReLU](conv(x) + b) of the conv2d kernels WITHOUT BatchNorm statistics (stats == NULL): the 3x3 layers of a frozen network
+    whose BatchNorm is folded into weight and bias."""
+    y = torch.empty((F, h, w, cout), dtype=torch.float32, device=x.device)
+    fl = (FLAG_RELU if relu else 0) | flags
+    with _Timed('extractor_conv', _conv2d_flops(F, h, w, cin, cout, flags)):
+        if split:
+            X.check(X.lib.mvx_conv2d_forward_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), None, h, w, cin, cout,
+                                                          fl | split_flags(split), F, X.stream()), 'mvx_conv2d_forward_split_frames')
+        else:
+            X.check(X.lib.mvx_conv2d_forward_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), None, h, w, cin, cout, fl, None, 0.0,
+                                                    None, X.ptr(_work_counter(x.device)), F, X.stream()), 'mvx_conv2d_forward_frames')
+    return y

@@ -16,15 +16,16 @@ from modules.layers.Blocks import fcn_rows
 
 
 class ImageFeatureExtractor(nn.Module):
-    """Frozen torchvision Faster-RCNN-v2 ResNet50-FPN trunk (reference Pipe.py:8-21).  Third-party,
-    forward-only and needs downloaded weights, so it is outside the hot path:
-    it is built lazily and only if torchvision is importable; FPN maps can always be passed to
-    ``ImageHead`` / ``MVXNet`` directly instead of an image."""
+    """Frozen torchvision Faster-RCNN-v2 ResNet50-FPN trunk (reference Pipe.py:8-21), forward only.  After
+    ``load_weights(state dict or path)`` an image runs through this library's own network (modules/imhead/Extractor.py: HIP
+    kernels, no torchvision).  Before it, FPN maps can always be passed to ``ImageHead`` / ``MVXNet`` directly instead of an
+    image, and an image goes through torchvision if that is importable (built lazily) and raises otherwise."""
 
     def __init__(self):
         super().__init__()
         self.transform = None
         self.backbone = None
+        self._net = None
 
     def _build(self):
         try:
@@ -36,9 +37,47 @@ class ImageFeatureExtractor(nn.Module):
         net = fasterrcnn_resnet50_fpn_v2(weights=FasterRCNN_ResNet50_FPN_V2_Weights.DEFAULT)
         self.transform, self.backbone = net.transform, net.backbone
 
+    def load_weights(self, src, min_size=800, max_size=1333):
+        """``src``: a state dict with torchvision's key names (bare, or below ``backbone.`` / ``head.extractor.backbone.``) or a
+        path to one (read with ``weights_only=True``).  The frozen tensors become buffers ``backbone.<torchvision key>`` of
+        this module -- only now, so a model without loaded weights keeps its state-dict keys -- and images run on the HIP
+        network from here on."""
+        from . import Extractor
+        sd = Extractor.clean_state_dict(src)
+        dev = next((b.device for b in self.buffers()), None)
+        self.backbone = Extractor.buffer_tree(sd)
+        if dev is not None:
+            self.backbone.to(dev)
+        self.transform = None
+        self.min_size, self.max_size = min_size, max_size          # of the transform; read when the network is built
+        self._net = None
+        self._hip = True
+        return self
+
+    def _network(self, device):
+        """The folded, packed network on ``device`` (rebuilt when the module has moved)."""
+        if self._net is None or self._net.device != device:
+            from . import Extractor
+            sd = {k: v.detach().cpu() for k, v in self.backbone.state_dict().items()}
+            self._net = Extractor.FrozenResNet50FPN(sd, device, self.min_size, self.max_size)
+        return self._net
+
+    def extract_frames(self, images):
+        """u8 (F, H, W, 3) device images (the layout ``gt_paste_image`` writes) -> per frame [f0, f1, f2], each a (1, 256, h, w)
+        channels-last view: all frames of a step in one chain of launches."""
+        if not getattr(self, '_hip', False):
+            raise RuntimeError('extract_frames needs load_weights() first')
+        with torch.no_grad():
+            maps = self._network(images.device).maps(images)
+        return [[m[k:k + 1].permute(0, 3, 1, 2) for m in maps] for k in range(images.shape[0])]
+
     def forward(self, x):
         if isinstance(x, (list, tuple)):              # precomputed FPN maps
             return list(x)
+        if getattr(self, '_hip', False):
+            with torch.no_grad():
+                maps = self._network(x.device).maps(x.contiguous() if x.dtype == torch.uint8 else x.float().contiguous())
+            return [m.permute(0, 3, 1, 2) for m in maps]
         if self.backbone is None:
             self._build()
         x, _ = self.transform(x)

@@ -612,8 +612,11 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     ``augment`` (default None: off): ``{'db': LoadGT.GTDatabase on ``device``, 'lim': 12}`` runs the GT-paste augmentation of
     train.py:28 on all frames first (modules/augment/Augment.augmentFrames: four launches, one host read; optional keys
     'rng', 'cand', 'thr' as there, 'images': True also pastes the camera images, kept as ``batch.images`` u8 (B,H,W,3),
-    'keep': a dict that receives the FramesResult); ``cap_points`` must leave room for the pasted points."""
+    'keep': a dict that receives the FramesResult, 'extractor': an ``ImageFeatureExtractor`` with loaded weights: the images are
+    pasted and the FPN maps of all frames come from it, after the paste, in one chain of launches -- ``fpn_fn`` is not called);
+    ``cap_points`` must leave room for the pasted points."""
     import numpy as np
+    extractor = augment.get('extractor') if augment is not None else None
     from modules import Calc
     from modules.data.Preprocessing import _calib_products
     B = len(group)
@@ -632,17 +635,20 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
             np.random.shuffle(a)
             perms[k, :P] = a
         n[k] = P
-        fpn.append(fpn_fn(names[k], device))
+        if extractor is None:
+            fpn.append(fpn_fn(names[k], device))
     batch = FrameBatch(pts6, torch.from_numpy(perms).to(device), torch.from_numpy(n).to(device), fpn)
     if augment is not None:
         from modules.augment import Augment
         images = None
-        if augment.get('images'):
+        if augment.get('images') or extractor is not None:
             images = torch.from_numpy(np.stack([np.ascontiguousarray(d[1], dtype=np.uint8) for d in group])).to(device)
         res = Augment.augmentFrames(batch, images, [None if d[3] is None else (d[2], d[3], d[4]) for d in group], augment['db'],
                                     lim=augment.get('lim', 12), cand=augment.get('cand'), thr=augment.get('thr'),
                                     rng=augment.get('rng'))
         batch.images = images
+        if extractor is not None:                 # the frozen extractor reads the images AFTER the paste
+            batch.fpn_levels = extractor.extract_frames(images)
         if augment.get('keep') is not None:
             augment['keep']['result'] = res
         boxes, gts = res.boxes, res.bbox3d

@@ -2,15 +2,17 @@
 loop, checkpoints and resume), running on this package's HIP modules.
 
     python train_like.py <dataroot> [-n EPOCHS] [-r LAST] [--steps K] [--mode module|fast] [--frames B] [--synthetic N]
-                         [--augment [--gtdatabase DIR]]
+                         [--augment [--gtdatabase DIR]] [--extractor-weights FILE]
 
 What is the same as train.py: createDataset -> createAnchors / bbox3d2bev -> MVXNet, VoxelLoss, AdamW(lr 1e-3, eps) ->
 per frame lidar2Img + (row, col) swap + group + classifyAnchors -> forward -> clsLoss (+ regLoss) -> backward -> step ->
 running loss statistics -> per-epoch ``checkpoints/epoch{n}.pkl`` / ``epoch{n}_opt.pkl`` and ``-r`` resume.
 The GT-paste augmentation of train.py:28 is there with ``--augment`` (modules/augment, on the GPU; ``--synthetic`` also writes
-a synthetic gtdatabase; off by default).  What is not there: the frozen torchvision extractor when torchvision is not
-installed (FPN maps are then deterministic synthetic tensors per frame; with torchvision the image goes through the real
-extractor).
+a synthetic gtdatabase; off by default).  The frozen image extractor runs on this package's own kernels with
+``--extractor-weights FILE`` (a state dict with torchvision's key names, e.g. a checkpoint of the reference's train.py;
+modules/imhead/Extractor.py): every frame's image then goes through it, after the GT paste when ``--augment`` is on.  Without
+the flag the FPN maps are deterministic synthetic tensors per frame (or, in --mode module with torchvision installed, come
+from torchvision).
 
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
@@ -52,6 +54,8 @@ def parse_args(argv=None):
     ap.add_argument('--augment', action='store_true', help='GT-paste augmentation (train.py:28: up to 12 cars per frame)')
     ap.add_argument('--gtdatabase', default=None, help='root that holds training/gtdatabase (default: dataroot)')
     ap.add_argument('--augment-objects', type=int, default=200, help='objects of the synthetic gtdatabase (--synthetic --augment)')
+    ap.add_argument('--extractor-weights', default=None,
+                    help='state dict of the frozen ResNet50-FPN extractor (torchvision key names): images go through the HIP extractor')
     return ap.parse_args(argv)
 
 
@@ -61,6 +65,14 @@ def fpn_maps_for(name, dev):
     g = torch.Generator(device=dev).manual_seed(3000 + int(name))
     return [torch.randn((1, 256, h, w), generator=g, device=dev).contiguous(memory_format=torch.channels_last)
             for h, w in ((104, 336), (52, 168), (26, 84))]
+
+
+def extractor_fpn_fn(extractor, images_by_name):
+    """``fpn_fn`` of the real extractor: the frame's camera image (H, W, 3) u8 -> its three FPN maps."""
+    def fpn_fn(name, dev):
+        img = torch.from_numpy(np.ascontiguousarray(images_by_name[name], dtype=np.uint8)).to(dev)
+        return extractor.extract_frames(img[None])[0]
+    return fpn_fn
 
 
 def have_torchvision():
@@ -157,6 +169,15 @@ def train(args):
         opt.load_state_dict(torch.load(os.path.join(args.checkpoints, 'epoch%d_opt.pkl' % args.lastiter), map_location=device))
     bucket = parallel.GradBucket(params, late=[model.head.fusion.fcn1.fc.weight]) if args.mode == 'fast' else None
     tv = have_torchvision()
+    fpn_fn = fpn_maps_for
+    if args.extractor_weights:
+        if args.prefetch and aug is not None:
+            raise SystemExit('--extractor-weights with --augment runs the extractor after the paste, inside the step: drop --prefetch')
+        model.head.extractor.load_weights(args.extractor_weights).to(device)
+        fpn_fn = extractor_fpn_fn(model.head.extractor, {n: d[1] for d, n in zip(trainDataSet, trainSet)})
+        if aug is not None:
+            aug['extractor'] = model.head.extractor
+        tv = True                                  # --mode module: the image itself goes to the model
 
     forwardTime = lossTime = backwardTime = 0.0
     steps_done, losses, loop_stats = 0, [], []
@@ -223,14 +244,14 @@ def train(args):
                         if not group:
                             yield None, None
                         else:
-                            yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_maps_for, cap_points=cap,
+                            yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_fn, cap_points=cap,
                                                         augment=aug)
                 loader = batches()
             else:
                 # batch k+1 is prepared by a worker thread on its own stream while step k runs (the reference overlaps its CPU
                 # preparation with a process pool, train.py:185-187)
                 from modules.data.Prefetch import PrefetchLoader
-                loader = PrefetchLoader(groups, lambda d: names[id(d)], device, anchorBevs, fpn_maps_for, cap,
+                loader = PrefetchLoader(groups, lambda d: names[id(d)], device, anchorBevs, fpn_fn, cap,
                                         depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug)
             pending = None                        # the losses of a step are read one step later: the host never waits for
                                                   # the step it has just enqueued
