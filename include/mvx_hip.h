@@ -1041,6 +1041,47 @@ int mvx_gt_paste_image_frames(uint8_t *img, int32_t n_frames, int32_t h, int32_t
                               int32_t n_db, int64_t max_patch_px, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Geometric augmentation (csrc/geom_augment.hip) for the frames of a step (1..MVX_MAX_FRAMES): the per-object noise, global
+ * scaling and global rotation of VoxelNet section 3.2 and the y flip of the common MVX-Net recipes, then the range filter.  The
+ * host draws every random number: noise f32 [n_frames][cap_boxes][n_trials][4] = (dx, dy, dz, dtheta) per box slot and trial,
+ * glob f32 [n_frames][4] = (phi, s, flip != 0, unused).  Rotations are Calc.getRotationMatrices' R(a) = [[cos a, -sin a],
+ * [sin a, cos a]] on row vectors (qx = px cos a + py sin a, qy = -px sin a + py cos a); boxes are x y z l w h r with z the
+ * bottom face and corners local @ R(r) + centre (Calc.bbox3d2bev).  Coordinates are computed in f64 from the f32 inputs and
+ * rounded to f32 once; range decisions are taken on the rounded values.  range6_host: 6 doubles on the HOST, lo xyz, hi xyz.
+ *
+ * mvx_geom_place_frames: one workgroup per frame.  box3d f32 [n_frames][cap_boxes][7] holds n_box[f] boxes (read only).  The
+ *   boxes are visited in index order; trial t of box i passes when the quad of (x + dx, y + dy, l, w, r + dtheta) has
+ *   IoU <= iou_thr (mvx_bbox_pairwise's arithmetic, trial quad first) with every other box of the frame -- boxes j < i in their
+ *   already moved pose, boxes j > i in their original one; pairs whose bounding circles cannot touch count as 0.  The lowest
+ *   passing trial is taken: trial i32 [n_frames][cap_boxes] (-1: none, the box keeps its pose; also for unused slots), move
+ *   f32 [n_frames][cap_boxes][4] = its noise row, or zeros.  Then the global step on every box: centre and bottom z as a
+ *   point (xy <- s (xy @ R(phi)), z <- s z, y <- -y with flip), l w h <- s (l w h), r <- r + phi, negated with flip, wrapped
+ *   into [-pi, pi).  A box is kept iff lo <= (x, y) < hi; the kept boxes, in order, go to out_box3d [n_frames][cap_boxes][7]
+ *   (columns 0..1 are the centres) and out_bev [n_frames][cap_boxes][4][2] (recomputed from the new box), their original
+ *   indices to kept_idx i32 [n_frames][cap_boxes] (-1 padded), their number to n_kept i32 [n_frames].
+ *   status i32 [n_frames] (OR-ed into): MVX_GEOM_BAD_COUNT when n_box[f] is outside 0..cap_boxes (the frame then has no box).
+ * mvx_geom_points_frames: one thread per point, two launches (count per block of 256 points; offsets from the counts, ballot
+ *   scan, ordered write).  A point inside ORIGINAL box i (|u| <= l/2, |v| <= w/2, 0 <= pz - z <= h as in mvx_gtdb_crop_count;
+ *   the lowest index wins) with trial[i] >= 0 moves as xy <- (xy - c) @ R(dtheta) + c + (dx, dy), z <- z + dz; then every point
+ *   takes the global step; a point is kept iff lo <= p < hi on all three axes.  Kept rows keep their order and go to
+ *   out_points6 (a different buffer, same shape) with columns 3..5 copied bitwise; n_points_out[f] = their number.  Rows behind
+ *   n_points[f] are never read.  Both buffers 16-byte aligned; workspace: mvx_geom_workspace_bytes bytes.
+ * Limits (MVX_EINVAL before any launch): cap_boxes <= MVX_GT_PASTE_MAX_BOXES, n_trials <= MVX_GEOM_MAX_TRIALS.  No float
+ * atomics (bitwise reproducible), no host synchronisation.
+ */
+#define MVX_GEOM_MAX_TRIALS 32
+#define MVX_GEOM_BAD_COUNT 2
+size_t mvx_geom_workspace_bytes(int32_t n_frames, int32_t cap_points);
+int mvx_geom_place_frames(const float *box3d, const int32_t *n_box, int32_t n_frames, int32_t cap_boxes, const float *noise,
+                          int32_t n_trials, const float *glob, float iou_thr, const double *range6_host, int32_t *trial,
+                          float *move, float *out_box3d, float *out_bev, int32_t *kept_idx, int32_t *n_kept, int32_t *status,
+                          void *stream);
+int mvx_geom_points_frames(const float *points6, const int32_t *n_points, int32_t n_frames, int32_t cap_points,
+                           const float *box3d, const int32_t *n_box, int32_t cap_boxes, const int32_t *trial, const float *move,
+                           const float *glob, const double *range6_host, float *out_points6, int32_t *n_points_out,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Builder of the GT-paste object database (csrc/gtdb.hip): the reference's create_gtdatabase.py for the frames of a call.
  * The host parses (label files, the KINS annotation file, images, clouds) and prepares the label rows; the kernels match,
  * rasterise and cut.  Tables, all on the device:

@@ -192,6 +192,9 @@ PROTOTYPES = {
                                          _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _p, _p]),
     'mvx_gt_paste_points_frames': (_i32, [_p, _p, _p, _i32, _i32, _p, _i32, _p, _p, _i32, _p, _p]),
     'mvx_gt_paste_image_frames': (_i32, [_p, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i64, _p]),
+    'mvx_geom_workspace_bytes': (_sz, [_i32, _i32]),
+    'mvx_geom_place_frames': (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _f32, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'mvx_geom_points_frames': (_i32, [_p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'mvx_gtdb_workspace_bytes': (_sz, [_i32, _i32]),
     'mvx_gtdb_match': (_i32, [_p, _p, _p, _i32, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p, _p]),
     'mvx_gtdb_crop_count': (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _i32, _p, _p, _sz, _p]),

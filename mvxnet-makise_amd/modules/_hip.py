@@ -2105,6 +2105,63 @@ def gt_paste_image(img, picked, db):
 
 
 # ---------------------------------------------------------------------------------------------
+# Geometric augmentation (csrc/geom_augment.hip): per-object noise, global rotation / scaling / flip, range filter
+# ---------------------------------------------------------------------------------------------
+GEOM_MAX_TRIALS, GEOM_BAD_COUNT = 32, 2      # MVX_GEOM_*
+
+
+class GeomPlaced:
+    """Device outputs of geom_place: trial i32 (F, B), move f32 (F, B, 4), box3d f32 (F, B, 7), bev f32 (F, B, 4, 2),
+    kept_idx i32 (F, B), n_kept i32 (F,)."""
+    __slots__ = ('trial', 'move', 'box3d', 'bev', 'kept_idx', 'n_kept')
+
+
+def _range6_host(range6):
+    import numpy as np
+    return np.ascontiguousarray([float(v) for v in range6], dtype=np.float64)
+
+
+def geom_place(box3d, n_box, noise, glob, range6, status, iou_thr=0.05):
+    """The per-object placement, the global step on the boxes and the box filter of all frames in one launch.  box3d f32
+    (F, B, 7) (read only), n_box i32 (F,), noise f32 (F, B, T, 4), glob f32 (F, 4); status i32 (F,) is OR-ed into."""
+    F, B = box3d.shape[0], box3d.shape[1]
+    T = noise.shape[2]
+    dev = box3d.device
+    assert box3d.shape == (F, B, 7) and noise.shape == (F, B, T, 4) and glob.shape == (F, 4) and n_box.shape == (F,)
+    assert box3d.dtype == noise.dtype == glob.dtype == torch.float32 and n_box.dtype == torch.int32
+    out = GeomPlaced()
+    out.trial = torch.empty((F, B), dtype=torch.int32, device=dev)
+    out.move = torch.empty((F, B, 4), dtype=torch.float32, device=dev)
+    out.box3d = torch.zeros((F, B, 7), dtype=torch.float32, device=dev)
+    out.bev = torch.zeros((F, B, 4, 2), dtype=torch.float32, device=dev)
+    out.kept_idx = torch.empty((F, B), dtype=torch.int32, device=dev)
+    out.n_kept = torch.empty((F,), dtype=torch.int32, device=dev)
+    r = _range6_host(range6)
+    X.check(X.lib.mvx_geom_place_frames(X.ptr(box3d), X.ptr(n_box), F, B, X.ptr(noise), T, X.ptr(glob), float(iou_thr), _host_ptr(r),
+                                        X.ptr(out.trial), X.ptr(out.move), X.ptr(out.box3d), X.ptr(out.bev), X.ptr(out.kept_idx),
+                                        X.ptr(out.n_kept), X.ptr(status), X.stream()), 'mvx_geom_place_frames')
+    return out
+
+
+def geom_points(points6, n_points, box3d, n_box, placed, glob, range6):
+    """Every point of every frame through the per-object move (membership in the ORIGINAL boxes ``box3d``), the global step
+    and the range filter, compacted in order into a new buffer.  Returns (points6 f32 (F, cap, 6), n_points i32 (F,))."""
+    F, cap = points6.shape[0], points6.shape[1]
+    B = box3d.shape[1]
+    dev = points6.device
+    assert points6.shape == (F, cap, 6) and points6.dtype == torch.float32 and n_points.dtype == torch.int32
+    out = torch.empty_like(points6)
+    n_out = torch.empty((F,), dtype=torch.int32, device=dev)
+    ws = workspace(X.lib.mvx_geom_workspace_bytes(F, cap), dev, 'geom')
+    r = _range6_host(range6)
+    with _timed_bytes('geom_points', F * cap * 6 * 4 * 3):
+        X.check(X.lib.mvx_geom_points_frames(X.ptr(points6), X.ptr(n_points), F, cap, X.ptr(box3d), X.ptr(n_box), B,
+                                             X.ptr(placed.trial), X.ptr(placed.move), X.ptr(glob), _host_ptr(r), X.ptr(out),
+                                             X.ptr(n_out), X.ptr(ws), ws.numel(), X.stream()), 'mvx_geom_points_frames')
+    return out, n_out
+
+
+# ---------------------------------------------------------------------------------------------
 # Builder of the GT-paste database (csrc/gtdb.hip); ``t`` holds the device tables of a call (modules.augment.BuildGT.pack):
 # lab_box2d / lab_box3d / lab_cs / lab_frame / lab_group, ann_box / ann_off, edges / edge_poly / edge_off, images / im_hw,
 # points / pts_off, and the host numbers n_labels, n_frames, max_frame_points

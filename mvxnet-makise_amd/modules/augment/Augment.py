@@ -160,18 +160,23 @@ def augmentTargetClasses(pcd, img, bbox2ds, bbox3ds, bevs, gtwithinfo, targets, 
 class FramesResult:
     """What ``augmentFrames`` leaves: ``boxes`` per frame ``(bev (n,4,2), centres (n,2))`` or None, as
     Calc.classifyAnchorsFrames takes them; ``bbox3d`` per frame (n,7) on the device or None; ``picked`` per frame the pasted
-    database indices in slot order; ``n_points`` the new point counts (host list); ``status`` per frame."""
-    __slots__ = ('boxes', 'bbox3d', 'bbox2d', 'picked', 'n_points', 'status', 'debug')
+    database indices in slot order; ``n_points`` the new point counts (host list); ``status`` per frame.  With the geometric
+    augmentation ``boxes`` / ``bbox3d`` / ``n_points`` are those behind it, ``bbox2d`` is None (the 2-D boxes are stale) and
+    ``geometry`` holds its Geometry.GeomResult (None otherwise)."""
+    __slots__ = ('boxes', 'bbox3d', 'bbox2d', 'picked', 'n_points', 'status', 'debug', 'geometry')
 
 
-def augmentFrames(batch, images, scene_boxes, db, lim=12, cand=None, thr=None, rng=None, debug=False, shuffle=True):
+def augmentFrames(batch, images, scene_boxes, db, lim=12, cand=None, thr=None, rng=None, debug=False, shuffle=True, geometry=None):
     """GT paste for the frames of ``batch`` (pipeline.FrameBatch with prepared ``points6`` / ``n_points``) in four launches.
     ``images``: u8 device tensor (F, H, W, 3) pasted in place, or None; ``scene_boxes``: per frame (bbox2d, bbox3d, bev) or
     None; ``db``: GTDatabase on the batch's device.  ``cand`` i32 (F, S, 30) / ``thr`` f32 (F, S): the draws, made here when
     None -- from ``np.random`` in the reference's order (frame by frame, slot by slot), or from the Generator ``rng``.
     The points go behind each frame's scene points, ``batch.n_points`` is replaced, and -- after the ONE host read of the
     call (picked, box counts, point counts, status) -- the shuffle permutations of scene plus pasted points are drawn
-    into ``batch.perms`` (``shuffle``; the permutation stays an input of the voxelizer)."""
+    into ``batch.perms`` (``shuffle``; the permutation stays an input of the voxelizer).
+    ``geometry`` (default None: off): a Geometry.GeomParams or a dict as Geometry.geometry_draws takes it -- the geometric
+    augmentation's launches then go behind the point paste, on scene plus pasted boxes and points, and its words ride in the
+    same host read; the paste's own decisions do not depend on it."""
     dev = batch.device
     F = batch.n_frames
     cap = _hip.GT_PASTE_MAX_BOXES
@@ -196,9 +201,15 @@ def augmentFrames(batch, images, scene_boxes, db, lim=12, cand=None, thr=None, r
     if images is not None:
         _hip.gt_paste_image(images, picked, db)
     S = picked.shape[1]
-    host = torch.cat([picked.reshape(-1), n_out, n_new, status]).cpu().numpy()          # the one host read
+    geo, words = None, [picked.reshape(-1), n_out, n_new, status]
+    if geometry is not None:
+        from modules.augment import Geometry
+        noise, glob, iou_thr = Geometry.geometry_draws(geometry, F, cap)
+        geo = Geometry.launch(batch.points6, n_new, b3, n_out, noise, glob, iou_thr)
+        words += geo.words()
+    host = torch.cat(words).cpu().numpy()          # the one host read
     out = FramesResult()
-    out.status = host[F * S + 2 * F:].tolist()
+    out.status = host[F * S + 2 * F:F * S + 3 * F].tolist()
     _raise_on(out.status)
     out.picked = [[int(p) for p in host[f * S:(f + 1) * S] if p >= 0] for f in range(F)]
     counts = host[F * S:F * S + F]
@@ -210,7 +221,12 @@ def augmentFrames(batch, images, scene_boxes, db, lim=12, cand=None, thr=None, r
         out.bbox3d.append(b3[f, :k] if k else None)
         out.bbox2d.append(b2[f, :k] if k else None)
     out.debug = res[2:] if debug else None
+    out.geometry = None
     batch.n_points = n_new
+    if geo is not None:
+        g = out.geometry = geo.finish(host[F * S + 3 * F:])
+        out.boxes, out.bbox3d, out.bbox2d, out.n_points = g.boxes, g.bbox3d, None, g.n_points
+        batch.points6, batch.n_points = geo.points6, geo.n_points
     if shuffle:
         perms = np.zeros(tuple(batch.perms.shape), np.int32)
         for f in range(F):

@@ -39,7 +39,7 @@ class _Staging:
 
 
 class PrefetchLoader:
-    def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1, augment=None):
+    def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1, augment=None, geometry=None):
         """``groups``: iterable of lists of frames as ``modules.data.Load.createDataset`` returns them; ``names_of(frame)``:
         the frame's name (for ``fpn_fn``); ``fpn_fn(name, device)``: the frame's FPN maps (the frozen extractor or its
         stand-in); ``cap_points``: point capacity per frame of the resident batch."""
@@ -47,6 +47,7 @@ class PrefetchLoader:
         self.names_of, self.device, self.anchor_bevs, self.fpn_fn = names_of, device, anchor_bevs, fpn_fn
         self.cap = int(cap_points)
         self.augment = augment          # pipeline.batch_from_dataset's ``augment``: the GT paste then runs on the training stream
+        self.geometry = geometry        # ... and its ``geometry``: the geometric augmentation, behind the paste or alone
         self.stream = torch.cuda.Stream(device=device, priority=priority)
         self.q = queue.Queue(maxsize=max(1, depth))
         self.slots = {}
@@ -91,7 +92,7 @@ class PrefetchLoader:
             st.free = torch.cuda.Event()
             st.free.record(self.stream)
             targets = [None] * B
-            if self.augment is None:          # with the GT paste the boxes are only known after it (__next__)
+            if self.augment is None and self.geometry is None:          # with an augmentation the boxes are only known after it (__next__)
                 boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
                 lists = Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)      # one pass, one host read
                 targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
@@ -165,7 +166,12 @@ class PrefetchLoader:
             from modules.augment import Augment
             a = self.augment
             res = Augment.augmentFrames(batch, None, [None if d[3] is None else (d[2], d[3], d[4]) for d in group], a['db'],
-                                        lim=a.get('lim', 12), rng=a.get('rng'))
+                                        lim=a.get('lim', 12), rng=a.get('rng'), geometry=self.geometry)
+        elif self.geometry is not None:
+            from modules.augment import Geometry
+            noise, glob, iou_thr = Geometry.geometry_draws(self.geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
+            res = Geometry.augmentGeometryFrames(batch, [d[3] for d in group], noise, glob, iou_thr=iou_thr)
+        if self.augment is not None or self.geometry is not None:
             lists = Calc.classifyAnchorsFrames(res.boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)
             targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, res.bbox3d)]
         return batch, targets

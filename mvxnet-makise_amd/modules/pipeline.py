@@ -605,7 +605,7 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
 
 
 # ---- whole model on the fast path: frame sets up to the BEV map, RPN + VoxelLoss per frame ------------------------------
-def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None):
+def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None, geometry=None):
     """Frames of ``modules.data.Load.createDataset`` -> (FrameBatch resident on the GPU, per-frame targets).  Per frame, as
     train.py:26-49: lidar2Img on the torch path + (row, col) swap, the shuffle permutation drawn with np.random, and
     classifyAnchors for the 'Car' boxes; (pi, ni, gi, gt) or None when the frame has no box.
@@ -614,7 +614,11 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     'rng', 'cand', 'thr' as there, 'images': True also pastes the camera images, kept as ``batch.images`` u8 (B,H,W,3),
     'keep': a dict that receives the FramesResult, 'extractor': an ``ImageFeatureExtractor`` with loaded weights: the images are
     pasted and the FPN maps of all frames come from it, after the paste, in one chain of launches -- ``fpn_fn`` is not called);
-    ``cap_points`` must leave room for the pasted points."""
+    ``cap_points`` must leave room for the pasted points.
+    ``geometry`` (default None: off): a Geometry.GeomParams, or ``{'params': GeomParams, 'rng': np.random.Generator}`` (optional
+    keys 'noise', 'glob': the draws themselves, 'keep': a dict that receives the GeomResult): the geometric augmentation
+    (modules/augment/Geometry.py: per-object noise, global rotation / scaling / flip, range filter) after the projection --
+    behind the paste inside its one host read with ``augment``, three launches and one host read of its own without."""
     import numpy as np
     extractor = augment.get('extractor') if augment is not None else None
     from modules import Calc
@@ -630,7 +634,7 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
         pts6[k, :P, :4] = src
         m, p2 = _calib_products(calib, True)
         _hip.lidar2img(src, m, p2, math_f32=True, out=pts6[k, :P], col_offset=4, swap_rc=True)
-        if augment is None:
+        if augment is None and geometry is None:      # otherwise drawn over the new counts
             a = np.arange(P, dtype=np.int32)
             np.random.shuffle(a)
             perms[k, :P] = a
@@ -645,16 +649,25 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
             images = torch.from_numpy(np.stack([np.ascontiguousarray(d[1], dtype=np.uint8) for d in group])).to(device)
         res = Augment.augmentFrames(batch, images, [None if d[3] is None else (d[2], d[3], d[4]) for d in group], augment['db'],
                                     lim=augment.get('lim', 12), cand=augment.get('cand'), thr=augment.get('thr'),
-                                    rng=augment.get('rng'))
+                                    rng=augment.get('rng'), geometry=geometry)
         batch.images = images
         if extractor is not None:                 # the frozen extractor reads the images AFTER the paste
             batch.fpn_levels = extractor.extract_frames(images)
         if augment.get('keep') is not None:
             augment['keep']['result'] = res
         boxes, gts = res.boxes, res.bbox3d
+        geo = res.geometry
+    elif geometry is not None:
+        from modules.augment import Geometry
+        noise, glob, iou_thr = Geometry.geometry_draws(geometry, B, _hip.GT_PASTE_MAX_BOXES)
+        geo = Geometry.augmentGeometryFrames(batch, [d[3] for d in group], noise, glob, iou_thr=iou_thr)
+        boxes, gts = geo.boxes, geo.bbox3d
     else:
+        geo = None
         boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
         gts = [None if d[3] is None else d[3].to(device) for d in group]
+    if geo is not None and isinstance(geometry, dict) and geometry.get('keep') is not None:
+        geometry['keep']['result'] = geo
     # target assignment of all frames in one kernel pass / one host read
     lists = Calc.classifyAnchorsFrames(boxes, anchorBevs, cfg.velorange, 0.45, 0.6)
     targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, gts)]

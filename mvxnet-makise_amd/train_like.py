@@ -2,13 +2,14 @@
 loop, checkpoints and resume), running on this package's HIP modules.
 
     python train_like.py <dataroot> [-n EPOCHS] [-r LAST] [--steps K] [--mode module|fast] [--frames B] [--synthetic N]
-                         [--augment [--gtdatabase DIR]] [--extractor-weights FILE]
+                         [--augment [--gtdatabase DIR]] [--augment-geometry] [--extractor-weights FILE]
 
 What is the same as train.py: createDataset -> createAnchors / bbox3d2bev -> MVXNet, VoxelLoss, AdamW(lr 1e-3, eps) ->
 per frame lidar2Img + (row, col) swap + group + classifyAnchors -> forward -> clsLoss (+ regLoss) -> backward -> step ->
 running loss statistics -> per-epoch ``checkpoints/epoch{n}.pkl`` / ``epoch{n}_opt.pkl`` and ``-r`` resume.
 The GT-paste augmentation of train.py:28 is there with ``--augment`` (modules/augment, on the GPU; ``--synthetic`` also writes
-a synthetic gtdatabase; off by default).  The frozen image extractor runs on this package's own kernels with
+a synthetic gtdatabase; off by default); ``--augment-geometry`` adds VoxelNet's per-object noise, global scaling and rotation and
+the y flip behind it or alone (modules/augment/Geometry.py).  The frozen image extractor runs on this package's own kernels with
 ``--extractor-weights FILE`` (a state dict with torchvision's key names, e.g. a checkpoint of the reference's train.py;
 modules/imhead/Extractor.py): every frame's image then goes through it, after the GT paste when ``--augment`` is on.  Without
 the flag the FPN maps are deterministic synthetic tensors per frame (or, in --mode module with torchvision installed, come
@@ -54,6 +55,9 @@ def parse_args(argv=None):
     ap.add_argument('--augment', action='store_true', help='GT-paste augmentation (train.py:28: up to 12 cars per frame)')
     ap.add_argument('--gtdatabase', default=None, help='root that holds training/gtdatabase (default: dataroot)')
     ap.add_argument('--augment-objects', type=int, default=200, help='objects of the synthetic gtdatabase (--synthetic --augment)')
+    ap.add_argument('--augment-geometry', action='store_true',
+                    help='geometric augmentation (VoxelNet 3.2: per-object noise, global scaling and rotation; plus the y flip), '
+                         'with or without --augment')
     ap.add_argument('--extractor-weights', default=None,
                     help='state dict of the frozen ResNet50-FPN extractor (torchvision key names): images go through the HIP extractor')
     return ap.parse_args(argv)
@@ -83,9 +87,10 @@ def have_torchvision():
         return False
 
 
-def cputask(data, anchorBevs, cfg, gtwithinfo=None):
+def cputask(data, anchorBevs, cfg, gtwithinfo=None, geometry=None):
     """train.py:26-49: (GT-paste augmentation when ``gtwithinfo`` is given,) projection, (row, col) swap, voxelization,
-    target assignment."""
+    target assignment.  ``geometry`` = {'params', 'rng'}: the geometric augmentation between the projection and the grouping,
+    so that every point keeps the pixel it was seen at."""
     from modules.Calc import classifyAnchors
     from modules.data import Preprocessing as pre
     from modules.utils import lidar2Img
@@ -103,6 +108,9 @@ def cputask(data, anchorBevs, cfg, gtwithinfo=None):
         for ap_, ac in zip(augpcd, augcalib):
             pcdxy.append(np.concatenate([ap_, lidar2Img(ap_, ac, True)[:, ::-1]], axis=1))
         pcd6 = np.concatenate(pcdxy, axis=0).astype(np.float32)          # train.py:125 casts the voxels to float32
+    if geometry is not None:
+        from modules.augment.Geometry import augmentGeometry
+        pcd6, bbox3d, bev = augmentGeometry(pcd6, bbox3d, params=geometry.get('params'), rng=geometry['rng'])
     voxel, idx = pre.group(pcd6, cfg.velorange, cfg.voxelsize, cfg.samplenum)
     if bev is not None and bev.shape[0] != 0:
         pi, ni, gi = classifyAnchors(bev, bbox3d[:, [0, 1]], anchorBevs, cfg.velorange, 0.45, 0.6)
@@ -151,6 +159,11 @@ def train(args):
         db = GTDatabase.from_gts(gtwithinfo['Car'], device)
         # --mode fast draws with a Generator: the reference-order draw permutes the whole database once per slot
         aug = {'db': db, 'lim': 12, 'rng': np.random.default_rng(rank)}
+    geo = None
+    if args.augment_geometry:
+        from modules.augment.Geometry import GeomParams
+        geo = {'params': GeomParams(), 'rng': np.random.default_rng([rank, 1])}          # per rank, apart from the paste's stream
+    if args.augment:
         say('gtdatabase: %d objects, %.1f MB resident, %d points dropped at load' % (db.n, db.nbytes() / 1e6, db.dropped_points))
 
     anchors = pre.createAnchors(cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2, cfg.velorange, cfg.carsize)
@@ -188,7 +201,7 @@ def train(args):
         clsCnt = regCnt = 0
         if args.mode == 'module':
             for i, data in enumerate(mine):
-                voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo)
+                voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo, geo)
                 calib = {k: torch.Tensor(calibCpu[k]).to(device) for k in calibCpu}
                 idx4 = np.concatenate([np.zeros((idx.shape[0], 1)), idx], axis=1)
                 opt.zero_grad()
@@ -245,14 +258,14 @@ def train(args):
                             yield None, None
                         else:
                             yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_fn, cap_points=cap,
-                                                        augment=aug)
+                                                        augment=aug, geometry=geo)
                 loader = batches()
             else:
                 # batch k+1 is prepared by a worker thread on its own stream while step k runs (the reference overlaps its CPU
                 # preparation with a process pool, train.py:185-187)
                 from modules.data.Prefetch import PrefetchLoader
                 loader = PrefetchLoader(groups, lambda d: names[id(d)], device, anchorBevs, fpn_fn, cap,
-                                        depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug)
+                                        depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug, geometry=geo)
             pending = None                        # the losses of a step are read one step later: the host never waits for
                                                   # the step it has just enqueued
 

@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.join(REPO, 'mvxnet-makise_amd'))
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 32
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 4
 AUG = len(sys.argv) > 3 and sys.argv[3] == 'augment'
+GEO = len(sys.argv) > 3 and sys.argv[3] == 'geometry'
 sys.argv = sys.argv[:1]
 import numpy as np  # noqa: E402
 import train_like  # noqa: E402
@@ -27,6 +28,11 @@ if AUG:
     # synthetic gtdatabase), alternating, in one process instead;
     # the first run writes the synthetic tree, and with --augment the synthetic gtdatabase too
     runs = (('no_prefetch_augment', ['--augment']), ('no_prefetch', []), ('no_prefetch_augment_2', ['--augment']), ('no_prefetch_2', []))
+if GEO:
+    # a third argument ``geometry``: the GT paste alone and with the geometric augmentation behind it (--augment-geometry),
+    # alternating, in one process
+    runs = (('augment_geometry', ['--augment', '--augment-geometry']), ('augment', ['--augment']),
+            ('augment_geometry_2', ['--augment', '--augment-geometry']), ('augment_2', ['--augment']))
 for label, extra in runs:
     args = train_like.parse_args([root, '-n', '2', '--mode', 'fast', '--frames', str(B), '--points', '20000', '--quiet',
                                   '--checkpoints', os.path.join(root, 'ck_' + label)] + extra + (['--synthetic', str(n)] if first else []))
