@@ -24,13 +24,9 @@ __global__ __launch_bounds__(PAIR_THREADS) void bbox_pairwise(const float *__res
     if (t >= (long long)n * m) return;
     const int i = (int)(t / m), j = (int)(t % m);
     const Polys w = polys_of(s_poly, PAIR_THREADS, threadIdx.x);
-    load_quad(w.q1, b1 + (size_t)i * 8);
-    load_quad(w.q2, b2 + (size_t)j * 8);
-    const float a1 = shoelace(w.q1, 4), a2 = shoelace(w.q2, 4);     // signed, before the re-orientation (as the reference)
-    orient_ccw(w.q1);
-    orient_ccw(w.q2);
+    const float a1 = load_oriented(w.q1, b1 + (size_t)i * 8), a2 = load_oriented(w.q2, b2 + (size_t)j * 8);
     const float inter = quad_intersection(w.q1, w.q2, w.p, w.q);
-    out[t] = iou ? inter / (a1 + a2 - inter) : inter;
+    out[t] = iou ? inter / (a1 + a2 - inter) : inter;     // bboxOverlap : bboxIntersection
 }
 
 // One workgroup per (ground truth g, orientation z).  LDS: (2R+1)^2 IoUs.
@@ -54,11 +50,9 @@ __global__ __launch_bounds__(256) void anchor_window_walk(const float *__restric
     }
     const Polys wk = polys_of(s_poly, 256, threadIdx.x);
     const LP gt = wk.q1, q = wk.q2;
-    load_quad(gt, gts + (size_t)g * 8);
-    const float gt_area = shoelace(gt, 4);
-    orient_ccw(gt);
+    const float gt_area = load_oriented(gt, gts + (size_t)g * 8);
     load_quad(q, anchors);
-    const float anchor_area = shoelace(q, 4);
+    const float anchor_area = shoelace(q, 4);         // of anchors[0], once, for every cell: the reference's arithmetic
     // Bounding circles: boxes whose centres are further apart than the two half diagonals (+ 1 %) cannot touch.  Their
     // true IoU is 0 and the reference's origin-fan sum gives rounding noise of ~1e-6 there; either ends the walk
     // (iou < 0.1) the same way and neither value is ever output, so those cells skip the clipping.

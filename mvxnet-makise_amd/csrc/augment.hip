@@ -84,11 +84,7 @@ __global__ __launch_bounds__(PLACE_THREADS) void gt_place(PlaceArgs a) {
             s_area[i] = (s_b2[i][2] - s_b2[i][0]) * (s_b2[i][3] - s_b2[i][1]);
 #pragma unroll
             for (int k = 0; k < 8; ++k) s_quad[i][k] = g_bev[i * 8 + k];
-            const P2 *q = (const P2 *)s_quad[i];
-            P2 c;
-            float r;
-            quad_circle(q, c, r);
-            s_circ[i][0] = c.x; s_circ[i][1] = c.y; s_circ[i][2] = r;
+            circle_of(s_quad[i], s_circ[i]);
         }
     }
     __syncthreads();
@@ -124,10 +120,7 @@ __global__ __launch_bounds__(PLACE_THREADS) void gt_place(PlaceArgs a) {
                 for (int k = 0; k < 4; ++k) c_b2[c][k] = a.db_box2d[(size_t)idx * 4 + k];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) c_quad[c][k] = a.db_bev[(size_t)idx * 8 + k];
-                P2 cc;
-                float r;
-                quad_circle((const P2 *)c_quad[c], cc, r);
-                c_circ[c][0] = cc.x; c_circ[c][1] = cc.y; c_circ[c][2] = r;
+                circle_of(c_quad[c], c_circ[c]);
             }
             c_idx[c] = idx;
             c_state[c] = state;
@@ -145,15 +138,7 @@ __global__ __launch_bounds__(PLACE_THREADS) void gt_place(PlaceArgs a) {
             s_iof[c][i] = (iw * ih) / s_area[i];
             float iou = 0.f;
             const P2 c1 = {c_circ[c][0], c_circ[c][1]}, c2 = {s_circ[i][0], s_circ[i][1]};
-            if (!circles_apart(c1, c_circ[c][2], c2, s_circ[i][2])) {
-                load_quad(w.q1, c_quad[c]);
-                load_quad(w.q2, s_quad[i]);
-                const float a1 = shoelace(w.q1, 4), a2 = shoelace(w.q2, 4);      // signed, before the re-orientation
-                orient_ccw(w.q1);
-                orient_ccw(w.q2);
-                const float inter = quad_intersection(w.q1, w.q2, w.p, w.q);
-                iou = inter / (a1 + a2 - inter);
-            }
+            if (!circles_apart(c1, c_circ[c][2], c2, s_circ[i][2])) iou = quad_iou(w, c_quad[c], s_quad[i]);
             s_iou[c][i] = iou;
         }
         __syncthreads();

@@ -1,4 +1,4 @@
-// BEV rotated-box IoU device functions shared by anchors.hip (target assignment) and detect.hip (NMS).
+// BEV rotated-box IoU device functions shared by target assignment, NMS, evaluation and the two augmentations.
 //
 // The arithmetic of the reference's cpp/voxelutil.cpp:18-116 (bboxOverlap), operation for operation in f32: origin-fan
 // triangulation, half-plane cuts with the 1e-6 tolerance, shoelace areas halved in f64.  Every translation unit that
@@ -103,6 +103,15 @@ __device__ __forceinline__ void load_quad(LP q, const float *src) {
     for (int k = 0; k < 4; ++k) { P2 v; v.x = src[2 * k]; v.y = src[2 * k + 1]; q[k] = v; }
 }
 
+// quad `src` (8 floats) into q (5 slots), oriented for quad_intersection; returns its SIGNED shoelace area, taken before
+// the re-orientation as the reference does (voxelutil.cpp:99-103)
+__device__ __forceinline__ float load_oriented(LP q, const float *src) {
+    load_quad(q, src);
+    const float area = shoelace(q, 4);
+    orient_ccw(q);
+    return area;
+}
+
 // the four polygon areas of this thread inside a [POLY_SLOTS][threads] LDS block
 struct Polys { LP p, q, q1, q2; };
 __device__ __forceinline__ Polys polys_of(P2 *block, int threads, int t) {
@@ -114,6 +123,13 @@ __device__ __forceinline__ Polys polys_of(P2 *block, int threads, int t) {
     return r;
 }
 
+// IoU of the quads qa, qb (8 floats each) as bboxOverlap computes it
+__device__ __forceinline__ float quad_iou(const Polys &w, const float *qa, const float *qb) {
+    const float a1 = load_oriented(w.q1, qa), a2 = load_oriented(w.q2, qb);
+    const float inter = quad_intersection(w.q1, w.q2, w.p, w.q);
+    return inter / (a1 + a2 - inter);
+}
+
 // Bounding circle of a quad (q[0..4) as P2): centre = mean of the corners, radius = largest corner distance from it
 template <class Quad>
 __device__ __forceinline__ void quad_circle(const Quad &q, P2 &c, float &r) {
@@ -123,6 +139,14 @@ __device__ __forceinline__ void quad_circle(const Quad &q, P2 &c, float &r) {
     for (int k = 0; k < 4; ++k) { const P2 v = q[k]; c.x += 0.25f * v.x; c.y += 0.25f * v.y; }
 #pragma unroll
     for (int k = 0; k < 4; ++k) { const P2 v = q[k]; r = fmaxf(r, sqrtf((v.x - c.x) * (v.x - c.x) + (v.y - c.y) * (v.y - c.y))); }
+}
+
+// ... as a table row [cx, cy, r] from the quad's 8 floats
+__device__ __forceinline__ void circle_of(const float *quad8, float *circ3) {
+    P2 c;
+    float r;
+    quad_circle((const P2 *)quad8, c, r);
+    circ3[0] = c.x; circ3[1] = c.y; circ3[2] = r;
 }
 
 // Boxes whose centres are further apart than the two radii (+ 1 %) cannot touch: their true IoU is 0 and the origin-fan sum

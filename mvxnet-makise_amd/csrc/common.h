@@ -59,6 +59,8 @@ int mvxi_linear_wgrad_split(const float *x, int ldx, const float *dz, int lddz, 
                             const SplitAmax &am = SplitAmax{nullptr, nullptr, 0});
 int mvxi_wgrad_step_list(const int32_t *in_halo_flags, int din, int dout, int ntiles, int stride_d, int pad_d, int *list,
                          int *count, hipStream_t st, int n_frames = 1);
+// geometry.hip: bcount[f][0..nblocks) -> its exclusive scan in place, totals[f] = the frame's sum; one workgroup per frame
+int mvxi_scan_block_counts(int *bcount, int nblocks, int n_frames, int *totals, hipStream_t st);
 int mvxi_wgrad_rank1(const float *tap_sums, const float *c_in, float *dw, int din, int dout, int cin, int cout, int stride_d,
                      int pad_d, hipStream_t st, int n_frames = 1);
 
@@ -143,35 +145,39 @@ __device__ __forceinline__ int mvx_dst_plane(int d, int din, int dout, int sd, i
 }
 
 // ---- wave / block reductions and scans -------------------------------------------------
-__device__ __forceinline__ int wave_incl_scan_i32(int v) {
+template <typename T>
+__device__ __forceinline__ T wave_incl_scan(T v) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
-        int t = __shfl_up(v, d, 64);
+        T t = __shfl_up(v, d, 64);
         if (lane >= d) v += t;
     }
     return v;
 }
 
-// Exclusive scan across a 1024-thread block (16 waves).  `smem` needs 17 ints.  Returns the
-// exclusive prefix of this thread's value; *total receives the block sum.
-__device__ __forceinline__ int block_excl_scan_i32(int v, int *smem, int *total) {
+// Exclusive scan across a block of up to 1024 threads (16 waves), T = int or long long.  `smem` needs 17 T.  Returns the
+// exclusive prefix of this thread's value; *total receives the block sum.  Ends with a barrier: smem is free on return.
+template <typename T>
+__device__ __forceinline__ T block_excl_scan(T v, T *smem, T *total) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int inc = wave_incl_scan_i32(v);
+    T inc = wave_incl_scan(v);
     if (lane == 63) smem[wid] = inc;
     __syncthreads();
     if (wid == 0) {
-        int w = lane < nw ? smem[lane] : 0;
-        int wi = wave_incl_scan_i32(w);
+        T w = lane < nw ? smem[lane] : 0;
+        T wi = wave_incl_scan(w);
         if (lane < nw) smem[lane] = wi - w;
         if (lane == nw - 1) smem[16] = wi;
     }
     __syncthreads();
-    int res = inc - v + smem[wid];
+    T res = inc - v + smem[wid];
     *total = smem[16];
     __syncthreads();
     return res;
 }
+__device__ __forceinline__ int wave_incl_scan_i32(int v) { return wave_incl_scan<int>(v); }
+__device__ __forceinline__ int block_excl_scan_i32(int v, int *smem, int *total) { return block_excl_scan<int>(v, smem, total); }
 
 // ---- BatchNorm finalisation by the last workgroup of the producing kernel ----------------------------
 // Every workgroup calls this after its statistics atomics (all threads, block-uniform arguments).  The workgroup that
@@ -255,6 +261,11 @@ __device__ __forceinline__ void bn_finalize_by_last_block(unsigned *done_counter
 }
 
 __device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;

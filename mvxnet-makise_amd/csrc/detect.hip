@@ -277,9 +277,7 @@ __global__ __launch_bounds__(MASK_THREADS) void detect_mask(Layout lay, unsigned
     unsigned bits = 0u;
     if (okv[i]) {
         const Polys w = polys_of(s_poly, MASK_THREADS, t);
-        load_quad(w.q1, quad + (size_t)i * 8);
-        const float a1 = shoelace(w.q1, 4);     // signed, before the re-orientation (bbox_pairwise)
-        orient_ccw(w.q1);
+        const float a1 = load_oriented(w.q1, quad + (size_t)i * 8);     // row i once, outside the column loop
         const P2 c1 = {circ[(size_t)i * 4], circ[(size_t)i * 4 + 1]};
         const float r1 = circ[(size_t)i * 4 + 2];
         const int jn = min(MASK_COLS, n_sel - j0);
@@ -288,9 +286,7 @@ __global__ __launch_bounds__(MASK_THREADS) void detect_mask(Layout lay, unsigned
             if (j <= i || !s_ok[jj]) continue;
             const P2 c2 = {s_circ[jj * 4], s_circ[jj * 4 + 1]};
             if (circles_apart(c1, r1, c2, s_circ[jj * 4 + 2])) continue;
-            load_quad(w.q2, s_quad + jj * 8);
-            const float a2 = shoelace(w.q2, 4);
-            orient_ccw(w.q2);
+            const float a2 = load_oriented(w.q2, s_quad + jj * 8);
             const float inter = quad_intersection(w.q1, w.q2, w.p, w.q);
             const float iou = inter / (a1 + a2 - inter);
             if (iou > iou_thr) bits |= 1u << jj;

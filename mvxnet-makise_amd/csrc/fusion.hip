@@ -15,7 +15,7 @@
 // Compact mode: the padded rows of a frame are all identical (zeros), so only the real rows are
 // sampled; row_map sends a dense row to its compact row (or -1), and one shared zero row stands
 // for every padded row downstream.
-#include "common.h"
+#include "compact.h"
 #include "split_common.h"
 
 namespace {
@@ -35,29 +35,12 @@ struct FrameLevels {
 
 __device__ __forceinline__ bool row_is_zero(const float *v) { return v[0] == 0.f && v[1] == 0.f && v[2] == 0.f; }
 
-// ---- dense-row -> compact-row map (three phases: block counts, scan of counts, map) -----------
+// ---- dense-row -> compact-row map (compact.h: block counts, mvxi_scan_block_counts, map) ------
 __global__ __launch_bounds__(256) void map_count(const float *__restrict__ vox, int vc, long long R, int *__restrict__ bcount) {
     __shared__ int s[4];
     const long long r = blockIdx.x * 256ll + threadIdx.x;
-    const int flag = (r < R) && !row_is_zero(vox + r * vc);
-    const unsigned long long b = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) bcount[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
-}
-
-__global__ __launch_bounds__(1024) void map_scan(int *__restrict__ bcount, int nblocks, int *__restrict__ n_real) {
-    __shared__ int smem[17];
-    int base = 0;
-    for (int t0 = 0; t0 < nblocks; t0 += 1024) {
-        const int i = t0 + threadIdx.x;
-        const int v = i < nblocks ? bcount[i] : 0;
-        int tot;
-        const int ex = block_excl_scan_i32(v, smem, &tot);
-        if (i < nblocks) bcount[i] = base + ex;
-        base += tot;
-    }
-    if (threadIdx.x == 0) *n_real = base;
+    const int total = block_kept_count<4>((r < R) && !row_is_zero(vox + r * vc), s);
+    if (threadIdx.x == 0) bcount[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void map_write(float *__restrict__ vox, int vc, long long R,
@@ -65,14 +48,9 @@ __global__ __launch_bounds__(256) void map_write(float *__restrict__ vox, int vc
                                                  int *__restrict__ rows_sel, int zero_padding) {
     __shared__ int s[4];
     const long long r = blockIdx.x * 256ll + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int flag = (r < R) && !row_is_zero(vox + r * vc);
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) s[wv] = __popcll(b);
-    __syncthreads();
-    int off = boff[blockIdx.x];
-    for (int k = 0; k < wv; ++k) off += s[k];
-    off += __popcll(b & ((1ull << lane) - 1ull));
+    const bool flag = (r < R) && !row_is_zero(vox + r * vc);
+    int total;
+    const int off = boff[blockIdx.x] + block_kept_rank<4>(flag, s, total);
     if (r < R) {
         row_map[r] = flag ? off : -1;
         if (flag && rows_sel) rows_sel[off] = (int)r;
@@ -277,8 +255,8 @@ extern "C" int mvx_row_compact_map_frames(float *voxels, int32_t vox_channels, i
     int *bc = (int *)workspace;
     hipLaunchKernelGGL(map_count, dim3(nb), dim3(256), 0, st, voxels, vox_channels, (long long)rows, bc);
     MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(map_scan, dim3(1), dim3(1024), 0, st, bc, (int)nb, n_real);
-    MVX_LAUNCH_CHECK();
+    const int rc = mvxi_scan_block_counts(bc, (int)nb, 1, n_real, st);
+    if (rc != MVX_OK) return rc;
     hipLaunchKernelGGL(map_write, dim3(nb), dim3(256), 0, st, voxels, vox_channels, (long long)rows, (const int *)bc,
                        row_map, rows_sel, 1);
     MVX_LAUNCH_CHECK();

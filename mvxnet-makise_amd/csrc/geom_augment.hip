@@ -6,14 +6,16 @@
 //                   -- the moved quad of every trial against every other box (j < i in its moved pose, j > i in its original
 //                   one) by bev_iou.h's clipping, pairs whose bounding circles cannot touch counting as 0 -- the first trial
 //                   whose largest IoU does not exceed iou_thr is taken (LDS integer atomicMin), none: the box keeps its pose.
-//                   Then the global step on every box, the centre filter and the ordered compaction (one wave ballot).
-//   2. geom_count   (grid (block of 256 points, frame), one thread per point): membership in the ORIGINAL boxes (gtdb.hip's
-//                   test, lowest index wins), the per-object move, the global step, the range test; kept points per block.
+//                   Then the global step on every box, the centre filter and the ordered compaction (one wave).
+//   2. geom_count   (grid (block of 256 points, frame), one thread per point): membership in the ORIGINAL boxes (box3d.h,
+//                   lowest index wins), the per-object move, the global step, the range test; kept points per block.
 //   3. geom_write   (same grid): the same arithmetic again, the block's offset = the sum of the counts of the blocks before it,
-//                   a ballot scan inside the block, rows stored in order with 16-byte accesses where the 24-byte rows allow.
+//                   the rank inside the block (compact.h), rows stored in order with 16-byte accesses where the 24-byte rows allow.
 // Coordinates are computed in f64 from the f32 inputs and rounded to f32 once; every decision on a stored value (range test,
 // box filter) is taken on the rounded f32 value, so what is kept is inside the range as stored.
 #include "bev_iou.h"
+#include "box3d.h"
+#include "compact.h"
 
 namespace {
 
@@ -39,13 +41,6 @@ __device__ void quad_of(double x, double y, double l, double w, double r, float 
         q[2 * k] = (float)(qx + x);
         q[2 * k + 1] = (float)(qy + y);
     }
-}
-
-__device__ __forceinline__ void circle_of(const float *quad, float *circ) {
-    P2 c;
-    float r;
-    quad_circle((const P2 *)quad, c, r);
-    circ[0] = c.x; circ[1] = c.y; circ[2] = r;
 }
 
 struct Glob { double c, s, scale; bool flip; };
@@ -119,15 +114,7 @@ __global__ __launch_bounds__(PLACE_THREADS) void geom_place(PlaceArgs a) {
             const int t = p / n, j = p - t * n;
             float iou = 0.f;
             const P2 c1 = {c_circ[t][0], c_circ[t][1]}, c2 = {s_circ[j][0], s_circ[j][1]};
-            if (j != i && !circles_apart(c1, c_circ[t][2], c2, s_circ[j][2])) {
-                load_quad(w.q1, c_quad[t]);
-                load_quad(w.q2, s_quad[j]);
-                const float a1 = shoelace(w.q1, 4), a2 = shoelace(w.q2, 4);      // signed, before the re-orientation
-                orient_ccw(w.q1);
-                orient_ccw(w.q2);
-                const float inter = quad_intersection(w.q1, w.q2, w.p, w.q);
-                iou = inter / (a1 + a2 - inter);
-            }
+            if (j != i && !circles_apart(c1, c_circ[t][2], c2, s_circ[j][2])) iou = quad_iou(w, c_quad[t], s_quad[j]);
             s_iou[t][j] = iou;
         }
         __syncthreads();
@@ -170,9 +157,9 @@ __global__ __launch_bounds__(PLACE_THREADS) void geom_place(PlaceArgs a) {
             o[6] = (float)r;
             keep = (double)o[0] >= a.r.lo[0] && (double)o[0] < a.r.hi[0] && (double)o[1] >= a.r.lo[1] && (double)o[1] < a.r.hi[1];
         }
-        const unsigned long long bits = __ballot(keep);
+        int total;
+        const int at = block_kept_rank<1>(keep, nullptr, total);
         if (keep) {
-            const int at = __popcll(bits & ((1ull << tid) - 1ull));
             float *d3 = a.out_box3d + ((size_t)f * B + at) * 7, *dq = a.out_bev + ((size_t)f * B + at) * 8;
             float q[8];
             quad_of((double)o[0], (double)o[1], (double)o[3], (double)o[4], (double)o[6], q);
@@ -182,7 +169,6 @@ __global__ __launch_bounds__(PLACE_THREADS) void geom_place(PlaceArgs a) {
             for (int k = 0; k < 8; ++k) dq[k] = q[k];
             a.kept_idx[(size_t)f * B + at] = tid;
         }
-        const int total = __popcll(bits);
         if (tid >= total && tid < B) a.kept_idx[(size_t)f * B + tid] = -1;
         if (tid == 0) {
             a.n_kept[f] = total;
@@ -208,7 +194,6 @@ struct PointArgs {
     int *n_out;                  // [F]
 };
 
-struct Box { double x, y, z, hl, hw, h, c, s; };                 // gtdb.hip's box: half sizes, cos and sin of the yaw
 struct Move { double c, s, dx, dy, dz; int on; };
 
 struct Tables {
@@ -224,11 +209,7 @@ __device__ void load_tables(const PointArgs &a, int f, Tables &t) {
     if (n < 0 || n > a.B) n = 0;
     if (tid < n) {
         const float *b3 = a.box3d + ((size_t)f * a.B + tid) * 7, *m = a.move + ((size_t)f * a.B + tid) * 4;
-        Box b;
-        b.x = (double)b3[0]; b.y = (double)b3[1]; b.z = (double)b3[2];
-        b.hl = (double)b3[3] / 2.0; b.hw = (double)b3[4] / 2.0; b.h = (double)b3[5];
-        b.c = cos((double)b3[6]); b.s = sin((double)b3[6]);
-        t.box[tid] = b;
+        t.box[tid] = load_box(b3, cos((double)b3[6]), sin((double)b3[6]));
         Move v;
         v.on = a.trial[(size_t)f * a.B + tid] >= 0;
         v.dx = (double)m[0]; v.dy = (double)m[1]; v.dz = (double)m[2];
@@ -237,13 +218,6 @@ __device__ void load_tables(const PointArgs &a, int f, Tables &t) {
     }
     if (tid == PT_THREADS - 1) { t.g = load_glob(a.glob + (size_t)f * 4); t.n = n; }
     __syncthreads();
-}
-
-// gtdb.hip's test: (u, v) = the point in the box frame, |u| <= l/2, |v| <= w/2, 0 <= dz <= h
-__device__ __forceinline__ bool inside(const Box &b, double x, double y, double z) {
-    const double dx = x - b.x, dy = y - b.y, dz = z - b.z;
-    const double u = dx * b.c - dy * b.s, v = dx * b.s + dy * b.c;
-    return fabs(u) <= b.hl && fabs(v) <= b.hw && dz >= 0.0 && dz <= b.h;
 }
 
 // rows of 24 B: a row whose index in the whole (16-byte aligned) buffer is even starts on 16 bytes, an odd one ends on them
@@ -312,10 +286,7 @@ __global__ __launch_bounds__(PT_THREADS) void geom_count(PointArgs a) {
             Row r = load_row(a.in, (size_t)f * a.cap + p);
             keep = transform(t, a.r, r);
         }
-        const unsigned long long bits = __ballot(keep);
-        if ((tid & 63) == 0) s_cnt[tid >> 6] = __popcll(bits);
-        __syncthreads();
-        for (int k = 0; k < PT_THREADS / MVX_WAVE; ++k) total += s_cnt[k];
+        total = block_kept_count<PT_THREADS / MVX_WAVE>(keep, s_cnt);
     }
     if (tid == 0) a.block_cnt[(size_t)f * a.n_blocks + blk] = total;
 }
@@ -330,7 +301,7 @@ __global__ __launch_bounds__(PT_THREADS) void geom_write(PointArgs a) {
     const int upto = blk == 0 ? a.n_blocks : blk;
     int part = 0;
     for (int k = tid; k < upto; k += PT_THREADS) part += cnt[k];
-    for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
+    part = wave_sum_i32(part);
     if (lane == 0) s_part[wv] = part;
     __syncthreads();
     int before = 0;
@@ -348,11 +319,8 @@ __global__ __launch_bounds__(PT_THREADS) void geom_write(PointArgs a) {
         r = load_row(a.in, (size_t)f * a.cap + p);
         keep = transform(t, a.r, r);
     }
-    const unsigned long long bits = __ballot(keep);
-    if (lane == 0) s_cnt[wv] = __popcll(bits);
-    __syncthreads();
-    for (int k = 0; k < wv; ++k) before += s_cnt[k];
-    const int dst = before + __popcll(bits & ((1ull << lane) - 1ull));
+    int kept;
+    const int dst = before + block_kept_rank<PT_THREADS / MVX_WAVE>(keep, s_cnt, kept);
     if (keep && dst < a.cap) store_row(a.out, (size_t)f * a.cap + dst, r);
 }
 

@@ -2,13 +2,14 @@
 //
 // Replaces modules/data/Preprocessing.py:12-55 (`crop`, `cropTensor`, `cropToSight`) and
 // modules/utils/Calib.py:47-69 (`lidar2Img`).  The crops are order-preserving stream compactions
-// (count / scan / write, one pass over the raw cloud each); both filters can run fused in one call
-// because `cropToSight(crop(x))` keeps exactly the points that pass both masks, in order.
+// (compact.h: count / scan / write); both filters can run fused in one call because
+// `cropToSight(crop(x))` keeps exactly the points that pass both masks, in order.  The scan kernel
+// of the block counts is the library's one (mvxi_scan_block_counts, defined here).
 //
 // Arithmetic follows the path being replaced: the numpy path compares f32 coordinates promoted to
 // f64 against f64 bounds and projects in f64 (calib is f64 there, cropdata.py:46-56); the torch
 // path rounds the bounds to f32 and projects in f32 (`math_f32`).
-#include "common.h"
+#include "compact.h"
 
 namespace {
 
@@ -64,14 +65,13 @@ __global__ __launch_bounds__(256) void crop_count(const float *__restrict__ pcd,
     const int f = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int n = min(n_in ? n_in[f] : cap, cap);
-    const int flag = i < n && keep_point(c, pcd + ((size_t)f * cap + i) * ncol);
-    const unsigned long long b = __ballot(flag);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) bcount[(size_t)f * nblocks + blockIdx.x] = s[0] + s[1] + s[2] + s[3];
+    const int total = block_kept_count<4>(i < n && keep_point(c, pcd + ((size_t)f * cap + i) * ncol), s);
+    if (threadIdx.x == 0) bcount[(size_t)f * nblocks + blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(1024) void crop_scan(int *__restrict__ bcount, int nblocks, int *__restrict__ n_out) {
+// The scan of every ordered compaction whose blocks count first: the workgroup of frame blockIdx.x turns that frame's block
+// counts into their exclusive scan in place, 1024 at a time with a carry, and stores the frame's sum.
+__global__ __launch_bounds__(1024) void scan_block_counts(int *__restrict__ bcount, int nblocks, int *__restrict__ totals) {
     __shared__ int smem[17];
     const int f = blockIdx.x;
     int *bc = bcount + (size_t)f * nblocks;
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(1024) void crop_scan(int *__restrict__ bcount, int 
         if (i < nblocks) bc[i] = base + ex;
         base += tot;
     }
-    if (threadIdx.x == 0) n_out[f] = base;
+    if (threadIdx.x == 0) totals[f] = base;
 }
 
 // has_proj: the kept row is written as [its ncol columns, row, col] with the f32 projection of train.py:31-34
@@ -96,16 +96,11 @@ __global__ __launch_bounds__(256) void crop_write(const float *__restrict__ pcd,
     __shared__ int s[4];
     const int f = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int n = min(n_in ? n_in[f] : cap, cap);
     const float *p = pcd + ((size_t)f * cap + i) * ncol;
-    const int flag = i < n && keep_point(c, p);
-    const unsigned long long b = __ballot(flag);
-    if (lane == 0) s[wv] = __popcll(b);
-    __syncthreads();
-    int off = boff[(size_t)f * nblocks + blockIdx.x];
-    for (int k = 0; k < wv; ++k) off += s[k];
-    off += __popcll(b & ((1ull << lane) - 1ull));
+    const bool flag = i < n && keep_point(c, p);
+    int total;
+    const int off = boff[(size_t)f * nblocks + blockIdx.x] + block_kept_rank<4>(flag, s, total);
     if (flag && off < cap_out) {
         float *o = out + ((size_t)f * cap_out + off) * ncol_out;
         for (int a = 0; a < ncol; ++a) o[a] = p[a];
@@ -156,7 +151,28 @@ inline void fill_params(CropParams &c, const double *range6, int bounds_f32, con
     c.lim_h = math_f32 ? (double)((float)h - 1e-3f) : h - 1e-3;
 }
 
+// count, scan, write: out rows [ncol_out], frame stride cap_out; bc = the workspace, one int per block of 256 points
+int launch_crop(const float *pcd, const int *n_in, int n_frames, int cap_points, int ncol, const CropParams &c, float *out,
+                int *n_out, int *src_index, int ncol_out, int cap_out, int has_proj, const CropParams &proj, int *bc,
+                hipStream_t st) {
+    const int nb = (int)mvx_cdiv(cap_points, 256);
+    hipLaunchKernelGGL(crop_count, dim3(nb, n_frames), dim3(256), 0, st, pcd, n_in, cap_points, ncol, c, bc, nb);
+    MVX_LAUNCH_CHECK();
+    const int rc = mvxi_scan_block_counts(bc, nb, n_frames, n_out, st);
+    if (rc != MVX_OK) return rc;
+    hipLaunchKernelGGL(crop_write, dim3(nb, n_frames), dim3(256), 0, st, pcd, n_in, cap_points, ncol, c, (const int *)bc,
+                       nb, out, src_index, ncol_out, cap_out, has_proj, proj);
+    MVX_LAUNCH_CHECK();
+    return MVX_OK;
+}
+
 }  // namespace
+
+int mvxi_scan_block_counts(int *bcount, int nblocks, int n_frames, int *totals, hipStream_t st) {
+    hipLaunchKernelGGL(scan_block_counts, dim3(n_frames), dim3(1024), 0, st, bcount, nblocks, totals);
+    MVX_LAUNCH_CHECK();
+    return MVX_OK;
+}
 
 extern "C" size_t mvx_crop_workspace_bytes(int32_t n_frames, int32_t cap_points) {
     if (n_frames <= 0 || cap_points <= 0) return 0;
@@ -174,17 +190,8 @@ extern "C" int mvx_crop_points(const float *pcd, const int32_t *n_in, int32_t n_
     MVX_CHECK_ARG(workspace_bytes >= mvx_crop_workspace_bytes(n_frames, cap_points));
     CropParams c;
     fill_params(c, range6_host, bounds_f32, cam_from_velo_host, p2_host, imsize_w, imsize_h, math_f32);
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = (int)mvx_cdiv(cap_points, 256);
-    int *bc = (int *)workspace;
-    hipLaunchKernelGGL(crop_count, dim3(nb, n_frames), dim3(256), 0, st, pcd, n_in, cap_points, ncol, c, bc, nb);
-    MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_scan, dim3(n_frames), dim3(1024), 0, st, bc, nb, n_out);
-    MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_write, dim3(nb, n_frames), dim3(256), 0, st, pcd, n_in, cap_points, ncol, c, (const int *)bc,
-                       nb, out, src_index, ncol, cap_points, 0, c);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
+    return launch_crop(pcd, n_in, n_frames, cap_points, ncol, c, out, n_out, src_index, ncol, cap_points, 0, c, (int *)workspace,
+                       (hipStream_t)stream);
 }
 
 extern "C" size_t mvx_crop_project_workspace_bytes(int32_t n_frames, int32_t cap_points) {
@@ -203,17 +210,8 @@ extern "C" int mvx_crop_project_points(const float *pcd, const int32_t *n_in, in
     CropParams c, pj;
     fill_params(c, range6_host, 0, cam_from_velo_host, p2_host, imsize_w, imsize_h, 0);        // numpy-path masks (f64)
     fill_params(pj, nullptr, 0, proj_cam_from_velo_host, proj_p2_host, 0.0, 0.0, 1);            // torch-path projection (f32)
-    hipStream_t st = (hipStream_t)stream;
-    const int nb = (int)mvx_cdiv(cap_points, 256);
-    int *bc = (int *)workspace;
-    hipLaunchKernelGGL(crop_count, dim3(nb, n_frames), dim3(256), 0, st, pcd, n_in, cap_points, ncol, c, bc, nb);
-    MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_scan, dim3(n_frames), dim3(1024), 0, st, bc, nb, n_out);
-    MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(crop_write, dim3(nb, n_frames), dim3(256), 0, st, pcd, n_in, cap_points, ncol, c, (const int *)bc,
-                       nb, out, (int *)nullptr, ncol + 2, cap_out, 1, pj);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
+    return launch_crop(pcd, n_in, n_frames, cap_points, ncol, c, out, n_out, nullptr, ncol + 2, cap_out, 1, pj, (int *)workspace,
+                       (hipStream_t)stream);
 }
 
 extern "C" int mvx_lidar2img(const float *pcd, int32_t ncol, int64_t n_points, const double *cam_from_velo_host,

@@ -12,11 +12,12 @@
 //   3. gtdb_raster (grid (band of 8 ROI rows, label)): the instance's polygon edges staged in LDS, a pixel is set when its
 //                  centre is inside any polygon by the even-odd rule; mask byte and patch = mask ? bgr : 0.  One thread owns
 //                  a pixel: its mask byte and its three patch bytes have no other writer.
-//   4. gtdb_write  (same grid as 2): the inside test again, a ballot scan inside the chunk, rows [x y z r] stored in file
-//                  order with 16-byte loads and stores.
+//   4. gtdb_write  (same grid as 2): the inside test again, the rank inside the chunk (compact.h), rows [x y z r] stored in
+//                  file order with 16-byte loads and stores.
 // The f64 decisions (crossing test, box faces) use a fixed operand order and the file is built with -ffp-contract=off, so a
 // host restatement in the same order gives the same bits.
-#include "common.h"
+#include "box3d.h"
+#include "compact.h"
 
 namespace {
 
@@ -25,23 +26,16 @@ constexpr int CHUNK = MVX_GTDB_CHUNK;       // points per workgroup of stages 2 
 constexpr int BAND = 8;                     // ROI rows per workgroup of stage 3
 constexpr int EDGES = 512;                  // polygon edges per LDS stage: 16 KB of f64 + 2 KB of polygon ids
 
-// inclusive scan of a[0..n) in place by ONE workgroup of THREADS threads
+// inclusive scan of a[0..n) in place by ONE workgroup of THREADS threads: trips of THREADS with a carry; s: 17 words
 __device__ void scan_inplace(long long *a, int n, long long *s) {
-    const int tid = threadIdx.x;
     long long carry = 0;
     for (int base = 0; base < n; base += THREADS) {
-        const int i = base + tid;
-        s[tid] = i < n ? a[i] : 0;
-        __syncthreads();
-        for (int d = 1; d < THREADS; d <<= 1) {
-            const long long v = tid >= d ? s[tid - d] : 0;
-            __syncthreads();
-            s[tid] += v;
-            __syncthreads();
-        }
-        if (i < n) a[i] = s[tid] + carry;
-        carry += s[THREADS - 1];
-        __syncthreads();
+        const int i = base + threadIdx.x;
+        const long long v = i < n ? a[i] : 0;
+        long long tot;
+        const long long ex = block_excl_scan<long long>(v, s, &tot);
+        if (i < n) a[i] = carry + ex + v;
+        carry += tot;
     }
 }
 
@@ -89,27 +83,15 @@ __global__ __launch_bounds__(THREADS) void gtdb_match(const float4 *__restrict__
 }
 
 __global__ __launch_bounds__(THREADS) void gtdb_scan(long long *off, int n) {
-    __shared__ long long s[THREADS];
+    __shared__ long long s[17];
     scan_inplace(off + 1, n, s);
 }
 
 // 2 / 4. ---------------------------------------------------------------------------------------------------------------
-struct Box { double x, y, z, hl, hw, h, c, s; };
-
-__device__ inline Box load_box(const float *__restrict__ b3, const float *__restrict__ cs) {
-    Box b;
-    b.x = (double)b3[0]; b.y = (double)b3[1]; b.z = (double)b3[2];
-    b.hl = (double)b3[3] / 2.0; b.hw = (double)b3[4] / 2.0; b.h = (double)b3[5];
-    b.c = (double)cs[0]; b.s = (double)cs[1];
-    return b;
+__device__ __forceinline__ Box label_box(const float *__restrict__ lab_box3d, const float *__restrict__ lab_cs, int i) {
+    return load_box(lab_box3d + (size_t)i * 7, (double)lab_cs[(size_t)i * 2], (double)lab_cs[(size_t)i * 2 + 1]);      // the host's cos / sin
 }
-
-// (u, v): the point in the box frame, the inverse of Calc.bbox3d2bev's corner @ [[c, -s], [s, c]] + (x, y)
-__device__ inline bool inside(const Box &b, const float4 &p) {
-    const double dx = (double)p.x - b.x, dy = (double)p.y - b.y, dz = (double)p.z - b.z;
-    const double u = dx * b.c - dy * b.s, v = dx * b.s + dy * b.c;
-    return fabs(u) <= b.hl && fabs(v) <= b.hw && dz >= 0.0 && dz <= b.h;
-}
+__device__ __forceinline__ bool inside(const Box &b, const float4 &p) { return inside(b, (double)p.x, (double)p.y, (double)p.z); }
 
 __global__ __launch_bounds__(THREADS) void gtdb_count(const float4 *__restrict__ points, const long long *__restrict__ pts_off,
                                                       int n_frames, const float *__restrict__ lab_box3d,
@@ -122,13 +104,13 @@ __global__ __launch_bounds__(THREADS) void gtdb_count(const float4 *__restrict__
     if (flag[i] == 3 && f >= 0 && f < n_frames) {                 // block-uniform
         const long long lo = pts_off[f], n = pts_off[f + 1] - lo;
         if ((long long)chunk * CHUNK < n) {
-            const Box b = load_box(lab_box3d + (size_t)i * 7, lab_cs + (size_t)i * 2);
+            const Box b = label_box(lab_box3d, lab_cs, i);
             int mine = 0;
             for (int k = 0; k < CHUNK / THREADS; ++k) {
                 const long long p = (long long)chunk * CHUNK + k * THREADS + tid;
                 if (p < n) mine += inside(b, points[lo + p]);
             }
-            for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d, 64);
+            mine = wave_sum_i32(mine);
             if ((tid & 63) == 0) s_cnt[tid >> 6] = mine;
             __syncthreads();
             for (int k = 0; k < THREADS / MVX_WAVE; ++k) total += s_cnt[k];
@@ -139,7 +121,7 @@ __global__ __launch_bounds__(THREADS) void gtdb_count(const float4 *__restrict__
 
 __global__ __launch_bounds__(THREADS) void gtdb_offsets(int *__restrict__ chunk_cnt, int n_chunks, long long *__restrict__ pt_off,
                                                         int n_labels) {
-    __shared__ long long s[THREADS];
+    __shared__ long long s[17];
     for (int i = threadIdx.x; i < n_labels; i += THREADS) {
         int *row = chunk_cnt + (size_t)i * n_chunks;
         int run = 0;
@@ -158,12 +140,12 @@ __global__ __launch_bounds__(THREADS) void gtdb_write(const float4 *__restrict__
                                                       const long long *__restrict__ pt_off, float4 *__restrict__ out,
                                                       long long out_rows) {
     __shared__ int s_cnt[2][THREADS / MVX_WAVE];
-    const int chunk = blockIdx.x, i = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int chunk = blockIdx.x, i = blockIdx.y, tid = threadIdx.x;
     const int f = lab_frame[i];
     if (flag[i] != 3 || f < 0 || f >= n_frames) return;            // block-uniform
     const long long lo = pts_off[f], n = pts_off[f + 1] - lo;
     if ((long long)chunk * CHUNK >= n) return;
-    const Box b = load_box(lab_box3d + (size_t)i * 7, lab_cs + (size_t)i * 2);
+    const Box b = label_box(lab_box3d, lab_cs, i);
     const long long end = pt_off[i + 1];
     long long at = pt_off[i] + chunk_off[(size_t)i * n_chunks + chunk];
     for (int k = 0; k < CHUNK / THREADS; ++k) {                    // file order: sub-chunk, then thread
@@ -171,12 +153,8 @@ __global__ __launch_bounds__(THREADS) void gtdb_write(const float4 *__restrict__
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         bool in = false;
         if (p < n) { v = points[lo + p]; in = inside(b, v); }
-        const unsigned long long bits = __ballot(in);
-        if (lane == 0) s_cnt[k & 1][wv] = __popcll(bits);
-        __syncthreads();                                           // s_cnt alternates, so one barrier per sub-chunk is enough
-        int before = 0, all = 0;
-        for (int w = 0; w < THREADS / MVX_WAVE; ++w) { const int c = s_cnt[k & 1][w]; before += w < wv ? c : 0; all += c; }
-        const long long dst = at + before + __popcll(bits & ((1ull << lane) - 1ull));
+        int all;
+        const long long dst = at + block_kept_rank<THREADS / MVX_WAVE>(in, s_cnt[k & 1], all);      // the rows alternate: one barrier per sub-chunk
         if (in && dst < end && dst < out_rows) out[dst] = v;
         at += all;
     }

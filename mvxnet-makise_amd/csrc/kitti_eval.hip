@@ -90,23 +90,15 @@ __global__ __launch_bounds__(OV_THREADS) void eval_overlaps(int F, const int *__
     overlaps[p] = image_overlap(a, b, false);
 
     // BEV intersection: f32 with bboxIntersection's arithmetic, 0 where the bounding circles cannot touch
-    P2 ca[4], cb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        ca[k].x = qa[2 * k]; ca[k].y = qa[2 * k + 1];
-        cb[k].x = qb[2 * k]; cb[k].y = qb[2 * k + 1];
-    }
     P2 c1, c2;
     float r1, r2;
-    quad_circle(ca, c1, r1);
-    quad_circle(cb, c2, r2);
+    quad_circle((const P2 *)qa, c1, r1);
+    quad_circle((const P2 *)qb, c2, r2);
     float inter = 0.f;
     if (!circles_apart(c1, r1, c2, r2)) {
         const Polys w = polys_of(s_poly, OV_THREADS, threadIdx.x);
-        load_quad(w.q1, qa);
-        orient_ccw(w.q1);
-        load_quad(w.q2, qb);
-        orient_ccw(w.q2);
+        load_oriented(w.q1, qa);                // the areas are not used: the denominators below are the f64 l * w
+        load_oriented(w.q2, qb);
         inter = quad_intersection(w.q1, w.q2, w.p, w.q);
     }
     const double I = (double)inter;
@@ -119,12 +111,6 @@ __global__ __launch_bounds__(OV_THREADS) void eval_overlaps(int F, const int *__
         iou3 = inc / (la * ha * wa + lb * hb * wb - inc);
     }
     overlaps[2 * sz.n_pairs + p] = iou3;
-}
-
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // (key desc, index asc) arg-best over the wave; index < 0 = no candidate.  Every lane returns the same pair.
@@ -342,8 +328,7 @@ __global__ __launch_bounds__(64) void eval_reduce(int F, StatLayout lay, const u
         fn += s_fn[o];
         sim += s_sim[o];
     }
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) sim += __shfl_xor(sim, m, 64);
+    sim = wave_sum_f64(sim);
     tp = wave_sum_i32(tp);
     fp = wave_sum_i32(fp);
     fn = wave_sum_i32(fn);

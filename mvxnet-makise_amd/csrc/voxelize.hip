@@ -182,9 +182,7 @@ __global__ __launch_bounds__(256) void vox_scan(const int *__restrict__ n_points
             const int val = (int)(unsigned)(word & 0xffffffffull);
             int part = ((int)threadIdx.x <= stop || stop < 0) ? val : 0;
             if (idx < 0) part = 0;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d, 64);
-            prefix += part;
+            prefix += wave_sum_i32(part);
             if (stop >= 0) break;
             k -= 64;
         }

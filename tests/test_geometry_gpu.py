@@ -45,3 +45,35 @@ def test_lidar2img_matches_reference(golden):
     p64 = lidar2Img(g['pcd'].copy(), O.KITTI_CALIB, True)
     np.testing.assert_allclose(p64, g['proj_f64'], rtol=1e-6, atol=1e-4)   # returned through f32
     assert lidar2Img(g['pcd'].copy(), O.KITTI_CALIB, False).shape[0] <= g['pcd'].shape[0]
+
+
+def test_crop_scan_carry_two_frames():
+    """The shared scan of the block counts beyond its first trip of 1024 blocks, with per-frame indexing: two frames of 1026
+    blocks each.  Frame 0 keeps rows in blocks 1024 and 1025, whose positions need the carry of the first trip, behind a block
+    with nothing kept that ends the first trip; frame 1 ends inside block 1023, so its second trip holds only zeros and its
+    count and offsets must not be touched by frame 0's."""
+    from modules import _hip
+    F, cap, ncol = 2, 1024 * 256 + 300, 4
+    n_in = [cap, 1024 * 256 - 77]
+    lo, hi = np.array(O.VELORANGE[:3]), np.array(O.VELORANGE[3:])
+    g = np.random.default_rng(20)
+    u = g.random((F, cap, ncol))
+    u[..., 0] *= 2.0                                            # x beyond the range for about half of the points
+    pcd = u.astype(np.float32)
+    pcd[..., :3] = (lo + (hi - lo) * u[..., :3]).astype(np.float32)
+    pcd[0, 1024 * 256 - 300:1024 * 256 + 100, 0] = np.float32(hi[0] + 1.0)      # 400 rejected rows across row 262,144
+    out, n_out, src = _hip.crop_points(torch.from_numpy(pcd).cuda(), torch.tensor(n_in, dtype=torch.int32).cuda(),
+                                       list(O.VELORANGE), want_index=True)
+    out, n_out, src = out.cpu().numpy(), n_out.cpu().numpy(), src.cpu().numpy()
+    for f in range(F):
+        p = pcd[f, :n_in[f]]
+        xyz = p[:, :3].astype(np.float64)                       # f32 values compared in f64, as Preprocessing.crop
+        mask = np.all((lo <= xyz) & (xyz < hi), axis=1)
+        n = int(mask.sum())
+        assert 0.4 * n_in[f] < n < 0.6 * n_in[f]
+        assert n_out[f] == n
+        assert np.array_equal(out[f, :n], p[mask])
+        assert np.array_equal(src[f, :n], np.flatnonzero(mask))
+    assert not np.any(np.all((lo <= pcd[0, 1023 * 256:1024 * 256, :3]) & (pcd[0, 1023 * 256:1024 * 256, :3] < hi), axis=1))
+    kept0 = src[0, :n_out[0]]
+    assert np.any((kept0 >= 1024 * 256) & (kept0 < 1025 * 256)) and np.any(kept0 >= 1025 * 256)      # both blocks of the second trip
