@@ -44,16 +44,16 @@ extern "C" {
                                   [planes][3][cout] per-depth-tap constants | [planes][9][cout] image-border position classes): in interior
                                   tiles a depth tap whose source halo holds no active site is not executed (its constant is added in the
                                   epilogue), and a border tile without any active source is filled from the class constants (exact rewrites) */
-#define MVX_FLAG_SPLIT 64      /* mvx_linear_forward*, mvx_linear_wgrad, mvx_conv3d_wgrad, mvx_conv3d_wgrad_bg*, mvx_conv2d_wgrad_frames (conv3d_wgrad4s: cin a
-                                  multiple of 64): bf16x3 split arithmetic (three bf16 MFMAs per product, f32 accumulate, ~2e-5 per
+#define MVX_FLAG_SPLIT 64      /* mvx_linear_forward*, mvx_linear_wgrad, mvx_conv3d_wgrad, mvx_conv3d_wgrad_bg*, mvx_conv2d_wgrad_frames (conv3d_wgrad4s, the
+                                  convolutions' only split-arithmetic weight gradient: cin a multiple of 64): bf16x3 split arithmetic (three bf16 MFMAs per product, f32 accumulate, ~2e-5 per
                                   product: the row-GEMM side of `convmath: bf16x3`) for layers with n > 64, k % 4 == 0, 16-byte aligned
                                   operands and a row-major weight (w_transposed = 0); other calls run the exact-f32 kernel */
 
-#define MVX_FLAG_SPLIT3 128    /* with MVX_FLAG_SPLIT, and on the *_split entry points: THREE bf16 pieces per f32 operand and six bf16 MFMAs per product
+#define MVX_FLAG_SPLIT3 128    /* with MVX_FLAG_SPLIT, and on the *_split convolution entry points (forward, input gradient, weight packing): THREE bf16 pieces per f32 operand and six bf16 MFMAs per product
                                   ("bf16x6": hi + mid + lo is the operand exactly, dropped cross terms < 2^-25: fp32-grade accuracy) instead of two / three */
 
 #define MVX_FLAG_PRE_XCD_STRIPS 4096  /* mvx_linear_wgrad_pre: every block of a row strip on the same XCD (shared L2) instead of consecutive block ids */
-#define MVX_FLAG_SPLIT_F16 512  /* with MVX_FLAG_SPLIT, and on the *_split entry points: TWO fp16 pieces per f32 operand (22 mantissa bits) and three
+#define MVX_FLAG_SPLIT_F16 512  /* with MVX_FLAG_SPLIT, and on the *_split convolution entry points: TWO fp16 pieces per f32 operand (22 mantissa bits) and three
                                   fp16 MFMAs per product ("fp16x3": fp32-grade accuracy at the matrix work of bf16x3) -- for operands inside fp16's
                                   range: values above 65,504 overflow and below ~1e-4 lose relative precision, so callers scale by powers of two */
 
@@ -371,7 +371,8 @@ int mvx_conv3d_input_grad_sums(const float *w, const float *tap_sums, int32_t di
 int mvx_conv3d_dgrad_tiles(const float *dz, const float *wpk_dgrad, float *dx, int32_t din, int32_t dout, int32_t h,
                            int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
                            const int32_t *dx_tile_flags, uint64_t *exec_stages, uint32_t *work_counter, void *stream);
-/* bf16x3 forms of the background-aware entry points (csrc/conv3d_split.hip; weights from mvx_conv3d_pack_weights_split) */
+/* bf16x3 forms of the background-aware forward and input gradient (csrc/conv3d_split.hip; weights from
+ * mvx_conv3d_pack_weights_split).  The weight gradient in these arithmetics is mvx_conv3d_wgrad_bg* with MVX_FLAG_SPLIT. */
 int mvx_conv3d_forward_bg_split(const float *in, const void *wsplit, const float *bias, float *out, double *stats,
                                 int32_t din, int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout,
                                 int32_t stride_d, int32_t pad_d, int32_t flags, const int32_t *in_halo_flags,
@@ -379,11 +380,6 @@ int mvx_conv3d_forward_bg_split(const float *in, const void *wsplit, const float
 int mvx_conv3d_dgrad_tiles_split(const float *dz, const void *wsplit_dgrad, float *dx, int32_t din, int32_t dout,
                                  int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
                                  int32_t flags, const int32_t *dx_tile_flags, void *stream);
-size_t mvx_conv3d_wgrad_bg_split_workspace_bytes(int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout);
-int mvx_conv3d_wgrad_bg_split(const float *in, const float *dz, float *dw, int32_t din, int32_t dout, int32_t h,
-                              int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d, int32_t flags,
-                              const int32_t *in_halo_flags, const float *c_in, const float *tap_sums, void *workspace,
-                              size_t workspace_bytes, void *stream);
 /* ... and their frame-set forms (planes of n_frames frames stacked along depth, per-frame statistics [F][R][2][cout];
  * exec_stages (optional) u64 [1] += executed (depth tap, 32-channel chunk) stages, as in the f32 kernels) */
 int mvx_conv3d_forward_bg_split_frames(const float *in, const void *wsplit, const float *bias, float *out, double *stats,
@@ -395,24 +391,14 @@ int mvx_conv3d_dgrad_tiles_split_frames(const float *dz, const void *wsplit_dgra
                                         int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
                                         int32_t flags, const int32_t *dx_tile_flags, uint64_t *exec_stages, int32_t n_frames,
                                         void *stream);
-size_t mvx_conv3d_wgrad_bg_split_workspace_bytes_frames(int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout,
-                                                        int32_t n_frames);
-int mvx_conv3d_wgrad_bg_split_frames(const float *in, const float *dz, float *dw, int32_t din, int32_t dout, int32_t h,
-                                     int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d, int32_t flags,
-                                     const int32_t *in_halo_flags, const float *c_in, const float *tap_sums,
-                                     void *workspace, size_t workspace_bytes, int32_t n_frames, void *stream);
-/* bf16x3 forms of the RPN's 2-D convolutions on frame sets (modules/voxelnet/Pipe.py:45-75; one plane per frame).  wsplit:
- * the 2-D kernel placed in the middle depth slice of a [cout][cin][3][3][3] tensor, packed by
- * mvx_conv3d_pack_weights_split; dw3 f32 [cout][cin][3][3][3] (overwritten): the 2-D gradient is its middle depth slice. */
+/* bf16x3 forms of the RPN's 2-D forward and input gradient on frame sets (modules/voxelnet/Pipe.py:45-75; one plane per
+ * frame).  wsplit: the 2-D kernel placed in the middle depth slice of a [cout][cin][3][3][3] tensor, packed by
+ * mvx_conv3d_pack_weights_split.  The weight gradient is mvx_conv2d_wgrad_frames with MVX_FLAG_SPLIT. */
 int mvx_conv2d_forward_split_frames(const float *in, const void *wsplit, const float *bias, float *out, double *stats,
                                     int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t flags, int32_t n_frames,
                                     void *stream);
 int mvx_conv2d_dgrad_split_frames(const float *dz, const void *wsplit_dgrad, float *dx, int32_t h, int32_t w, int32_t cin,
                                   int32_t cout, int32_t flags, int32_t n_frames, void *stream);
-size_t mvx_conv2d_wgrad_split_workspace_bytes_frames(int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t n_frames);
-int mvx_conv2d_wgrad_split_frames(const float *in, const float *dz, float *dw3, int32_t h, int32_t w, int32_t cin,
-                                  int32_t cout, int32_t flags, void *workspace, size_t workspace_bytes, int32_t n_frames,
-                                  void *stream);
 size_t mvx_bn_relu_backward_tiles_workspace_bytes(int32_t planes, int32_t h, int32_t w, int32_t channels);
 int mvx_bn_relu_backward_tiles(const float *dyhat, const float *y, const float *mean_inv, const float *c_bg,
                                const float *y_bg, const float *plane_grad_sums, const int32_t *tile_flags,
@@ -620,7 +606,7 @@ int mvx_sparse_conv_gather_dz(const float *dz, const int64_t *coords, int32_t n_
                               int32_t stride_d, int32_t pad_d, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * "bf16x3" variants of the dense convolution: every f32 operand is split into hi + lo bf16 and a
+ * "bf16x3" variants of the dense convolution's forward and input gradient: every f32 operand is split into hi + lo bf16 and a
  * product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with f32 accumulation (per-product
  * relative error ~2e-5, i.e. fp32-grade for the 1e-4 feature bar; ~5x the rate of the exact-f32
  * MFMA).  Same arguments and layouts as the f32 entry points; weights are packed (and pre-split) by
@@ -630,6 +616,9 @@ int mvx_sparse_conv_gather_dz(const float *dz, const int64_t *coords, int32_t n_
  * (hi + mid + lo = the f32 value exactly) and the six products hh + hm + mh + hl + lh + mm; the dropped cross terms are
  * below 2^-25 of a product, i.e. under its f32 rounding: fp32-GRADE accuracy (tests hold it to the bounds of the
  * exact-f32 kernels) at 6/16 of the exact-f32 MFMA's matrix cycles.  Every `flags` below takes MVX_FLAG_SPLIT3.
+ *
+ * The weight gradient in these arithmetics has no entry point of its own: mvx_conv3d_wgrad with MVX_FLAG_SPLIT (cin a
+ * multiple of 64).
  */
 size_t mvx_conv3d_packed_weight_bytes_split(int32_t cout, int32_t cin, int32_t flags);
 int mvx_conv3d_pack_weights_split(const float *w, void *wsplit, int32_t cout, int32_t cin, int32_t for_dgrad,
@@ -640,9 +629,6 @@ int mvx_conv3d_forward_split(const float *in, const void *wsplit, const float *b
 int mvx_conv3d_dgrad_split(const float *dz, const void *wsplit_dgrad, float *dx, int32_t din, int32_t dout,
                            int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
                            int32_t flags, void *stream);
-int mvx_conv3d_wgrad_split(const float *in, const float *dz, float *dw, int32_t din, int32_t dout, int32_t h,
-                           int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d, int32_t flags,
-                           void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Frame-set forms (see mvx_frames_t above): the same operations as the entry points of the same name without `_frames`,

@@ -31,7 +31,6 @@ void mvxi_count_launch();       // diagnostics only: kernel launches issued by t
 static inline unsigned mvx_cdiv(long long a, long long b) { return (unsigned)((a + b - 1) / b); }
 
 // ---- internal helpers shared between translation units (NOT part of the C ABI) -----------------------
-// conv3d.hip: compacted (plane, tile) step lists of the background-aware weight gradient and its closed-form term
 struct FrameMap;
 // fp16-piece operand scaling (split_common.h): the addresses bound by mvx_split_operand_amax for the calling thread's next split
 // launch; taking them clears the binding (defined in voxelize.hip)
@@ -57,12 +56,8 @@ int mvxi_linear_forward_k128(const float *x, int ldx, const float *w, int ldw, c
 int mvxi_linear_wgrad_split(const float *x, int ldx, const float *dz, int lddz, float *slabs, long long rows, int k, int n,
                             long long rows_per_strip, long long strips, int pieces, hipStream_t st,
                             const SplitAmax &am = SplitAmax{nullptr, nullptr, 0});
-int mvxi_wgrad_step_list(const int32_t *in_halo_flags, int din, int dout, int ntiles, int stride_d, int pad_d, int *list,
-                         int *count, hipStream_t st, int n_frames = 1);
 // geometry.hip: bcount[f][0..nblocks) -> its exclusive scan in place, totals[f] = the frame's sum; one workgroup per frame
 int mvxi_scan_block_counts(int *bcount, int nblocks, int n_frames, int *totals, hipStream_t st);
-int mvxi_wgrad_rank1(const float *tap_sums, const float *c_in, float *dw, int din, int dout, int cin, int cout, int stride_d,
-                     int pad_d, hipStream_t st, int n_frames = 1);
 
 // ---- frame sets: the frames of a step processed by ONE launch -----------------------------------------
 // The reference is strictly batch-1 (config.yml:18, VoxelNet.py:19): a batch is B independent forwards with per-frame

@@ -24,6 +24,7 @@
 //     and a 32(c) x 64(n) accumulator; the reduction runs over sites; per-strip partial slabs
 //     are summed by a second, deterministic kernel (no float atomics).
 #include "common.h"
+#include "conv_geom.h"
 #include "split_common.h"
 
 namespace {
@@ -46,42 +47,7 @@ __device__ volatile int g_stamp_wg = -1;               // workgroup that ran the
 #define MVX_STAMP(k) do { } while (0)
 #endif
 
-constexpr int TH = 8, TW = 16;          // output patch of a workgroup
-constexpr int HH = TH + 2, HW = TW + 2; // halo
-constexpr int BK = 32;                  // channels per K chunk
 constexpr int PITCH = BK + 4;           // LDS row pitch in floats (bank-conflict padding)
-constexpr int BN = 64;                  // output channels per workgroup
-
-struct Geom {
-    int Din, Dout, H, W, Cin, Cout;     // gather view: in has Cin channels, out has Cout; Din / Dout = planes PER FRAME
-    int sd, pd;                         // depth stride / padding of the FORWARD conv
-    int mode;                           // 0 forward gather, 1 dgrad gather
-    int F = 1;                          // frames stacked along the depth axis: global plane = frame * planes + local plane
-    int tap_lo = 0, tap_hi = 3;         // in-plane taps (rows AND columns) [tap_lo, tap_hi) carry weight; the others are skipped
-                                        // (stride-2 convolutions evaluated on the space-to-depth image use a 2x2 window)
-    int s2d = 0;                        // > 0: the 2x2 window stands for a stride-2 3x3 kernel on the space-to-depth image whose
-                                        // channels are four parity blocks [pr][pc] of s2d channels each: window tap (ta, tb)
-                                        // carries weight for parity (pr, pc) only if (ta == 1 || pr == 1) && (tb == 1 || pc == 1)
-                                        // (include/mvx_hip.h, MVX_FLAG_TAPS2) -- 9 of the 16 (tap, parity) blocks; the others are
-                                        // structural zeros and are not executed
-};
-
-// valid window taps of parity block p = pr * 2 + pc as a 4-bit mask, bit (ta * 2 + tb) (see Geom::s2d)
-__device__ __forceinline__ unsigned s2d_tap_mask(int p) {
-    const int pr = p >> 1, pc = p & 1;
-    unsigned m = 8u;                                   // (1,1) always
-    if (pr) m |= 2u;                                   // (0,1)
-    if (pc) m |= 4u;                                   // (1,0)
-    if (pr && pc) m |= 1u;                             // (0,0)
-    return m;
-}
-
-// source depth plane (global) of GLOBAL output plane d for depth tap kd; -1 if the tap falls outside the frame's volume
-__device__ __forceinline__ int src_depth(const Geom &g, int d, int kd) {
-    if (g.mode == 0) return mvx_src_plane(d, g.Din, g.Dout, g.sd, g.pd, kd);
-    // dgrad gather: the result (dx) has g.Dout planes per frame, the source (dz) g.Din
-    return mvx_dst_plane(d, g.Dout, g.Din, g.sd, g.pd, kd);
-}
 
 // ------------------------------------------------------------------------------------------
 // weight packing: torch layout W[co][ci][kd][kh][kw] -> wpk[kd][a][b][chunk][n][BK]
@@ -1293,14 +1259,6 @@ extern "C" int mvx_conv3d_pack_weights(const float *w, float *wpk, int32_t cout,
     return MVX_OK;
 }
 
-static int check_geom(int32_t din, int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t sd,
-                      int32_t pd) {
-    if (din <= 0 || dout <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return MVX_EINVAL;
-    if (sd < 1 || sd > 2 || pd < 0 || pd > 1) return MVX_EINVAL;
-    if (cin % BK || cout % BN) return MVX_ESIZE;
-    return MVX_OK;
-}
-
 // Launch the gather kernel: persistent form when the caller supplies a zeroed work counter, classic grid otherwise.
 static int persistent_grid() {
     static int cached = 0;
@@ -1371,15 +1329,12 @@ extern "C" int mvx_conv3d_forward(const float *in, const float *wpk, const float
                                   int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
                                   int32_t flags, uint32_t *work_counter, void *stream) {
     MVX_CHECK_ARG(in && wpk && out);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
+    int rc = conv_check_forward(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
-    MVX_CHECK_ARG(dout == (din + 2 * pad_d - 3) / stride_d + 1);
     hipStream_t st = (hipStream_t)stream;
     const int relu = flags & MVX_FLAG_RELU;
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * cout, st);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = conv_zero_stats(stats, nullptr, cout, 1, flags, st);
+    if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0};
     launch_gather(st, in, wpk, bias, out, stats, g, relu, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0.0,
                   nullptr, (unsigned *)work_counter);
@@ -1394,22 +1349,13 @@ extern "C" int mvx_conv3d_forward_bg_frames(const float *in, const float *wpk, c
                                             uint64_t *exec_stages, uint32_t *done_counter, double count, double eps,
                                             float *mean_inv, uint32_t *work_counter, int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(in && wpk && out && in_halo_flags && out_mask && bg_pre);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
+    int rc = conv_check_forward(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
-    MVX_CHECK_ARG(dout == (din + 2 * pad_d - 3) / stride_d + 1);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
+    if ((rc = conv_check_frames(n_frames))) return rc;
+    MVX_CHECK_ARG(!done_counter || (stats && mean_inv && count > 0));
     hipStream_t st = (hipStream_t)stream;
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * cout * n_frames, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (done_counter) {
-        MVX_CHECK_ARG(stats && mean_inv && count > 0);
-        if (!(flags & MVX_FLAG_PREZEROED)) {
-            hipError_t e = hipMemsetAsync(done_counter, 0, sizeof(uint32_t), st);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
+    hipError_t e = conv_zero_stats(stats, done_counter, cout, n_frames, flags, st);
+    if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0, n_frames};
     launch_gather(st, in, wpk, bias, out, stats, g, flags & MVX_FLAG_RELU, in_halo_flags, out_mask, bg_pre,
                   (border_active ? 1 : 0) | ((flags & MVX_FLAG_BG_TAPS) ? 2 : 0),
@@ -1432,13 +1378,14 @@ extern "C" int mvx_conv3d_forward_bg(const float *in, const float *wpk, const fl
 
 static int launch_dgrad(const float *dz, const float *wpk_dgrad, float *dx, int32_t din, int32_t dout, int32_t h,
                         int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d, const int32_t *only_tiles,
-                        uint64_t *exec_stages, uint32_t *work_counter, void *stream, int32_t n_frames = 1) {
+                        uint64_t *exec_stages, uint32_t *work_counter, void *stream, int32_t n_frames = 1, int32_t flags = 0) {
     MVX_CHECK_ARG(dz && wpk_dgrad && dx);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    // gather view: source = dz (dout planes, cout channels), result = dx (din planes, cin channels)
-    int rc = check_geom(din, dout, h, w, cout, cin, stride_d, pad_d);
+    int rc = conv_check_frames(n_frames);
     if (rc) return rc;
+    // gather view: source = dz (dout planes, cout channels), result = dx (din planes, cin channels)
+    if ((rc = conv_check_geom(din, dout, h, w, cout, cin, stride_d, pad_d))) return rc;
     Geom g{dout, din, h, w, cout, cin, stride_d, pad_d, 1, n_frames};
+    conv_set_taps2(g, flags, CONV_INPUT_GRAD, BN);
     launch_gather((hipStream_t)stream, dz, wpk_dgrad, nullptr, dx, nullptr, g, 0, nullptr, nullptr, nullptr, 0,
                   (unsigned long long *)exec_stages, only_tiles, nullptr, 0.0, 0.0, nullptr, (unsigned *)work_counter);
     MVX_LAUNCH_CHECK();
@@ -1472,7 +1419,7 @@ extern "C" int mvx_conv3d_dgrad_tiles_frames(const float *dz, const float *wpk_d
 static int wgrad_strips(int h, int w, int cin) {
     // Two workgroups fit a CU (LDS), so 512 run at once; all have the same length, so the grid
     // should fill exactly one round: strips x (3 depth taps x channel chunks) <= 512.
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
+    const int ntiles = conv_ntiles(h, w);
     const int chunks = (cin % W4_C == 0) ? cin / W4_C : cin / BK;
     int strips = 512 / (3 * chunks);
     if (strips < 1) strips = 1;
@@ -1483,9 +1430,8 @@ static int wgrad_strips(int h, int w, int cin) {
 
 extern "C" size_t mvx_conv3d_wgrad_workspace_bytes(int32_t h, int32_t w, int32_t cin, int32_t cout) {
     if (h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cout % BN) return 0;
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
     const int per = wgrad_strips(h, w, cin);
-    const int nstrips = (ntiles + per - 1) / per;
+    const int nstrips = (conv_ntiles(h, w) + per - 1) / per;
     return (size_t)(cout / BN) * nstrips * 27 * cin * BN * sizeof(float);
 }
 
@@ -1494,14 +1440,13 @@ extern "C" int mvx_conv3d_wgrad(const float *in, const float *dz, float *dw, int
                                 int32_t pad_d, int32_t flags, void *workspace, size_t workspace_bytes, void *stream) {
     const SplitAmax am = mvxi_take_split_amax();         // (in, dz) bound for this call (fp16 pieces); cleared whatever kernel runs
     MVX_CHECK_ARG(in && dz && dw && workspace);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
+    int rc = conv_check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
     const int nblk = cout / BN;                     // the 4-wave kernel takes any multiple of 64 output channels
     if (cout != BN && cin % W4_C) return MVX_ESIZE;
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
     const int per = wgrad_strips(h, w, cin);
-    const int nstrips = (ntiles + per - 1) / per;
-    MVX_CHECK_ARG(workspace_bytes >= (size_t)nblk * nstrips * 27 * cin * BN * sizeof(float));
+    const int nstrips = (conv_ntiles(h, w) + per - 1) / per;
+    MVX_CHECK_ARG(workspace_bytes >= mvx_conv3d_wgrad_workspace_bytes(h, w, cin, cout));
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0};
     hipStream_t st = (hipStream_t)stream;
     if (cin % W4_C == 0)
@@ -1521,7 +1466,7 @@ extern "C" int mvx_conv3d_wgrad(const float *in, const float *dz, float *dw, int
 
 // mvx_conv3d_wgrad_bg: one workgroup per CU (the kernel's 9 accumulator tiles leave room for one wave per SIMD),
 // strips x 3 depth taps x channel chunks = 255..256 workgroups, steps dealt round-robin from the compacted lists.
-// workspace: [slabs][R f64 replicas][T][step lists][step counts]
+// workspace: conv_carve_wgrad (conv_geom.h)
 static int wgrad_bg_strips(int cin) {
     // slab capacity per depth tap: up to half of the 256 workgroups of a chunk set (the busiest tap of a stride-2
     // layer has twice the planes of the others)
@@ -1529,23 +1474,6 @@ static int wgrad_bg_strips(int cin) {
     return s < 1 ? 1 : s;
 }
 static size_t wgrad_bg_slab_bytes(int cin) { return (size_t)wgrad_bg_strips(cin) * 27 * cin * BN * sizeof(float); }
-
-int mvxi_wgrad_step_list(const int32_t *in_halo_flags, int din, int dout, int ntiles, int stride_d, int pad_d, int *list,
-                         int *count, hipStream_t st, int n_frames) {
-    Geom g{din, dout, 0, 0, 0, 0, stride_d, pad_d, 0, n_frames};
-    hipLaunchKernelGGL(wgrad_step_list, dim3(3), dim3(1024), 0, st, in_halo_flags, g, ntiles, list, count);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
-}
-
-int mvxi_wgrad_rank1(const float *tap_sums, const float *c_in, float *dw, int din, int dout, int cin, int cout, int stride_d,
-                     int pad_d, hipStream_t st, int n_frames) {
-    Geom g{din, dout, 0, 0, cin, cout, stride_d, pad_d, 0, n_frames};
-    const size_t total = (size_t)27 * cin * cout;
-    hipLaunchKernelGGL(wgrad_rank1, dim3(mvx_cdiv(total, 256)), dim3(256), 0, st, tap_sums, c_in, dw, g);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
-}
 
 extern "C" size_t mvx_plane_tap_sums_workspace_bytes(int32_t planes, int32_t channels) {
     return planes > 0 && channels > 0 ? sizeof(double) * RREP * planes * RK * channels : 0;
@@ -1563,7 +1491,7 @@ extern "C" int mvx_plane_tap_sums(const float *dz, int32_t planes, int32_t h, in
     hipError_t e = hipMemsetAsync(R, 0, sizeof(double) * RREP * planes * RK * channels, st);
     if (e != hipSuccess) return (int)e;
     if (tile_flags)
-        hipLaunchKernelGGL(plane_region_sums_tiles, dim3(mvx_cdiv(w, TW) * mvx_cdiv(h, TH), planes), dim3(256), 0, st, dz,
+        hipLaunchKernelGGL(plane_region_sums_tiles, dim3(conv_ntiles(h, w), planes), dim3(256), 0, st, dz,
                            tile_flags, planes, h, w, channels, R);
     else
         hipLaunchKernelGGL(plane_region_sums, dim3(h, planes), dim3(256), 0, st, dz, planes, h, w, channels, R);
@@ -1578,7 +1506,7 @@ extern "C" int mvx_conv3d_input_grad_sums_frames(const float *w, const float *ta
                                                  int32_t cout, int32_t stride_d, int32_t pad_d, float *plane_grad_sums,
                                                  int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(w && tap_sums && plane_grad_sums && din > 0 && dout > 0 && cin > 0 && cout > 0);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
+    if (int rc = conv_check_frames(n_frames)) return rc;
     Geom g{din, dout, 0, 0, cin, cout, stride_d, pad_d, 0, n_frames};
     hipLaunchKernelGGL(input_grad_sums, dim3(cin, din * n_frames), dim3(64), 0, (hipStream_t)stream, w, tap_sums, g,
                        plane_grad_sums);
@@ -1595,8 +1523,7 @@ extern "C" int mvx_conv3d_input_grad_sums(const float *w, const float *tap_sums,
 extern "C" size_t mvx_conv3d_wgrad_bg_workspace_bytes_frames(int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout,
                                                             int32_t n_frames) {
     if (dout <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout != BN || cin % W4_C || n_frames <= 0) return 0;
-    const size_t ntiles = (size_t)mvx_cdiv(w, TW) * mvx_cdiv(h, TH);
-    return wgrad_bg_slab_bytes(cin) + sizeof(int) * (3 * (size_t)dout * n_frames * ntiles + 4);
+    return conv_carve_wgrad(nullptr, wgrad_bg_slab_bytes(cin), dout * n_frames, conv_ntiles(h, w), false).bytes;
 }
 
 extern "C" size_t mvx_conv3d_wgrad_bg_workspace_bytes(int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout) {
@@ -1609,12 +1536,13 @@ extern "C" int mvx_conv3d_wgrad_bg_frames(const float *in, const float *dz, floa
                                           void *workspace, size_t workspace_bytes, int32_t n_frames, void *stream) {
     const SplitAmax am = mvxi_take_split_amax();         // (in, dz) bound for this call (fp16 pieces); cleared whatever kernel runs
     MVX_CHECK_ARG(in && dz && dw && workspace && in_halo_flags && c_in && tap_sums);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
+    int rc = conv_check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
     if (cout != BN || cin % W4_C) return MVX_ESIZE;
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    MVX_CHECK_ARG(workspace_bytes >= mvx_conv3d_wgrad_bg_workspace_bytes_frames(dout, h, w, cin, cout, n_frames));
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
+    if ((rc = conv_check_frames(n_frames))) return rc;
+    const int ntiles = conv_ntiles(h, w);
+    const WgradWorkspace ws = conv_carve_wgrad(workspace, wgrad_bg_slab_bytes(cin), dout * n_frames, ntiles, false);
+    MVX_CHECK_ARG(workspace_bytes >= ws.bytes);
     const int nstrips = wgrad_bg_strips(cin);       // slab capacity = the largest share a depth tap can get
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0, n_frames};
     hipStream_t st = (hipStream_t)stream;
@@ -1637,15 +1565,12 @@ extern "C" int mvx_conv3d_wgrad_bg_frames(const float *in, const float *dz, floa
         ks.n[kd] = share;
         if (share > widest) widest = share;
     }
-    float *slabs = (float *)workspace;
-    int *list = (int *)((char *)workspace + wgrad_bg_slab_bytes(cin));
-    int *count = list + (size_t)3 * dout * n_frames * ntiles;
-    hipLaunchKernelGGL(wgrad_step_list, dim3(3), dim3(1024), 0, st, in_halo_flags, g, ntiles, list, count);
+    hipLaunchKernelGGL(wgrad_step_list, dim3(3), dim3(1024), 0, st, in_halo_flags, g, ntiles, ws.list, ws.count);
     MVX_LAUNCH_CHECK();
-    launch_wgrad4<false>(flags, dim3(widest, 3 * (cin / W4_C)), st, in, dz, slabs, g, 0, list, count, c_in, ks, am);
+    launch_wgrad4<false>(flags, dim3(widest, 3 * (cin / W4_C)), st, in, dz, ws.slabs, g, 0, ws.list, ws.count, c_in, ks, am);
     MVX_LAUNCH_CHECK();
     const size_t per_slab = (size_t)27 * cin * BN;
-    hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, (const float *)slabs, dw, widest, cin,
+    hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, (const float *)ws.slabs, dw, widest, cin,
                        flags & MVX_FLAG_ACCUMULATE, 0, ks);
     MVX_LAUNCH_CHECK();
     hipLaunchKernelGGL(wgrad_rank1, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, tap_sums, c_in, dw, g);
@@ -1667,35 +1592,20 @@ extern "C" int mvx_conv3d_wgrad_bg(const float *in, const float *dz, float *dw, 
 // MVX_FLAG_TAPS2: only the 2x2 window of taps {0,1}^2 carries weight (a stride-2 3x3 convolution evaluated on the
 // space-to-depth image of its input); the dgrad of such a layer reads the flipped window {1,2}^2.
 // ------------------------------------------------------------------------------------------
-static int conv2d_geom_ok(int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t n_frames) {
-    if (h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || n_frames < 1 || n_frames > MVX_MAX_FRAMES) return MVX_EINVAL;
-    if (cin % BK || cout % BN) return MVX_ESIZE;
-    return MVX_OK;
-}
-
 extern "C" int mvx_conv2d_forward_frames(const float *in, const float *wpk, const float *bias, float *out, double *stats,
                                          int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t flags,
                                          uint32_t *done_counter, double eps, float *mean_inv, uint32_t *work_counter,
                                          int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(in && wpk && out);
-    int rc = conv2d_geom_ok(h, w, cin, cout, n_frames);
+    int rc = conv_check_frames(n_frames);
     if (rc) return rc;
+    if ((rc = conv_check_geom(1, 1, h, w, cin, cout, 1, 1))) return rc;
+    MVX_CHECK_ARG(!done_counter || (stats && mean_inv));
     hipStream_t st = (hipStream_t)stream;
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * cout * n_frames, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (done_counter) {
-        MVX_CHECK_ARG(stats && mean_inv);
-        if (!(flags & MVX_FLAG_PREZEROED)) {
-            hipError_t e = hipMemsetAsync(done_counter, 0, sizeof(uint32_t), st);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames, 0, (flags & MVX_FLAG_TAPS2) ? 2 : 3};
-    // the structurally zero (window tap, parity) blocks of the rearranged stride-2 kernel are not executed (7 of 16), when
-    // the parity blocks are whole K chunks
-    if ((flags & MVX_FLAG_TAPS2) && cin % 4 == 0 && (cin / 4) % BK == 0) g.s2d = cin / 4;
+    hipError_t e = conv_zero_stats(stats, done_counter, cout, n_frames, flags, st);
+    if (e != hipSuccess) return (int)e;
+    Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames};
+    conv_set_taps2(g, flags, CONV_FORWARD, BK);
     launch_gather(st, in, wpk, bias, out, stats, g, flags & MVX_FLAG_RELU, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
                   (unsigned *)done_counter, (double)h * w, eps, mean_inv, (unsigned *)work_counter);
     MVX_LAUNCH_CHECK();
@@ -1704,15 +1614,7 @@ extern "C" int mvx_conv2d_forward_frames(const float *in, const float *wpk, cons
 
 extern "C" int mvx_conv2d_dgrad_frames(const float *dz, const float *wpk_dgrad, float *dx, int32_t h, int32_t w, int32_t cin,
                                        int32_t cout, int32_t flags, uint32_t *work_counter, int32_t n_frames, void *stream) {
-    MVX_CHECK_ARG(dz && wpk_dgrad && dx);
-    int rc = conv2d_geom_ok(h, w, cout, cin, n_frames);          // gather view: source dz (cout channels) -> dx (cin channels)
-    if (rc) return rc;
-    Geom g{1, 1, h, w, cout, cin, 1, 1, 1, n_frames, (flags & MVX_FLAG_TAPS2) ? 1 : 0, 3};
-    if ((flags & MVX_FLAG_TAPS2) && cin % 4 == 0 && (cin / 4) % BN == 0) g.s2d = cin / 4;      // parity of the OUTPUT channel block
-    launch_gather((hipStream_t)stream, dz, wpk_dgrad, nullptr, dx, nullptr, g, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                  nullptr, 0.0, 0.0, nullptr, (unsigned *)work_counter);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
+    return launch_dgrad(dz, wpk_dgrad, dx, 1, 1, h, w, cin, cout, 1, 1, nullptr, nullptr, work_counter, stream, n_frames, flags);
 }
 
 static int conv2d_wgrad_strips(int cin, int cout) {
@@ -1721,11 +1623,14 @@ static int conv2d_wgrad_strips(int cin, int cout) {
     return s < 1 ? 1 : s;
 }
 
+// slab capacity of the workspace (the launch may use fewer strips)
+static size_t conv2d_wgrad_slab_bytes(int cin, int cout) {
+    return (size_t)(cout / BN) * conv2d_wgrad_strips(cin, cout) * 27 * cin * BN * sizeof(float);
+}
+
 extern "C" size_t mvx_conv2d_wgrad_workspace_bytes_frames(int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t n_frames) {
     if (h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cin % W4_C || cout % BN || n_frames <= 0) return 0;
-    const size_t ntiles = (size_t)mvx_cdiv(w, TW) * mvx_cdiv(h, TH);
-    const size_t slabs = (size_t)(cout / BN) * conv2d_wgrad_strips(cin, cout) * 27 * cin * BN * sizeof(float);
-    return slabs + sizeof(int) * (3 * (size_t)n_frames * ntiles + 4) + sizeof(int) * (size_t)n_frames * ntiles;
+    return conv_carve_wgrad(nullptr, conv2d_wgrad_slab_bytes(cin, cout), n_frames, conv_ntiles(h, w), true).bytes;
 }
 
 // dw f32 [cout][cin][3][3] (ADDED to with MVX_FLAG_ACCUMULATE) = sum over all frames and sites of in (x) dz
@@ -1734,35 +1639,34 @@ extern "C" int mvx_conv2d_wgrad_frames(const float *in, const float *dz, float *
                                        void *stream) {
     const SplitAmax am = mvxi_take_split_amax();         // (in, dz) bound for this call (fp16 pieces); cleared whatever kernel runs
     MVX_CHECK_ARG(in && dz && dw && workspace);
-    int rc = conv2d_geom_ok(h, w, cin, cout, n_frames);
+    int rc = conv_check_frames(n_frames);
     if (rc) return rc;
+    if ((rc = conv_check_geom(1, 1, h, w, cin, cout, 1, 1))) return rc;
     if (cin % W4_C) return MVX_ESIZE;
-    MVX_CHECK_ARG(workspace_bytes >= mvx_conv2d_wgrad_workspace_bytes_frames(h, w, cin, cout, n_frames));
+    const int ntiles = conv_ntiles(h, w);
+    const WgradWorkspace ws = conv_carve_wgrad(workspace, conv2d_wgrad_slab_bytes(cin, cout), n_frames, ntiles, true);
+    MVX_CHECK_ARG(workspace_bytes >= ws.bytes);
     hipStream_t st = (hipStream_t)stream;
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
     int nstrips = conv2d_wgrad_strips(cin, cout);
     if (nstrips > (n_frames * ntiles + 3) / 4) nstrips = (n_frames * ntiles + 3) / 4;     // >= 4 tile steps per strip: the slabs
     if (nstrips < 1) nstrips = 1;                                                       // (589 KB per strip at cin 128) stay small
     const int nblk = cout / BN;
-    Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames, 0, (flags & MVX_FLAG_TAPS2) ? 2 : 3};
-    if ((flags & MVX_FLAG_TAPS2) && cin % 4 == 0 && (cin / 4) % W4_C == 0) g.s2d = cin / 4;
-    float *slabs = (float *)workspace;
-    int *list = (int *)((char *)workspace + (size_t)nblk * nstrips * 27 * cin * BN * sizeof(float));
-    int *count = list + (size_t)3 * n_frames * ntiles;
-    int *ones = count + 4;                                         // "every tile is a step": any non-zero word is a set flag
-    hipError_t e = hipMemsetAsync(ones, 0x01, sizeof(int) * (size_t)n_frames * ntiles, st);
+    Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames};
+    conv_set_taps2(g, flags, CONV_WEIGHT_GRAD, W4_C);
+    // "every tile is a step": any non-zero word is a set flag
+    hipError_t e = hipMemsetAsync(ws.ones, 0x01, sizeof(int) * (size_t)n_frames * ntiles, st);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(wgrad_step_list, dim3(3), dim3(1024), 0, st, (const int *)ones, g, ntiles, list, count);
+    hipLaunchKernelGGL(wgrad_step_list, dim3(3), dim3(1024), 0, st, (const int *)ws.ones, g, ntiles, ws.list, ws.count);
     MVX_LAUNCH_CHECK();
     Strips ks;
     ks.n[0] = 1; ks.n[1] = nstrips; ks.n[2] = 1;                    // depth tap 1 is the only one with a source plane
     if (flags & MVX_FLAG_TAPS2)
-        launch_wgrad4<true>(flags, dim3(nstrips, 3 * (cin / W4_C), nblk), st, in, dz, slabs, g, 0, list, count, nullptr, ks, am);
+        launch_wgrad4<true>(flags, dim3(nstrips, 3 * (cin / W4_C), nblk), st, in, dz, ws.slabs, g, 0, ws.list, ws.count, nullptr, ks, am);
     else
-        launch_wgrad4<false>(flags, dim3(nstrips, 3 * (cin / W4_C), nblk), st, in, dz, slabs, g, 0, list, count, nullptr, ks, am);
+        launch_wgrad4<false>(flags, dim3(nstrips, 3 * (cin / W4_C), nblk), st, in, dz, ws.slabs, g, 0, ws.list, ws.count, nullptr, ks, am);
     MVX_LAUNCH_CHECK();
     const size_t per_slab = (size_t)27 * cin * BN;
-    hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256), nblk), dim3(256), 0, st, (const float *)slabs, dw, nstrips, cin,
+    hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256), nblk), dim3(256), 0, st, (const float *)ws.slabs, dw, nstrips, cin,
                        flags & MVX_FLAG_ACCUMULATE, 1, ks);
     MVX_LAUNCH_CHECK();
     return MVX_OK;

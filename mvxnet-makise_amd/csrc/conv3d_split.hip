@@ -1,4 +1,4 @@
-// Dense 3x3x3 convolution on the bf16 matrix cores with fp32-grade accuracy ("bf16x3" split).
+// Dense 3x3x3 convolution, forward and input gradient, on the bf16 matrix cores with fp32-grade accuracy ("bf16x3" split).
 //
 // Every f32 operand x is split on the fly into two bf16 numbers, hi = bf16(x) and
 // lo = bf16(x - hi) (together 16 mantissa bits), and a product is evaluated as
@@ -16,48 +16,14 @@
 //     hi + mid + lo is the f32 operand exactly and the dropped cross terms are below the rounding of an f32 product;
 //   - weights are pre-split by the pack kernel and staged three taps (one kernel row) at a time, so a
 //     barrier pair covers 3 taps x 12 MFMAs per wave instead of one tap.
+// The weight gradient in these arithmetics is conv3d_wgrad4s (conv3d.hip), behind the f32 entry points with MVX_FLAG_SPLIT.
 #include "common.h"
+#include "conv_geom.h"
 #include "split_common.h"
 
 namespace {
 
-
-constexpr int TH = 8, TW = 16, HH = TH + 2, HW = TW + 2;
-constexpr int BK = 32, BN = 64;
 constexpr int TH2 = 16;                           // patch height of the 16 x 16-site gather units
-
-struct Geom {
-    int Din, Dout, H, W, Cin, Cout, sd, pd, mode;
-    int F = 1;                                     // frames stacked along depth: planes [F * Dout] <- [F * Din]
-    int tap_lo = 0, tap_hi = 3;                    // in-plane taps (rows AND columns) [tap_lo, tap_hi) carry weight (MVX_FLAG_TAPS2:
-                                                   // the 2x2 window of a stride-2 kernel on the space-to-depth image)
-    int s2d = 0;                                   // > 0: channels per parity block of that image: the structurally zero (window tap,
-                                                   // parity) blocks are not executed (see Geom::s2d in conv3d.hip)
-};
-
-// valid window taps of parity block p = pr * 2 + pc as a 4-bit mask, bit (ta * 2 + tb) (conv3d.hip: s2d_tap_mask)
-__device__ __forceinline__ unsigned s2d_tap_mask(int p) {
-    const int pr = p >> 1, pc = p & 1;
-    unsigned m = 8u;
-    if (pr) m |= 2u;
-    if (pc) m |= 4u;
-    if (pr && pc) m |= 1u;
-    return m;
-}
-
-// source plane of output plane d (a GLOBAL plane index: frame * Dout + plane) for depth tap kd, or -1; planes of
-// different frames never connect (same rule as mvx_src_plane / mvx_dst_plane in common.h)
-__device__ __forceinline__ int src_depth(const Geom &g, int d, int kd) {
-    const int f = d / g.Dout, dl = d - f * g.Dout;
-    if (g.mode == 0) {
-        const int s = dl * g.sd - g.pd + kd;
-        return (s >= 0 && s < g.Din) ? f * g.Din + s : -1;
-    }
-    const int t = dl + g.pd - kd;
-    if (t < 0 || (t % g.sd) != 0) return -1;
-    const int s = t / g.sd;
-    return s < g.Din ? f * g.Din + s : -1;
-}
 
 // torch W[co][ci][kd][kh][kw] -> wsp[kd][tap][32-channel chunk][n][piece][32] (bf16), forward or dgrad view
 __global__ void pack_weights_split(const float *__restrict__ w, unsigned short *__restrict__ wsp, int Co, int Ci, int dgrad, int np, int fmt) {
@@ -469,6 +435,9 @@ extern "C" int mvx_tuning_set(int32_t key, int64_t value) {
     return MVX_EINVAL;
 }
 
+static inline int pieces_of(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 2 : (flags & MVX_FLAG_SPLIT3) ? 3 : 2; }
+static inline int fmt_of(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 1 : 0; }
+
 static void launch_gather_split(hipStream_t st, int flags, int planes, int nblocks, const float *in, const unsigned short *wsp,
                                 const float *bias, float *out, double *stats, const Geom &g, int relu, const int *in_hflag,
                                 const unsigned char *out_mask, const float *bg_pre, int border_active, const int *only_tiles,
@@ -478,7 +447,6 @@ static void launch_gather_split(hipStream_t st, int flags, int planes, int nbloc
     const bool big = units16 >= g_split16_min_units;
     const dim3 grid(tiles_x * mvx_cdiv(g.H, big ? TH2 : TH), planes, nblocks);
     const bool win = g.tap_lo != 0 || g.tap_hi != 3 || g.s2d > 0;
-    const int np = (flags & MVX_FLAG_SPLIT_F16) ? 2 : (flags & MVX_FLAG_SPLIT3) ? 3 : 2;
     const SplitAmax am = mvxi_take_split_amax();         // bound by mvx_split_operand_amax for this launch (fp16 pieces), else NULLs
 #define MVX_GO(NP_, BK_, MT_, F_)                                                                                                        \
     do {                                                                                                                             \
@@ -489,206 +457,11 @@ static void launch_gather_split(hipStream_t st, int flags, int planes, int nbloc
             hipLaunchKernelGGL((conv3d_gather_splitT<NP_, BK_, MT_, false, F_>), grid, dim3(256), 0, st, in, wsp, bias, out, stats, g,   \
                                relu, in_hflag, out_mask, bg_pre, border_active, only_tiles, exec_stages, am.a);         \
     } while (0)
-    if (flags & MVX_FLAG_SPLIT_F16) { if (big) MVX_GO(2, 32, 2, 1); else MVX_GO(2, 32, 1, 1); }
-    else if (np == 3) { if (big) MVX_GO(3, 16, 2, 0); else MVX_GO(3, 32, 1, 0); }
+    if (fmt_of(flags)) { if (big) MVX_GO(2, 32, 2, 1); else MVX_GO(2, 32, 1, 1); }
+    else if (pieces_of(flags) == 3) { if (big) MVX_GO(3, 16, 2, 0); else MVX_GO(3, 32, 1, 0); }
     else              { if (big) MVX_GO(2, 32, 2, 0); else MVX_GO(2, 32, 1, 0); }
 #undef MVX_GO
 }
-
-// ------------------------------------------------------------------------------------------
-// weight gradient, bf16x3.  dW[kd][a][b][c][n] = sum_sites x[site + tap][c] * dz[site][n]: the MFMA
-// reduction index is the SITE, so both operands are needed "k-major" while memory is channel-major.
-// The tiles are staged as [site][32 channels] bf16 rows (64 B) and fetched with ds_read_b64_tr_b16,
-// the LDS transpose read: a 16-lane group reads a 4-site x 16-channel block and each lane receives
-// 4 consecutive sites of its own channel -- exactly half of a 32x32x16 operand fragment, for any tap
-// shift (the shift only changes which rows are addressed).  One 9-wave workgroup per (strip of
-// patches, depth tap, 32-channel chunk); wave t owns in-plane tap t and a 32(c) x 64(n) accumulator.
-// ------------------------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-constexpr int WG_THREADS = 9 * 64;
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned short *row0, const unsigned short *row1) {
-    typedef __attribute__((address_space(3))) s16x4 lds4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row1);
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-}
-
-template <int NP, int FMT>
-__global__ __launch_bounds__(WG_THREADS) void conv3d_wgrad_split(const float *__restrict__ in,
-                                                                 const float *__restrict__ dz,
-                                                                 float *__restrict__ slabs, Geom g,
-                                                                 int tiles_per_strip, const int *__restrict__ step_list,
-                                                                 const int *__restrict__ step_count,
-                                                                 const float *__restrict__ c_in, SplitAmax am) {
-    float x_scale = 1.f, z_scale = 1.f;                       // fp16 pieces: operands scaled by their bound amax (split_common.h)
-    if constexpr (FMT == 1) { x_scale = split_scale_coarse(am.a); z_scale = split_scale_of(am.b); }     // x: activations, dz: gradients
-    __shared__ __attribute__((aligned(16))) unsigned short s_x[NP][HH * HW][BK];          // [piece][halo site][channel]
-    __shared__ __attribute__((aligned(16))) unsigned short s_z[NP][2][TH * TW][32];       // [piece][32-channel half][site][channel]
-    const int tiles_x = (g.W + TW - 1) / TW, tiles_y = (g.H + TH - 1) / TH;
-    const int ntiles = tiles_x * tiles_y;
-    const int strip = blockIdx.x;
-    const int nchunks = g.Cin / BK;
-    const int kd = blockIdx.y / nchunks, cc = blockIdx.y % nchunks;
-    const int tid = threadIdx.x, lane = tid & 63, tap = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const int ta = tap / 3, tb = tap % 3;
-    // transpose-read roles of this lane
-    const int grp = lane >> 4, i16 = lane & 15, q = i16 >> 2, pcol = (grp & 1) * 16 + 4 * (i16 & 3), kbase = (grp >> 1) * 8;
-
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-
-    // steps: dense = (valid plane) x (tile of the strip); background-aware = entries of the compacted list of this depth
-    // tap dealt round-robin to the strips (see conv3d_wgrad4 in conv3d.hip)
-    const int nstrips = gridDim.x;
-    int dlo = 0, dhi = -1;
-    for (int dd = 0; dd < g.Dout; ++dd) {
-        const int ds = dd * g.sd - g.pd + kd;
-        if (ds >= 0 && ds < g.Din) { if (dhi < 0) dlo = dd; dhi = dd; }
-    }
-    const int nd = dhi >= dlo ? dhi - dlo + 1 : 0;
-    const int per = tiles_per_strip;
-    const int *my_list = step_list ? step_list + (size_t)kd * g.Dout * g.F * ntiles : nullptr;
-    const int nlist = step_list ? step_count[kd] : 0;
-    const int nsteps = step_list ? (nlist > strip ? (nlist - strip + nstrips - 1) / nstrips : 0) : nd * per;
-    auto step_of = [&](int i, int &d, int &t) {
-        if (my_list) { const int e = my_list[strip + i * nstrips]; d = e / ntiles; t = e - d * ntiles; }
-        else { d = dlo + i / per; t = strip * per + i % per; }
-    };
-    auto next_live = [&](int i) {
-        if (!my_list)
-            while (i < nsteps && strip * per + i % per >= ntiles) ++i;
-        return i < nsteps ? i : nsteps;
-    };
-    constexpr int NX = (HH * HW * 8 + WG_THREADS - 1) / WG_THREADS;
-    constexpr int NZ = (TH * TW * 16 + WG_THREADS - 1) / WG_THREADS;
-    float4 xr[NX], zr[NZ];
-    auto load_step = [&](int i) {
-        int d, t;
-        step_of(i, d, t);
-        const int ds = src_depth(g, d, kd);                       // listed / dense steps always have a valid source plane
-        const int tx0 = (t % tiles_x) * TW, ty0 = (t / tiles_x) * TH;
-#pragma unroll
-        for (int u = 0; u < NX; ++u) {
-            const int c = tid + WG_THREADS * u;
-            xr[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < HH * HW * 8) {
-                const int r = c >> 3, part = c & 7;
-                const int gy = ty0 - 1 + r / HW, gx = tx0 - 1 + r % HW;
-                if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
-                    float4 v = *(const float4 *)(in + (((size_t)ds * g.H + gy) * g.W + gx) * g.Cin + cc * BK + part * 4);
-                    if (c_in) {
-                        const float4 cb = *(const float4 *)(c_in + (size_t)ds * g.Cin + cc * BK + part * 4);
-                        v.x -= cb.x; v.y -= cb.y; v.z -= cb.z; v.w -= cb.w;
-                    }
-                    xr[u] = v;
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NZ; ++u) {
-            const int c = tid + WG_THREADS * u;
-            zr[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (c < TH * TW * 16) {
-                const int r = c >> 4, part = c & 15;
-                const int gy = ty0 + (r >> 4), gx = tx0 + (r & 15);
-                if (gy < g.H && gx < g.W)
-                    zr[u] = *(const float4 *)(dz + (((size_t)d * g.H + gy) * g.W + gx) * g.Cout + part * 4);
-            }
-        }
-    };
-    int cur = next_live(0);
-    if (cur < nsteps) load_step(cur);
-    while (cur < nsteps) {
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < NX; ++u) {
-            const int c = tid + WG_THREADS * u;
-            if (c < HH * HW * 8) {
-                uint2 pc[NP];
-                if constexpr (FMT == 1) { xr[u].x *= x_scale; xr[u].y *= x_scale; xr[u].z *= x_scale; xr[u].w *= x_scale; }
-                split_n<NP, FMT>(xr[u].x, xr[u].y, xr[u].z, xr[u].w, pc);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) *(uint2 *)(&s_x[p][c >> 3][(c & 7) * 4]) = pc[p];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < NZ; ++u) {
-            const int c = tid + WG_THREADS * u;
-            if (c < TH * TW * 16) {
-                const int r = c >> 4, part = c & 15;
-                uint2 pc[NP];
-                if constexpr (FMT == 1) { zr[u].x *= z_scale; zr[u].y *= z_scale; zr[u].z *= z_scale; zr[u].w *= z_scale; }
-                split_n<NP, FMT>(zr[u].x, zr[u].y, zr[u].z, zr[u].w, pc);
-#pragma unroll
-                for (int p = 0; p < NP; ++p) *(uint2 *)(&s_z[p][part >> 3][r][(part & 7) * 4]) = pc[p];
-            }
-        }
-        __syncthreads();
-        const int nxt = next_live(cur + 1);
-        if (nxt < nsteps) load_step(nxt);
-#pragma unroll 2
-        for (int ks = 0; ks < TH; ++ks) {                 // 16 sites (one patch row) per MFMA k-step
-            const int hr0 = (ks + ta) * HW + tb + kbase + q, hr1 = hr0 + 4;      // halo rows of sites kbase+q, +4
-            const int zr0 = ks * TW + kbase + q, zr1 = zr0 + 4;
-            bf16x8 av[NP], b0[NP], b1[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                av[p] = tr_frag(&s_x[p][hr0][pcol], &s_x[p][hr1][pcol]);
-                b0[p] = tr_frag(&s_z[p][0][zr0][pcol], &s_z[p][0][zr1][pcol]);
-                b1[p] = tr_frag(&s_z[p][1][zr0][pcol], &s_z[p][1][zr1][pcol]);
-            }
-            split_mac2<NP, FMT>(acc0, acc1, av, b0, b1);
-        }
-        cur = nxt;
-    }
-    float *o = slabs + ((((size_t)strip * 3 + kd) * 9 + tap) * g.Cin + cc * BK) * BN;
-    if constexpr (FMT == 1) {
-        const float o_scale = split_inverse(x_scale) * split_inverse(z_scale);
-        acc0 *= o_scale; acc1 *= o_scale;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        o[(size_t)row * BN + li] = acc0[r];
-        o[(size_t)row * BN + 32 + li] = acc1[r];
-    }
-}
-
-__global__ void wgrad_reduce_split(const float *__restrict__ slabs, float *__restrict__ dw, int nstrips, int Ci, int accumulate) {
-    const size_t per = (size_t)27 * Ci * BN;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < per; e += (size_t)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int k = 0; k < nstrips; ++k) s += slabs[(size_t)k * per + e];
-        const int co = (int)(e % BN);
-        size_t r = e / BN;
-        const int ci = (int)(r % Ci); r /= Ci;
-        const int tap = (int)(r % 9);
-        const int kd = (int)(r / 9);
-        float *dst = dw + ((((size_t)co * Ci + ci) * 3 + kd) * 3 + tap / 3) * 3 + tap % 3;
-        *dst = accumulate ? *dst + s : s;
-    }
-}
-
-int check_geom(int32_t din, int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t sd, int32_t pd) {
-    // a rejected call drops the operand ranges bound for it (common.h MVX_CHECK_ARG)
-    MVX_CHECK_ARG(!(din <= 0 || dout <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0));
-    MVX_CHECK_ARG(!(sd < 1 || sd > 2 || pd < 0 || pd > 1));
-    if (cin % BK || cout % BN) {
-        mvxi_drop_split_amax();
-        return MVX_ESIZE;
-    }
-    return MVX_OK;
-}
-
-static inline int pieces_of(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 2 : (flags & MVX_FLAG_SPLIT3) ? 3 : 2; }
-static inline int fmt_of(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 1 : 0; }
 
 }  // namespace
 
@@ -713,14 +486,11 @@ extern "C" int mvx_conv3d_forward_split(const float *in, const void *wsplit, con
                                         int32_t stride_d, int32_t pad_d, int32_t flags, void *stream) {
     MVX_CHECK_ARG(in && wsplit && out);
     const int relu = flags & MVX_FLAG_RELU;
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
+    int rc = conv_check_forward(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
-    MVX_CHECK_ARG(dout == (din + 2 * pad_d - 3) / stride_d + 1);
     hipStream_t st = (hipStream_t)stream;
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * cout, st);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = conv_zero_stats(stats, nullptr, cout, 1, flags, st);
+    if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0};
     launch_gather_split(st, flags, dout, cout / BN, in, (const unsigned short *)wsplit, bias, out, stats, g, relu, nullptr, nullptr, nullptr,
                         0, nullptr, nullptr);
@@ -734,15 +504,12 @@ extern "C" int mvx_conv3d_forward_bg_split_frames(const float *in, const void *w
                                                   const int32_t *in_halo_flags, const uint8_t *out_mask, const float *bg_pre,
                                                   int32_t border_active, uint64_t *exec_stages, int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(in && wsplit && out && in_halo_flags && out_mask && bg_pre);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
+    int rc = conv_check_frames(n_frames);
     if (rc) return rc;
-    MVX_CHECK_ARG(dout == (din + 2 * pad_d - 3) / stride_d + 1);
+    if ((rc = conv_check_forward(din, dout, h, w, cin, cout, stride_d, pad_d))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * cout * n_frames, st);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = conv_zero_stats(stats, nullptr, cout, n_frames, flags, st);
+    if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0, n_frames};
     launch_gather_split(st, flags, dout * n_frames, cout / BN, in, (const unsigned short *)wsplit, bias, out, stats, g,
                         flags & MVX_FLAG_RELU, in_halo_flags, out_mask, bg_pre,
@@ -764,14 +531,11 @@ static int launch_dgrad_split(const float *dz, const void *wsplit_dgrad, float *
                               int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d, int32_t flags,
                               const int32_t *only_tiles, uint64_t *exec_stages, int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(dz && wsplit_dgrad && dx);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    int rc = check_geom(din, dout, h, w, cout, cin, stride_d, pad_d);
+    int rc = conv_check_frames(n_frames);
     if (rc) return rc;
+    if ((rc = conv_check_geom(din, dout, h, w, cout, cin, stride_d, pad_d))) return rc;
     Geom g{dout, din, h, w, cout, cin, stride_d, pad_d, 1, n_frames};
-    if (flags & MVX_FLAG_TAPS2) {                   // the input gradient of such a layer reads the flipped window {1,2}^2
-        g.tap_lo = 1; g.tap_hi = 3;
-        if (cin % 4 == 0 && (cin / 4) % BN == 0) g.s2d = cin / 4;      // parity of the OUTPUT channel block
-    }
+    conv_set_taps2(g, flags, CONV_INPUT_GRAD, BN);
     launch_gather_split((hipStream_t)stream, flags, din * n_frames, cin / BN, dz, (const unsigned short *)wsplit_dgrad, nullptr, dx, nullptr,
                         g, 0, nullptr, nullptr, nullptr, 0, only_tiles, (unsigned long long *)exec_stages);
     MVX_LAUNCH_CHECK();
@@ -802,127 +566,24 @@ extern "C" int mvx_conv3d_dgrad_split(const float *dz, const void *wsplit_dgrad,
     return launch_dgrad_split(dz, wsplit_dgrad, dx, din, dout, h, w, cin, cout, stride_d, pad_d, flags, nullptr, nullptr, 1, stream);
 }
 
-extern "C" int mvx_conv3d_wgrad_split(const float *in, const float *dz, float *dw, int32_t din, int32_t dout, int32_t h,
-                                      int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
-                                      int32_t flags, void *workspace, size_t workspace_bytes, void *stream) {
-    const SplitAmax am = mvxi_take_split_amax();         // (x, dz) of an fp16-piece launch, else NULLs
-    MVX_CHECK_ARG(in && dz && dw && workspace);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
-    if (rc) return rc;
-    if (cout != BN) return MVX_ESIZE;
-    // same strip decomposition (and workspace size) as mvx_conv3d_wgrad
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
-    int strips = 512 / (3 * (cin / BK));             // one full round of 2 workgroups per CU (see conv3d.hip)
-    if (strips < 1) strips = 1;
-    int per = (ntiles + strips - 1) / strips;
-    if (per < 1) per = 1;
-    const int nstrips = (ntiles + per - 1) / per;
-    MVX_CHECK_ARG(workspace_bytes >= (size_t)nstrips * 27 * cin * BN * sizeof(float));
-    Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0};
-    hipStream_t st = (hipStream_t)stream;
-    if (fmt_of(flags))
-        hipLaunchKernelGGL((conv3d_wgrad_split<2, 1>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in, dz,
-                           (float *)workspace, g, per, (const int *)nullptr, (const int *)nullptr, (const float *)nullptr, am);
-    else if (pieces_of(flags) == 3)
-        hipLaunchKernelGGL((conv3d_wgrad_split<3, 0>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in, dz,
-                           (float *)workspace, g, per, (const int *)nullptr, (const int *)nullptr, (const float *)nullptr, am);
-    else
-        hipLaunchKernelGGL((conv3d_wgrad_split<2, 0>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in, dz,
-                           (float *)workspace, g, per, (const int *)nullptr, (const int *)nullptr, (const float *)nullptr, am);
-    MVX_LAUNCH_CHECK();
-    const size_t per_slab = (size_t)27 * cin * BN;
-    hipLaunchKernelGGL(wgrad_reduce_split, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, (const float *)workspace, dw,
-                       nstrips, cin, flags & MVX_FLAG_ACCUMULATE);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
-}
-
-// background-aware weight gradient, bf16x3: same decomposition as mvx_conv3d_wgrad_bg (conv3d.hip)
-static int wgrad_bg_split_strips(int cin) {
-    const int s = 256 / (3 * (cin / BK));
-    return s < 1 ? 1 : s;
-}
-
-extern "C" size_t mvx_conv3d_wgrad_bg_split_workspace_bytes_frames(int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout,
-                                                                  int32_t n_frames) {
-    if (dout <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout != BN || cin % BK || n_frames <= 0) return 0;
-    const size_t ntiles = (size_t)mvx_cdiv(w, TW) * mvx_cdiv(h, TH);
-    return (size_t)wgrad_bg_split_strips(cin) * 27 * cin * BN * sizeof(float) + sizeof(int) * (3 * dout * n_frames * ntiles + 4);
-}
-
-extern "C" size_t mvx_conv3d_wgrad_bg_split_workspace_bytes(int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout) {
-    return mvx_conv3d_wgrad_bg_split_workspace_bytes_frames(dout, h, w, cin, cout, 1);
-}
-
-extern "C" int mvx_conv3d_wgrad_bg_split_frames(const float *in, const float *dz, float *dw, int32_t din, int32_t dout,
-                                                int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t stride_d,
-                                                int32_t pad_d, int32_t flags, const int32_t *in_halo_flags, const float *c_in,
-                                                const float *tap_sums, void *workspace, size_t workspace_bytes,
-                                                int32_t n_frames, void *stream) {
-    const SplitAmax am = mvxi_take_split_amax();         // (x, dz) of an fp16-piece launch, else NULLs
-    MVX_CHECK_ARG(in && dz && dw && workspace && in_halo_flags && c_in && tap_sums);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    int rc = check_geom(din, dout, h, w, cin, cout, stride_d, pad_d);
-    if (rc) return rc;
-    if (cout != BN) return MVX_ESIZE;
-    MVX_CHECK_ARG(workspace_bytes >= mvx_conv3d_wgrad_bg_split_workspace_bytes_frames(dout, h, w, cin, cout, n_frames));
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
-    const int nstrips = wgrad_bg_split_strips(cin);
-    Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0, n_frames};
-    hipStream_t st = (hipStream_t)stream;
-    float *slabs = (float *)workspace;
-    int *list = (int *)((char *)workspace + (size_t)nstrips * 27 * cin * BN * sizeof(float));
-    int *count = list + (size_t)3 * dout * n_frames * ntiles;
-    rc = mvxi_wgrad_step_list(in_halo_flags, din, dout, ntiles, stride_d, pad_d, list, count, st, n_frames);
-    if (rc) return rc;
-    if (fmt_of(flags))
-        hipLaunchKernelGGL((conv3d_wgrad_split<2, 1>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in, dz, slabs, g, 0,
-                           (const int *)list, (const int *)count, c_in, am);
-    else if (pieces_of(flags) == 3)
-        hipLaunchKernelGGL((conv3d_wgrad_split<3, 0>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in, dz, slabs, g, 0,
-                           (const int *)list, (const int *)count, c_in, am);
-    else
-        hipLaunchKernelGGL((conv3d_wgrad_split<2, 0>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in, dz, slabs, g, 0,
-                           (const int *)list, (const int *)count, c_in, am);
-    MVX_LAUNCH_CHECK();
-    const size_t per_slab = (size_t)27 * cin * BN;
-    hipLaunchKernelGGL(wgrad_reduce_split, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, (const float *)slabs, dw, nstrips,
-                       cin, flags & MVX_FLAG_ACCUMULATE);
-    MVX_LAUNCH_CHECK();
-    return mvxi_wgrad_rank1(tap_sums, c_in, dw, din, dout, cin, cout, stride_d, pad_d, st, n_frames);
-}
-
-extern "C" int mvx_conv3d_wgrad_bg_split(const float *in, const float *dz, float *dw, int32_t din, int32_t dout, int32_t h,
-                                         int32_t w, int32_t cin, int32_t cout, int32_t stride_d, int32_t pad_d,
-                                         int32_t flags, const int32_t *in_halo_flags, const float *c_in,
-                                         const float *tap_sums, void *workspace, size_t workspace_bytes, void *stream) {
-    return mvx_conv3d_wgrad_bg_split_frames(in, dz, dw, din, dout, h, w, cin, cout, stride_d, pad_d, flags, in_halo_flags, c_in,
-                                            tap_sums, workspace, workspace_bytes, 1, stream);
-}
-
 // ------------------------------------------------------------------------------------------
 // 2-D convolutions of the RPN on frame sets, bf16x3 (modules/voxelnet/Pipe.py:45-75): the same kernels with one plane
 // per frame (din = dout = 1, pad_d = 1: only the middle depth tap exists).  Weights: the 2-D kernel placed in the middle
 // depth slice of a 3-D one and packed with mvx_conv3d_pack_weights_split.  The stride-2 layers run on the space-to-depth
-// image with their rearranged 3x3 kernel (zeros where the 2x2 window has no tap: all nine taps are executed here).
+// image with their rearranged 3x3 kernel (MVX_FLAG_TAPS2: only its 2x2 window is executed, conv_set_taps2).
 // ------------------------------------------------------------------------------------------
 extern "C" int mvx_conv2d_forward_split_frames(const float *in, const void *wsplit, const float *bias, float *out, double *stats,
                                                int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t flags,
                                                int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(in && wsplit && out);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    int rc = check_geom(1, 1, h, w, cin, cout, 1, 1);
+    int rc = conv_check_frames(n_frames);
     if (rc) return rc;
+    if ((rc = conv_check_geom(1, 1, h, w, cin, cout, 1, 1))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * cout * n_frames, st);
-        if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = conv_zero_stats(stats, nullptr, cout, n_frames, flags, st);
+    if (e != hipSuccess) return (int)e;
     Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames};
-    if (flags & MVX_FLAG_TAPS2) {                   // stride-2 kernel on the space-to-depth image: window {0,1}^2, structural zeros skipped
-        g.tap_lo = 0; g.tap_hi = 2;
-        if (cin % 4 == 0 && (cin / 4) % BK == 0) g.s2d = cin / 4;
-    }
+    conv_set_taps2(g, flags, CONV_FORWARD, BK);
     launch_gather_split(st, flags, n_frames, cout / BN, in, (const unsigned short *)wsplit, bias, out, stats, g, flags & MVX_FLAG_RELU,
                         nullptr, nullptr, nullptr, 0, nullptr, nullptr);
     MVX_LAUNCH_CHECK();
@@ -932,58 +593,4 @@ extern "C" int mvx_conv2d_forward_split_frames(const float *in, const void *wspl
 extern "C" int mvx_conv2d_dgrad_split_frames(const float *dz, const void *wsplit_dgrad, float *dx, int32_t h, int32_t w,
                                              int32_t cin, int32_t cout, int32_t flags, int32_t n_frames, void *stream) {
     return launch_dgrad_split(dz, wsplit_dgrad, dx, 1, 1, h, w, cin, cout, 1, 1, flags, nullptr, nullptr, n_frames, stream);
-}
-
-static int conv2d_wgrad_split_strips(int cin) {
-    const int s = 256 / (cin / BK);                 // one depth tap carries work: 256 workgroups per 64-channel block of dz
-    return s < 1 ? 1 : (s > 64 ? 64 : s);
-}
-
-
-extern "C" size_t mvx_conv2d_wgrad_split_workspace_bytes_frames(int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t n_frames) {
-    if (h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cin % BK || cout % BN || n_frames <= 0) return 0;
-    const size_t ntiles = (size_t)mvx_cdiv(w, TW) * mvx_cdiv(h, TH);
-    return (size_t)conv2d_wgrad_split_strips(cin) * 27 * cin * BN * sizeof(float) +
-           sizeof(int) * (3 * (size_t)n_frames * ntiles + 4) + sizeof(int) * (size_t)n_frames * ntiles;
-}
-
-// dw3 f32 [cout][cin][3][3][3]: the 2-D gradient is its middle depth slice (slices 0 and 2 come out zero)
-extern "C" int mvx_conv2d_wgrad_split_frames(const float *in, const float *dz, float *dw3, int32_t h, int32_t w, int32_t cin,
-                                             int32_t cout, int32_t flags, void *workspace, size_t workspace_bytes,
-                                             int32_t n_frames, void *stream) {
-    const SplitAmax am = mvxi_take_split_amax();         // (x, dz) of an fp16-piece launch, else NULLs
-    MVX_CHECK_ARG(in && dz && dw3 && workspace);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
-    int rc = check_geom(1, 1, h, w, cin, cout, 1, 1);
-    if (rc) return rc;
-    MVX_CHECK_ARG(workspace_bytes >= mvx_conv2d_wgrad_split_workspace_bytes_frames(h, w, cin, cout, n_frames));
-    hipStream_t st = (hipStream_t)stream;
-    const int ntiles = (int)(mvx_cdiv(w, TW) * mvx_cdiv(h, TH));
-    const int nstrips = conv2d_wgrad_split_strips(cin);
-    float *slabs = (float *)workspace;
-    int *list = (int *)((char *)workspace + (size_t)nstrips * 27 * cin * BN * sizeof(float));
-    int *count = list + (size_t)3 * n_frames * ntiles;
-    int *ones = count + 4;                          // "every tile is a step": any non-zero word is a set flag
-    hipError_t e = hipMemsetAsync(ones, 0x01, sizeof(int) * (size_t)n_frames * ntiles, st);
-    if (e != hipSuccess) return (int)e;
-    rc = mvxi_wgrad_step_list(ones, 1, 1, ntiles, 1, 1, list, count, st, n_frames);
-    if (rc) return rc;
-    Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames};
-    const size_t per_slab = (size_t)27 * cin * BN;
-    for (int nb = 0; nb < cout / BN; ++nb) {        // the kernel owns 64 channels of dz per launch
-        if (fmt_of(flags))
-            hipLaunchKernelGGL((conv3d_wgrad_split<2, 1>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in,
-                               dz + (size_t)nb * BN, slabs, g, 0, (const int *)list, (const int *)count, (const float *)nullptr, am);
-        else if (pieces_of(flags) == 3)
-            hipLaunchKernelGGL((conv3d_wgrad_split<3, 0>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in,
-                               dz + (size_t)nb * BN, slabs, g, 0, (const int *)list, (const int *)count, (const float *)nullptr, am);
-        else
-            hipLaunchKernelGGL((conv3d_wgrad_split<2, 0>), dim3(nstrips, 3 * (cin / BK)), dim3(WG_THREADS), 0, st, in,
-                               dz + (size_t)nb * BN, slabs, g, 0, (const int *)list, (const int *)count, (const float *)nullptr, am);
-        MVX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(wgrad_reduce_split, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, (const float *)slabs,
-                           dw3 + (size_t)nb * BN * cin * 27, nstrips, cin, 0);
-        MVX_LAUNCH_CHECK();
-    }
-    return MVX_OK;
 }

@@ -239,8 +239,8 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_split(const float *__restri
 // Weight gradient of a row layer in bf16x3: slab[strip][n][k] = sum over the rows of the strip of dz[r][n] * x[r][k].
 // The MFMA reduction index is the ROW, so both operands are needed row-major along k while memory is channel-major:
 // 32-row x 128-column tiles of dz and x are split (hi, lo) while they are staged as [column block of 32][row][32] bf16
-// (64-byte rows) and fetched with ds_read_b64_tr_b16, the LDS transpose read (the recipe of conv3d_wgrad_split,
-// csrc/conv3d_split.hip): a 16-lane group reads 4 rows x 16 columns and every lane receives 4 consecutive rows of its
+// (64-byte rows) and fetched with ds_read_b64_tr_b16, the LDS transpose read (the recipe of conv3d_wgrad4s,
+// csrc/conv3d.hip): a 16-lane group reads 4 rows x 16 columns and every lane receives 4 consecutive rows of its
 // column.  Workgroup block 128(n) x 128(k); wave (wn, wk) owns 64 x 64 = 2 x 2 accumulator tiles: per 16-row k-step 8
 // operand fragments (16 transpose reads) feed 12 MFMAs.  Same strips / slabs / slab_reduce as the f32 kernel (linear.hip).
 // ------------------------------------------------------------------------------------------
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_split(const float *__restric
     const int n0 = by * 128, k0 = bz * 128;
     const long long rbeg = (long long)strip * rows_per_strip;
     const long long rend = rbeg + rows_per_strip < R ? rbeg + rows_per_strip : R;
-    // transpose-read roles of this lane (conv3d_wgrad_split)
+    // transpose-read roles of this lane (as in conv3d_wgrad4s)
     const int grp = lane >> 4, i16 = lane & 15, q = i16 >> 2, pcol = (grp & 1) * 16 + 4 * (i16 & 3), kbase = (grp >> 1) * 8;
     f32x16 acc[2][2];
 #pragma unroll

@@ -21,7 +21,8 @@ FLAG_SPLIT_F16 = 512                                                     # MVX_F
 
 def split_flags(split, row=False):
     """``split``: 0 / False = exact-f32 MFMA, 2 / True = bf16x3, 3 = bf16x6 -> the flag bits of a call (row GEMMs also need
-    MVX_FLAG_SPLIT; the *_split convolution entry points only look at MVX_FLAG_SPLIT3)."""
+    MVX_FLAG_SPLIT, and so do the convolution weight gradients, which run behind the f32 entry points; the *_split
+    convolution entry points -- forward, input gradient, weight packing -- only look at MVX_FLAG_SPLIT3 / MVX_FLAG_SPLIT_F16)."""
     if not split:
         return 0
     return (FLAG_SPLIT if row else 0) | (FLAG_SPLIT3 if int(split) == 3 else 0) | (FLAG_SPLIT_F16 if int(split) == 4 else 0)
@@ -798,7 +799,8 @@ def conv3d_dgrad(dz, wpk_d, din, cin, sd, pd, split=False):
 
 def conv3d_wgrad(x, dz, sd, pd, split=False, accumulate_into=None, two_d=False):
     """accumulate_into: existing (cout,cin,3,3,3) gradient buffer to ADD to (returns None then).
-    two_d: the gradient of a 2-D kernel (cout,cin,3,3) (depth-1 tensors, pad_d = 1)."""
+    two_d: the gradient of a 2-D kernel (cout,cin,3,3) (depth-1 tensors, pad_d = 1).
+    split: the split arithmetic of conv3d_wgrad4s, which takes cin in multiples of 64."""
     din, H, W, cin = x.shape
     dout, _, _, cout = dz.shape
     if accumulate_into is not None:
@@ -809,17 +811,16 @@ def conv3d_wgrad(x, dz, sd, pd, split=False, accumulate_into=None, two_d=False):
     if two_d:
         assert not split and din == 1 and dout == 1 and pd == 1
         flags |= FLAG_CONV2D
-    # split arithmetic: conv3d_wgrad4s behind the same entry point (cin a multiple of 64), else the older 9-wave split kernel
-    new_split = bool(split) and cin % 64 == 0
-    flags |= split_flags(split, new_split)
+    if split and cin % 64:
+        raise ValueError('conv3d_wgrad: split arithmetic needs cin %% 64 == 0 (got cin = %d)' % cin)
+    flags |= split_flags(split, True)
     nbytes = X.lib.mvx_conv3d_wgrad_workspace_bytes(H, W, cin, cout)
-    fn, name = (X.lib.mvx_conv3d_wgrad_split, 'conv3d_wgrad_split') if (split and not new_split) else (X.lib.mvx_conv3d_wgrad, 'conv3d_wgrad')
     with _wgrad_scope(accumulate_into, x, dz) as scope:
         ws = workspace(nbytes, x.device, 'wgrad_side' if isinstance(scope, _SideStream) else 'wgrad')
-        with _Timed(name, conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):
+        with _Timed('conv3d_wgrad', conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):
             bind_amax(split, x, dz)
-            X.check(fn(X.ptr(x), X.ptr(dz), X.ptr(dw), din, dout, H, W, cin, cout, sd, pd, flags, X.ptr(ws), ws.numel(),
-                       X.stream()), 'mvx_' + name)
+            X.check(X.lib.mvx_conv3d_wgrad(X.ptr(x), X.ptr(dz), X.ptr(dw), din, dout, H, W, cin, cout, sd, pd, flags, X.ptr(ws),
+                                           ws.numel(), X.stream()), 'mvx_conv3d_wgrad')
     return None if accumulate_into is not None else dw
 
 

@@ -59,6 +59,88 @@ def test_no_cpu_fallback_and_loud_failure():
                               None, None, None, None, None, None, 0, None) == -1
 
 
+# (h, w, cin, cout, n_frames) -> bytes of mvx_conv3d_wgrad_workspace_bytes(h, w, cin, cout),
+# mvx_conv3d_wgrad_bg_workspace_bytes_frames(dout = 3, h, w, cin, cout, n_frames) and
+# mvx_conv2d_wgrad_workspace_bytes_frames(h, w, cin, cout, n_frames).  The values are those of the library BEFORE the
+# convolution files shared their host scaffold (csrc/conv_geom.h), recorded once by calling that build; ragged h x w (no
+# multiples of the 8 x 16 tile), every channel count of the network, and the shapes each query rejects (0).
+CONV_WORKSPACE_BYTES = {
+    (11, 37, 64, 64, 1): (2654208, 56623336, 56623216),
+    (11, 37, 64, 64, 4): (2654208, 56623984, 56623504),
+    (9, 17, 128, 64, 1): (3538944, 56623264, 113246288),
+    (50, 44, 128, 256, 4): (74317824, 0, 113247568),
+    (25, 22, 256, 256, 1): (56623104, 0, 113246352),
+    (19, 35, 256, 64, 4): (15925248, 56624416, 113246800),
+    (352, 400, 128, 64, 4): (75202560, 56781520, 113316624),
+    (352, 400, 64, 64, 1): (69894144, 56662720, 56640720),
+    (176, 200, 128, 256, 4): (254803968, 0, 113264528),
+    (9, 17, 32, 64, 1): (884736, 0, 0),
+    (9, 17, 33, 64, 1): (912384, 0, 0),
+    (9, 17, 64, 32, 1): (0, 0, 0),
+    (9, 17, 64, 128, 1): (3538944, 0, 113246288),
+    (0, 17, 64, 64, 1): (0, 0, 0),
+    (9, 17, 64, 64, 0): (1769472, 0, 0),
+}
+
+
+def test_conv_wgrad_workspace_sizes_are_those_of_the_separate_copies():
+    from modules import Extension as X
+    for (h, w, cin, cout, nf), want in CONV_WORKSPACE_BYTES.items():
+        got = (X.lib.mvx_conv3d_wgrad_workspace_bytes(h, w, cin, cout),
+               X.lib.mvx_conv3d_wgrad_bg_workspace_bytes_frames(3, h, w, cin, cout, nf),
+               X.lib.mvx_conv2d_wgrad_workspace_bytes_frames(h, w, cin, cout, nf))
+        assert got == want, ((h, w, cin, cout, nf), got, want)
+    assert X.lib.mvx_conv3d_wgrad_bg_workspace_bytes(3, 11, 37, 64, 64) == CONV_WORKSPACE_BYTES[(11, 37, 64, 64, 1)][1]
+    assert X.lib.mvx_conv3d_wgrad_bg_workspace_bytes_frames(0, 11, 37, 64, 64, 1) == 0
+
+
+def _header_parameters(name):
+    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    params = re.search(r'\b%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S).group(1)
+    return [re.search(r'(\w+)\s*$', q).group(1) for q in params.split(',')]
+
+
+# every convolution entry point that launches a gather or a weight gradient: f32 and split, 3-D and 2-D
+CONV_ENTRY_POINTS = (
+    'mvx_conv3d_forward', 'mvx_conv3d_forward_bg', 'mvx_conv3d_forward_bg_frames', 'mvx_conv3d_dgrad', 'mvx_conv3d_dgrad_tiles',
+    'mvx_conv3d_dgrad_tiles_frames', 'mvx_conv3d_wgrad', 'mvx_conv3d_wgrad_bg', 'mvx_conv3d_wgrad_bg_frames',
+    'mvx_conv2d_forward_frames', 'mvx_conv2d_dgrad_frames', 'mvx_conv2d_wgrad_frames',
+    'mvx_conv3d_forward_split', 'mvx_conv3d_forward_bg_split', 'mvx_conv3d_forward_bg_split_frames', 'mvx_conv3d_dgrad_split',
+    'mvx_conv3d_dgrad_tiles_split', 'mvx_conv3d_dgrad_tiles_split_frames', 'mvx_conv2d_forward_split_frames',
+    'mvx_conv2d_dgrad_split_frames')
+# one bad argument each -> the parameter it needs (a function without it is not called with that case), the code.  The
+# codes are those the library returned BEFORE the shared geometry check (recorded once from that build, for every pair of
+# entry point and case below): MVX_ESIZE (-2) for a channel granule, MVX_EINVAL (-1) for everything else.
+CONV_BAD_ARGUMENTS = (
+    ('cin', 33, -2), ('stride_d', 3, -1), ('pad_d', 2, -1), ('h', 0, -1), ('n_frames', 0, -1), ('n_frames', 17, -1),
+    ('dout', 5, -1))
+
+
+def test_conv_entry_points_reject_bad_geometry_before_any_launch():
+    """Dummy non-null pointers and ONE bad argument: the call must come back with the argument error -- a launch on these
+    pointers would fault, and without a GPU it would return a HIP error instead.  `dout = 5` is wrong for the forward
+    convolutions only (din = 4, stride 1, padding 1 -> 4); the gradients take any dout."""
+    from modules import Extension as X
+    dummy = (ctypes.c_double * 64)()
+    good = dict(din=4, dout=4, h=9, w=17, cin=64, cout=64, stride_d=1, pad_d=1, flags=0, n_frames=1, border_active=0,
+                count=1.0, eps=1e-5, workspace_bytes=1 << 40, stream=None)
+    calls = 0
+    for name in CONV_ENTRY_POINTS:
+        names = _header_parameters(name)
+        assert len(names) == len(X.PROTOTYPES[name][1])
+        for param, value, code in CONV_BAD_ARGUMENTS:
+            if param not in names or (param == 'dout' and 'forward' not in name):
+                continue
+            args = [value if n == param else good[n] if n in good else ctypes.addressof(dummy) for n in names]
+            assert getattr(X.lib, name)(*args) == code, (name, param, value)
+            calls += 1
+    assert calls == 96
+    # the frame-set form of the closed-form input-gradient term has no channel granule: frame count only
+    for nf in (0, 17):
+        assert X.lib.mvx_conv3d_input_grad_sums_frames(ctypes.addressof(dummy), ctypes.addressof(dummy), 4, 4, 64, 64, 1, 1,
+                                                       ctypes.addressof(dummy), nf, None) == -1
+
+
 def test_product_path_never_imports_the_oracle():
     pkg = os.path.join(REPO, 'mvxnet-makise_amd')
     for root, _, files in os.walk(pkg):

@@ -176,6 +176,16 @@ def test_conv3d_bf16x3_split_accuracy(cin, cout, din, H, W, sd, pd, split_units,
         assert rel_err(dw.cpu(), wg.grad) < tol
 
 
+def test_conv3d_wgrad_split_refuses_cin_off_the_64_channel_block():
+    """The split weight gradient is conv3d_wgrad4s (64 input channels per workgroup): another cin raises, there is no silent
+    exact-f32 run -- and no library call, the exception comes from the wrapper."""
+    from modules import _hip
+    x = torch.zeros((3, 9, 17, 32), device=DEV)
+    dz = torch.zeros((3, 9, 17, 64), device=DEV)
+    with pytest.raises(ValueError, match='cin % 64'):
+        _hip.conv3d_wgrad(x, dz, 1, 1, split=3)
+
+
 @pytest.mark.parametrize('split', [False, 2, 3, 4])
 def test_conv3d_full_size_adjoint_identities(split):
     """BASELINE-size grid (conv2 geometry, 5x352x400x64): the three passes must be mutually adjoint,

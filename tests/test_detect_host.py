@@ -12,7 +12,7 @@ import torch
 def test_detect_symbols_and_workspace_query():
     from modules import Extension as X
     from modules import detect  # noqa: F401  (importable without a GPU)
-    assert X.ABI_VERSION == 9 and X.lib.mvx_abi_version() == 9
+    assert X.ABI_VERSION == 10 and X.lib.mvx_abi_version() == 10
     lib = ctypes.CDLL(X.LIB_PATH)
     for name in ('mvx_detect_workspace_bytes', 'mvx_detect_frames'):
         assert hasattr(lib, name) and name in X.PROTOTYPES

@@ -227,7 +227,7 @@ def test_kitti_eval_symbols_and_workspace_query():
     for name in ('mvx_kitti_eval_workspace_bytes', 'mvx_kitti_eval_overlaps', 'mvx_kitti_eval_tp_scores',
                  'mvx_kitti_eval_thresholds', 'mvx_kitti_eval_counts'):
         assert hasattr(lib, name) and name in X.PROTOTYPES
-    assert X.ABI_VERSION == 9 and X.lib.mvx_abi_version() == 9
+    assert X.ABI_VERSION == 10 and X.lib.mvx_abi_version() == 10
     one = X.lib.mvx_kitti_eval_workspace_bytes(3769, 18)
     assert one >= 3769 * 18 * 41 * 20
     assert X.lib.mvx_kitti_eval_workspace_bytes(3769, 54) > 2 * one
