@@ -1141,6 +1141,34 @@ int mvx_gather_stride2_frames(const float *in, float *out, int32_t n_frames, int
 int mvx_topdown_merge_frames(const float *lateral, const float *top, float *out, int32_t n_frames, int32_t lat_h, int32_t lat_w,
                              int32_t top_h, int32_t top_w, int32_t channels, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fused AdamW over a flat gradient buffer (csrc/optim.hip): global gradient norm, clipping, a guard against non-finite
+ * gradients and the update, three launches, no host read, no float atomics (bitwise reproducible).
+ *   grad_flat f32 [n] (read only), m_flat / v_flat f32 [n]: first and second moment in the same layout; n < 2^31.
+ *   chunk_table i64 [n_chunks][3] on the device: {address of the chunk's first parameter element, its offset in the flat
+ *     layout, its element count}, 1 <= count <= MVX_OPTIM_CHUNK, a chunk inside ONE parameter; the chunks cover [0, n) once.
+ *     The table lives on the device, so only its size is checked here; an entry that leaves [0, n) or the count limit is
+ *     skipped by the kernel.  The parameter addresses are the caller's responsibility.
+ *   count_or_null: f32 device scalar, the number of samples summed into the gradient: the gradient is scaled by
+ *     1 / max(count, 1) on the fly (NULL: by 1).
+ *   state f64 [8], kept by the caller between steps, zeros at the start: [0] step t, [1] skipped steps, [2] the last norm,
+ *     [3] the last clip coefficient, [4] 1.0 when the last step was skipped.
+ * norm = sqrt(sum g^2, f64) * gscale; coef = min(1, max_norm / (norm + 1e-6)) for max_norm > 0, else 1
+ * (torch.nn.utils.clip_grad_norm_).  With guard != 0 a step whose gradient holds an inf or a NaN, or whose norm is not finite,
+ * changes no parameter and no moment, leaves t as it is and counts one skipped step.  Otherwise t += 1 and, per element in
+ * f32, torch's single-tensor AdamW:  g' = g * (gscale * coef);  p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);
+ * v = v * beta2 + (1 - beta2) * g' * g';  p -= lr / (1 - beta1^t) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)), the division
+ * by sqrt(1 - beta2^t) as a multiplication by its reciprocal; the scalar factors are computed in f64 and rounded to f32 once.
+ * workspace: mvx_optim_workspace_bytes bytes, 8-byte aligned.  Argument errors return MVX_EINVAL before any launch:
+ * 0 <= beta < 1, lr, eps, weight_decay, max_norm >= 0 and finite.
+ */
+#define MVX_OPTIM_CHUNK 4096
+size_t mvx_optim_workspace_bytes(int64_t n);
+int mvx_optim_adamw_step(const int64_t *chunk_table, int32_t n_chunks, const float *grad_flat, float *m_flat, float *v_flat,
+                         int64_t n, const float *count_or_null, double *state, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, double max_norm, int32_t guard, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

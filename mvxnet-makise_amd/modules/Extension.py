@@ -198,6 +198,8 @@ PROTOTYPES = {
     'mvx_add_relu_frames': (_i32, [_p, _p, _p, _i64, _p]),
     'mvx_gather_stride2_frames': (_i32, [_p, _p, _i32, _i32, _i32, _i32, _p]),
     'mvx_topdown_merge_frames': (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
+    'mvx_optim_workspace_bytes': (_sz, [_i64]),
+    'mvx_optim_adamw_step': (_i32, [_p, _i32, _p, _p, _p, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p, _sz, _p]),
 }
 
 

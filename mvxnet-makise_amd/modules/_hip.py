@@ -2319,3 +2319,25 @@ def conv2d_forward_plain(x, wpk, bias, F, h, w, cin, cout, flags, relu, split=Fa
             X.check(X.lib.mvx_conv2d_forward_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), None, h, w, cin, cout, fl, None, 0.0,
                                                     None, X.ptr(_work_counter(x.device)), F, X.stream()), 'mvx_conv2d_forward_frames')
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# Fused AdamW over the flat gradient bucket (csrc/optim.hip; modules/optim.py)
+# ---------------------------------------------------------------------------------------------
+OPTIM_CHUNK = 4096          # MVX_OPTIM_CHUNK
+
+
+def optim_adamw_step(table, grad_flat, m_flat, v_flat, count, state, lr, beta1, beta2, eps, weight_decay, max_norm, guard):
+    """One guarded, clipped AdamW step on the current stream: norm, prepare and update launches, no host read.  table i64
+    (n_chunks, 3) on the device, grad_flat / m_flat / v_flat f32 (n,), count f32 (1,) or None, state f64 (8,)."""
+    n = grad_flat.numel()
+    dev = grad_flat.device
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3
+    assert grad_flat.dtype == m_flat.dtype == v_flat.dtype == torch.float32 and m_flat.numel() == v_flat.numel() == n
+    assert state.dtype == torch.float64 and state.numel() == 8 and (count is None or count.dtype == torch.float32)
+    ws = workspace(X.lib.mvx_optim_workspace_bytes(n), dev, 'optim')
+    with _timed_bytes('optim_adamw', 7 * 4 * n):
+        X.check(X.lib.mvx_optim_adamw_step(X.ptr(table), table.shape[0], X.ptr(grad_flat), X.ptr(m_flat), X.ptr(v_flat), n,
+                                           X.ptr(count), X.ptr(state), float(lr), float(beta1), float(beta2), float(eps),
+                                           float(weight_decay), float(max_norm), 1 if guard else 0, X.ptr(ws), ws.numel(),
+                                           X.stream()), 'mvx_optim_adamw_step')

@@ -92,12 +92,20 @@ class GradBucket:
         s.record(stream)
         return s, e
 
-    def all_reduce_mean(self, frames_total=None, frames_local=None):
+    def count_slot(self):
+        """The count slot as a one-element f32 tensor: after ``all_reduce_mean(frames_local=, divide=False)`` it holds the
+        global number of frames, for a consumer that applies ``1 / max(count, 1)`` itself (modules/optim.py)."""
+        return self._count
+
+    def all_reduce_mean(self, frames_total=None, frames_local=None, divide=True):
         """Sum over ranks, then divide by the global number of frames: ``frames_total`` when the caller knows it (every rank
         ran the same number of frames), else ``frames_local`` = this rank's count, summed through the bucket's count slot and
-        applied on the device (at least 1)."""
+        applied on the device (at least 1).  ``divide=False`` (with ``frames_local``) stops after the collective: the buffer
+        keeps the SUM and the count slot the global count, and the optimizer folds the division into its update -- one
+        launch and one read-modify-write of the whole buffer less per step."""
         self.check_views()
         assert (frames_total is None) != (frames_local is None)
+        assert divide or frames_local is not None, 'divide=False leaves the divisor in the count slot: pass frames_local='
         n = self.flat.numel()
         if frames_local is not None:
             self._count.fill_(float(frames_local))
@@ -145,6 +153,8 @@ class GradBucket:
                     t[1].record(torch.cuda.current_stream(self.flat.device))
                     self.times.append(('all', ) + t)
                 self.calls.append('single')
+        if not divide:
+            return
         if frames_local is not None:
             self.flat.div_(self._count.clamp_min(1.0))
         else:

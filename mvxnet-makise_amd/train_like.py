@@ -3,6 +3,7 @@ loop, checkpoints and resume), running on this package's HIP modules.
 
     python train_like.py <dataroot> [-n EPOCHS] [-r LAST] [--steps K] [--mode module|fast] [--frames B] [--synthetic N]
                          [--augment [--gtdatabase DIR]] [--augment-geometry] [--extractor-weights FILE]
+                         [--optimizer torch|hip [--clip-grad-norm X] [--lr-schedule constant|cosine --warmup-steps N --lr-min LR]]
 
 What is the same as train.py: createDataset -> createAnchors / bbox3d2bev -> MVXNet, VoxelLoss, AdamW(lr 1e-3, eps) ->
 per frame lidar2Img + (row, col) swap + group + classifyAnchors -> forward -> clsLoss (+ regLoss) -> backward -> step ->
@@ -14,6 +15,11 @@ the y flip behind it or alone (modules/augment/Geometry.py).  The frozen image e
 modules/imhead/Extractor.py): every frame's image then goes through it, after the GT paste when ``--augment`` is on.  Without
 the flag the FPN maps are deterministic synthetic tensors per frame (or, in --mode module with torchvision installed, come
 from torchvision).
+
+``--optimizer hip`` replaces torch.optim.AdamW by the library's fused AdamW (modules/optim.py: one streaming pass over the flat
+gradient bucket, the division by the frame count folded in), with global gradient-norm clipping (``--clip-grad-norm``), a guard
+that skips a step with a non-finite gradient on the device, and a warm-up + cosine learning-rate schedule.  Checkpoints keep
+torch.optim.AdamW's format: a run can resume with either optimizer from a checkpoint of the other.
 
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
@@ -60,7 +66,24 @@ def parse_args(argv=None):
                          'with or without --augment')
     ap.add_argument('--extractor-weights', default=None,
                     help='state dict of the frozen ResNet50-FPN extractor (torchvision key names): images go through the HIP extractor')
+    ap.add_argument('--optimizer', choices=['torch', 'hip'], default='torch',
+                    help='hip: the fused AdamW of modules/optim.py (clipping, non-finite guard, schedule); same checkpoint format')
+    ap.add_argument('--clip-grad-norm', type=float, default=0.0, help='--optimizer hip: clip the global gradient norm to this (0 = off)')
+    ap.add_argument('--lr-schedule', choices=['constant', 'cosine'], default='constant', help='--optimizer hip: cosine = linear warm-up, then cosine')
+    ap.add_argument('--warmup-steps', type=int, default=0)
+    ap.add_argument('--lr-min', type=float, default=0.0)
     return ap.parse_args(argv)
+
+
+def check_optimizer_args(args):
+    """Flags that only the HIP optimizer implements must not be silently ignored with the torch one."""
+    if args.optimizer == 'torch':
+        if args.clip_grad_norm:
+            raise SystemExit('--clip-grad-norm needs --optimizer hip (the torch optimizer path does not clip)')
+        if args.lr_schedule != 'constant' or args.warmup_steps or args.lr_min:
+            raise SystemExit('--lr-schedule / --warmup-steps / --lr-min need --optimizer hip (the torch optimizer path trains at a constant 1e-3)')
+    if args.clip_grad_norm < 0 or args.warmup_steps < 0 or args.lr_min < 0:
+        raise SystemExit('--clip-grad-norm, --warmup-steps and --lr-min must not be negative')
 
 
 def fpn_maps_for(name, dev):
@@ -126,6 +149,7 @@ def fast_chunks(n_frames, frames_per_rank, world):
 
 
 def train(args):
+    check_optimizer_args(args)
     import modules.config as cfg
     from modules import parallel
     from modules.Calc import bbox3d2bev
@@ -173,14 +197,20 @@ def train(args):
     criterion = VoxelLoss()
     params = [p for p in model.parameters() if p.requires_grad]
     # train.py:64; on the GPU as one fused multi-tensor kernel per step (same update, ~10 launches fewer; bench.py has the numbers)
-    opt = torch.optim.AdamW(params, lr=0.001, eps=cfg.eps, fused=(device.type == 'cuda'))
+    hip_opt = args.optimizer == 'hip'
+    bucket = parallel.GradBucket(params, late=[model.head.fusion.fcn1.fc.weight]) if args.mode == 'fast' else None
+    if hip_opt:
+        from modules import optim
+        # --mode fast: on the step's own bucket; --mode module: on a bucket the optimizer makes (autograd then accumulates into it)
+        opt = optim.AdamW(params, lr=0.001, eps=cfg.eps, max_norm=args.clip_grad_norm, bucket=bucket)
+    else:
+        opt = torch.optim.AdamW(params, lr=0.001, eps=cfg.eps, fused=(device.type == 'cuda'))
     anchors = anchors.to(device)
     imsize = torch.Tensor(cfg.imsize).to(device)
     os.makedirs(args.checkpoints, exist_ok=True)
     if args.lastiter > 0:
         model.load_state_dict(torch.load(os.path.join(args.checkpoints, 'epoch%d.pkl' % args.lastiter), map_location=device))
         opt.load_state_dict(torch.load(os.path.join(args.checkpoints, 'epoch%d_opt.pkl' % args.lastiter), map_location=device))
-    bucket = parallel.GradBucket(params, late=[model.head.fusion.fcn1.fc.weight]) if args.mode == 'fast' else None
     tv = have_torchvision()
     fpn_fn = fpn_maps_for
     if args.extractor_weights:
@@ -194,6 +224,26 @@ def train(args):
 
     forwardTime = lossTime = backwardTime = 0.0
     steps_done, losses, loop_stats = 0, [], []
+    if args.mode == 'module':
+        steps_per_epoch = len(trainDataSet)
+    else:
+        steps_per_epoch = len(fast_chunks(len(trainDataSet), args.frames, world))
+    # position in the schedule: host calls of step(), skipped ones included; a resumed run continues where epoch `lastiter` ended
+    sched_k = args.lastiter * steps_per_epoch
+    sched_total = (args.lastiter + args.numepochs) * steps_per_epoch
+
+    def next_lr():
+        nonlocal sched_k
+        lr = optim.lr_at(sched_k, 0.001, args.lr_schedule, args.warmup_steps, sched_total, args.lr_min)
+        sched_k += 1
+        return lr
+
+    def report_optimizer(n):
+        if hip_opt:                               # one host read per epoch
+            d = opt.diagnostics()
+            say('Epoch%d optimizer: step %d, last gradient norm %.6g (clip coefficient %.4g), %d step(s) skipped for a non-finite gradient'
+                % (n, d['step'], d['norm'], d['coef'], d['skipped']))
+
     for epoch in range(args.numepochs):
         random.Random(epoch + args.lastiter).shuffle(trainDataSet)
         mine = trainDataSet
@@ -222,7 +272,10 @@ def train(args):
                 lossTime += time.perf_counter() - st
                 st = time.perf_counter()
                 loss.backward()
-                opt.step()
+                if hip_opt:
+                    opt.step(lr=next_lr())
+                else:
+                    opt.step()
                 backwardTime += time.perf_counter() - st
                 c = float(clsLoss.detach())
                 if c == c:
@@ -295,8 +348,13 @@ def train(args):
                 forwardTime += time.perf_counter() - st
                 # this rank's frame count rides in the bucket's count slot: the global divisor is applied on the device, with no
                 # second collective and no host read (a blocking count exchange undid read=False)
-                bucket.all_reduce_mean(frames_local=used)
-                opt.step()
+                if hip_opt:
+                    # the sum and the global count stay in the buffer: the update applies 1 / max(count, 1) as it reads the gradient
+                    bucket.all_reduce_mean(frames_local=used, divide=False)
+                    opt.step(lr=next_lr(), count=bucket.count_slot())
+                else:
+                    bucket.all_reduce_mean(frames_local=used)
+                    opt.step()
                 account(pending)
                 pending = out
                 frames_epoch += hi - lo
@@ -316,6 +374,7 @@ def train(args):
             say('Epoch%d: %d frames in %.2f s = %.1f frames/s (all ranks, %s)'
                 % (epoch + args.lastiter + 1, frames_epoch, loop_s, frames_epoch / max(loop_s, 1e-9),
                    'prefetch thread' if args.prefetch else 'batches prepared inside the step'))
+        report_optimizer(epoch + args.lastiter + 1)
         if rank == 0:
             n = epoch + args.lastiter + 1
             torch.save(model.state_dict(), os.path.join(args.checkpoints, 'epoch%d.pkl' % n))
