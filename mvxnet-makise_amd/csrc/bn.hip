@@ -98,11 +98,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce(const float *__restrict__ d
     const size_t blk_lo = blockIdx.x * rows_per_block;
     const size_t blk_hi = blk_lo + rows_per_block < rows ? blk_lo + rows_per_block : rows;
     if (blk_lo < blk_hi) {
-    const int s_lo = fm.F == 1 ? 0 : fm_seg_of(fm, (long long)blk_lo), s_hi = fm.F == 1 ? 0 : fm_seg_of(fm, (long long)blk_hi - 1);
+    const int s_lo = fm_seg_at(fm, (long long)blk_lo), s_hi = fm_seg_at(fm, (long long)blk_hi - 1);
     for (int sg = s_lo; sg <= s_hi; ++sg) {
-        const int f = fm.F == 1 ? 0 : (int)fm.seg_frame[sg];
-        const size_t lo = fm.F == 1 ? blk_lo : max(blk_lo, (size_t)fm.bound[sg]);
-        const size_t hi = fm.F == 1 ? blk_hi : min(blk_hi, (size_t)fm.bound[sg + 1]);
+        const int f = fm_seg_frame(fm, sg);
+        const size_t lo = max(blk_lo, (size_t)fm_seg_lo(fm, sg));
+        const size_t hi = min(blk_hi, fm_seg_hi(fm, sg, blk_hi));
         const float *fmi = mi + (size_t)f * 2 * C;
         double *fsums = sums + (size_t)f * REP * 3 * C;
         for (int cb = 0; cb < c4; cb += 256) {
@@ -217,15 +217,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float *__restrict__ dy
     const size_t blk_lo = gblock * rows_per_block;
     const size_t blk_hi = blk_lo + rows_per_block < rows ? blk_lo + rows_per_block : rows;
     const bool live = blk_lo < blk_hi;
-    const int s_lo = (fm.F == 1 || !live) ? 0 : fm_seg_of(fm, (long long)blk_lo);
-    const int s_hi = (fm.F == 1 || !live) ? 0 : fm_seg_of(fm, (long long)blk_hi - 1);
+    const int s_lo = live ? fm_seg_at(fm, (long long)blk_lo) : 0, s_hi = live ? fm_seg_at(fm, (long long)blk_hi - 1) : 0;
     for (int cb = 0; cb < c4; cb += 256) {
         const int col = cb + ct;
         float4 sb = make_float4(0, 0, 0, 0);
         for (int sg = s_lo; sg <= s_hi && live; ++sg) {
-            const int f = fm.F == 1 ? 0 : (int)fm.seg_frame[sg];
-            const size_t lo = fm.F == 1 ? blk_lo : max(blk_lo, (size_t)fm.bound[sg]);
-            const size_t hi = fm.F == 1 ? blk_hi : min(blk_hi, (size_t)fm.bound[sg + 1]);
+            const int f = fm_seg_frame(fm, sg);
+            const size_t lo = max(blk_lo, (size_t)fm_seg_lo(fm, sg));
+            const size_t hi = min(blk_hi, fm_seg_hi(fm, sg, blk_hi));
             const float *fmi = mi + (size_t)f * 2 * C;
             if (rt < rpi && col < c4) {
                 const float4 m = *(const float4 *)(fmi + col * 4), iv = *(const float4 *)(fmi + C + col * 4);

@@ -43,19 +43,6 @@ SplitAmax mvxi_take_split_amax();
 // arithmetic code of the split kernels from a flags word: 2 = bf16x3, 3 = bf16x6, 4 = fp16x3 (two fp16 pieces)
 static inline int mvx_split_code(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 4 : (flags & MVX_FLAG_SPLIT3) ? 3 : 2; }
 
-int mvxi_linear_forward_split(const float *x, int ldx, const float *w, int ldw, const float *bias, float *y,
-                              int ldy, double *stats, const float *row_w, long long rows, int k, int n, int relu,
-                              unsigned *fin_counter, double fin_eps, float *fin_mean_inv, const FrameMap &fm, int pieces,
-                              hipStream_t st, const SplitAmax &am = SplitAmax{nullptr, nullptr, 0});
-// K = 128 (rowgemm_k128.hip): weights resident in LDS, rows streamed through registers; same contract and numbers
-bool mvxi_rowgemm_k128_ok(int ldx, int ldw, int ldy, int k, int n);
-void mvxi_rowgemm_k128_enable(long long v);
-int mvxi_linear_forward_k128(const float *x, int ldx, const float *w, int ldw, const float *bias, float *y, int ldy, double *stats,
-                             const float *row_w, long long rows, int n, int relu, unsigned *fin_counter, double fin_eps,
-                             float *fin_mean_inv, const FrameMap &fm, int pieces, hipStream_t st, const SplitAmax &am);
-int mvxi_linear_wgrad_split(const float *x, int ldx, const float *dz, int lddz, float *slabs, long long rows, int k, int n,
-                            long long rows_per_strip, long long strips, int pieces, hipStream_t st,
-                            const SplitAmax &am = SplitAmax{nullptr, nullptr, 0});
 // geometry.hip: bcount[f][0..nblocks) -> its exclusive scan in place, totals[f] = the frame's sum; one workgroup per frame
 int mvxi_scan_block_counts(int *bcount, int nblocks, int n_frames, int *totals, hipStream_t st);
 
@@ -77,6 +64,23 @@ __device__ __forceinline__ int fm_seg_of(const FrameMap &m, long long r) {
     return s;
 }
 __device__ __forceinline__ int fm_frame_of(const FrameMap &m, long long r) { return m.F == 1 ? 0 : (int)m.seg_frame[fm_seg_of(m, r)]; }
+// What a kernel that reduces per frame asks of the map.  A single frame (F == 1, the common case outside frame sets) is
+// answered without touching the tables: segment 0 = frame 0 = all `rows` rows.
+// (the segments met by the rows [a, b], in segment order: fm_seg_at(m, a) .. fm_seg_at(m, b))
+__device__ __forceinline__ int fm_seg_at(const FrameMap &m, long long r) { return m.F == 1 ? 0 : fm_seg_of(m, r); }
+__device__ __forceinline__ int fm_seg_frame(const FrameMap &m, int sg) { return m.F == 1 ? 0 : (int)m.seg_frame[sg]; }
+__device__ __forceinline__ int fm_seg_lo(const FrameMap &m, int sg) { return m.F == 1 ? 0 : m.bound[sg]; }
+template <typename T>
+__device__ __forceinline__ T fm_seg_hi(const FrameMap &m, int sg, T rows) { return m.F == 1 ? rows : (T)m.bound[sg + 1]; }
+// BatchNorm sums of (frame f, replica rep) inside stats f64 [F][MVX_REP][2][C]: C sums, then C sums of squares
+__device__ __forceinline__ double *fm_stats_slot(double *stats, int f, unsigned rep, int C) {
+    return stats + (size_t)f * MVX_REP * 2 * C + (size_t)rep * 2 * C;
+}
+
+// Row (0..31) of a 32 x 32 MFMA accumulator tile that register r (0..15) of a lane in the LOWER lane half holds (its column is
+// lane & 31): four consecutive rows per register quad, the quads 8 rows apart.  The upper half (lh = lane >> 5) sits 4 rows
+// on: call sites write `mfma32_row(r) + 4 * lh`, the lane term last, so that r folds to a constant in front of it.
+__device__ __forceinline__ constexpr int mfma32_row(int r) { return (r & 3) + 8 * (r >> 2); }
 
 // Host side: segment table of a row layout.  kind: MVX_ROWS_* of the header; fr == NULL -> one frame of `rows` rows
 // with population `count`.  Returns false on an inconsistent description.

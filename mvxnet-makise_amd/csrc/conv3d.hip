@@ -29,9 +29,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // In-kernel time stamps of ONE unit of the gather kernel (tools/probes/gather_stamps.hip compiles this file with
 // -DMVX_GATHER_STAMPS; the library build has none of it): s_memtime read by thread 0 right after a barrier, where
 // lgkmcnt is zero anyway.
@@ -384,7 +381,7 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
         const float *bg_cls = bg_pre + (size_t)4 * g.Dout * g.F * g.Cout + (size_t)d * 9 * g.Cout;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int row = mfma32_row(r) + 4 * lh;
             const int gy = ty0 + 2 * wv + (row >> 4), gx = tx0 + (row & 15);
             const int q = 3 * (gy == 0 ? 0 : (gy >= g.H - 1 ? 2 : 1)) + (gx == 0 ? 0 : (gx >= g.W - 1 ? 2 : 1));
             acc0[r] = bg_cls[q * g.Cout + n0];
@@ -410,7 +407,7 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
         unsigned char mk[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int row = mfma32_row(r) + 4 * lh;
             const int gy = min(ty0 + 2 * wv + (row >> 4), g.H - 1), gx = min(tx0 + (row & 15), g.W - 1);
             mk[r] = out_mask[((size_t)d * g.H + gy) * g.W + gx];
         }
@@ -421,7 +418,7 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
     double s1a = 0.0, s2a = 0.0, s1b = 0.0, s2b = 0.0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int row = mfma32_row(r) + 4 * lh;
         const int gy = ty0 + 2 * wv + (row >> 4), gx = tx0 + (row & 15);
         float v0 = (acc0[r] + skip0) + bias0, v1 = (acc1[r] + skip1) + bias1;
         if (relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
@@ -629,7 +626,7 @@ __global__ __launch_bounds__(WG_THREADS) void conv3d_wgrad(const float *__restri
     float *o = slabs + ((((size_t)strip * 3 + kd) * 9 + tap) * g.Cin + cc * BK) * BN;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int row = mfma32_row(r) + 4 * lh;
         o[(size_t)row * BN + li] = acc0[r];
         o[(size_t)row * BN + 32 + li] = acc1[r];
     }
@@ -820,7 +817,7 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
         float *o = slabs + ((((size_t)strip * 3 + kd) * 9 + t9) * g.Cin + cc * W4_C + wm * 32) * BN + wn * 32;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int row = mfma32_row(r) + 4 * lh;
             o[(size_t)row * BN + li] = acc[i][r];
         }
     }
@@ -844,19 +841,6 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
 // step a wave reads NP fragments of dz once and NP fragments of x per tap: (taps + 1) NP fragments for taps x 3 (6) MFMAs.
 // LDS 79 KB (NP = 2) / 118 KB (NP = 3): one workgroup, two waves per SIMD, per CU.
 // ------------------------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ bf16x8 w4s_frag(const unsigned short *row0, const unsigned short *row1) {
-    typedef __attribute__((address_space(3))) s16x4 lds4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row1);
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-}
-
 // One staged tile (8 x 16 sites = eight 16-site k steps) of conv3d_wgrad4s for tap group GRP (compile time, like
 // wgrad4_mfma_step: the tap offsets are constants and the loop unrolls without branches).  All operand fragments of a k step
 // are fetched before its MFMAs, so the transpose reads of one tap are in flight under the MFMAs of the previous one.
@@ -871,13 +855,13 @@ __device__ __forceinline__ void wgrad4s_mfma_step(const unsigned short (*__restr
         const int zr0 = ks16 * TW + kq, zr1 = zr0 + 4;
         bf16x8 bz[NP], ax[NC][NP];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) bz[p] = w4s_frag(&s_z[p][wn][zr0][pcol], &s_z[p][wn][zr1][pcol]);
+        for (int p = 0; p < NP; ++p) bz[p] = tr_frag(&s_z[p][wn][zr0][pcol], &s_z[p][wn][zr1][pcol]);
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
             const int t9 = w4_own(T2, GRP, i);
             const int hr0 = (ks16 + t9 / 3) * HW + (t9 % 3) + kq, hr1 = hr0 + 4;
 #pragma unroll
-            for (int p = 0; p < NP; ++p) ax[i][p] = w4s_frag(&s_x[p][wm][hr0][pcol], &s_x[p][wm][hr1][pcol]);
+            for (int p = 0; p < NP; ++p) ax[i][p] = tr_frag(&s_x[p][wm][hr0][pcol], &s_x[p][wm][hr1][pcol]);
         }
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
@@ -1020,7 +1004,7 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4s(const float *__rest
         float *o = slabs + ((((size_t)strip * 3 + kd) * 9 + t9) * g.Cin + cc * W4_C + wm * 32) * BN + wn * 32;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int row = mfma32_row(r) + 4 * lh;
             o[(size_t)row * BN + li] = FMT == 1 ? acc[i][r] * o_scale : acc[i][r];
         }
     }

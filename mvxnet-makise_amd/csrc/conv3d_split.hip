@@ -20,6 +20,7 @@
 #include "common.h"
 #include "conv_geom.h"
 #include "split_common.h"
+#include "rowgemm_common.h"      // mvxi_rowgemm_k128_enable (mvx_tuning_set lives in this file)
 
 namespace {
 
@@ -215,7 +216,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
             if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) h_off[u] = (gy * g.W + gx) * g.Cin + part * 4;
         }
     }
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
     f32x4 hreg[NH];
     auto load_halo = [&](int st) __attribute__((always_inline)) {
         int kd, ds, cc;
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
             const float *bg_cls = bg_pre + (size_t)4 * g.Dout * g.F * g.Cout + (size_t)d * 9 * g.Cout;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int row = mfma32_row(r) + 4 * lh;
                 const int gy = py + (row >> 4), gx = tx0 + (row & 15);
                 const int q = 3 * (gy == 0 ? 0 : (gy >= g.H - 1 ? 2 : 1)) + (gx == 0 ? 0 : (gx >= g.W - 1 ? 2 : 1));
                 acc[m][0][r] = bg_cls[q * g.Cout + n0];
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
             unsigned char mk[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int row = mfma32_row(r) + 4 * lh;
                 const int gy = min(py + (row >> 4), g.H - 1), gx = min(tx0 + (row & 15), g.W - 1);
                 mk[r] = out_mask[((size_t)d * g.H + gy) * g.W + gx];
             }
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int row = mfma32_row(r) + 4 * lh;
             const int gy = py + (row >> 4), gx = tx0 + (row & 15);
             float v0 = (acc[m][0][r] + skip0) + bias0, v1 = (acc[m][1][r] + skip1) + bias1;
             if (relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }

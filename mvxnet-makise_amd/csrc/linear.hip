@@ -18,12 +18,10 @@
 // consecutive k per lane, same k permutation for both operands); the next chunk's global loads
 // are issued before the current chunk's MFMAs (register prefetch).  16-byte global loads when the
 // leading dimensions allow it, scalar otherwise (only the 23-column VFE input).
-#include "common.h"
+#include "rowgemm_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int BM = 128, BK = 32, PITCH = BK + 4;
 
 template <bool WT, int NT, bool VEC>
@@ -158,98 +156,8 @@ __global__ __launch_bounds__(256, 2) void linear_fwd(const float *__restrict__ x
         }
     }
 
-    // Epilogue.  Every load it needs (bias, row weights) is issued FIRST and unconditionally from clamped addresses, the
-    // accumulators become the outputs in place, and only then come the stores: vector-memory operations return in order
-    // (one vmcnt), so a load issued between stores -- or under a condition the waitcnt pass cannot see through -- made
-    // every store wait for all earlier ones (`s_waitcnt vmcnt(0)` in front of each of the 16 * NT stores).
-    float bsv[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = n0 + t * 32 + li;
-        bsv[t] = bias ? bias[c < N ? c : N - 1] : 0.f;
-    }
-    float rwv[16];
-    if (stats && row_w) {                      // one uniform branch around the whole batch of loads
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const long long gr = r0 + wv * 32 + row;
-            rwv[r] = row_w[gr < R ? gr : R - 1];
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rwv[r] = 1.f;
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = acc[t][r] + bsv[t];
-            if (relu) v = fmaxf(v, 0.f);
-            acc[t][r] = v;
-        }
-    // store, then the BatchNorm sums.  A 128-row block almost always lies inside one frame; a block that straddles a
-    // frame boundary repeats the (register-only) reduction once per frame with the other frames' rows masked out.
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = n0 + t * 32 + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const long long gr = r0 + wv * 32 + row;
-            if (gr < R && c < N) y[gr * ldy + c] = acc[t][r];
-        }
-    }
-    if (stats) {
-        const long long r_last = (r0 + BM - 1 < R ? r0 + BM - 1 : R - 1);
-        const int f_lo = fm_frame_of(fm, r0), f_hi = fm.F == 1 ? 0 : fm_frame_of(fm, r_last);
-        const int s_lo = fm.F == 1 ? 0 : fm_seg_of(fm, r0), s_hi = fm.F == 1 ? 0 : fm_seg_of(fm, r_last);
-        // frames met by this block, in segment order (a block can cross from the real rows into the padded rows, whose
-        // frame order starts again at 0): walk the segments, one reduction per segment
-        for (int sg = s_lo; sg <= s_hi; ++sg) {
-            const int f = fm.F == 1 ? 0 : (int)fm.seg_frame[sg];
-            const long long lo = fm.F == 1 ? 0 : fm.bound[sg], hi = fm.F == 1 ? R : fm.bound[sg + 1];
-            double s1[NT], s2[NT];          // f64 from the first addition on (var = E[y^2] - mean^2 cancels)
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int c = n0 + t * 32 + li;
-                s1[t] = 0.0; s2[t] = 0.0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const long long gr = r0 + wv * 32 + row;
-                    float v = acc[t][r];
-                    asm volatile("" : "+v"(v));     // opaque per segment: keeps the 64 f64 conversions and squares from being
-                                                    // hoisted out of the segment loop (they cost 256 VGPRs = the second wave)
-                    if (gr < R && c < N && gr >= lo && gr < hi) {
-                        const double rw = (double)rwv[r];
-                        s1[t] += rw * (double)v;
-                        s2[t] += rw * (double)v * (double)v;
-                    }
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const double a = s1[t] + __shfl_xor(s1[t], 32, 64), b = s2[t] + __shfl_xor(s2[t], 32, 64);
-                if (lh == 0) { s_red[wv][t * 32 + li] = a; s_red[wv][BNL + t * 32 + li] = b; }
-            }
-            __syncthreads();
-            double *fstats = stats + (size_t)f * MVX_REP * 2 * N;
-            for (int e = tid; e < 2 * BNL; e += 256) {
-                const int which = e / BNL, c = e % BNL;
-                if (n0 + c < N) {
-                    const double t = s_red[0][e] + s_red[1][e] + s_red[2][e] + s_red[3][e];
-                    atomicAdd(fstats + ((size_t)(blockIdx.y % MVX_REP) * 2 + which) * N + n0 + c, t);
-                }
-            }
-        }
-        (void)f_lo; (void)f_hi;
-        if (done_counter) {
-            __shared__ int s_last;
-            bn_finalize_by_last_block(done_counter, gridDim.x * gridDim.y, stats, N, fm, fin_eps, fin_mean_inv, &s_last);
-        }
-    }
+    rowgemm_tile_epilogue<NT>(acc, bias, y, ldy, stats, row_w, R, N, relu, r0, n0, blockIdx.y % MVX_REP, gridDim.x * gridDim.y,
+                              done_counter, fin_eps, fin_mean_inv, fm, s_red);
 }
 
 // dW partial: slab[strip][n][k] over the rows of the strip.  Workgroup block = 128(n) x 128(k),
@@ -321,19 +229,7 @@ __global__ __launch_bounds__(256) void linear_wgrad(const float *__restrict__ x,
             }
         }
     }
-    if (wave_on) {
-        float *o = slabs + (size_t)blockIdx.x * N * K;
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int n = n0 + wn * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const int k = k0 + wk * 64 + b * 32 + li;
-                    if (n < N && k < K) o[(size_t)n * K + k] = acc[a][b][r];
-                }
-    }
+    if (wave_on) store_slab_2x2(slabs + (size_t)blockIdx.x * N * K, acc, n0 + wn * 64, k0 + wk * 64, N, K, li, lh);
 }
 
 // out[e] = sum over slabs, in a FIXED order: lane l of a 16-lane group adds slabs l, l+16, ... sequentially, the 16
@@ -403,12 +299,8 @@ static int linear_forward_impl(const float *x, int32_t ldx, const float *w, int3
     MVX_CHECK_ARG(ldw >= (w_transposed ? n : k));
     hipStream_t st = (hipStream_t)stream;
     FrameMap fm;
-    MVX_CHECK_ARG(mvx_build_frame_map(fm, frames, row_kind, rows, fin_count));
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * n * fm.F, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (rows == 0) return MVX_OK;
+    const int rc = mvx_stats_preamble(fm, frames, row_kind, rows, fin_count, stats, n, flags, st);
+    if (rc || rows == 0) return rc;
     // 16-byte loads need: aligned bases, leading dimensions and (for chunk tails) K, N multiples of 4
     const bool vec = aligned16(x) && aligned16(w) && ldx % 4 == 0 && ldw % 4 == 0 && k % 4 == 0 &&
                      (!w_transposed || n % 4 == 0);
@@ -476,10 +368,8 @@ extern "C" int mvx_linear_forward_bn(const float *x, int32_t ldx, const float *w
                                      int64_t rows, int32_t k, int32_t n, int32_t flags, uint32_t *done_counter,
                                      double count, double eps, float *mean_inv, void *stream) {
     MVX_CHECK_ARG(stats && done_counter && mean_inv && count > 0 && rows > 0);
-    if (!(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(done_counter, 0, sizeof(uint32_t), (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
+    const int rc = mvx_clear_unless_prezeroed(done_counter, sizeof(uint32_t), flags, (hipStream_t)stream);
+    if (rc) return rc;
     return linear_forward_impl(x, ldx, w, ldw, w_transposed, bias, y, ldy, stats, row_w, rows, k, n, flags, nullptr, 0,
                                done_counter, count, eps, mean_inv, nullptr, MVX_ROWS_SINGLE, stream);
 }
@@ -490,10 +380,8 @@ extern "C" int mvx_linear_forward_bn_frames(const float *x, int32_t ldx, const f
                                             double eps, float *mean_inv, const mvx_frames_t *frames_host, int32_t row_kind,
                                             void *stream) {
     MVX_CHECK_ARG(stats && done_counter && mean_inv && rows > 0 && frames_host);
-    if (!(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(done_counter, 0, sizeof(uint32_t), (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-    }
+    const int rc = mvx_clear_unless_prezeroed(done_counter, sizeof(uint32_t), flags, (hipStream_t)stream);
+    if (rc) return rc;
     return linear_forward_impl(x, ldx, w, ldw, w_transposed, bias, y, ldy, stats, row_w, rows, k, n, flags, nullptr, 0,
                                done_counter, 1.0, eps, mean_inv, frames_host, row_kind, stream);
 }

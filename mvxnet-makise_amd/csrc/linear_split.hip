@@ -12,33 +12,14 @@
 // of 64: LDS rows are 272 bytes = 64 hi (128 B) | 64 lo (128 B) | 16 B pad (17 16-byte slots, odd: the ds_read_b128
 // fragment reads of 32 consecutive rows spread over all banks).  Per 16-k step a wave reads 2 A and 8 B fragments for
 // 12 MFMAs.  The next chunk's global loads are issued before the current chunk's MFMAs (register prefetch).
-#include "common.h"
-#include "split_common.h"
+#include "rowgemm_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int BM = 128, BNL = 128, NT = 4;
 
-// Workgroup -> tile mapping that follows the chip: workgroups are dealt round-robin over the 8 XCDs (blocks h and h + 8 share
-// one, MI355X_MICROARCH.md), and every XCD has its own L2.  With the plain (column block fastest) order the 6 column blocks
-// of a 768-wide layer that share a 128-row block of x land on 6 different XCDs and each L2 fetches those rows for itself:
-// 6 x 246 MB of HBM / Infinity-Cache reads for the 80 k x 768 x 768 layer, which made the GEMM memory-bound at 0.3-0.4 of the
-// matrix pipe.  Here the launch is one-dimensional: XCD x = h % 8 runs the row blocks {8 j + x} and walks a row block's column
-// blocks in consecutive slots, so the blocks that share rows run on the SAME L2 at the same time.  (Speed only: nothing
-// depends on the placement.)  Blocks beyond the last row block exit.
-struct XcdTile { unsigned rb, cb; bool on; };
-__device__ __forceinline__ XcdTile xcd_tile(unsigned h, unsigned nbx, unsigned nby) {
-    const unsigned xcd = h & 7u, s = h >> 3;
-    XcdTile t;
-    t.rb = (s / nbx) * 8u + xcd;
-    t.cb = s % nbx;
-    t.on = t.rb < nby;
-    return t;
-}
-static inline unsigned xcd_grid(unsigned nbx, unsigned nby) { return 8u * ((nby + 7u) / 8u) * nbx; }
-
 // NP pieces per operand; K in chunks of BK (64 for bf16x3, 32 for bf16x6: 61 KB of LDS either way, two workgroups per CU)
+// (workgroups in the XCD-aware order of xcd_tile, rowgemm_common.h: the column blocks of a row block share an L2)
 template <int NP, int BK, int FMT>
 __global__ __launch_bounds__(256, 2) void linear_fwd_split(const float *__restrict__ x, int ldx, const float *__restrict__ w,
                                                         int ldw, const float *__restrict__ bias, float *__restrict__ y,
@@ -151,88 +132,8 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_split(const float *__restri
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] *= o_scale;
     }
-    // ---- epilogue: the one of linear_fwd (loads first, then the stores, then the per-frame BatchNorm sums in f64)
-    float bsv[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = n0 + t * 32 + li;
-        bsv[t] = bias ? bias[c < N ? c : N - 1] : 0.f;
-    }
-    float rwv[16];
-    if (stats && row_w) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const long long gr = r0 + wv * 32 + row;
-            rwv[r] = row_w[gr < R ? gr : R - 1];
-        }
-    } else {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) rwv[r] = 1.f;
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float v = acc[t][r] + bsv[t];
-            if (relu) v = fmaxf(v, 0.f);
-            acc[t][r] = v;
-        }
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int c = n0 + t * 32 + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const long long gr = r0 + wv * 32 + row;
-            if (gr < R && c < N) y[gr * ldy + c] = acc[t][r];
-        }
-    }
-    if (stats) {
-        const long long r_last = (r0 + BM - 1 < R ? r0 + BM - 1 : R - 1);
-        const int s_lo = fm.F == 1 ? 0 : fm_seg_of(fm, r0), s_hi = fm.F == 1 ? 0 : fm_seg_of(fm, r_last);
-        for (int sg = s_lo; sg <= s_hi; ++sg) {
-            const int f = fm.F == 1 ? 0 : (int)fm.seg_frame[sg];
-            const long long lo = fm.F == 1 ? 0 : fm.bound[sg], hi = fm.F == 1 ? R : fm.bound[sg + 1];
-            double s1[NT], s2[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int c = n0 + t * 32 + li;
-                s1[t] = 0.0; s2[t] = 0.0;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const long long gr = r0 + wv * 32 + row;
-                    float v = acc[t][r];
-                    asm volatile("" : "+v"(v));
-                    if (gr < R && c < N && gr >= lo && gr < hi) {
-                        const double rw = (double)rwv[r];
-                        s1[t] += rw * (double)v;
-                        s2[t] += rw * (double)v * (double)v;
-                    }
-                }
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const double a = s1[t] + __shfl_xor(s1[t], 32, 64), b = s2[t] + __shfl_xor(s2[t], 32, 64);
-                if (lh == 0) { s_red[wv][t * 32 + li] = a; s_red[wv][BNL + t * 32 + li] = b; }
-            }
-            __syncthreads();
-            double *fstats = stats + (size_t)f * MVX_REP * 2 * N;
-            for (int e = tid; e < 2 * BNL; e += 256) {
-                const int which = e / BNL, c = e % BNL;
-                if (n0 + c < N) {
-                    const double t = s_red[0][e] + s_red[1][e] + s_red[2][e] + s_red[3][e];
-                    atomicAdd(fstats + ((size_t)(tile.rb % MVX_REP) * 2 + which) * N + n0 + c, t);
-                }
-            }
-        }
-        if (done_counter) {
-            __shared__ int s_last;
-            bn_finalize_by_last_block(done_counter, nbx * nby, stats, N, fm, fin_eps, fin_mean_inv, &s_last);
-        }
-    }
+    rowgemm_tile_epilogue<NT>(acc, bias, y, ldy, stats, row_w, R, N, relu, r0, n0, tile.rb % MVX_REP, nbx * nby, done_counter,
+                              fin_eps, fin_mean_inv, fm, s_red);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -244,19 +145,7 @@ __global__ __launch_bounds__(256, 2) void linear_fwd_split(const float *__restri
 // column.  Workgroup block 128(n) x 128(k); wave (wn, wk) owns 64 x 64 = 2 x 2 accumulator tiles: per 16-row k-step 8
 // operand fragments (16 transpose reads) feed 12 MFMAs.  Same strips / slabs / slab_reduce as the f32 kernel (linear.hip).
 // ------------------------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 constexpr int WRS = 32;                 // rows per LDS step (two MFMA k-steps; 64 rows: 232 VGPRs, one wave per SIMD, 0.517 -> 0.585 ms)
-
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned short *row0, const unsigned short *row1) {
-    typedef __attribute__((address_space(3))) s16x4 lds4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row0);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row1);
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 template <int NP, int FMT>
 __global__ __launch_bounds__(256) void linear_wgrad_split(const float *__restrict__ x, int ldx, const float *__restrict__ dz,
@@ -347,16 +236,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_split(const float *__restric
 #pragma unroll
                 for (int b = 0; b < 2; ++b) acc[a][b] *= o_scale;
         }
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int n = n0 + wn * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const int k = k0 + wk * 64 + b * 32 + li;
-                    if (n < N && k < K) o[(size_t)n * K + k] = acc[a][b][r];
-                }
+        store_slab_2x2(o, acc, n0 + wn * 64, k0 + wk * 64, N, K, li, lh);
     }
 }
 
@@ -367,15 +247,10 @@ int mvxi_linear_wgrad_split(const float *x, int ldx, const float *dz, int lddz, 
                             long long rows_per_strip, long long strips, int pieces, hipStream_t st, const SplitAmax &am) {
     const unsigned nblk = mvx_cdiv(n, 128) * mvx_cdiv(k, 128);
     const dim3 grid(xcd_grid(nblk, (unsigned)strips));
-    if (pieces == 4)
-        hipLaunchKernelGGL((linear_wgrad_split<2, 1>), grid, dim3(256), 0, st, x, ldx, dz, lddz, slabs, rows, k, n, rows_per_strip, am,
-                           nblk, (unsigned)strips);
-    else if (pieces == 3)
-        hipLaunchKernelGGL((linear_wgrad_split<3, 0>), grid, dim3(256), 0, st, x, ldx, dz, lddz, slabs, rows, k, n, rows_per_strip, am,
-                           nblk, (unsigned)strips);
-    else
-        hipLaunchKernelGGL((linear_wgrad_split<2, 0>), grid, dim3(256), 0, st, x, ldx, dz, lddz, slabs, rows, k, n, rows_per_strip, am,
-                           nblk, (unsigned)strips);
+    mvx_dispatch_pieces(pieces, [&](auto np, auto fmt) {
+        hipLaunchKernelGGL((linear_wgrad_split<decltype(np)::value, decltype(fmt)::value>), grid, dim3(256), 0, st, x, ldx, dz, lddz,
+                           slabs, rows, k, n, rows_per_strip, am, nblk, (unsigned)strips);
+    });
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -387,13 +262,12 @@ int mvxi_linear_forward_split(const float *x, int ldx, const float *w, int ldw, 
                               hipStream_t st, const SplitAmax &am) {
     const unsigned nbx = mvx_cdiv(n, BNL), nby = mvx_cdiv(rows, BM);
     const dim3 grid(xcd_grid(nbx, nby));
-#define MVX_GO(NP_, BK_, F_)                                                                                                     \
-    hipLaunchKernelGGL((linear_fwd_split<NP_, BK_, F_>), grid, dim3(256), 0, st, x, ldx, w, ldw, bias, y, ldy, stats, row_w, rows, k, \
-                       n, relu, fin_counter, fin_eps, fin_mean_inv, fm, am.a, am.coarse_a, nbx, nby)
-    if (pieces == 4) MVX_GO(2, 64, 1);
-    else if (pieces == 3) MVX_GO(3, 32, 0);
-    else MVX_GO(2, 64, 0);
-#undef MVX_GO
+    mvx_dispatch_pieces(pieces, [&](auto np, auto fmt) {       // three pieces: K in chunks of 32 (the same LDS bytes)
+        constexpr int NP = decltype(np)::value;
+        hipLaunchKernelGGL((linear_fwd_split<NP, NP == 3 ? 32 : 64, decltype(fmt)::value>), grid, dim3(256), 0, st, x, ldx, w, ldw,
+                           bias, y, ldy, stats, row_w, rows, k, n, relu, fin_counter, fin_eps, fin_mean_inv, fm, am.a, am.coarse_a,
+                           nbx, nby);
+    });
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }

@@ -15,12 +15,10 @@
 // the weight fragments from LDS.  Waves never wait for each other, so their loads, cuts and MFMAs interleave on a SIMD by
 // themselves.  The next block's operand is requested half a block ahead.  N > 128: column chunk c of the output belongs to the
 // workgroups {c, c + chunks, ...}; the rows are then read once per chunk (they are L2 / MALL resident: 128 floats per row).
-#include "common.h"
-#include "split_common.h"
+#include "rowgemm_common.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int K128 = 128, NCH = 128, WROW = K128 * 2 + 16;       // weight row in LDS: 128 pieces + 16 B pad (17 16-byte slots)
 
 template <int NP, int FMT>
@@ -105,8 +103,7 @@ __global__ __launch_bounds__(512) void rowgemm_k128(const float *__restrict__ x,
     const unsigned rep = (unsigned)((wg * 8 + wv) % MVX_REP);
     auto flush = [&]() __attribute__((always_inline)) {
         if (cur_seg < 0) return;
-        const int f = fm.F == 1 ? 0 : (int)fm.seg_frame[cur_seg];
-        double *fstats = stats + (size_t)f * MVX_REP * 2 * N + (size_t)rep * 2 * N;
+        double *fstats = fm_stats_slot(stats, fm_seg_frame(fm, cur_seg), rep, N);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const double u = s1[t] + __shfl_xor(s1[t], 32, 64), v = s2[t] + __shfl_xor(s2[t], 32, 64);
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(512) void rowgemm_k128(const float *__restrict__ x,
         float *yb = y + (r0 + 4 * lh) * ldy + n0 + li;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int rc = (r & 3) + 8 * (r >> 2);
+            const int rc = mfma32_row(r);
             if (live == 32 || rc + 4 * lh < live) {
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
@@ -163,16 +160,15 @@ __global__ __launch_bounds__(512) void rowgemm_k128(const float *__restrict__ x,
         }
         __builtin_amdgcn_sched_barrier(0);
         if (stats) {
-            const long long r_last = r0 + live - 1;
-            const int s_lo = fm.F == 1 ? 0 : fm_seg_of(fm, r0), s_hi = fm.F == 1 ? 0 : fm_seg_of(fm, r_last);
+            const int s_lo = fm_seg_at(fm, r0), s_hi = fm_seg_at(fm, r0 + live - 1);
             if (s_lo != cur_seg || s_hi != s_lo) flush();
             for (int sg = s_lo; sg <= s_hi; ++sg) {
-                const long long lo = fm.F == 1 ? 0 : fm.bound[sg], hi = fm.F == 1 ? R : fm.bound[sg + 1];
+                const long long lo = fm_seg_lo(fm, sg), hi = fm_seg_hi(fm, sg, R);
                 const int lo_rel = lo > r0 ? (int)(lo - r0) : 0, hi_rel = hi - r0 < live ? (int)(hi - r0) : live;   // wave-uniform
                 cur_seg = sg;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int rc = (r & 3) + 8 * (r >> 2), row = rc + 4 * lh;
+                    const int rc = mfma32_row(r), row = rc + 4 * lh;
                     // the weight of row rc / rc + 4 by lane half: two constant-lane reads instead of a shuffle (whose 16 lane
                     // addresses would live in registers across the whole loop)
                     const float w0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rwl), rc));
@@ -222,13 +218,10 @@ int mvxi_linear_forward_k128(const float *x, int ldx, const float *w, int ldw, c
     if (per_chunk * 8 > blocks) per_chunk = (blocks + 7) / 8;
     if (per_chunk < 1) per_chunk = 1;
     const dim3 grid((unsigned)(per_chunk * chunks));
-#define MVX_GO(NP_, F_)                                                                                                        \
-    hipLaunchKernelGGL((rowgemm_k128<NP_, F_>), grid, dim3(512), 0, st, x, ldx, w, ldw, bias, y, ldy, stats, row_w, rows, n, relu, \
-                       fin_counter, fin_eps, fin_mean_inv, fm, am.a, am.coarse_a, chunks)
-    if (pieces == 4) MVX_GO(2, 1);
-    else if (pieces == 3) MVX_GO(3, 0);
-    else MVX_GO(2, 0);
-#undef MVX_GO
+    mvx_dispatch_pieces(pieces, [&](auto np, auto fmt) {
+        hipLaunchKernelGGL((rowgemm_k128<decltype(np)::value, decltype(fmt)::value>), grid, dim3(512), 0, st, x, ldx, w, ldw, bias, y,
+                           ldy, stats, row_w, rows, n, relu, fin_counter, fin_eps, fin_mean_inv, fm, am.a, am.coarse_a, chunks);
+    });
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }

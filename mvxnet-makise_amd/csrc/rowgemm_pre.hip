@@ -29,15 +29,11 @@
 //
 // x = the sum of its pieces EXACTLY for NP = 3 bf16 pieces (bf16x6) and products accumulate k-step by k-step in ascending k
 // with the piece order of split_mac2: the forward is bit-identical to linear_fwd_split.
-#include "common.h"
-#include "split_common.h"
+#include "rowgemm_common.h"
 
 namespace {
 
 typedef __attribute__((address_space(3))) void lds_void;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 constexpr int PT = 256;                 // workgroup tile: PT x PT
 constexpr int PKS = 16;                 // k-step = stage depth
 constexpr int NSTG = 3;
@@ -59,16 +55,6 @@ __global__ __launch_bounds__(256) void split_rows_kernel(const float *__restrict
 #pragma unroll
         for (int q = 0; q < NP; ++q) *(uint2 *)(planes + q * plane_stride + r * ldp + part * 4) = pc[q];
     }
-}
-
-__device__ __forceinline__ bf16x8 pre_tr_frag(const unsigned char *p) {
-    typedef __attribute__((address_space(3))) s16x4 lds4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)p);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)(p + 256));      // four rows further
-    s16x8 v;
-    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
-    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
-    return __builtin_bit_cast(bf16x8, v);
 }
 
 // The shared main loop.  WG = 0: C[i][j] += sum_k A[i][k] B[j][k]  (forward / input gradient; planes [piece][row][k], a stage
@@ -167,12 +153,12 @@ __device__ __forceinline__ void pre_mainloop(unsigned char *smem, f32x16 (&acc)[
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 if constexpr (WG == 0) av[t][q] = __builtin_bit_cast(bf16x8, *(const uint4 *)(sb + fa + q * 8192 + t * 1024));
-                else av[t][q] = pre_tr_frag(sb + fa + q * 8192 + t * 1024);
+                else av[t][q] = tr_frag(sb + fa + q * 8192 + t * 1024, sb + fa + q * 8192 + t * 1024 + 256);    // + 256: four rows on
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 if constexpr (WG == 0) bv[t][q] = __builtin_bit_cast(bf16x8, *(const uint4 *)(sb + fb + q * 8192 + t * 1024));
-                else bv[t][q] = pre_tr_frag(sb + fb + q * 8192 + t * 1024);
+                else bv[t][q] = tr_frag(sb + fb + q * 8192 + t * 1024, sb + fb + q * 8192 + t * 1024 + 256);
             }
         }
         stamp();                                                       // 0: reads issued
@@ -203,20 +189,9 @@ __device__ __forceinline__ void pre_mainloop(unsigned char *smem, f32x16 (&acc)[
     if (g == 0) bar();                                                 // group 0 joins group 1's last barrier
 }
 
-// XCD-aware tile order: XCD x = h % 8 runs the row blocks {8 j + x} and a row block's column blocks in consecutive slots, so
-// the blocks that share rows share an L2 (speed only).
-struct PreTile { unsigned rb, cb; bool on; };
-__device__ __forceinline__ PreTile pre_tile(unsigned h, unsigned nbx, unsigned nby) {
-    const unsigned xcd = h & 7u, s = h >> 3;
-    PreTile t;
-    t.rb = (s / nbx) * 8u + xcd;
-    t.cb = s % nbx;
-    t.on = t.rb < nby;
-    return t;
-}
-
 // y[r][n] = [ReLU](out_scale * sum_k a[r][k] b[n][k] + bias[n]), per-frame BatchNorm sums in f64, optional finalisation by the
-// last workgroup -- the contract of linear_fwd_split (linear_split.hip) with both operands as planes.
+// last workgroup -- the contract of linear_fwd_split (linear_split.hip) with both operands as planes; workgroups in the
+// XCD-aware order of xcd_tile (rowgemm_common.h).
 template <int NP, int FMT, bool STAMP = false>
 __global__ __launch_bounds__(512, 2) void rowgemm_fwd_pre(const unsigned short *__restrict__ a, unsigned a_plane_bytes, int lda,
                                                           const unsigned short *__restrict__ b, unsigned b_plane_bytes, int ldb,
@@ -230,7 +205,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_fwd_pre(const unsigned short *
     // ALL the LDS of the kernel is this one array (a second __shared__ object beside a DMA staging array makes hipcc wait
     // vmcnt(0) in front of every k-step's first ds_read: cdna_hip_programming.md section 5)
     __shared__ __attribute__((aligned(1024))) unsigned char smem[NSTG * STAGE];
-    const PreTile tile = pre_tile(blockIdx.x, nbx, nby);
+    const XcdTile tile = xcd_tile(blockIdx.x, nbx, nby);
     if (!tile.on) return;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 31, lh = lane >> 5;
     const int tm = wv >> 2, tn = wv & 3;
@@ -321,12 +296,11 @@ __global__ __launch_bounds__(512, 2) void rowgemm_fwd_pre(const unsigned short *
         float *s_rw = (float *)(smem + 64 * TP * sizeof(float));  // [PT] row weights of the tile
         int *s_last = (int *)(s_rw + PT);
         const int r_last = min(ir0 + PT, iR) - 1;
-        const int s_lo = fm.F == 1 ? 0 : fm_seg_of(fm, ir0), s_hi = fm.F == 1 ? 0 : fm_seg_of(fm, r_last);
+        const int s_lo = fm_seg_at(fm, ir0), s_hi = fm_seg_at(fm, r_last);
         if (tid < PT) s_rw[tid] = row_w ? row_w[min(ir0 + tid, iR - 1)] : 1.f;
         const int sc = tid & (PT - 1), sh = tid >> 8;             // this thread's column of the tile and row half (the waves' tm)
         for (int sg = s_lo; sg <= s_hi; ++sg) {
-            const int f = fm.F == 1 ? 0 : (int)fm.seg_frame[sg];
-            const int lo = fm.F == 1 ? 0 : fm.bound[sg], hi = fm.F == 1 ? iR : fm.bound[sg + 1];
+            const int lo = fm_seg_lo(fm, sg), hi = fm_seg_hi(fm, sg, iR);
             double t1 = 0.0, t2 = 0.0;
 #pragma unroll 1
             for (int m = 0; m < 4; ++m) {
@@ -338,7 +312,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_fwd_pre(const unsigned short *
                         float v;
                         // (m is a loop variable: select the accumulator statically)
                         v = m == 0 ? acc[0][n][r] : (m == 1 ? acc[1][n][r] : (m == 2 ? acc[2][n][r] : acc[3][n][r]));
-                        s_t[(tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * TP + tn * 64 + n * 32 + li] = v;
+                        s_t[(tm * 32 + mfma32_row(r) + 4 * lh) * TP + tn * 64 + n * 32 + li] = v;
                     }
                 __syncthreads();
                 const int rb = sh * 128 + m * 32;                 // tile row of this thread's first value
@@ -353,7 +327,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_fwd_pre(const unsigned short *
                 }
             }
             if (n0 + sc < N) {
-                double *fstats = stats + (size_t)f * MVX_REP * 2 * N + (size_t)(tile.rb % MVX_REP) * 2 * N;
+                double *fstats = fm_stats_slot(stats, fm_seg_frame(fm, sg), tile.rb % MVX_REP, N);
                 atomicAdd(fstats + n0 + sc, t1);
                 atomicAdd(fstats + N + n0 + sc, t2);
             }
@@ -368,7 +342,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_fwd_pre(const unsigned short *
         float *yp = y + (size_t)rb * ldy + col0;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int ro = (r & 3) + 8 * (r >> 2);
+            const int ro = mfma32_row(r);
             if (full || (rb + ro < iR && col0 < N)) yp[(size_t)ro * ldy] = acc[m][0][r];
             if (full || (rb + ro < iR && col0 + 32 < N)) yp[(size_t)ro * ldy + 32] = acc[m][1][r];
         }
@@ -392,9 +366,9 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wgrad_pre(const unsigned short
     const unsigned nblk = nba * nbb;
     unsigned strip, blk;
     if (order == 1) {
-        const unsigned xcd = blockIdx.x & 7u, s = blockIdx.x >> 3;
-        strip = (s / nblk) * 8u + xcd;
-        blk = s % nblk;
+        const XcdTile t = xcd_tile(blockIdx.x, nblk, strips);
+        strip = t.rb;
+        blk = t.cb;
     } else {
         strip = blockIdx.x / nblk;
         blk = blockIdx.x % nblk;
@@ -447,7 +421,7 @@ __global__ __launch_bounds__(512, 2) void rowgemm_wgrad_pre(const unsigned short
         for (int n = 0; n < 2; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int ai = a0 + tm * 128 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int ai = a0 + tm * 128 + m * 32 + mfma32_row(r) + 4 * lh;
                 const int bi = b0 + tn * 64 + n * 32 + li;
                 if (ai < NA && bi < NB) o[(size_t)ai * NB + bi] = acc[m][n][r];
             }
@@ -470,29 +444,25 @@ __global__ __launch_bounds__(256) void pre_slab_reduce(const float *__restrict__
 // ---------------------------------------------------------------------------------------------------------------------
 // C ABI (include/mvx_hip.h)
 // ---------------------------------------------------------------------------------------------------------------------
-static inline int pre_pieces(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 2 : (flags & MVX_FLAG_SPLIT3) ? 3 : 0; }
-
 extern "C" size_t mvx_split_planes_bytes(int64_t rows, int32_t k, int32_t flags) {
-    const int np = pre_pieces(flags);
+    const int np = mvx_split_planes(flags);
     if (rows <= 0 || k <= 0 || np == 0) return 0;
     return (size_t)np * (size_t)rows * (size_t)k * sizeof(unsigned short);
 }
 
 extern "C" int mvx_split_rows(const float *x, int32_t ldx, int64_t rows, int32_t k, void *planes, int32_t flags, float scale,
                               void *stream) {
-    const int np = pre_pieces(flags);
+    const int np = mvx_split_planes(flags);
     MVX_CHECK_ARG(x && planes && rows >= 0 && k > 0 && k % 4 == 0 && ldx >= k && ldx % 4 == 0 && np != 0);
     MVX_CHECK_ARG((((uintptr_t)x) & 15) == 0 && (((uintptr_t)planes) & 15) == 0);
     if (rows == 0) return MVX_OK;
     hipStream_t st = (hipStream_t)stream;
     const long long total = rows * (k / 4);
     const unsigned grid = (unsigned)(total / 256 + 1 > 8192 ? 8192 : total / 256 + 1);
-    if (np == 3)
-        hipLaunchKernelGGL((split_rows_kernel<3, 0>), dim3(grid), dim3(256), 0, st, x, ldx, (long long)rows, k,
-                           (unsigned short *)planes, (long long)rows * k, k, 1.f);
-    else
-        hipLaunchKernelGGL((split_rows_kernel<2, 1>), dim3(grid), dim3(256), 0, st, x, ldx, (long long)rows, k,
-                           (unsigned short *)planes, (long long)rows * k, k, scale);
+    mvx_dispatch_pieces<false>(mvx_split_code(flags), [&](auto pieces, auto fmt) {
+        hipLaunchKernelGGL((split_rows_kernel<decltype(pieces)::value, decltype(fmt)::value>), dim3(grid), dim3(256), 0, st, x, ldx,
+                           (long long)rows, k, (unsigned short *)planes, (long long)rows * k, k, scale);
+    });
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -504,30 +474,24 @@ extern "C" int mvx_linear_forward_pre_frames(const void *a_planes, const void *b
                                              double *stats, const float *row_w, int64_t rows, int32_t k, int32_t n, int32_t flags,
                                              float out_scale, uint32_t *fin_counter, double fin_eps, float *fin_mean_inv,
                                              const mvx_frames_t *frames_host, int32_t row_kind, void *stream) {
-    const int np = pre_pieces(flags);
+    const int np = mvx_split_planes(flags);
     MVX_CHECK_ARG(a_planes && b_planes && y && rows >= 0 && k > 0 && n > 0 && ldy >= n && np != 0);
     MVX_CHECK_ARG(k % PKS == 0 && (((uintptr_t)a_planes) & 15) == 0 && (((uintptr_t)b_planes) & 15) == 0);
     MVX_CHECK_ARG((size_t)np * rows * k * 2 < (1ull << 32) && (size_t)np * n * k * 2 < (1ull << 32));
     hipStream_t st = (hipStream_t)stream;
     FrameMap fm;
-    MVX_CHECK_ARG(mvx_build_frame_map(fm, frames_host, row_kind, rows, (double)rows));
-    if (stats && !(flags & MVX_FLAG_PREZEROED)) {
-        hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * n * fm.F, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (rows == 0) return MVX_OK;
+    const int rc = mvx_stats_preamble(fm, frames_host, row_kind, rows, (double)rows, stats, n, flags, st);
+    if (rc || rows == 0) return rc;
     const unsigned nbx = mvx_cdiv(n, PT), nby = mvx_cdiv(rows, PT);
-    const dim3 grid(8u * ((nby + 7u) / 8u) * nbx);
+    const dim3 grid(xcd_grid(nbx, nby));
     const unsigned aps = (unsigned)((size_t)rows * k * 2), bps = (unsigned)((size_t)n * k * 2);
     const int relu = flags & MVX_FLAG_RELU;
-    if (np == 3)
-        hipLaunchKernelGGL((rowgemm_fwd_pre<3, 0>), grid, dim3(512), 0, st, (const unsigned short *)a_planes, aps, k,
-                           (const unsigned short *)b_planes, bps, k, bias, y, ldy, stats, row_w, (long long)rows, k, n, relu,
-                           fin_counter, fin_eps, fin_mean_inv, fm, out_scale, nbx, nby, (unsigned long long *)nullptr, 0u);
-    else
-        hipLaunchKernelGGL((rowgemm_fwd_pre<2, 1>), grid, dim3(512), 0, st, (const unsigned short *)a_planes, aps, k,
-                           (const unsigned short *)b_planes, bps, k, bias, y, ldy, stats, row_w, (long long)rows, k, n, relu,
-                           fin_counter, fin_eps, fin_mean_inv, fm, out_scale, nbx, nby, (unsigned long long *)nullptr, 0u);
+    mvx_dispatch_pieces<false>(mvx_split_code(flags), [&](auto pieces, auto fmt) {
+        hipLaunchKernelGGL((rowgemm_fwd_pre<decltype(pieces)::value, decltype(fmt)::value>), grid, dim3(512), 0, st,
+                           (const unsigned short *)a_planes, aps, k, (const unsigned short *)b_planes, bps, k, bias, y, ldy, stats,
+                           row_w, (long long)rows, k, n, relu, fin_counter, fin_eps, fin_mean_inv, fm, out_scale, nbx, nby,
+                           (unsigned long long *)nullptr, 0u);
+    });
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -553,7 +517,7 @@ extern "C" size_t mvx_linear_wgrad_pre_workspace_bytes(int64_t rows, int32_t k, 
 static int wgrad_pre_launch(const unsigned char *x_planes, const unsigned char *dz_planes, float *dw, int64_t plane_rows,
                             int64_t row_lo, int64_t rows, int32_t k, int32_t n, int32_t flags, float out_scale, void *workspace,
                             size_t workspace_bytes, void *stream) {
-    const int np = pre_pieces(flags);
+    const int np = mvx_split_planes(flags);
     MVX_CHECK_ARG(x_planes && dz_planes && dw && workspace && rows > 0 && k > 0 && n > 0 && np != 0);
     MVX_CHECK_ARG(row_lo >= 0 && row_lo + rows <= plane_rows);
     MVX_CHECK_ARG(k % 32 == 0 && n % 32 == 0 && (((uintptr_t)dw) & 15) == 0 && ((size_t)n * k) % 4 == 0);
@@ -568,13 +532,11 @@ static int wgrad_pre_launch(const unsigned char *x_planes, const unsigned char *
     const unsigned short *a = (const unsigned short *)(dz_planes + (size_t)row_lo * n * 2);
     const unsigned short *b = (const unsigned short *)(x_planes + (size_t)row_lo * k * 2);
     const int order = (flags & MVX_FLAG_PRE_XCD_STRIPS) ? 1 : 0;
-    const unsigned nwg = order ? 8u * (unsigned)((strips + 7) / 8) * nba * nbb : (unsigned)strips * nba * nbb;
-    if (np == 3)
-        hipLaunchKernelGGL((rowgemm_wgrad_pre<3, 0>), dim3(nwg), dim3(512), 0, st, a, aps, n, b, bps, k, (float *)workspace,
-                           (long long)rows, n, k, per, nba, nbb, (unsigned)strips, order);
-    else
-        hipLaunchKernelGGL((rowgemm_wgrad_pre<2, 1>), dim3(nwg), dim3(512), 0, st, a, aps, n, b, bps, k, (float *)workspace,
-                           (long long)rows, n, k, per, nba, nbb, (unsigned)strips, order);
+    const unsigned nwg = order ? xcd_grid(nba * nbb, (unsigned)strips) : (unsigned)strips * nba * nbb;
+    mvx_dispatch_pieces<false>(mvx_split_code(flags), [&](auto pieces, auto fmt) {
+        hipLaunchKernelGGL((rowgemm_wgrad_pre<decltype(pieces)::value, decltype(fmt)::value>), dim3(nwg), dim3(512), 0, st, a, aps, n, b,
+                           bps, k, (float *)workspace, (long long)rows, n, k, per, nba, nbb, (unsigned)strips, order);
+    });
     MVX_LAUNCH_CHECK();
     const size_t total = (size_t)n * k;
     hipLaunchKernelGGL(pre_slab_reduce, dim3((unsigned)(total / 1024 + 1 > 2048 ? 2048 : total / 1024 + 1)), dim3(256), 0, st,
@@ -605,7 +567,7 @@ extern "C" int mvx_debug_rowgemm_fwd_pre_stamps(const void *a_planes, const void
     FrameMap fm;
     if (!mvx_build_frame_map(fm, nullptr, MVX_ROWS_SINGLE, rows, (double)rows)) return MVX_EINVAL;
     const unsigned nbx = mvx_cdiv(n, PT), nby = mvx_cdiv(rows, PT);
-    const dim3 grid(8u * ((nby + 7u) / 8u) * nbx);
+    const dim3 grid(xcd_grid(nbx, nby));
     hipLaunchKernelGGL((rowgemm_fwd_pre<3, 0, true>), grid, dim3(512), 0, (hipStream_t)stream, (const unsigned short *)a_planes,
                        (unsigned)((size_t)rows * k * 2), k, (const unsigned short *)b_planes, (unsigned)((size_t)n * k * 2), k,
                        (const float *)nullptr, y, n, stats, (const float *)nullptr, (long long)rows, k, n, 1,

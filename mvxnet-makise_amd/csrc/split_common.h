@@ -1,4 +1,4 @@
-// Split arithmetic on the bf16 matrix cores, shared by conv3d_split.hip and linear_split.hip.
+// Split arithmetic on the bf16 matrix cores, shared by the convolutions (conv3d.hip, conv3d_split.hip) and the row GEMMs.
 //
 // An f32 operand is cut into NP bf16 pieces while it is staged (round to nearest even; every remainder is exact in f32):
 //   NP = 2 ("bf16x3"): x ~ hi + lo (16 mantissa bits); a product is hi*hi + hi*lo + lo*hi: three v_mfma_f32_32x32x16_bf16,
@@ -11,6 +11,9 @@
 #include <hip/hip_runtime.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));      // also the raw container of eight 16-bit pieces of either format
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
@@ -112,4 +115,17 @@ __device__ __forceinline__ void split_mac2(f32x16 &acc0, f32x16 &acc1, const bf1
         MVX_T(0, 2) MVX_T(2, 0) MVX_T(1, 1) MVX_T(0, 1) MVX_T(1, 0) MVX_T(0, 0)
     }
 #undef MVX_T
+}
+
+// One operand fragment from a tile staged with the reduction index along the ROWS (the weight gradients: [row][32 columns] of
+// 16-bit pieces): two ds_read_b64_tr_b16, the LDS transpose read.  A 16-lane group reads 4 rows x 16 columns and every lane
+// receives 4 consecutive rows of its column; row1 points four rows behind row0, together the 8 k values of a 32x32x16 MFMA.
+__device__ __forceinline__ bf16x8 tr_frag(const void *row0, const void *row1) {
+    typedef __attribute__((address_space(3))) s16x4 lds4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row0);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4 *)row1);
+    s16x8 v;
+    v[0] = lo[0]; v[1] = lo[1]; v[2] = lo[2]; v[3] = lo[3];
+    v[4] = hi[0]; v[5] = hi[1]; v[6] = hi[2]; v[7] = hi[3];
+    return __builtin_bit_cast(bf16x8, v);
 }

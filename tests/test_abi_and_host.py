@@ -141,6 +141,85 @@ def test_conv_entry_points_reject_bad_geometry_before_any_launch():
                                                        ctypes.addressof(dummy), nf, None) == -1
 
 
+# (rows, k, n) -> bytes of mvx_linear_splitk_workspace_bytes(rows, n), mvx_linear_wgrad_workspace_bytes(rows, k, n),
+# mvx_linear_wgrad_pre_workspace_bytes(rows, k, n) and mvx_split_planes_bytes(rows, k, flags) for the flags MVX_FLAG_SPLIT3,
+# MVX_FLAG_SPLIT_F16 and MVX_FLAG_SPLIT alone (no piece format: 0).  The values are those of the library BEFORE the row GEMMs
+# shared their host helpers (csrc/rowgemm_common.h), recorded once by calling that build.
+ROWGEMM_WORKSPACE_BYTES = {
+    (0, 23, 16): (0, 256, 0, 0, 0, 0),
+    (0, 128, 128): (0, 256, 0, 0, 0, 0),
+    (0, 768, 768): (0, 256, 0, 0, 0, 0),
+    (0, 768, 128): (0, 256, 0, 0, 0, 0),
+    (37, 23, 16): (37888, 1472, 4416, 5106, 3404, 0),
+    (37, 128, 128): (303104, 65536, 196608, 28416, 18944, 0),
+    (37, 768, 768): (1818624, 2359296, 7077888, 170496, 113664, 0),
+    (37, 768, 128): (303104, 393216, 1179648, 170496, 113664, 0),
+    (4099, 23, 16): (4197376, 48576, 189888, 565662, 377108, 0),
+    (4099, 128, 128): (33579008, 2162688, 8454144, 3148032, 2098688, 0),
+    (4099, 768, 768): (201474048, 77856768, 61341696, 18888192, 12592128, 0),
+    (4099, 768, 128): (33579008, 12976128, 25559040, 18888192, 12592128, 0),
+    (80000, 23, 16): (81920000, 736000, 368000, 11040000, 7360000, 0),
+    (80000, 128, 128): (655360000, 32768000, 16384000, 61440000, 40960000, 0),
+    (80000, 768, 768): (3932160000, 99090432, 66060288, 368640000, 245760000, 0),
+    (80000, 768, 128): (655360000, 36569088, 33423360, 368640000, 245760000, 0),
+}
+
+
+def test_rowgemm_workspace_sizes_are_those_of_the_separate_copies():
+    from modules import Extension as X
+    for (rows, k, n), want in ROWGEMM_WORKSPACE_BYTES.items():
+        got = (X.lib.mvx_linear_splitk_workspace_bytes(rows, n), X.lib.mvx_linear_wgrad_workspace_bytes(rows, k, n),
+               X.lib.mvx_linear_wgrad_pre_workspace_bytes(rows, k, n), X.lib.mvx_split_planes_bytes(rows, k, 128),
+               X.lib.mvx_split_planes_bytes(rows, k, 512), X.lib.mvx_split_planes_bytes(rows, k, 64))
+        assert got == want, ((rows, k, n), got, want)
+
+
+# every mvx_linear_* entry point and mvx_split_rows -> the pointers it cannot do without
+ROWGEMM_ENTRY_POINTS = {
+    'mvx_linear_forward': ('x', 'w', 'y'),
+    'mvx_linear_forward_bn': ('x', 'w', 'y', 'stats', 'done_counter', 'mean_inv'),
+    'mvx_linear_forward_bn_frames': ('x', 'w', 'y', 'stats', 'done_counter', 'mean_inv', 'frames_host'),
+    'mvx_linear_wgrad': ('x', 'dz', 'dw', 'workspace'),
+    'mvx_split_rows': ('x', 'planes'),
+    'mvx_linear_forward_pre_frames': ('a_planes', 'b_planes', 'y'),
+    'mvx_linear_wgrad_pre': ('x_planes', 'dz_planes', 'dw', 'workspace'),
+    'mvx_linear_wgrad_pre_rows': ('x_planes', 'dz_planes', 'dw', 'workspace'),
+}
+# one bad argument each (after a null for every pointer above): k = 0, a leading dimension below the row length, a k that is
+# no multiple of the DMA step (the entry points on pre-cut planes only: the others take it), an empty row range
+ROWGEMM_BAD_ARGUMENTS = (('k', 0), ('ldx', 8), ('ldy', 8), ('lddz', 8), ('k', 40), ('row_hi', 0))
+
+
+def test_rowgemm_entry_points_reject_a_bad_argument_before_any_launch():
+    """As for the convolutions: 64-byte-aligned dummy pointers, a valid one-frame descriptor, MVX_FLAG_PREZEROED (no memset
+    either) and ONE bad argument.  Every code is MVX_EINVAL (-1), which is what the library returned for each of these
+    pairs BEFORE the row GEMMs shared their argument checks and stats preamble (recorded once from that build).  Not covered:
+    whether a check comes before or after the clearing of the sums -- with MVX_FLAG_PREZEROED nothing is cleared, and without it
+    a rejected call and a failed memset on these host pointers could not be told apart by a code that differs per machine."""
+    from modules import Extension as X
+    buf = ctypes.create_string_buffer(4096 + 64)
+    dummy = (ctypes.addressof(buf) + 63) & ~63
+    fr = X.FramesDesc()
+    fr.n_frames, fr.t = 1, 1
+    fr.real_off[1] = fr.vox_off[1] = 256
+    good = dict(ldx=64, ldw=64, w_transposed=0, ldy=64, lddz=64, rows=256, k=64, n=64, flags=2 | 128, splitk_workspace_bytes=0,
+                count=1.0, eps=1e-5, scale=1.0, out_scale=1.0, workspace_bytes=1 << 40, plane_rows=256, row_lo=0, row_hi=256,
+                frames_host=ctypes.addressof(fr), row_kind=5, stream=None)
+    calls = 0
+    for name, pointers in ROWGEMM_ENTRY_POINTS.items():
+        names = _header_parameters(name)
+        assert len(names) == len(X.PROTOTYPES[name][1])
+        for param, value in tuple((p, None) for p in pointers) + ROWGEMM_BAD_ARGUMENTS:
+            if param not in names or ((param, value) == ('k', 40) and 'pre' not in name):
+                continue
+            args = [value if q == param else good[q] if q in good else dummy for q in names]
+            assert getattr(X.lib, name)(*args) == -1, (name, param, value)
+            calls += 1
+    assert calls == 55
+    assert sorted(n for n in X.PROTOTYPES if n.startswith('mvx_linear_') and X.PROTOTYPES[n][0] is ctypes.c_int32) == \
+        sorted(n for n in ROWGEMM_ENTRY_POINTS if n != 'mvx_split_rows')
+
+
 def test_product_path_never_imports_the_oracle():
     pkg = os.path.join(REPO, 'mvxnet-makise_amd')
     for root, _, files in os.walk(pkg):
