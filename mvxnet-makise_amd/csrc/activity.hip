@@ -609,6 +609,8 @@ extern "C" int mvx_tile_dilate_flags_frames(const int32_t *in_tile_flags, const 
                                             int32_t *out_tile_flags, int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(in_tile_flags && out_tile_flags && din > 0 && dout > 0 && h > 0 && w > 0);
     MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
+    MVX_CHECK_ARG(stride_d >= 1 && stride_d <= 2 && pad_d >= 0 && pad_d <= 1);
+    MVX_CHECK_ARG(dout == (din + 2 * pad_d - 3) / stride_d + 1);      // out / self are [n_frames * dout]: the planes split into frames by it
     const int ty = (int)mvx_cdiv(h, ATH), tx = (int)mvx_cdiv(w, ATW);
     hipLaunchKernelGGL(tile_dilate_flags, dim3(mvx_cdiv((long long)n_frames * dout * ty * tx, 256)), dim3(256), 0,
                        (hipStream_t)stream, in_tile_flags, self_tile_flags, din, dout, ty, tx, stride_d, pad_d, out_tile_flags,
@@ -696,6 +698,7 @@ extern "C" int mvx_tile_read_flags_frames(const int32_t *in_halo_flags, int32_t 
                                           int32_t stride_d, int32_t pad_d, int32_t *read_flags, int32_t n_frames, void *stream) {
     MVX_CHECK_ARG(in_halo_flags && read_flags && din > 0 && dout > 0 && h > 0 && w > 0);
     MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES && stride_d >= 1 && stride_d <= 2 && pad_d >= 0 && pad_d <= 1);
+    MVX_CHECK_ARG(dout == (din + 2 * pad_d - 3) / stride_d + 1);
     const int ty = (int)mvx_cdiv(h, ATH), tx = (int)mvx_cdiv(w, ATW);
     hipLaunchKernelGGL(tile_read_flags, dim3(mvx_cdiv((long long)n_frames * din * ty * tx, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const int *)in_halo_flags, din, dout, ty, tx, stride_d, pad_d, (int *)read_flags, n_frames);
