@@ -314,8 +314,10 @@ int mvx_conv3d_wgrad(const float *in, const float *dz, float *dw, int32_t din, i
  *                         mvx_conv3d_wgrad
  *   mvx_conv3d_input_grad_sums  plane_grad_sums f32 [din][cin] = per input plane, the sum over all its sites of the
  *                         input gradient (what mvx_conv3d_dgrad would write), from tap_sums in closed form
- *   mvx_conv3d_dgrad_tiles      mvx_conv3d_dgrad for the output tiles with dx_tile_flags i32 [din][tiles] set; the
- *                         other tiles of dx are left untouched
+ *   mvx_conv3d_dgrad_tiles      mvx_conv3d_dgrad for the output tiles with dx_tile_flags i32 [din][tiles] set.  An unflagged
+ *                         tile is left untouched, except that the 16 x 16-site units of the split forms (_split, which
+ *                         pair the tile rows 2k and 2k + 1) also write the unflagged vertical partner of a flagged tile:
+ *                         its content is then unspecified (it may be computed from parts of dz the caller left undefined)
  *   mvx_bn_relu_backward_tiles  mvx_bn_relu_backward of a layer whose output is the background (y_bg, c_bg per plane)
  *                         outside the flagged tiles and whose incoming gradient dyhat is only valid ON them:
  *                         the batch sums take the rest from plane_grad_sums; dz is written on the flagged tiles only;
