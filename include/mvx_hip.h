@@ -175,8 +175,11 @@ uint64_t mvx_launch_count(void);
  *   all frames are written BACK TO BACK in frame order -- voxels [cap_voxels][T][C], coords [cap_voxels][4] with
  *   coords[:,0] = frame index (the batch column of train.py:119), counts [cap_voxels]; cap_voxels is then the TOTAL
  *   capacity (n_frames * cap_points always suffices).  vox_off (optional) i32 [n_frames + 1] on the device = voxel
- *   offsets of the frames (vox_off[n_frames] = total).  n_frames <= 255.
- * Three launches (insert, one look-back scan over all frames, gather) and two memsets per call.
+ *   offsets of the frames (vox_off[n_frames] = total).
+ * Both entry points take 1 <= n_frames <= 63 (the gathers hold the n_frames + 1 voxel offsets one per lane of a wave);
+ * anything else is MVX_EINVAL.
+ * Four launches (insert, one look-back scan over all frames, gather of the voxels with at most 16 members, gather of the
+ * rest) and two memsets per call.
  */
 size_t mvx_voxelize_workspace_bytes(int32_t n_frames, int32_t cap_points);
 

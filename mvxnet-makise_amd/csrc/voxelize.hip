@@ -1,7 +1,7 @@
 // Point-cloud voxelizer for gfx950.
 //
 // Replaces the reference's sequential hash-map grouping (cpp/voxelutil.cpp:325-360 and the
-// Python loop of modules/data/Preprocessing.py:94-116) with THREE stream-ordered launches (+ two memsets) that
+// Python loop of modules/data/Preprocessing.py:94-116) with FOUR stream-ordered launches (+ two memsets) that
 // reproduce its ORDER semantics exactly:
 //   voxel order  = order of first appearance in the (shuffled) point stream,
 //   kept points  = the first T stream positions that fall in the voxel, in stream order,
@@ -14,9 +14,12 @@
 //   K2 scan   : "I am my voxel's first point" flags -> voxel ids in first-appearance order: ONE decoupled-look-back scan
 //               over the positions of ALL frames (work-item ticket per block, packed flag|value words, no fences), so a
 //               frame's voxels follow the previous frame's; per-frame voxel offsets fall out of it
-//   K3 gather : one wave per voxel: sorts the bucket (<= 64 members: wave-wide rank counting over the actual member
+//   K3 gather : four voxels per wave: a 16-lane group ranks the bucket of a voxel with at most 16 (and at most T) members,
+//               sums the centroid in stream order and writes the [T][C] block; the other voxels are listed for K4
+//   K4 wide   : one wave per listed voxel: sorts the bucket (<= 64 members: wave-wide rank counting over the actual member
 //               count) or, for the few voxels with more members, walks the frame's stream in order until T members are
 //               found; stages the point group in LDS, reduces the centroid, writes the [T][C] block with coalesced stores.
+// The gathers hold the F + 1 frame bases one per lane of a wave, so a call takes at most 63 frames.
 // Outputs either with a fixed stride per frame ([F][cap_voxels]...) or back to back over all frames (concat: the batch
 // layout of the frame-set path, coords[:,0] = frame index = the batch column of train.py:119).
 #include <atomic>
@@ -349,7 +352,7 @@ __global__ __launch_bounds__(256) void vox_gather(const float *__restrict__ pcd,
         }
         if (f == F && concat && w.frame_base[F] > cap_voxels) atomicOr(status, 2);
     }
-    // frame of the voxels: the F + 1 bases in ONE load (lane k holds base k; F < 64)
+    // frame of the voxels: the F + 1 bases in ONE load (lane k holds base k; F <= 63, checked by the entry point)
     const int fb = lane <= F ? w.frame_base[lane] : 0x7fffffff;
     const int Vtot = __shfl(fb, F, 64);
     // the launch cannot know the voxel count (it lives on the device): a fixed grid walks the voxels, so that the cost follows the
@@ -507,7 +510,7 @@ extern "C" int mvx_voxelize_frames(const float *pcd, const int32_t *perm, const 
                                    float *voxels, int64_t *coords, int32_t *counts, int32_t *n_voxels, int32_t *vox_off,
                                    int32_t *status, void *workspace, size_t workspace_bytes, void *stream) {
     MVX_CHECK_ARG(pcd && n_points && voxels && coords && counts && n_voxels && status && workspace);
-    MVX_CHECK_ARG(n_frames > 0 && n_frames <= 255 && cap_points > 0 && cap_voxels > 0 && ncol >= 4);
+    MVX_CHECK_ARG(n_frames > 0 && n_frames <= 63 && cap_points > 0 && cap_voxels > 0 && ncol >= 4);
     MVX_CHECK_ARG(T > 0 && T <= 64);
     MVX_CHECK_ARG(out_channels == 7 || out_channels == 9);
     MVX_CHECK_ARG(size_x > 0 && size_y > 0 && size_z > 0);

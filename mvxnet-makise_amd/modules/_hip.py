@@ -488,6 +488,7 @@ def voxelize(pcd, perm, n_points, lo, size, T, out_channels, cap_voxels=None, ex
     (= every frame full).  Returns capacity-sized outputs plus device-side counts."""
     assert pcd.dim() == 3 and pcd.dtype == torch.float32
     F, cap, ncol = pcd.shape
+    assert 1 <= F <= 63, 'the voxelizer takes 1..63 frames per call (include/mvx_hip.h)'
     dev = pcd.device
     if n_points is None:
         n_points = torch.full((F,), cap, dtype=torch.int32, device=dev)
@@ -516,6 +517,7 @@ def voxelize_concat(pcd, perm, n_points, lo, size, T, out_channels):
     index in column 0, counts, n_voxels i32 (F,), vox_off i32 (F+1,), status) -- capacity-sized, offsets on the device."""
     assert pcd.dim() == 3 and pcd.dtype == torch.float32
     F, cap, ncol = pcd.shape
+    assert 1 <= F <= 63, 'the voxelizer takes 1..63 frames per call (include/mvx_hip.h)'
     dev = pcd.device
     if n_points is None:
         n_points = torch.full((F,), cap, dtype=torch.int32, device=dev)
