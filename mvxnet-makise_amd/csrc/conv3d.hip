@@ -24,8 +24,7 @@
 //     and a 32(c) x 64(n) accumulator; the reduction runs over sites; per-strip partial slabs
 //     are summed by a second, deterministic kernel (no float atomics).
 #include "common.h"
-#include "conv_geom.h"
-#include "split_common.h"
+#include "conv_kernels.h"
 
 namespace {
 
@@ -124,7 +123,8 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
     // restricted launch: only the flagged output tiles are produced, the others are left untouched
     if (only_tiles && !only_tiles[(size_t)d * ntiles + tile]) return;
 
-    f32x16 acc0, acc1;
+    f32x16 acc[1][2];                            // one site tile per wave: channels n0 + lane and + 32
+    f32x16 &acc0 = acc[0][0], &acc1 = acc[0][1];
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
 
@@ -136,50 +136,16 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
 #pragma unroll
     for (int q = 0; q < BK / 8; ++q) b_off[q] = li * BK + 4 * (((2 * q) | lh) ^ wkey);
 
-    // valid depth taps of this output plane (block-uniform), packed as (kd, source plane) pairs.
-    // border_active bit 0: tiles on the image border always count as active (zero padding is not the background);
-    // bit 1: bg_pre is followed by per-depth-tap constants bg_tap[plane][kd][cout] -- in an INTERIOR tile a depth tap whose
-    // source halo holds no active site contributes exactly that constant (every source site is the plane's background
-    // value and the window stays inside the image), so it is not executed: `skipped` collects those taps for the epilogue.
+    // executed depth taps of this output plane, skipped ones and the tile's state (conv_kernels.h)
     const bool on_border = tx0 == 0 || ty0 == 0 || tx0 + TW >= g.W || ty0 + TH >= g.H;
-    const bool skip_taps = in_hflag && (border_active & 2) && !on_border;
-    int kd_l[3] = {0, 0, 0}, ds_l[3] = {0, 0, 0}, nk = 0;
-    unsigned skipped = 0;
-    int any_flag = 0;
-#pragma unroll
-    for (int kd = 0; kd < 3; ++kd) {
-        const int ds = src_depth(g, d, kd);
-        if (ds >= 0) {
-            const int fl = in_hflag ? in_hflag[(size_t)ds * ntiles + tile] : 1;
-            any_flag |= fl;
-            if (skip_taps && !fl) { skipped |= 1u << kd; continue; }
-            if (nk == 0) { kd_l[0] = kd; ds_l[0] = ds; }
-            else if (nk == 1) { kd_l[1] = kd; ds_l[1] = ds; }
-            else { kd_l[2] = kd; ds_l[2] = ds; }
-            ++nk;
-        }
-    }
-    // ... and a BORDER tile without any active source site is not convolved either: its sites are the plane's background
-    // inside and, on the outermost ring, the background minus the taps that fall into the zero padding -- nine
-    // per-(plane, channel) constants by position class (bg_cls, after bg_tap in the buffer).
-    const bool idle_border = in_hflag && (border_active & 2) && on_border && !any_flag;
-    if (idle_border) nk = 0;
-    const int nstages = nk * nchunks;
+    const TilePlan plan = tile_plan<1>(g, d, on_border, in_hflag, border_active, ntiles, tile, tile);
+    const bool active = plan.active;
+    const int nstages = plan.nk * nchunks;
 
-    // Background tiles (see activity.hip): no non-background source site in the halo of any depth tap and the
-    // window never leaves the image -> every output site of the tile is the per-plane constant.
-    bool active = true;
-    if (in_hflag) active = (((border_active & 1) && on_border) || any_flag) != 0;
     // executed work only, in 64-channel stages: the two narrow units of a channel pair run the same stages (activity
     // does not depend on nb), so the even one reports for both
     if (exec_stages && active && threadIdx.x == 0 && (NB2 == 2 || !(nb & 1))) atomicAdd(exec_stages, (unsigned long long)nstages);
     if (active && nstages > 0) {
-    auto stage_kd = [&](int st, int &kd, int &ds, int &cc) __attribute__((always_inline)) {
-        const int i = st / nchunks;
-        cc = st - i * nchunks;
-        kd = i == 0 ? kd_l[0] : (i == 1 ? kd_l[1] : kd_l[2]);
-        ds = i == 0 ? ds_l[0] : (i == 1 ? ds_l[1] : ds_l[2]);
-    };
 
     // per-thread halo slots: site r = c >> 3, 16-byte part c & 7, c = tid + 256 u
     int h_off[6];               // global float offset inside a (plane, chunk) image, or -1 (outside -> zeros)
@@ -200,7 +166,7 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
     f32x4 hreg[6], wreg[6];     // native vectors: HIP's float4 struct copies become memcpy and pin the arrays in scratch
     auto load_halo = [&](int st) __attribute__((always_inline)) {
         int kd, ds, cc;
-        stage_kd(st, kd, ds, cc);
+        plan_stage(plan, nchunks, st, kd, ds, cc);
         const float *img = in + (size_t)ds * g.H * g.W * g.Cin + cc * BK;
 #pragma unroll
         for (int u = 0; u < 6; ++u)
@@ -213,7 +179,7 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
     };
     auto load_wrow = [&](int st, int row) __attribute__((always_inline)) {
         int kd, ds, cc;
-        stage_kd(st, kd, ds, cc);
+        plan_stage(plan, nchunks, st, kd, ds, cc);
         const float *row0 = wpk + ((((size_t)kd * 9 + row * 3) * nchunks + cc) * g.Cout + (size_t)nb * BNW) * BK + (size_t)tid * 4;
         const size_t tap_stride = (size_t)nchunks * g.Cout * BK;
         if (NB2 == 2) {
@@ -328,7 +294,7 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
         int p;
         if (g.mode == 0) {
             int kd, ds, cc;
-            stage_kd(st, kd, ds, cc);
+            plan_stage(plan, nchunks, st, kd, ds, cc);
             p = (cc * BK) / g.s2d;
         } else {
             p = (nb * BNW) / g.s2d;
@@ -374,81 +340,9 @@ __device__ __forceinline__ void gather_unit(const int tile, const int d, const i
     }
     }   // active
 
-    // ---- epilogue: bias, ReLU, store, BatchNorm statistics (identical to conv3d_gather)
-    const int n0 = nb * BNW + li, n1 = NB2 == 2 ? n0 + 32 : n0;      // narrow unit: the second channel tile does not exist
-    const float bias0 = bias ? bias[n0] : 0.f, bias1 = bias ? bias[n1] : 0.f;
-    if (idle_border) {                         // the accumulators are still zero: they take the position-class constants
-        const float *bg_cls = bg_pre + (size_t)4 * g.Dout * g.F * g.Cout + (size_t)d * 9 * g.Cout;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma32_row(r) + 4 * lh;
-            const int gy = ty0 + 2 * wv + (row >> 4), gx = tx0 + (row & 15);
-            const int q = 3 * (gy == 0 ? 0 : (gy >= g.H - 1 ? 2 : 1)) + (gx == 0 ? 0 : (gx >= g.W - 1 ? 2 : 1));
-            acc0[r] = bg_cls[q * g.Cout + n0];
-            acc1[r] = bg_cls[q * g.Cout + n1];
-        }
-    }
-    float skip0 = 0.f, skip1 = 0.f;            // constants of the depth taps that were not executed (see the stage list)
-    if (skipped && active) {
-        const float *bg_tap = bg_pre + (size_t)g.Dout * g.F * g.Cout + (size_t)d * 3 * g.Cout;
-#pragma unroll
-        for (int kd = 0; kd < 3; ++kd)
-            if ((skipped >> kd) & 1u) { skip0 += bg_tap[kd * g.Cout + n0]; skip1 += bg_tap[kd * g.Cout + n1]; }
-    }
-    // background value of this plane: the same fp32 operations as a computed site, on the constant
-    float bgv0 = (bg_pre ? bg_pre[(size_t)d * g.Cout + n0] : 0.f) + bias0, bgv1 = (bg_pre ? bg_pre[(size_t)d * g.Cout + n1] : 0.f) + bias1;
-    if (relu) { bgv0 = fmaxf(bgv0, 0.f); bgv1 = fmaxf(bgv1, 0.f); }
-    // BatchNorm sums in f64 from the first addition on: var = E[y^2] - mean^2 cancels, and f32 partial sums cost
-    // mean^2 / var times their 1e-7 in the variance (the reference's torch-CPU BatchNorm accumulates in double too)
-    // the 16 site-mask bytes of this lane are fetched up front, unconditionally from clamped coordinates: a load between the
-    // stores (vector-memory operations return in order) made every store pair wait for the previous one to complete
-    unsigned site_on = active ? 0xffffu : 0u;          // bit r: site r is a computed (non-background) site
-    if (out_mask && active) {
-        unsigned char mk[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma32_row(r) + 4 * lh;
-            const int gy = min(ty0 + 2 * wv + (row >> 4), g.H - 1), gx = min(tx0 + (row & 15), g.W - 1);
-            mk[r] = out_mask[((size_t)d * g.H + gy) * g.W + gx];
-        }
-        site_on = 0u;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) site_on |= (mk[r] ? 1u : 0u) << r;
-    }
-    double s1a = 0.0, s2a = 0.0, s1b = 0.0, s2b = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = mfma32_row(r) + 4 * lh;
-        const int gy = ty0 + 2 * wv + (row >> 4), gx = tx0 + (row & 15);
-        float v0 = (acc0[r] + skip0) + bias0, v1 = (acc1[r] + skip1) + bias1;
-        if (relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-        // a background SITE holds the constant bit for bit, also inside a computed tile
-        if (out_mask && !((site_on >> r) & 1u)) { v0 = bgv0; v1 = bgv1; }
-        if (gy < g.H && gx < g.W) {
-            float *o = out + (((size_t)d * g.H + gy) * g.W + gx) * g.Cout;
-            o[n0] = v0;
-            if (NB2 == 2) o[n1] = v1;
-            s1a += (double)v0; s2a += (double)v0 * (double)v0;
-            s1b += (double)v1; s2b += (double)v1 * (double)v1;
-        }
-    }
-    if (stats) {
-        s1a += __shfl_xor(s1a, 32, 64); s2a += __shfl_xor(s2a, 32, 64);
-        s1b += __shfl_xor(s1b, 32, 64); s2b += __shfl_xor(s2b, 32, 64);
-        __syncthreads();
-        if (lh == 0) {
-            s_red[wv][li] = s1a; s_red[wv][32 + li] = s1b;
-            s_red[wv][BN + li] = s2a; s_red[wv][BN + 32 + li] = s2b;
-        }
-        __syncthreads();
-        if (tid < 2 * BNW) {
-            const int which = tid / BNW, c = tid % BNW, j = which * BN + c;
-            const double t = s_red[0][j] + s_red[1][j] + s_red[2][j] + s_red[3][j];
-            const unsigned rep = (unsigned)(tile + d * ntiles) % MVX_REP;
-            double *fstats = stats + (size_t)(d / g.Dout) * MVX_REP * 2 * g.Cout;       // the plane's frame
-            atomicAdd(fstats + ((size_t)rep * 2 + which) * g.Cout + nb * BNW + c, t);
-        }
-    }
+    // ---- epilogue (conv_kernels.h): f64 sums from the first addition on
+    gather_epilogue<1, NB2, double>(acc, plan, g, d, nb, tx0, ty0, (unsigned)(tile + d * ntiles), s_red, bias, out, stats, relu,
+                                    out_mask, bg_pre);
 #ifdef MVX_GATHER_STAMPS
     if (TLO == 0 && THI == 3 && threadIdx.x == 0 && tile == g_stamp_unit[0] && d == g_stamp_unit[1] && nb == g_stamp_unit[2]) {
         __builtin_amdgcn_s_waitcnt(0);                          // the unit's stores have been issued and its loads returned
@@ -641,19 +535,10 @@ __global__ __launch_bounds__(WG_THREADS) void conv3d_wgrad(const float *__restri
 // (all nine taps per wave, 144 accumulator + 80 prefetch VGPRs = 300, ONE wave per SIMD) ran at 0.46 of the matrix peak
 // in isolation.  Here: 80 accumulator + 40 prefetch VGPRs, one workgroup (2 waves per SIMD) per CU.
 // ------------------------------------------------------------------------------------------
-struct Strips { int n[3]; };       // workgroups (strips) per depth tap in list mode
-constexpr int W4_THREADS = 512;
-constexpr int W4_C = 64;               // input channels per workgroup
+// Strips, W4_THREADS, W4_C, w4_own / w4_ncomp and what this kernel shares with conv3d_wgrad4s -- the step walk W4Walk, the slot
+// mask and the slab store -- are in conv_kernels.h; LDS staging and the MFMA step are its own.
 
-// tap OWNED (written) by slot i of a tap group (-1: none); the first w4_ncomp() slots are computed, the rest stay zero
-__host__ __device__ constexpr int w4_own(bool t2, int grp, int i) {
-    return t2 ? (grp == 0 ? (i < 3 ? i : i + 2) : (i < 2 ? i + 3 : (i < 4 ? i + 5 : -1)))      // {0,1,2,5,6} / {3,4,7,8}
-              : (grp == 0 ? i : (i < 4 ? i + 5 : -1));                                         // {0,1,2,3,4} / {5,6,7,8}
-}
-__host__ __device__ constexpr int w4_ncomp(bool t2, int grp) { return t2 ? 2 : (grp == 0 ? 5 : 4); }
-
-// ``slots``: bit i = slot i of the group is executed (block-uniform; all ones except for the structurally zero (tap, parity)
-// blocks of a stride-2 kernel in space-to-depth form, Geom::s2d)
+// One staged tile of conv3d_wgrad4 for tap group GRP; ``slots``: w4_slots
 template <bool T2, int GRP>
 __device__ __forceinline__ void wgrad4_mfma_step(const float *__restrict__ s_x, const float *__restrict__ s_z, f32x16 (&acc)[5],
                                                  int wm, int wn, int li, int lh, unsigned slots) {
@@ -681,14 +566,8 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
                                                             const float *__restrict__ c_in, Strips ks) {
     __shared__ __attribute__((aligned(16))) float s_x[HH * HW * W4_C];
     __shared__ __attribute__((aligned(16))) float s_z[TH * TW * ZP];
-    const int tiles_x = (g.W + TW - 1) / TW, tiles_y = (g.H + TH - 1) / TH;
-    const int ntiles = tiles_x * tiles_y;
-    const int nchunks = g.Cin / W4_C;
-    const int kd = blockIdx.y / nchunks, cc = blockIdx.y % nchunks;
-    // strips of this depth tap: the list mode hands each tap a share of the workgroups proportional to its number of
-    // valid planes (conv3: 1 / 2 / 1); the dense mode uses the whole grid for every tap
-    const int strip = blockIdx.x, nstrips = step_list ? (kd == 0 ? ks.n[0] : (kd == 1 ? ks.n[1] : ks.n[2])) : (int)gridDim.x;
-    if (strip >= nstrips) return;
+    W4Walk wk;                                       // strips, steps and their operand loads (conv_kernels.h)
+    if (!wk.init(g, tiles_per_strip, step_list, step_count, ks)) return;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int grp = wv >> 2;                         // tap group
@@ -703,90 +582,28 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-    // Steps of this workgroup: (output plane d with a valid source plane for kd) x (tile).
-    // Dense: the strip's contiguous tile range for every valid plane.  With a background description the
-    // steps whose source halo holds a non-background site were compacted into step_list[kd][] (everywhere
-    // else x - c is exactly zero) and are dealt round-robin to the strips: balanced and deterministic.
-    int dlo = 0, dhi = -1;                           // valid output planes form a contiguous range
-    for (int d = 0; d < g.Dout; ++d) {
-        const int ds = d * g.sd - g.pd + kd;
-        if (ds >= 0 && ds < g.Din) { if (dhi < 0) dlo = d; dhi = d; }
-    }
-    const int nd = dhi >= dlo ? dhi - dlo + 1 : 0;
-    const int per = tiles_per_strip;
-    const int *my_list = step_list ? step_list + (size_t)kd * g.Dout * g.F * ntiles : nullptr;
-    const int nlist = step_list ? step_count[kd] : 0;
-    const int nsteps = step_list ? (nlist > strip ? (nlist - strip + nstrips - 1) / nstrips : 0) : nd * per;
-    // step i -> (plane, tile); dense steps past the last tile are dead (ragged last strip)
-    auto step_of = [&](int i, int &d, int &t) {
-        if (my_list) { const int e = my_list[strip + i * nstrips]; d = e / ntiles; t = e - d * ntiles; }
-        else { d = dlo + i / per; t = strip * per + i % per; }
-    };
-
-    constexpr int NX = (HH * HW * 16 + W4_THREADS - 1) / W4_THREADS;    // float4 per thread, halo (64 ch)
-    constexpr int NZ = TH * TW * 16 / W4_THREADS;                       // float4 per thread, dz
-    f32x4 xr[NX], zr[NZ];
-    auto load_step = [&](int i) __attribute__((always_inline)) {
-        int d, t;
-        step_of(i, d, t);
-        const int ds = mvx_src_plane(d, g.Din, g.Dout, g.sd, g.pd, kd);      // listed / dense steps always have a valid source
-        const int tx0 = (t % tiles_x) * TW, ty0 = (t / tiles_x) * TH;
-#pragma unroll
-        for (int u = 0; u < NX; ++u) {
-            const int c = tid + W4_THREADS * u;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (c < HH * HW * 16) {
-                const int r = c >> 4, part = c & 15;
-                const int gy = ty0 - 1 + r / HW, gx = tx0 - 1 + r % HW;
-                if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
-                    v = *(const f32x4 *)(in + (((size_t)ds * g.H + gy) * g.W + gx) * g.Cin + cc * W4_C + part * 4);
-                    if (c_in) v -= *(const f32x4 *)(c_in + (size_t)ds * g.Cin + cc * W4_C + part * 4);
-                }
-            }
-            xr[u] = v;
-        }
-#pragma unroll
-        for (int u = 0; u < NZ; ++u) {
-            const int c = tid + W4_THREADS * u;
-            const int r = c >> 4, part = c & 15;
-            const int gy = ty0 + (r >> 4), gx = tx0 + (r & 15);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (gy < g.H && gx < g.W)
-                v = *(const f32x4 *)(dz + (((size_t)d * g.H + gy) * g.W + gx) * g.Cout + part * 4);
-            zr[u] = v;
-        }
-    };
-    auto next_live = [&](int i) {
-        if (my_list) return i < nsteps ? i : nsteps;
-        while (i < nsteps && strip * per + i % per >= ntiles) ++i;      // ragged last strip
-        return i < nsteps ? i : nsteps;
-    };
-    // stride-2 kernel in space-to-depth form: the window taps that carry weight for this workgroup's parity block
-    // (group 0 owns window taps (0,0), (0,1) = slots 0, 1; group 1 owns (1,0), (1,1))
-    unsigned slots = 0x1fu;
-    if (T2 && g.s2d > 0) {
-        const unsigned m = s2d_tap_mask((cc * W4_C) / g.s2d);
-        slots = grp == 0 ? (m & 3u) : ((m >> 2) & 3u);
-    }
-    int cur = next_live(0);
+    f32x4 xr[W4_NX], zr[W4_NZ];
+    const unsigned slots = w4_slots<T2>(g, wk.cc, grp);
+    const int nsteps = wk.nsteps;
+    int cur = wk.next_live(0);
 #ifdef MVX_GATHER_STAMPS
-    const bool stamped = strip == g_stamp_unit[0] && (int)blockIdx.y == g_stamp_unit[1] && nb == g_stamp_unit[2];
+    const bool stamped = wk.strip == g_stamp_unit[0] && (int)blockIdx.y == g_stamp_unit[1] && nb == g_stamp_unit[2];
     int sidx = 0;
 #endif
     MVX_STAMP(0);
-    if (cur < nsteps) load_step(cur);
+    if (cur < nsteps) wk.load_step(cur, g, in, dz, c_in, xr, zr);
     while (cur < nsteps) {
         __syncthreads();
 #ifdef MVX_GATHER_STAMPS
         MVX_STAMP(1 + 3 * sidx);
 #endif
 #pragma unroll
-        for (int u = 0; u < NX; ++u) {
+        for (int u = 0; u < W4_NX; ++u) {
             const int c = tid + W4_THREADS * u;
             if (c < HH * HW * 16) *(f32x4 *)(s_x + (c >> 4) * W4_C + (c & 15) * 4) = xr[u];
         }
 #pragma unroll
-        for (int u = 0; u < NZ; ++u) {
+        for (int u = 0; u < W4_NZ; ++u) {
             const int c = tid + W4_THREADS * u;
             *(f32x4 *)(s_z + (c >> 4) * ZP + (c & 15) * 4) = zr[u];
         }
@@ -794,8 +611,8 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
 #ifdef MVX_GATHER_STAMPS
         MVX_STAMP(2 + 3 * sidx);
 #endif
-        const int nxt = next_live(cur + 1);
-        load_step(nxt < nsteps ? nxt : cur);          // unconditional (see conv3d_gather_pf): the last one is dropped
+        const int nxt = wk.next_live(cur + 1);
+        wk.load_step(nxt < nsteps ? nxt : cur, g, in, dz, c_in, xr, zr);      // unconditional (see gather_unit): the last one is dropped
         if (grp == 0) wgrad4_mfma_step<T2, 0>(s_x, s_z, acc, wm, wn, li, lh, slots);
         else wgrad4_mfma_step<T2, 1>(s_x, s_z, acc, wm, wn, li, lh, slots);
 #ifdef MVX_GATHER_STAMPS
@@ -809,18 +626,7 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
     MVX_STAMP(250);
     if (stamped && threadIdx.x == 0) g_stamps[251] = (unsigned long long)nsteps;
 #endif
-    // slab[strip][kd][tap][c (Cin)][n (64)]: every tap is written by the group that owns it (zeros where nothing was computed)
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int t9 = grp == 0 ? w4_own(T2, 0, i) : w4_own(T2, 1, i);
-        if (t9 < 0) continue;
-        float *o = slabs + ((((size_t)strip * 3 + kd) * 9 + t9) * g.Cin + cc * W4_C + wm * 32) * BN + wn * 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma32_row(r) + 4 * lh;
-            o[(size_t)row * BN + li] = acc[i][r];
-        }
-    }
+    w4_store_slabs<T2>(acc, slabs, wk, g, 1.f);
 #ifdef MVX_GATHER_STAMPS
     if (stamped && threadIdx.x == 0) {
         __builtin_amdgcn_s_waitcnt(0);
@@ -831,7 +637,7 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4(const float *__restr
 
 // ------------------------------------------------------------------------------------------
 // conv3d_wgrad4s<T2, NP>: conv3d_wgrad4 in split arithmetic on the bf16 matrix cores (split_common.h: NP = 2 "bf16x3",
-// NP = 3 "bf16x6" = fp32-grade).  Same workgroup decomposition, step lists, strips and slab layout as conv3d_wgrad4 --
+// NP = 3 "bf16x6" = fp32-grade).  Same workgroup decomposition, step lists, strips and slab layout as conv3d_wgrad4 (W4Walk) --
 // eight waves, wave (grp, wm, wn) owns the 32(c) x 32(n) block (wm, wn) of the taps of its group, waves w and w + 4 share
 // a SIMD so that every SIMD carries nine taps per k step -- so the host code and wgrad_reduce are shared.  The MFMA
 // reduction index is the SITE while memory is channel-major: the 10 x 18-site halo of x and the 8 x 16-site tile of dz are
@@ -882,14 +688,9 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4s(const float *__rest
     if constexpr (FMT == 1) { x_scale = split_scale_coarse(am.a); z_scale = split_scale_of(am.b); }     // x: activations, dz: gradients
     __shared__ __attribute__((aligned(16))) unsigned short s_x[NP][2][HH * HW][32];      // [piece][32-channel block][halo site][channel]
     __shared__ __attribute__((aligned(16))) unsigned short s_z[NP][2][TH * TW][32];      // [piece][32-channel block][site][channel]
-    const int tiles_x = (g.W + TW - 1) / TW, tiles_y = (g.H + TH - 1) / TH;
-    const int ntiles = tiles_x * tiles_y;
-    const int nchunks = g.Cin / W4_C;
-    const int kd = blockIdx.y / nchunks, cc = blockIdx.y % nchunks;
-    const int strip = blockIdx.x, nstrips = step_list ? (kd == 0 ? ks.n[0] : (kd == 1 ? ks.n[1] : ks.n[2])) : (int)gridDim.x;
-    if (strip >= nstrips) return;
+    W4Walk wk;                                       // strips, steps and their operand loads (conv_kernels.h)
+    if (!wk.init(g, tiles_per_strip, step_list, step_count, ks)) return;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
     const int grp = wv >> 2;                         // tap group
     const int wm = (wv >> 1) & 1, wn = wv & 1;
     const int nb = blockIdx.z;                       // 64-channel block of dz / dW (Cout = 64 * gridDim.z)
@@ -904,69 +705,15 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4s(const float *__rest
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
-    int dlo = 0, dhi = -1;                           // valid output planes form a contiguous range
-    for (int d = 0; d < g.Dout; ++d) {
-        const int ds = d * g.sd - g.pd + kd;
-        if (ds >= 0 && ds < g.Din) { if (dhi < 0) dlo = d; dhi = d; }
-    }
-    const int nd = dhi >= dlo ? dhi - dlo + 1 : 0;
-    const int per = tiles_per_strip;
-    const int *my_list = step_list ? step_list + (size_t)kd * g.Dout * g.F * ntiles : nullptr;
-    const int nlist = step_list ? step_count[kd] : 0;
-    const int nsteps = step_list ? (nlist > strip ? (nlist - strip + nstrips - 1) / nstrips : 0) : nd * per;
-    auto step_of = [&](int i, int &d, int &t) {
-        if (my_list) { const int e = my_list[strip + i * nstrips]; d = e / ntiles; t = e - d * ntiles; }
-        else { d = dlo + i / per; t = strip * per + i % per; }
-    };
-    constexpr int NX = (HH * HW * 16 + W4_THREADS - 1) / W4_THREADS;    // float4 per thread, halo (64 ch)
-    constexpr int NZ = TH * TW * 16 / W4_THREADS;                       // float4 per thread, dz
-    f32x4 xr[NX], zr[NZ];
-    auto load_step = [&](int i) __attribute__((always_inline)) {
-        int d, t;
-        step_of(i, d, t);
-        const int ds = mvx_src_plane(d, g.Din, g.Dout, g.sd, g.pd, kd);      // listed / dense steps always have a valid source
-        const int tx0 = (t % tiles_x) * TW, ty0 = (t / tiles_x) * TH;
-#pragma unroll
-        for (int u = 0; u < NX; ++u) {
-            const int c = tid + W4_THREADS * u;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (c < HH * HW * 16) {
-                const int r = c >> 4, part = c & 15;
-                const int gy = ty0 - 1 + r / HW, gx = tx0 - 1 + r % HW;
-                if (gy >= 0 && gy < g.H && gx >= 0 && gx < g.W) {
-                    v = *(const f32x4 *)(in + (((size_t)ds * g.H + gy) * g.W + gx) * g.Cin + cc * W4_C + part * 4);
-                    if (c_in) v -= *(const f32x4 *)(c_in + (size_t)ds * g.Cin + cc * W4_C + part * 4);
-                }
-            }
-            xr[u] = v;
-        }
-#pragma unroll
-        for (int u = 0; u < NZ; ++u) {
-            const int c = tid + W4_THREADS * u;
-            const int r = c >> 4, part = c & 15;
-            const int gy = ty0 + (r >> 4), gx = tx0 + (r & 15);
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (gy < g.H && gx < g.W)
-                v = *(const f32x4 *)(dz + (((size_t)d * g.H + gy) * g.W + gx) * g.Cout + part * 4);
-            zr[u] = v;
-        }
-    };
-    auto next_live = [&](int i) {
-        if (my_list) return i < nsteps ? i : nsteps;
-        while (i < nsteps && strip * per + i % per >= ntiles) ++i;      // ragged last strip
-        return i < nsteps ? i : nsteps;
-    };
-    unsigned slots = 0x1fu;                          // see conv3d_wgrad4: the window taps that carry weight for this parity block
-    if (T2 && g.s2d > 0) {
-        const unsigned m = s2d_tap_mask((cc * W4_C) / g.s2d);
-        slots = grp == 0 ? (m & 3u) : ((m >> 2) & 3u);
-    }
-    int cur = next_live(0);
-    if (cur < nsteps) load_step(cur);
+    f32x4 xr[W4_NX], zr[W4_NZ];
+    const unsigned slots = w4_slots<T2>(g, wk.cc, grp);
+    const int nsteps = wk.nsteps;
+    int cur = wk.next_live(0);
+    if (cur < nsteps) wk.load_step(cur, g, in, dz, c_in, xr, zr);
     while (cur < nsteps) {
         __syncthreads();
 #pragma unroll
-        for (int u = 0; u < NX; ++u) {
+        for (int u = 0; u < W4_NX; ++u) {
             const int c = tid + W4_THREADS * u;
             if (c < HH * HW * 16) {
                 const int r = c >> 4, part = c & 15;
@@ -978,7 +725,7 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4s(const float *__rest
             }
         }
 #pragma unroll
-        for (int u = 0; u < NZ; ++u) {
+        for (int u = 0; u < W4_NZ; ++u) {
             const int c = tid + W4_THREADS * u;
             const int r = c >> 4, part = c & 15;
             uint2 pc[NP];
@@ -988,26 +735,15 @@ __global__ __launch_bounds__(W4_THREADS) void conv3d_wgrad4s(const float *__rest
             for (int p = 0; p < NP; ++p) *(uint2 *)(&s_z[p][part >> 3][r][(part & 7) * 4]) = pc[p];
         }
         __syncthreads();
-        const int nxt = next_live(cur + 1);
-        load_step(nxt < nsteps ? nxt : cur);          // unconditional (see conv3d_gather_pf): the last one is dropped
+        const int nxt = wk.next_live(cur + 1);
+        wk.load_step(nxt < nsteps ? nxt : cur, g, in, dz, c_in, xr, zr);      // unconditional (see gather_unit): the last one is dropped
         if (grp == 0) wgrad4s_mfma_step<T2, NP, 0, FMT>(s_x, s_z, acc, wm, wn, pcol, kbase + q, slots);
         else wgrad4s_mfma_step<T2, NP, 1, FMT>(s_x, s_z, acc, wm, wn, pcol, kbase + q, slots);
         cur = nxt;
     }
     float o_scale = 1.f;
     if constexpr (FMT == 1) o_scale = split_inverse(x_scale) * split_inverse(z_scale);
-    // slab[strip][kd][tap][c (Cin)][n (64)]: every tap is written by the group that owns it (zeros where nothing was computed)
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int t9 = grp == 0 ? w4_own(T2, 0, i) : w4_own(T2, 1, i);
-        if (t9 < 0) continue;
-        float *o = slabs + ((((size_t)strip * 3 + kd) * 9 + t9) * g.Cin + cc * W4_C + wm * 32) * BN + wn * 32;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma32_row(r) + 4 * lh;
-            o[(size_t)row * BN + li] = FMT == 1 ? acc[i][r] * o_scale : acc[i][r];
-        }
-    }
+    w4_store_slabs<T2>(acc, slabs, wk, g, o_scale);
 }
 
 // conv3d_wgrad4 in the arithmetic the flags ask for: exact f32, or the split forms (MVX_FLAG_SPLIT: bf16x3, + MVX_FLAG_SPLIT3: bf16x6)
@@ -1268,10 +1004,7 @@ static int persistent_grid() {
 static long long g_gather_narrow_max_units = -1;
 void mvxi_gather_narrow_max_units(long long v) { g_gather_narrow_max_units = v; }
 
-static void launch_gather(hipStream_t st, const float *in, const float *wpk, const float *bias, float *out, double *stats,
-                          const Geom &g, int relu, const int *in_hflag, const unsigned char *out_mask, const float *bg_pre,
-                          int border_active, unsigned long long *exec_stages, const int *only_tiles, unsigned *done_counter,
-                          double fin_count, double fin_eps, float *fin_mean_inv, unsigned *work_counter) {
+static void launch_gather(hipStream_t st, const Geom &g, const float *wpk, const GatherArgs &a) {
     dim3 grid = gather_grid(g);
     const long long narrow_max = g_gather_narrow_max_units >= 0 ? g_gather_narrow_max_units : 3ll * (persistent_grid() / 2) / 2 + 1;
     const bool narrow = (long long)grid.x * grid.y * grid.z < narrow_max;
@@ -1282,14 +1015,15 @@ static void launch_gather(hipStream_t st, const float *in, const float *wpk, con
     const long long pf_max = 3ll * (persistent_grid() / 2);
 #define MVX_LAUNCH_GATHER_N(TLO, THI, NB2)                                                                                       \
     do {                                                                                                                         \
-        if (work_counter && units > pf_max)                                                                                      \
-            hipLaunchKernelGGL((conv3d_gather_pw<TLO, THI, NB2>), dim3(persistent_grid()), dim3(256), 0, st, in, wpk, bias, out,  \
-                               stats, g, relu, in_hflag, out_mask, bg_pre, border_active, exec_stages, only_tiles, done_counter,  \
-                               fin_count, fin_eps, fin_mean_inv, work_counter, (int)grid.x, (int)grid.y, (int)grid.z);            \
+        if (a.work_counter && units > pf_max)                                                                                    \
+            hipLaunchKernelGGL((conv3d_gather_pw<TLO, THI, NB2>), dim3(persistent_grid()), dim3(256), 0, st, a.in, wpk, a.bias,   \
+                               a.out, a.stats, g, a.relu, a.in_hflag, a.out_mask, a.bg_pre, a.border_active, a.exec_stages,       \
+                               a.only_tiles, a.done_counter, a.fin_count, a.fin_eps, a.fin_mean_inv, a.work_counter,              \
+                               (int)grid.x, (int)grid.y, (int)grid.z);                                                            \
         else                                                                                                                     \
-            hipLaunchKernelGGL((conv3d_gather_pf<TLO, THI, NB2>), grid, dim3(256), 0, st, in, wpk, bias, out, stats, g, relu,     \
-                               in_hflag, out_mask, bg_pre, border_active, exec_stages, only_tiles, done_counter, fin_count,       \
-                               fin_eps, fin_mean_inv);                                                                            \
+            hipLaunchKernelGGL((conv3d_gather_pf<TLO, THI, NB2>), grid, dim3(256), 0, st, a.in, wpk, a.bias, a.out, a.stats, g,   \
+                               a.relu, a.in_hflag, a.out_mask, a.bg_pre, a.border_active, a.exec_stages, a.only_tiles,            \
+                               a.done_counter, a.fin_count, a.fin_eps, a.fin_mean_inv);                                           \
     } while (0)
 #define MVX_LAUNCH_GATHER(TLO, THI)                                                                                              \
     do {                                                                                                                         \
@@ -1316,12 +1050,13 @@ extern "C" int mvx_conv3d_forward(const float *in, const float *wpk, const float
     int rc = conv_check_forward(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int relu = flags & MVX_FLAG_RELU;
     hipError_t e = conv_zero_stats(stats, nullptr, cout, 1, flags, st);
     if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0};
-    launch_gather(st, in, wpk, bias, out, stats, g, relu, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0.0, 0.0,
-                  nullptr, (unsigned *)work_counter);
+    GatherArgs a;
+    a.in = in; a.bias = bias; a.out = out; a.stats = stats; a.relu = flags & MVX_FLAG_RELU;
+    a.work_counter = (unsigned *)work_counter;
+    launch_gather(st, g, wpk, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -1341,10 +1076,14 @@ extern "C" int mvx_conv3d_forward_bg_frames(const float *in, const float *wpk, c
     hipError_t e = conv_zero_stats(stats, done_counter, cout, n_frames, flags, st);
     if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0, n_frames};
-    launch_gather(st, in, wpk, bias, out, stats, g, flags & MVX_FLAG_RELU, in_halo_flags, out_mask, bg_pre,
-                  (border_active ? 1 : 0) | ((flags & MVX_FLAG_BG_TAPS) ? 2 : 0),
-                  (unsigned long long *)exec_stages, nullptr, (unsigned *)done_counter, count, eps, mean_inv,
-                  (unsigned *)work_counter);
+    GatherArgs a;
+    a.in = in; a.bias = bias; a.out = out; a.stats = stats; a.relu = flags & MVX_FLAG_RELU;
+    a.in_hflag = in_halo_flags; a.out_mask = out_mask; a.bg_pre = bg_pre;
+    a.border_active = (border_active ? 1 : 0) | ((flags & MVX_FLAG_BG_TAPS) ? 2 : 0);
+    a.exec_stages = (unsigned long long *)exec_stages;
+    a.done_counter = (unsigned *)done_counter; a.fin_count = count; a.fin_eps = eps; a.fin_mean_inv = mean_inv;
+    a.work_counter = (unsigned *)work_counter;
+    launch_gather(st, g, wpk, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -1370,8 +1109,10 @@ static int launch_dgrad(const float *dz, const float *wpk_dgrad, float *dx, int3
     if ((rc = conv_check_geom(din, dout, h, w, cout, cin, stride_d, pad_d))) return rc;
     Geom g{dout, din, h, w, cout, cin, stride_d, pad_d, 1, n_frames};
     conv_set_taps2(g, flags, CONV_INPUT_GRAD, BN);
-    launch_gather((hipStream_t)stream, dz, wpk_dgrad, nullptr, dx, nullptr, g, 0, nullptr, nullptr, nullptr, 0,
-                  (unsigned long long *)exec_stages, only_tiles, nullptr, 0.0, 0.0, nullptr, (unsigned *)work_counter);
+    GatherArgs a;
+    a.in = dz; a.out = dx; a.only_tiles = only_tiles; a.exec_stages = (unsigned long long *)exec_stages;
+    a.work_counter = (unsigned *)work_counter;
+    launch_gather((hipStream_t)stream, g, wpk_dgrad, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -1590,8 +1331,11 @@ extern "C" int mvx_conv2d_forward_frames(const float *in, const float *wpk, cons
     if (e != hipSuccess) return (int)e;
     Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames};
     conv_set_taps2(g, flags, CONV_FORWARD, BK);
-    launch_gather(st, in, wpk, bias, out, stats, g, flags & MVX_FLAG_RELU, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                  (unsigned *)done_counter, (double)h * w, eps, mean_inv, (unsigned *)work_counter);
+    GatherArgs a;
+    a.in = in; a.bias = bias; a.out = out; a.stats = stats; a.relu = flags & MVX_FLAG_RELU;
+    a.done_counter = (unsigned *)done_counter; a.fin_count = (double)h * w; a.fin_eps = eps; a.fin_mean_inv = mean_inv;
+    a.work_counter = (unsigned *)work_counter;
+    launch_gather(st, g, wpk, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }

@@ -18,8 +18,7 @@
 //     barrier pair covers 3 taps x 12 MFMAs per wave instead of one tap.
 // The weight gradient in these arithmetics is conv3d_wgrad4s (conv3d.hip), behind the f32 entry points with MVX_FLAG_SPLIT.
 #include "common.h"
-#include "conv_geom.h"
-#include "split_common.h"
+#include "conv_kernels.h"
 #include "rowgemm_common.h"      // mvxi_rowgemm_k128_enable (mvx_tuning_set lives in this file)
 
 namespace {
@@ -111,28 +110,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
     const int d = blockIdx.y, nb = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, lh = lane >> 5;
     const int nchunks = g.Cin / BKT;
-    // background rewrite (see conv3d.hip / activity.hip): restricted launches and constant tiles
+    // restricted launch: only the units with a flagged output tile are produced
     if (only_tiles && !(only_tiles[(size_t)d * ntiles8 + t_top] | only_tiles[(size_t)d * ntiles8 + t_bot])) return;
-    // border_active bit 0: border tiles always count as active; bit 1: bg_pre carries the per-depth-tap and position-class
-    // constants (see gather_unit in conv3d.hip): interior tiles skip depth taps with a background-only source halo, border
-    // tiles without any active source are filled from the class constants
+    // executed depth taps, skipped ones and the unit's state from the ORed flags of its MT tiles (conv_kernels.h)
     const bool on_border = tx0 == 0 || ty0 == 0 || tx0 + TW >= g.W || ty0 + THT >= g.H;
-    const bool skip_taps = in_hflag && (border_active & 2) && !on_border;
-    unsigned skipped = 0;
-    int any_flag = 0;
-    bool active = true;
-    if (in_hflag) {
-        for (int kd = 0; kd < 3; ++kd) {
-            const int ds = src_depth(g, d, kd);
-            if (ds >= 0) {
-                const int fl = in_hflag[(size_t)ds * ntiles8 + t_top] | in_hflag[(size_t)ds * ntiles8 + t_bot];
-                any_flag |= fl;
-                if (skip_taps && !fl) skipped |= 1u << kd;
-            }
-        }
-        active = (((border_active & 1) && on_border) || any_flag) != 0;
-    }
-    const bool idle_border = in_hflag && (border_active & 2) && on_border && !any_flag;
+    const TilePlan plan = tile_plan<MT>(g, d, on_border, in_hflag, border_active, ntiles8, t_top, t_bot);
 
     f32x16 acc[MT][2];                                   // [site tile m: patch rows 2 MT wv + 2 m, + 1][channel tile: n0, n0 + 32]
 #pragma unroll
@@ -181,27 +163,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
     // stage s + 1 is fetched into registers while stage s computes (split into its pieces when it is written to LDS), the
     // weight rows go to LDS one kernel row at a time with the next row in flight, and the row needed next is always issued
     // BEFORE the long-latency halo fetch (vector-memory returns are in order).
-    int kd_l[3] = {0, 0, 0}, ds_l[3] = {0, 0, 0}, nk = 0;
-#pragma unroll
-    for (int kd = 0; kd < 3; ++kd) {
-        const int ds = src_depth(g, d, kd);
-        if (ds >= 0 && !((skipped >> kd) & 1u) && !idle_border) {
-            if (nk == 0) { kd_l[0] = kd; ds_l[0] = ds; }
-            else if (nk == 1) { kd_l[1] = kd; ds_l[1] = ds; }
-            else { kd_l[2] = kd; ds_l[2] = ds; }
-            ++nk;
-        }
-    }
-    const int nstages = active ? nk * nchunks : 0;
+    const int nstages = plan.active ? plan.nk * nchunks : 0;
     // executed work in units of the 8 x 16-tile, 32-channel stage (what the roofline prices)
     if (exec_stages && nstages > 0 && threadIdx.x == 0)
-        atomicAdd(exec_stages, (unsigned long long)(nk * (g.Cin / BK)) * (has_bot ? 2 : 1));
-    auto stage_of = [&](int st, int &kd, int &ds, int &cc) __attribute__((always_inline)) {
-        const int i = st / nchunks;
-        cc = st - i * nchunks;
-        kd = i == 0 ? kd_l[0] : (i == 1 ? kd_l[1] : kd_l[2]);
-        ds = i == 0 ? ds_l[0] : (i == 1 ? ds_l[1] : ds_l[2]);
-    };
+        atomicAdd(exec_stages, (unsigned long long)(plan.nk * (g.Cin / BK)) * (has_bot ? 2 : 1));
     int h_off[NH], h_lds[NH];     // per-thread halo slots: global float offset inside a (plane, chunk) image or -1; LDS byte offset or -1
 #pragma unroll
     for (int u = 0; u < NH; ++u) {
@@ -219,7 +184,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
     f32x4 hreg[NH];
     auto load_halo = [&](int st) __attribute__((always_inline)) {
         int kd, ds, cc;
-        stage_of(st, kd, ds, cc);
+        plan_stage(plan, nchunks, st, kd, ds, cc);
         const float *img = in + (size_t)ds * g.H * g.W * g.Cin + cc * BKT;
 #pragma unroll
         for (int u = 0; u < NH; ++u)
@@ -238,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
     };
     auto load_wrow = [&](int st, int a) __attribute__((always_inline)) {
         int kd, ds, cc;
-        stage_of(st, kd, ds, cc);
+        plan_stage(plan, nchunks, st, kd, ds, cc);
         load_w3(kd, a, cc);
     };
     auto compute_row = [&](int a, unsigned colmask) __attribute__((always_inline)) {
@@ -347,80 +312,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_gather_splitT(const float *__re
 #pragma unroll
         for (int m = 0; m < MT; ++m) { acc[m][0] *= o_scale; acc[m][1] *= o_scale; }
     }
-    // ---- epilogue
-    const int n0 = nb * BN + li, n1 = n0 + 32;
-    const float bias0 = bias ? bias[n0] : 0.f, bias1 = bias ? bias[n1] : 0.f;
-    float skip0 = 0.f, skip1 = 0.f;            // constants of the depth taps that were not executed
-    if (skipped && active) {
-        const float *bg_tap = bg_pre + (size_t)g.Dout * g.F * g.Cout + (size_t)d * 3 * g.Cout;
-#pragma unroll
-        for (int kd = 0; kd < 3; ++kd)
-            if ((skipped >> kd) & 1u) { skip0 += bg_tap[kd * g.Cout + n0]; skip1 += bg_tap[kd * g.Cout + n1]; }
-    }
-    float bgv0 = (bg_pre ? bg_pre[(size_t)d * g.Cout + n0] : 0.f) + bias0, bgv1 = (bg_pre ? bg_pre[(size_t)d * g.Cout + n1] : 0.f) + bias1;
-    if (relu) { bgv0 = fmaxf(bgv0, 0.f); bgv1 = fmaxf(bgv1, 0.f); }
-    float s1a = 0.f, s2a = 0.f, s1b = 0.f, s2b = 0.f;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-        const int py = ty0 + 2 * MT * wv + 2 * m;       // first of this site tile's two patch rows
-        if (idle_border) {                              // the accumulators are still zero: they take the position-class constants
-            const float *bg_cls = bg_pre + (size_t)4 * g.Dout * g.F * g.Cout + (size_t)d * 9 * g.Cout;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mfma32_row(r) + 4 * lh;
-                const int gy = py + (row >> 4), gx = tx0 + (row & 15);
-                const int q = 3 * (gy == 0 ? 0 : (gy >= g.H - 1 ? 2 : 1)) + (gx == 0 ? 0 : (gx >= g.W - 1 ? 2 : 1));
-                acc[m][0][r] = bg_cls[q * g.Cout + n0];
-                acc[m][1][r] = bg_cls[q * g.Cout + n1];
-            }
-        }
-        // site-mask bytes fetched up front (see conv3d.hip: a load between the stores made every store pair wait)
-        unsigned site_on = active ? 0xffffu : 0u;
-        if (out_mask && active) {
-            unsigned char mk[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = mfma32_row(r) + 4 * lh;
-                const int gy = min(py + (row >> 4), g.H - 1), gx = min(tx0 + (row & 15), g.W - 1);
-                mk[r] = out_mask[((size_t)d * g.H + gy) * g.W + gx];
-            }
-            site_on = 0u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) site_on |= (mk[r] ? 1u : 0u) << r;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = mfma32_row(r) + 4 * lh;
-            const int gy = py + (row >> 4), gx = tx0 + (row & 15);
-            float v0 = (acc[m][0][r] + skip0) + bias0, v1 = (acc[m][1][r] + skip1) + bias1;
-            if (relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-            if (out_mask && !((site_on >> r) & 1u)) { v0 = bgv0; v1 = bgv1; }
-            if (gy < g.H && gx < g.W) {
-                float *o = out + (((size_t)d * g.H + gy) * g.W + gx) * g.Cout;
-                o[n0] = v0;
-                o[n1] = v1;
-                s1a += v0; s2a += v0 * v0;
-                s1b += v1; s2b += v1 * v1;
-            }
-        }
-    }
-    if (stats) {
-        s1a += __shfl_xor(s1a, 32, 64); s2a += __shfl_xor(s2a, 32, 64);
-        s1b += __shfl_xor(s1b, 32, 64); s2b += __shfl_xor(s2b, 32, 64);
-        __syncthreads();
-        if (lh == 0) {
-            s_red[wv][li] = s1a; s_red[wv][32 + li] = s1b;
-            s_red[wv][BN + li] = s2a; s_red[wv][BN + 32 + li] = s2b;
-        }
-        __syncthreads();
-        if (tid < 2 * BN) {
-            const double t = (double)s_red[0][tid] + (double)s_red[1][tid] + (double)s_red[2][tid] + (double)s_red[3][tid];
-            const int which = tid / BN, c = tid % BN;
-            const unsigned rep = (blockIdx.x + blockIdx.y * gridDim.x) % MVX_REP;
-            double *fstats = stats + (size_t)(d / g.Dout) * MVX_REP * 2 * g.Cout;       // the plane's frame
-            atomicAdd(fstats + ((size_t)rep * 2 + which) * g.Cout + nb * BN + c, t);
-        }
-    }
+    // ---- epilogue (conv_kernels.h): f32 sums per lane, f64 across the waves
+    gather_epilogue<MT, 2, float>(acc, plan, g, d, nb, tx0, ty0, blockIdx.x + blockIdx.y * gridDim.x, s_red, bias, out, stats, relu,
+                                  out_mask, bg_pre);
 }
 
 // 16 x 16-site units when the launch has enough of them to fill two workgroup slots on every CU with a margin, else 8 x 16.
@@ -438,10 +332,9 @@ extern "C" int mvx_tuning_set(int32_t key, int64_t value) {
 static inline int pieces_of(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 2 : (flags & MVX_FLAG_SPLIT3) ? 3 : 2; }
 static inline int fmt_of(int flags) { return (flags & MVX_FLAG_SPLIT_F16) ? 1 : 0; }
 
-static void launch_gather_split(hipStream_t st, int flags, int planes, int nblocks, const float *in, const unsigned short *wsp,
-                                const float *bias, float *out, double *stats, const Geom &g, int relu, const int *in_hflag,
-                                const unsigned char *out_mask, const float *bg_pre, int border_active, const int *only_tiles,
-                                unsigned long long *exec_stages) {
+// (no BatchNorm finalize and no persistent launch here: those fields of GatherArgs stay off)
+static void launch_gather_split(hipStream_t st, int flags, const Geom &g, const unsigned short *wsp, const GatherArgs &a) {
+    const int planes = g.Dout * g.F, nblocks = g.Cout / BN;
     const int tiles_x = (int)mvx_cdiv(g.W, TW);
     const long long units16 = (long long)tiles_x * mvx_cdiv(g.H, TH2) * planes * nblocks;
     const bool big = units16 >= g_split16_min_units;
@@ -451,11 +344,13 @@ static void launch_gather_split(hipStream_t st, int flags, int planes, int nbloc
 #define MVX_GO(NP_, BK_, MT_, F_)                                                                                                        \
     do {                                                                                                                             \
         if (win)                                                                                                                     \
-            hipLaunchKernelGGL((conv3d_gather_splitT<NP_, BK_, MT_, true, F_>), grid, dim3(256), 0, st, in, wsp, bias, out, stats, g,    \
-                               relu, in_hflag, out_mask, bg_pre, border_active, only_tiles, exec_stages, am.a);         \
+            hipLaunchKernelGGL((conv3d_gather_splitT<NP_, BK_, MT_, true, F_>), grid, dim3(256), 0, st, a.in, wsp, a.bias, a.out,        \
+                               a.stats, g, a.relu, a.in_hflag, a.out_mask, a.bg_pre, a.border_active, a.only_tiles,                  \
+                               a.exec_stages, am.a);                                                                                 \
         else                                                                                                                         \
-            hipLaunchKernelGGL((conv3d_gather_splitT<NP_, BK_, MT_, false, F_>), grid, dim3(256), 0, st, in, wsp, bias, out, stats, g,   \
-                               relu, in_hflag, out_mask, bg_pre, border_active, only_tiles, exec_stages, am.a);         \
+            hipLaunchKernelGGL((conv3d_gather_splitT<NP_, BK_, MT_, false, F_>), grid, dim3(256), 0, st, a.in, wsp, a.bias, a.out,       \
+                               a.stats, g, a.relu, a.in_hflag, a.out_mask, a.bg_pre, a.border_active, a.only_tiles,                  \
+                               a.exec_stages, am.a);                                                                                 \
     } while (0)
     if (fmt_of(flags)) { if (big) MVX_GO(2, 32, 2, 1); else MVX_GO(2, 32, 1, 1); }
     else if (pieces_of(flags) == 3) { if (big) MVX_GO(3, 16, 2, 0); else MVX_GO(3, 32, 1, 0); }
@@ -485,15 +380,15 @@ extern "C" int mvx_conv3d_forward_split(const float *in, const void *wsplit, con
                                         int32_t din, int32_t dout, int32_t h, int32_t w, int32_t cin, int32_t cout,
                                         int32_t stride_d, int32_t pad_d, int32_t flags, void *stream) {
     MVX_CHECK_ARG(in && wsplit && out);
-    const int relu = flags & MVX_FLAG_RELU;
     int rc = conv_check_forward(din, dout, h, w, cin, cout, stride_d, pad_d);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = conv_zero_stats(stats, nullptr, cout, 1, flags, st);
     if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0};
-    launch_gather_split(st, flags, dout, cout / BN, in, (const unsigned short *)wsplit, bias, out, stats, g, relu, nullptr, nullptr, nullptr,
-                        0, nullptr, nullptr);
+    GatherArgs a;
+    a.in = in; a.bias = bias; a.out = out; a.stats = stats; a.relu = flags & MVX_FLAG_RELU;
+    launch_gather_split(st, flags, g, (const unsigned short *)wsplit, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -511,9 +406,12 @@ extern "C" int mvx_conv3d_forward_bg_split_frames(const float *in, const void *w
     hipError_t e = conv_zero_stats(stats, nullptr, cout, n_frames, flags, st);
     if (e != hipSuccess) return (int)e;
     Geom g{din, dout, h, w, cin, cout, stride_d, pad_d, 0, n_frames};
-    launch_gather_split(st, flags, dout * n_frames, cout / BN, in, (const unsigned short *)wsplit, bias, out, stats, g,
-                        flags & MVX_FLAG_RELU, in_halo_flags, out_mask, bg_pre,
-                        (border_active ? 1 : 0) | ((flags & MVX_FLAG_BG_TAPS) ? 2 : 0), nullptr, (unsigned long long *)exec_stages);
+    GatherArgs a;
+    a.in = in; a.bias = bias; a.out = out; a.stats = stats; a.relu = flags & MVX_FLAG_RELU;
+    a.in_hflag = in_halo_flags; a.out_mask = out_mask; a.bg_pre = bg_pre;
+    a.border_active = (border_active ? 1 : 0) | ((flags & MVX_FLAG_BG_TAPS) ? 2 : 0);
+    a.exec_stages = (unsigned long long *)exec_stages;
+    launch_gather_split(st, flags, g, (const unsigned short *)wsplit, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -536,8 +434,9 @@ static int launch_dgrad_split(const float *dz, const void *wsplit_dgrad, float *
     if ((rc = conv_check_geom(din, dout, h, w, cout, cin, stride_d, pad_d))) return rc;
     Geom g{dout, din, h, w, cout, cin, stride_d, pad_d, 1, n_frames};
     conv_set_taps2(g, flags, CONV_INPUT_GRAD, BN);
-    launch_gather_split((hipStream_t)stream, flags, din * n_frames, cin / BN, dz, (const unsigned short *)wsplit_dgrad, nullptr, dx, nullptr,
-                        g, 0, nullptr, nullptr, nullptr, 0, only_tiles, (unsigned long long *)exec_stages);
+    GatherArgs a;
+    a.in = dz; a.out = dx; a.only_tiles = only_tiles; a.exec_stages = (unsigned long long *)exec_stages;
+    launch_gather_split((hipStream_t)stream, flags, g, (const unsigned short *)wsplit_dgrad, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -584,8 +483,9 @@ extern "C" int mvx_conv2d_forward_split_frames(const float *in, const void *wspl
     if (e != hipSuccess) return (int)e;
     Geom g{1, 1, h, w, cin, cout, 1, 1, 0, n_frames};
     conv_set_taps2(g, flags, CONV_FORWARD, BK);
-    launch_gather_split(st, flags, n_frames, cout / BN, in, (const unsigned short *)wsplit, bias, out, stats, g, flags & MVX_FLAG_RELU,
-                        nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+    GatherArgs a;
+    a.in = in; a.bias = bias; a.out = out; a.stats = stats; a.relu = flags & MVX_FLAG_RELU;
+    launch_gather_split(st, flags, g, (const unsigned short *)wsplit, a);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }

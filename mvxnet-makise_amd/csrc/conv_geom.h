@@ -1,7 +1,9 @@
 // What the exact-f32 convolution (conv3d.hip) and its split-arithmetic form (conv3d_split.hip) agree on: the workgroup tile,
 // the launch geometry `Geom` with its plane and tap-window rules, and the host scaffold of their entry points (argument
-// checks, statistics zeroing, the MVX_FLAG_TAPS2 window, the layout of a weight-gradient workspace).  Per-kernel constants
-// (LDS pitches, TH2, W4_C, ...) and the strip-count heuristics stay with their kernels.
+// checks, statistics zeroing, the MVX_FLAG_TAPS2 window, the operands of a gather launch `GatherArgs`, the layout of a
+// weight-gradient workspace).  The device code the kernels share -- tile plan, gather epilogue, weight-gradient step walk --
+// is in conv_kernels.h, which includes this file.  Per-kernel constants (LDS pitches, TH2, ...) and the strip-count
+// heuristics stay with their kernels.
 //
 // Everything sits in an unnamed namespace, like the kernels that take a Geom by value: each of the two files gets its own copy.
 #pragma once
@@ -101,6 +103,28 @@ static inline void conv_set_taps2(Geom &g, int32_t flags, ConvDir dir, int granu
     const int c = dir == CONV_INPUT_GRAD ? g.Cout : g.Cin;      // channels of the space-to-depth image
     if (c % 4 == 0 && (c / 4) % granule == 0) g.s2d = c / 4;
 }
+
+// Operands of a gather launch (launch_gather in conv3d.hip, launch_gather_split in conv3d_split.hip), by name: an entry point
+// fills what it has and the rest stays off.  The packed weights, whose type differs between the two, are passed beside it.
+struct GatherArgs {
+    const float *in = nullptr, *bias = nullptr;
+    float *out = nullptr;
+    double *stats = nullptr;                    // BatchNorm sums of the output, see conv_zero_stats
+    int relu = 0;
+    // background rewrite (conv_kernels.h): halo activity [source plane][tile], computed output sites [plane][y][x], constants
+    const int *in_hflag = nullptr;
+    const unsigned char *out_mask = nullptr;
+    const float *bg_pre = nullptr;
+    int border_active = 0;                      // bit 0: border tiles always active, bit 1: bg_pre has bg_tap and bg_cls
+    const int *only_tiles = nullptr;            // [output plane][tile] restricted launch: only flagged tiles are produced
+    unsigned long long *exec_stages = nullptr;  // counter of executed K stages
+    // f32 gather only: BatchNorm finalize by the last workgroup (counter, sites per channel, eps, result) and the zeroed unit
+    // counter that allows the persistent launch
+    unsigned *done_counter = nullptr;
+    double fin_count = 0.0, fin_eps = 0.0;
+    float *fin_mean_inv = nullptr;
+    unsigned *work_counter = nullptr;
+};
 
 // Workspace of a weight gradient on compacted step lists: [slabs f32, slab_bytes][step list i32 3 x planes x ntiles]
 // [step counts i32 4][ones i32 planes x ntiles], planes = output planes of all frames.  `ones` (with_ones) are the all-set
