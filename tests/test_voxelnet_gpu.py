@@ -426,8 +426,15 @@ def test_pipeline_skips_empty_frames(executor):
 def test_row_gemm_bf16x3_split_accuracy(R, K, N, pieces, tol):
     """MVX_FLAG_SPLIT: the wide row GEMMs of `convmath: bf16x3` (csrc/linear_split.hip: three bf16 MFMAs per product, f32
     accumulate) against float64 -- forward with bias + ReLU + BatchNorm sums, and the input-gradient form (no epilogue);
-    fp32-grade accuracy like the split convolutions (2e-5; bf16x6, MVX_FLAG_SPLIT3: the exact-f32 kernel's 2e-6), row counts that are no multiple of the 128-row tile."""
+    fp32-grade accuracy like the split convolutions (2e-5; bf16x6, MVX_FLAG_SPLIT3: the exact-f32 kernel's 2e-6), row counts that are no multiple of the 128-row tile.
+
+    The no-epilogue form runs twice.  `yn` comes from the wrapper, which hands every K >= 256 call without an epilogue a split-K
+    workspace; linear_forward_impl then splits along K, and because the split kernels need splits == 1 that call reaches the
+    exact-f32 linear_fwd + slab_reduce for K = 768 and 1728 (the split arithmetic only for K = 128: rowgemm_k128).  `yc` is the
+    same product through the C ABI with splitk_workspace = NULL: splits stays 1 and the call reaches linear_fwd_split (K = 768,
+    1728) or the K = 128 kernel, in the split arithmetic at every shape."""
     from modules import _hip
+    from modules import Extension as X
     g = torch.Generator().manual_seed(R + K)
     x = torch.randn((R, K), generator=g)
     w = torch.randn((N, K), generator=g) / np.sqrt(K)
@@ -441,6 +448,14 @@ def test_row_gemm_bf16x3_split_accuracy(R, K, N, pieces, tol):
     assert rel_err(y32.cpu(), ref) < 2e-6                      # the exact-f32 kernel, for scale
     yn, _ = _hip.linear_forward(x.to(DEV), w.to(DEV), None, relu=False, want_stats=False, split=pieces)
     assert rel_err(yn.cpu(), x.double() @ w.double().t()) < tol
+    xd, wd = x.to(DEV), w.to(DEV)
+    yc = torch.full((R, N), float('nan'), device=DEV)
+    if pieces == 4:
+        _hip.guard_fp16_weight(wd)
+    _hip.bind_amax(pieces, xd)
+    X.check(X.lib.mvx_linear_forward(X.ptr(xd), K, X.ptr(wd), K, 0, None, X.ptr(yc), N, None, None, R, K, N,
+                                     _hip.split_flags(pieces, True), None, 0, X.stream()), 'mvx_linear_forward')
+    assert rel_err(yc.cpu(), x.double() @ w.double().t()) < tol
 
 
 @pytest.mark.parametrize('pieces,tol', [(2, 2e-5), (3, 2e-6), (4, 2e-6)])
