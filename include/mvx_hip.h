@@ -1174,6 +1174,62 @@ int mvx_optim_adamw_step(const int64_t *chunk_table, int32_t n_chunks, const flo
                          double weight_decay, double max_norm, int32_t guard, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame rendering (csrc/render.hip): a bird's-eye view and a camera view of the frames of a step (1..MVX_MAX_FRAMES) with a
+ * list of coloured boxes, u8 RGB images [n_frames][h][w][3], h and w in 1..MVX_RENDER_MAX_SIDE.  Three launches per view for
+ * all frames; the planes the kernels meet on are u32 words combined by integer atomicMax / atomicMin / atomicAdd (no float
+ * atomics), every pixel is decided by integer arithmetic on f64 geometry: bitwise reproducible, independent of the order of
+ * points and boxes.  The planes are cleared on `stream`; no host synchronisation.
+ *   points6 f32 [n_frames][cap_points][ld] (ld >= 6: x y z r row col), n_points i32 [n_frames] on the device (clamped to
+ *   0..cap_points).  The draw list: boxes f32 [n_frames][cap_boxes][7] x y z l w h r in the LiDAR frame, z the bottom face
+ *   (Calc.bbox3d2corner), n_boxes i32 [n_frames] on the device (clamped to 0..cap_boxes), colors u32 [n_frames][cap_boxes] =
+ *   prio << 24 | R << 16 | G << 8 | B; cap_boxes = 0: nothing is drawn and the three pointers may be null.  Where segments
+ *   meet on a pixel the larger word wins; 0 draws nothing.  The kernels know colours, not classes.
+ *   A box with a non-finite field, or with a segment end whose pixel row or column is not below 2^24 in magnitude, is dropped
+ *   whole and sets MVX_RENDER_BAD_BOX in status i32 [n_frames] (written by the call).
+ * Segment rule (both views), integer ends (r0, c0), (r1, c1): the major axis is rows iff |dr| >= |dc|; the end with the smaller
+ *   (major, minor) pair comes first; n = max(|dr|, |dc|); pixel k = 0..n: major = m0 + k, minor = q0 + sgn(dq) *
+ *   ((2 k |dq| + n) / (2 n)) in i64 (n = 0: one pixel).  Only the k whose major coordinate is inside the image are visited
+ *   (the range is computed); pixels whose minor coordinate is outside are skipped.  Each pixel stamps a thickness x thickness
+ *   square with offsets -(T / 2) .. T - 1 - (T / 2), clipped to the image; thickness 1..3.
+ * mvx_render_bev_frames: cell i = floor(((double)x - x0) / res), j = floor(((double)y - y0) / res); image row h - 1 - i, column
+ *   w - 1 - j; a point is drawn iff 0 <= i < h and 0 <= j < w and x, y, z are finite.  Per pixel the largest
+ *   key = ((zq << 8) | iq) + 1, zq = clamp(floor((z - z0) / (z1 - z0) * 65535), 0, 65535), iq = clamp(floor(r * 255), 0, 255)
+ *   (a NaN clamps to 0), and the number of points.  Shading, integer floor divisions: idx = zq >> 8 (MVX_RENDER_BY_HEIGHT) or
+ *   iq (MVX_RENDER_BY_INTENSITY); out[ch] = lut[idx][ch] * (64 + 191 * min(count, cmax) / cmax) / 255; pixels without a point
+ *   take `background` (R << 16 | G << 8 | B).  lut u8 [256][3] on the device.  Boxes: corners as Calc.bbox3d2bev with cos and
+ *   sin of (double)yaw, each mapped to a pixel by the floor rule above; the four edges and a heading marker from the centre to
+ *   the midpoint of the edge at u = +l/2.
+ * mvx_render_camera_frames: background = image_or_null u8 [n_frames][h][w][3] (channels swapped when image_is_bgr != 0) or
+ *   black.  A point's pixel is (floor(row), floor(col)) of columns 4 and 5; it stamps a (2 R + 1)^2 square, R = point_radius in
+ *   0..2, clipped to the image, with dq = clamp(floor(x / depth_max * 65535), 0, 65535) under atomicMin; a pixel with a point
+ *   takes lut_depth[dq >> 8].  Points with a non-finite x, row or col are skipped.  Boxes: the eight corners in the order of
+ *   Calc.bbox3d2corner through image_from_lidar f64 [n_frames][4][4] on the device (rows 0..2: u' v' w', each
+ *   ((m0 X + m1 Y) + m2 Z) + m3); the twelve edges and the two diagonals of the face at u = +l/2; a segment with both ends at
+ *   w' < z_near is dropped, one with a single end there has that end moved to the plane (t = (z_near - wa) / (wb - wa),
+ *   a + t (b - a), w' = z_near); then column = floor(u' / w'), row = floor(v' / w').  Order: background, points, boxes.
+ * workspace: mvx_render_workspace_bytes(n_frames, h, w) bytes (0 for sizes outside the limits), 16-byte aligned; out and
+ * image_or_null 4-byte aligned.  MVX_EINVAL before any launch: a null required pointer, n_frames, h or w outside the limits,
+ * res <= 0, z1 <= z0, cmax < 1, thickness outside 1..3, point_radius outside 0..2, z_near or depth_max <= 0, ld < 6, a
+ * workspace that is too small.
+ */
+#define MVX_RENDER_MAX_SIDE 4096
+#define MVX_RENDER_BAD_BOX 1
+#define MVX_RENDER_BY_HEIGHT 0
+#define MVX_RENDER_BY_INTENSITY 1
+size_t mvx_render_workspace_bytes(int32_t n_frames, int32_t h, int32_t w);
+int mvx_render_bev_frames(const float *points6, int32_t ld, const int32_t *n_points, int32_t n_frames, int32_t cap_points,
+                          const float *boxes, const int32_t *n_boxes, const uint32_t *colors, int32_t cap_boxes, double x0,
+                          double y0, double res, double z0, double z1, int32_t h, int32_t w, const uint8_t *lut,
+                          int32_t color_by, int32_t cmax, uint32_t background, int32_t thickness, uint8_t *out,
+                          int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+int mvx_render_camera_frames(const float *points6, int32_t ld, const int32_t *n_points, int32_t n_frames, int32_t cap_points,
+                             const float *boxes, const int32_t *n_boxes, const uint32_t *colors, int32_t cap_boxes,
+                             const double *image_from_lidar, double z_near, double depth_max, int32_t h, int32_t w,
+                             const uint8_t *lut_depth, int32_t point_radius, const uint8_t *image_or_null,
+                             int32_t image_is_bgr, int32_t thickness, uint8_t *out, int32_t *status, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@ GPU).  The feature maps come from the same stand-in as train_like.py when torchv
     python detect_like.py <dataroot> --checkpoint checkpoints/epoch10.pkl [--split val] [--out results/data]
     python detect_like.py /tmp/kitti --synthetic 8          # a synthetic tree, an untrained (seeded) model
     python detect_like.py <dataroot> --split val --eval     # then score the files against the split's label_2 (eval_like.py)
+    python detect_like.py <dataroot> --render pictures      # and a bird's-eye and a camera picture of every frame (visualize_like.py)
 """
 import argparse
 import os
@@ -38,6 +39,8 @@ def parse_args(argv=None):
     ap.add_argument('--classes', nargs='+', default=['Car'], help='classes scored by --eval')
     ap.add_argument('--extractor-weights', default=None,
                     help='state dict of the frozen ResNet50-FPN extractor (torchvision key names): images go through the HIP extractor')
+    ap.add_argument('--render', default=None, metavar='DIR',
+                    help='also write <name>_bev.png and <name>_cam.png of every frame (ground truth green, detections red to yellow)')
     return ap.parse_args(argv)
 
 
@@ -83,6 +86,12 @@ def main(args):
         for name, d, frame in zip(gnames, dets, group):
             write_kitti_results(os.path.join(out_dir, name + '.txt'), d, frame[5], cfg.imsize)
             n_boxes += d['boxes'].shape[0]
+        if args.render:                  # straight from the device tensors of the step just run
+            from modules import render
+            draw = render.draw_list([frame[3] for frame in group], dets, device=device)
+            bev, _ = render.render_bev(batch, draw)
+            cam, _ = render.render_camera(batch, draw, [frame[5] for frame in group], [frame[1] for frame in group])
+            render.save_frames(args.render, gnames, bev, cam)
     dt = time.perf_counter() - t0
     print('%d frames, %d boxes -> %s (%.1f frames/s including file I/O)' % (len(data), n_boxes, out_dir, len(data) / max(dt, 1e-9)))
     if args.eval:

@@ -200,6 +200,11 @@ PROTOTYPES = {
     'mvx_topdown_merge_frames': (_i32, [_p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     'mvx_optim_workspace_bytes': (_sz, [_i64]),
     'mvx_optim_adamw_step': (_i32, [_p, _i32, _p, _p, _p, _i64, _p, _p, _f64, _f64, _f64, _f64, _f64, _f64, _i32, _p, _sz, _p]),
+    'mvx_render_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'mvx_render_bev_frames': (_i32, [_p, _i32, _p, _i32, _i32, _p, _p, _p, _i32, _f64, _f64, _f64, _f64, _f64, _i32, _i32, _p,
+                                     _i32, _i32, ctypes.c_uint32, _i32, _p, _p, _p, _sz, _p]),
+    'mvx_render_camera_frames': (_i32, [_p, _i32, _p, _i32, _i32, _p, _p, _p, _i32, _p, _f64, _f64, _i32, _i32, _p, _i32, _p,
+                                        _i32, _i32, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -2343,3 +2343,60 @@ def optim_adamw_step(table, grad_flat, m_flat, v_flat, count, state, lr, beta1, 
                                            X.ptr(count), X.ptr(state), float(lr), float(beta1), float(beta2), float(eps),
                                            float(weight_decay), float(max_norm), 1 if guard else 0, X.ptr(ws), ws.numel(),
                                            X.stream()), 'mvx_optim_adamw_step')
+
+
+# ---------------------------------------------------------------------------------------------
+# Frame rendering (csrc/render.hip; modules/render.py).  The draw list of both views: boxes f32 (F, Bcap, 7), n_boxes i32 (F,),
+# colors (F, Bcap) = prio << 24 | R << 16 | G << 8 | B, the u32 words carried in an int32 tensor
+# ---------------------------------------------------------------------------------------------
+RENDER_MAX_SIDE, RENDER_BAD_BOX = 4096, 1      # MVX_RENDER_*
+RENDER_COLOR_BY = {'height': 0, 'intensity': 1}
+
+
+def _render_common(points6, n_points, boxes, n_boxes, colors, lut, H, W):
+    F, cap, ld = points6.shape
+    dev = points6.device
+    assert points6.dtype == torch.float32 and ld >= 6 and n_points.dtype == torch.int32 and n_points.shape == (F,)
+    assert lut.dtype == torch.uint8 and lut.shape == (256, 3)
+    Bcap = 0 if boxes is None else boxes.shape[1]
+    if Bcap:
+        assert boxes.shape == (F, Bcap, 7) and boxes.dtype == torch.float32
+        assert n_boxes.shape == (F,) and n_boxes.dtype == torch.int32 and colors.shape == (F, Bcap) and colors.dtype == torch.int32
+    else:
+        boxes = n_boxes = colors = None
+    out = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    status = torch.empty((F,), dtype=torch.int32, device=dev)
+    ws = workspace(X.lib.mvx_render_workspace_bytes(F, H, W), dev, 'render')
+    return F, cap, ld, Bcap, boxes, n_boxes, colors, out, status, ws
+
+
+def render_bev_frames(points6, n_points, boxes, n_boxes, colors, x0, y0, res, z0, z1, H, W, lut, color_by='height', cmax=8,
+                      background=0, thickness=1):
+    """The bird's-eye view of F frames in three launches: (image u8 (F, H, W, 3) RGB, status i32 (F,)) on the device.
+    points6 f32 (F, cap, >= 6), n_points i32 (F,); lut u8 (256, 3); ``background`` = R << 16 | G << 8 | B."""
+    if color_by not in RENDER_COLOR_BY:
+        raise X.MvxHipError("color_by must be 'height' or 'intensity', not %r" % (color_by,))
+    F, cap, ld, Bcap, boxes, n_boxes, colors, out, status, ws = _render_common(points6, n_points, boxes, n_boxes, colors, lut, H, W)
+    with _timed_bytes('render_bev', F * (cap * ld * 4 + H * W * 15)):
+        X.check(X.lib.mvx_render_bev_frames(X.ptr(points6), ld, X.ptr(n_points), F, cap, X.ptr(boxes), X.ptr(n_boxes), X.ptr(colors),
+                                            Bcap, float(x0), float(y0), float(res), float(z0), float(z1), int(H), int(W), X.ptr(lut),
+                                            RENDER_COLOR_BY[color_by], int(cmax), int(background) & 0xFFFFFF, int(thickness),
+                                            X.ptr(out), X.ptr(status), X.ptr(ws), ws.numel(), X.stream()), 'mvx_render_bev_frames')
+    return out, status
+
+
+def render_camera_frames(points6, n_points, boxes, n_boxes, colors, image_from_lidar, H, W, lut_depth, z_near=0.5, depth_max=70.4,
+                         point_radius=1, images=None, images_bgr=True, thickness=1):
+    """The camera view of F frames in three launches: (image u8 (F, H, W, 3) RGB, status i32 (F,)) on the device.
+    image_from_lidar f64 (F, 4, 4) on the device; ``images`` u8 (F, H, W, 3) or None (black)."""
+    F, cap, ld, Bcap, boxes, n_boxes, colors, out, status, ws = _render_common(points6, n_points, boxes, n_boxes, colors, lut_depth,
+                                                                               H, W)
+    assert image_from_lidar.dtype == torch.float64 and image_from_lidar.shape == (F, 4, 4)
+    assert images is None or (images.dtype == torch.uint8 and images.shape == (F, H, W, 3))
+    with _timed_bytes('render_camera', F * (cap * ld * 4 + H * W * (11 + (3 if images is not None else 0)))):
+        X.check(X.lib.mvx_render_camera_frames(X.ptr(points6), ld, X.ptr(n_points), F, cap, X.ptr(boxes), X.ptr(n_boxes),
+                                               X.ptr(colors), Bcap, X.ptr(image_from_lidar), float(z_near), float(depth_max), int(H),
+                                               int(W), X.ptr(lut_depth), int(point_radius), X.ptr(images), 1 if images_bgr else 0,
+                                               int(thickness), X.ptr(out), X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
+                'mvx_render_camera_frames')
+    return out, status
