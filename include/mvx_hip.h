@@ -875,6 +875,39 @@ int mvx_voxel_loss(const float *score, int64_t score_sl, int64_t score_sw, int64
                    float *losses, double *scratch, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Focal loss of the RPN heads for the frames of a step (csrc/loss_frames.hip).  The reference has none: its
+ * VoxelLoss is a plain log loss.  Forward + backward of all frames in three launches and one memset, for any n_frames.
+ *
+ * mvx_focal_loss_frames: per frame f < n_frames (1..MVX_MAX_FRAMES), A = anchors_per_loc (1..4):
+ *   heads f32 [n_frames*l*w][8A] contiguous, 16-byte aligned, a row = [A cls logits | 7A regression]: the raw output of the
+ *     heads (rpn_frames.rpn_forward, 16 wide), logits and not probabilities;
+ *   pos_idx / neg_idx i64 [n_frames][3][cap], gi i64 [n_frames][cap], counts i32 [n_frames][2] = (n_pos, n_notneg) on the
+ *     device: what mvx_classify_anchors_frames writes.  Entries beyond a frame's count are never read; a count is taken as
+ *     min(max(count, 0), cap); an entry outside the grid (or a gi outside the frame's boxes) is skipped;
+ *   gts f32 [n][gt_ld >= 7] xyzlwhr, the boxes of all frames back to back, gt_off i32 [n_frames + 1] on the DEVICE the first
+ *     row of every frame (gi is local to the frame); anchors f32 [l][w][A][7].
+ *   By set membership: an anchor is positive when pos_idx lists it at least once, ignored when neg_idx (the NOT-negative
+ *   anchors) lists it and it is not positive, negative otherwise.  With x a logit, p = sigmoid(x), N_f = max(1, n_pos):
+ *     cls_f = cls_weight / N_f * ( sum_positive alpha (1-p)^gamma (-log p) + sum_negative (1-alpha) p^gamma (-log(1-p)) )
+ *     reg_f = reg_weight * mvx_voxel_loss's regLoss (its targets, SmoothL1 with beta 1, once per pos_idx entry, mean over
+ *             n_pos*7; 0 when n_pos = 0)
+ *   all from the logit (softplus forms, accurate expf / log1pf), per-frame sums in f64.
+ *   losses f32 [n_frames][2] = (cls_f, reg_f).  d_heads (optional; 16-byte aligned, layout of heads) = d(cls_f + reg_f)/d(row),
+ *   with respect to the LOGITS, zero on ignored anchors; written in full, so it need not be zero on entry.
+ *   workspace: mvx_focal_loss_frames_workspace_bytes(n_frames, l, w, anchors_per_loc) bytes, 8-byte aligned (0 for a shape the
+ *   call rejects; pure host code).  MVX_EINVAL before any launch: a NULL required pointer, n_frames or anchors_per_loc outside
+ *   their ranges, cap < 1, gt_ld < 7, alpha outside [0, 1], gamma < 0, a workspace that is too small.
+ *   No host read, no f64 atomic: losses are bitwise reproducible, and d_heads too whenever pos_idx lists no anchor twice (the
+ *   regression columns are float atomicAdd-ed per entry).
+ */
+int64_t mvx_focal_loss_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc);
+int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                          const int64_t *pos_idx, const int64_t *neg_idx, const int64_t *gi, int64_t cap,
+                          const int32_t *counts, const float *gts, int32_t gt_ld, const int32_t *gt_off,
+                          const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight,
+                          float *d_heads, float *losses, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Detection output (csrc/detect.hip): score selection, top-K, box decoding and rotated BEV NMS for the frames of a step.
  * The reference has none of it (its Calc.decodeRegression is never called).
  *

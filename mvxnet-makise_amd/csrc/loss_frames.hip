@@ -1,0 +1,227 @@
+// Focal loss of the RPN heads for all frames of a step: forward + backward in three launches and one memset, for any F.
+//
+// Reads the raw head output of rpn_frames.rpn_forward, rows [A cls logits | 7A regression] (A anchors per location), and the
+// lists mvx_classify_anchors_frames writes.  Per frame f, by SET membership of the anchors (VoxelLoss subtracts an anchor
+// that is listed twice two times; here it counts once):
+//   positive = listed in pos_idx; ignored = listed in neg_idx (the NOT-negative anchors) and not positive; negative = the rest
+//   cls_f = cls_weight / max(1, n_pos) * ( sum_pos alpha (1-p)^gamma (-log p) + sum_neg (1-alpha) p^gamma (-log(1-p)) )
+//   reg_f = reg_weight * VoxelLoss's regression term (csrc/loss.hip: its targets, SmoothL1 with beta 1, once per pos_idx
+//           entry, mean over n_pos * 7; 0 without a positive)
+// Everything is evaluated from the logit x, so that nothing overflows or cancels:
+//   -log(1-p) = softplus(x) = max(x,0) + log1p(exp(-|x|)),  -log p = softplus(-x),  p and 1-p from exp(-|x|),
+//   p^gamma = exp(-gamma softplus(-x)),  (1-p)^gamma = exp(-gamma softplus(x)).
+//
+//   1. focal_flags   the lists of all frames -> one flag byte per anchor (bit 0 positive, bit 1 listed in neg_idx), OR-ed
+//                    into the zeroed workspace: the result does not depend on the order
+//   2. focal_dense   all rows of all frames: the whole 8A-wide gradient row (regression columns zero) and ONE f64 partial
+//                    sum per workgroup, each reduced in a fixed order
+//   3. focal_lists   one workgroup per frame: the regression term (float atomicAdd into the regression columns only:
+//                    entries that name the same anchor collide there), then the frame's partials summed in index order
+// No f64 atomic, no atomic across workgroups on a sum: the losses are bitwise reproducible, and so is the gradient whenever
+// no anchor is listed twice in pos_idx.  counts and gt_off are read on the device: the host reads nothing.
+#include "common.h"
+
+namespace {
+
+constexpr int DENSE_THREADS = 256;
+constexpr int DENSE_MAX_BLOCKS = 128;      // workgroups (= partial sums) per frame at most
+constexpr int LIST_BLOCKS = 8;             // workgroups per frame of the flag pass
+constexpr int LIST_THREADS = 1024;
+
+struct Layout {
+    long long n_anchors;      // per frame
+    long long flag_bytes;     // all frames, one byte per anchor, rounded up to 256
+    int nb;                   // workgroups of the dense pass per frame
+    bool ok;
+    Layout(int F, int l, int w, int A) {
+        ok = F >= 1 && F <= MVX_MAX_FRAMES && l > 0 && w > 0 && A >= 1 && A <= 4 && (long long)F * l * w * A * 8 < (1ll << 31);
+        n_anchors = ok ? (long long)l * w * A : 0;
+        flag_bytes = ((long long)F * n_anchors + 255) & ~255ll;
+        const long long chunks = (long long)l * w * 2 * A;      // float4 pieces of a frame's rows
+        const long long want = ok ? (chunks + DENSE_THREADS * 4 - 1) / (DENSE_THREADS * 4) : 0;
+        nb = (int)(want > DENSE_MAX_BLOCKS ? DENSE_MAX_BLOCKS : want);
+    }
+    long long partials() const { return flag_bytes; }
+    long long total(int F) const { return ok ? flag_bytes + (long long)F * nb * (long long)sizeof(double) : 0; }
+};
+
+struct Lists {
+    const long long *pos, *neg, *gi;      // (F,3,cap), (F,3,cap), (F,cap)
+    long long cap;
+    const int *counts;                    // (F,2)
+};
+
+__device__ __forceinline__ int list_count(const Lists &ls, int f, int which) {
+    const int n = ls.counts[2 * f + which];
+    return n < 0 ? 0 : ((long long)n > ls.cap ? (int)ls.cap : n);
+}
+
+// anchor (x, y, z) of entry k of a (3,cap) list -> index inside the frame, or -1 when it lies outside the grid
+__device__ __forceinline__ long long list_anchor(const long long *idx, long long cap, int k, int L, int W, int A) {
+    const long long x = idx[k], y = idx[cap + k], z = idx[2 * cap + k];
+    if (x < 0 || x >= L || y < 0 || y >= W || z < 0 || z >= A) return -1;
+    return (x * W + y) * A + z;
+}
+
+__global__ void focal_flags(Lists ls, int L, int W, int A, unsigned *__restrict__ flags) {
+    const int f = blockIdx.y;
+    const long long base = (long long)f * L * W * A;
+    const int n_pos = list_count(ls, f, 0), n_neg = list_count(ls, f, 1);
+    const long long *pos = ls.pos + (size_t)f * 3 * ls.cap, *neg = ls.neg + (size_t)f * 3 * ls.cap;
+    const int step = gridDim.x * blockDim.x;
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_pos; k += step) {
+        const long long a = list_anchor(pos, ls.cap, k, L, W, A);
+        if (a >= 0) atomicOr(flags + ((base + a) >> 2), 1u << (8 * (unsigned)((base + a) & 3)));
+    }
+    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n_neg; k += step) {
+        const long long a = list_anchor(neg, ls.cap, k, L, W, A);
+        if (a >= 0) atomicOr(flags + ((base + a) >> 2), 2u << (8 * (unsigned)((base + a) & 3)));
+    }
+}
+
+// sum over the workgroup in a fixed order (lanes by xor shuffles, then the waves in index order); valid in thread 0
+__device__ __forceinline__ double block_sum_f64(double v, double *s_part) {
+    v = wave_sum_f64(v);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) s_part[wid] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0)
+        for (int k = 0; k < (int)(blockDim.x >> 6); ++k) t += s_part[k];
+    return t;
+}
+
+// One thread per float4 of a row; the first float4 of a row holds its A <= 4 logits.
+__global__ void __launch_bounds__(DENSE_THREADS)
+focal_dense(const float *__restrict__ heads, int rows, int A, const unsigned char *__restrict__ flags, Lists ls, float alpha,
+            float gamma, float cls_weight, float *__restrict__ d_heads, double *__restrict__ partials) {
+    const int f = blockIdx.y;
+    const int cpr = 2 * A;                                   // float4 pieces per row
+    const long long chunks = (long long)rows * cpr;
+    const float4 *src = (const float4 *)(heads + (size_t)f * rows * 8 * A);
+    float4 *dst = d_heads ? (float4 *)(d_heads + (size_t)f * rows * 8 * A) : nullptr;
+    const unsigned char *fl = flags + (size_t)f * rows * A;
+    const int n_pos = list_count(ls, f, 0);
+    const float scale = cls_weight / (float)(n_pos > 1 ? n_pos : 1);
+    double part = 0.0;
+    for (long long i = (long long)blockIdx.x * DENSE_THREADS + threadIdx.x; i < chunks; i += (long long)gridDim.x * DENSE_THREADS) {
+        const long long row = i / cpr;
+        float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i - row * cpr == 0) {
+            const float4 in = src[i];
+            const float xs[4] = {in.x, in.y, in.z, in.w};
+            float g[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                if (a >= A) break;
+                const unsigned flag = fl[row * A + a];
+                if (flag == 2u) continue;                    // ignored: no loss, no gradient
+                const float x = xs[a];
+                const float e = expf(-fabsf(x));
+                const float l1p = log1pf(e);
+                const float sp_x = fmaxf(x, 0.f) + l1p;      // softplus(x)  = -log(1 - p)
+                const float sp_mx = fmaxf(-x, 0.f) + l1p;    // softplus(-x) = -log p
+                const float inv = 1.f / (1.f + e);
+                const float p = x >= 0.f ? inv : e * inv, q = x >= 0.f ? e * inv : inv;
+                if (flag & 1u) {
+                    const float m = alpha * expf(-gamma * sp_x);               // alpha (1-p)^gamma
+                    part += (double)(m * sp_mx);
+                    g[a] = -scale * m * (q + gamma * p * sp_mx);
+                } else {
+                    const float m = (1.f - alpha) * expf(-gamma * sp_mx);      // (1-alpha) p^gamma
+                    part += (double)(m * sp_x);
+                    g[a] = scale * m * (p + gamma * q * sp_x);
+                }
+            }
+            out = make_float4(g[0], g[1], g[2], g[3]);
+        }
+        if (dst) dst[i] = out;
+    }
+    __shared__ double s_part[DENSE_THREADS / 64];
+    const double t = block_sum_f64(part, s_part);
+    if (threadIdx.x == 0) partials[(size_t)f * gridDim.x + blockIdx.x] = t;
+}
+
+__global__ void __launch_bounds__(LIST_THREADS)
+focal_lists(const float *__restrict__ heads, Lists ls, const float *__restrict__ gts, int gt_ld, const int *__restrict__ gt_off,
+            const float *__restrict__ anchors, int L, int W, int A, float cls_weight, float reg_weight,
+            float *__restrict__ d_heads, const double *__restrict__ partials, int nb, float *__restrict__ losses) {
+    const int f = blockIdx.x;
+    const int n_pos = list_count(ls, f, 0);
+    const long long *pos = ls.pos + (size_t)f * 3 * ls.cap, *gi = ls.gi + (size_t)f * ls.cap;
+    const int g_lo = gt_off[f], n_gt = gt_off[f + 1] - g_lo;
+    const size_t frame = (size_t)f * L * W * 8 * A;
+    const float reg_scale = n_pos > 0 ? reg_weight / (float)(n_pos * 7) : 0.f;
+    double s_reg = 0.0;
+    for (int k = threadIdx.x; k < n_pos; k += blockDim.x) {
+        const long long a = list_anchor(pos, ls.cap, k, L, W, A);
+        const long long gk = gi[k];
+        if (a < 0 || gk < 0 || gk >= n_gt) continue;
+        const int z = (int)(a % A);
+        const float *g = gts + (size_t)(g_lo + gk) * gt_ld;
+        const float *an = anchors + (size_t)a * 7;
+        const float d = sqrtf(an[3] * an[3] + an[4] * an[4]);
+        float t[7];
+        t[0] = (g[0] - an[0]) / d;
+        t[1] = (g[1] - an[1]) / d;
+        t[2] = (g[2] - an[2]) / an[5];
+        t[3] = logf(g[3] / an[3]);
+        t[4] = logf(g[4] / an[4]);
+        t[5] = logf(g[5] / an[5]);
+        t[6] = g[6] - an[6];
+        const size_t col0 = frame + (size_t)(a / A) * 8 * A + A + z * 7;
+#pragma unroll
+        for (int c = 0; c < 7; ++c) {
+            const float diff = heads[col0 + c] - t[c];
+            const float ad = fabsf(diff);
+            s_reg += (double)(ad < 1.f ? 0.5f * diff * diff : ad - 0.5f);
+            if (d_heads) atomicAdd(d_heads + col0 + c, reg_scale * (ad < 1.f ? diff : (diff > 0.f ? 1.f : -1.f)));
+        }
+    }
+    __shared__ double s_part[LIST_THREADS / 64];
+    __shared__ double s_cls[DENSE_MAX_BLOCKS];
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) s_cls[k] = partials[(size_t)f * nb + k];
+    const double tr = block_sum_f64(s_reg, s_part);      // its barrier also publishes s_cls
+    if (threadIdx.x == 0) {
+        double tc = 0.0;
+        for (int k = 0; k < nb; ++k) tc += s_cls[k];
+        losses[2 * f] = (float)((double)cls_weight * tc / (double)(n_pos > 1 ? n_pos : 1));
+        losses[2 * f + 1] = n_pos > 0 ? (float)((double)reg_weight * tr / (double)(n_pos * 7)) : 0.f;
+    }
+}
+
+}  // namespace
+
+extern "C" int64_t mvx_focal_loss_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc) {
+    return Layout(n_frames, l, w, anchors_per_loc).total(n_frames);
+}
+
+extern "C" int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                     const int64_t *pos_idx, const int64_t *neg_idx, const int64_t *gi, int64_t cap,
+                                     const int32_t *counts, const float *gts, int32_t gt_ld, const int32_t *gt_off,
+                                     const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight,
+                                     float *d_heads, float *losses, void *workspace, int64_t workspace_bytes, void *stream) {
+    const Layout lay(n_frames, l, w, anchors_per_loc);
+    MVX_CHECK_ARG(lay.ok);
+    MVX_CHECK_ARG(heads && pos_idx && neg_idx && gi && counts && gts && gt_off && anchors && losses && workspace);
+    MVX_CHECK_ARG(cap >= 1 && cap < (1ll << 31) && gt_ld >= 7);
+    MVX_CHECK_ARG(alpha >= 0.f && alpha <= 1.f && gamma >= 0.f);
+    MVX_CHECK_ARG(workspace_bytes >= lay.total(n_frames));
+    // rows are read and written as float4; the flag words and the f64 partials sit in the workspace
+    MVX_CHECK_ARG(((uintptr_t)heads & 15) == 0 && ((uintptr_t)d_heads & 15) == 0 && ((uintptr_t)workspace & 7) == 0);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char *ws = (unsigned char *)workspace;
+    double *partials = (double *)(ws + lay.partials());
+    hipError_t e = hipMemsetAsync(ws, 0, (size_t)lay.flag_bytes, st);
+    if (e != hipSuccess) return (int)e;
+    const Lists ls = {(const long long *)pos_idx, (const long long *)neg_idx, (const long long *)gi, (long long)cap, counts};
+    hipLaunchKernelGGL(focal_flags, dim3(LIST_BLOCKS, n_frames), dim3(256), 0, st, ls, l, w, anchors_per_loc, (unsigned *)ws);
+    MVX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(focal_dense, dim3(lay.nb, n_frames), dim3(DENSE_THREADS), 0, st, heads, l * w, anchors_per_loc, ws, ls, alpha,
+                       gamma, cls_weight, d_heads, partials);
+    MVX_LAUNCH_CHECK();
+    hipLaunchKernelGGL(focal_lists, dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ls, gts, gt_ld, gt_off, anchors, l, w,
+                       anchors_per_loc, cls_weight, reg_weight, d_heads, partials, lay.nb, losses);
+    MVX_LAUNCH_CHECK();
+    return MVX_OK;
+}

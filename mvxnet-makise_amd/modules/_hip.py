@@ -1944,6 +1944,29 @@ def voxel_loss(score, reg, pos_idx, neg_idx, gi, n_pos, n_neg, gts, anchors, A, 
     return losses, dscore, dreg
 
 
+def focal_loss_frames(heads, F, l, w, A, pos_idx, neg_idx, gi, counts, gts, gt_off, anchors, alpha, gamma, cls_weight, reg_weight,
+                      want_grads=True):
+    """Focal loss of all frames of a step in three launches and one memset (csrc/loss_frames.hip).  ``heads`` f32 (F*l*w, 8A)
+    contiguous = [A cls logits | 7A regression]; pos_idx / neg_idx i64 (F,3,cap), gi i64 (F,cap), counts i32 (F,2), gts f32
+    (n, >= 7) of all frames back to back, gt_off i32 (F+1,) and anchors f32 [l][w][A][7], all on the device.
+    Returns (losses f32 (F,2) = (cls, reg) per frame, d_heads in the layout of ``heads`` or None without ``want_grads``)."""
+    dev = heads.device
+    assert heads.dtype == torch.float32 and tuple(heads.shape) == (F * l * w, 8 * A)
+    assert tuple(pos_idx.shape) == tuple(neg_idx.shape) == (F, 3, gi.shape[1]) and tuple(gi.shape) == (F, gi.shape[1])
+    assert pos_idx.dtype == neg_idx.dtype == gi.dtype == torch.int64 and counts.dtype == gt_off.dtype == torch.int32
+    assert tuple(counts.shape) == (F, 2) and tuple(gt_off.shape) == (F + 1,) and gts.dtype == anchors.dtype == torch.float32
+    assert gts.dim() == 2 and gts.shape[0] >= 1 and anchors.numel() == l * w * A * 7
+    losses = torch.empty((F, 2), dtype=torch.float32, device=dev)
+    d_heads = torch.empty_like(heads) if want_grads else None
+    nbytes = X.lib.mvx_focal_loss_frames_workspace_bytes(int(F), int(l), int(w), int(A))
+    ws = workspace(nbytes, dev, 'focal_loss')
+    X.check(X.lib.mvx_focal_loss_frames(X.ptr(heads), int(F), int(l), int(w), int(A), X.ptr(pos_idx), X.ptr(neg_idx), X.ptr(gi),
+                                        gi.shape[1], X.ptr(counts), X.ptr(gts), gts.shape[1], X.ptr(gt_off), X.ptr(anchors),
+                                        float(alpha), float(gamma), float(cls_weight), float(reg_weight), X.ptr(d_heads),
+                                        X.ptr(losses), X.ptr(ws), ws.numel(), X.stream()), 'mvx_focal_loss_frames')
+    return losses, d_heads
+
+
 # ---------------------------------------------------------------------------------------------
 # detection output (csrc/detect.hip)
 # ---------------------------------------------------------------------------------------------

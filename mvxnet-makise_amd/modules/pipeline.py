@@ -714,6 +714,8 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     BatchNorm statistics, exactly B reference forwards, train.py:131-161), VoxelLoss per frame, and the whole way back.
     ``targets``: per frame (pi, ni, gi, gt boxes) or None.  Gradients are ADDED into the existing .grad buffers
     (GradBucket).  ``rpn_hip=False`` runs the RPN + loss through the torch modules under autograd instead (comparison).
+    A ``criterion`` that has ``heads_loss_frames`` (voxelnet/FocalLoss.py) computes the loss of all frames in one call on the
+    raw head output, in place of the per-frame VoxelLoss; it needs ``rpn_hip=True``.
     ``prepare_next`` = (next batch, callable returning its targets): voxelized, mapped and target-assigned on the
     preparation stream after this step has been enqueued; returned as out['next'] = (ready, targets) for the next call.
     ``read=False`` leaves the losses on the device (out['losses_dev'] (F,2)) and skips the status read: the caller reads
@@ -723,7 +725,11 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     from modules import frames as fr
     from modules import rpn_frames as rf
     dev = batch.device
-    target_tensors = (x for t in targets if t is not None for x in tuple(t[0]) + tuple(t[1]) + (t[2], t[3])
+    # a criterion for all frames at once on the raw head output (voxelnet/FocalLoss.py) takes the place of heads_loss
+    frames_loss = hasattr(criterion, 'heads_loss_frames')
+    if frames_loss and not rpn_hip:
+        raise _hip.X.MvxHipError('a criterion with heads_loss_frames reads the logits of the frame-set heads: it needs rpn_hip=True')
+    target_tensors =(x for t in targets if t is not None for x in tuple(t[0]) + tuple(t[1]) + (t[2], t[3])
                       if isinstance(x, torch.Tensor) and x.is_cuda)      # written on the preparation stream too (target_fn)
     fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev), also=target_tensors)
     out = {'loss': [], 'cls': [], 'reg': [], 'voxels': counts, 'live': live}
@@ -741,7 +747,10 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
                     fr.cml_forward(model, fs, feat, saved, statuses, want_bev=False)
                     rpn = model.backbone.rpn
                     heads, rs = rf.rpn_forward(rpn, saved.x3, F, saved.D3, saved.H, saved.W, saved.C3)
-                    losses, has_reg, d_heads = heads_loss(heads, F, rs['h1'], rs['w1'], tl, criterion, anchors)
+                    if frames_loss:
+                        losses, has_reg, d_heads = criterion.heads_loss_frames(heads, F, rs['h1'], rs['w1'], tl, anchors)
+                    else:
+                        losses, has_reg, d_heads = heads_loss(heads, F, rs['h1'], rs['w1'], tl, criterion, anchors)
                     if keep is not None:
                         keep.update(x3=saved.x3, heads=heads, geom=(F, saved.D3, saved.H, saved.W, saved.C3, rs['h1'], rs['w1']))
                     g_cl = rf.rpn_backward(rpn, rs, d_heads)

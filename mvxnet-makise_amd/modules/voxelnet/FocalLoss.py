@@ -1,0 +1,108 @@
+"""Focal loss for the RPN heads (Lin et al., "Focal Loss for Dense Object Detection"; the classification loss of SECOND,
+PointPillars and mmdetection3d's MVXNet), for all frames of a step in one HIP call (csrc/loss_frames.hip):
+
+    positive = listed in pi;  ignored = listed in ni (classifyAnchors' NOT-negative anchors) and not positive;  negative = the rest
+    clsLoss = cls_weight / max(1, len(pi)) * ( sum_positive alpha (1-p)^gamma (-log p) + sum_negative (1-alpha) p^gamma (-log(1-p)) )
+    regLoss = reg_weight * VoxelLoss's regLoss               (same targets, SmoothL1, mean over len(pi) * 7)
+
+with p = sigmoid(logit).  It reads the raw head output -- logits, not probabilities: a focal loss from probabilities that
+have saturated to 0 or 1 in f32 cannot be computed -- so it is used through ``heads_loss_frames`` on the frame-set path
+(``pipeline.train_step_full(..., criterion=FocalLoss())``) and not through the reference's per-frame ``forward``.
+"""
+import collections
+
+import numpy as np
+import torch
+from torch import nn
+
+from modules import _hip
+from modules import Extension as X
+
+PackedTargets = collections.namedtuple('PackedTargets', 'pos_idx neg_idx gi counts gts gt_off')
+
+
+def _length(col):
+    return int(col.shape[0]) if hasattr(col, 'shape') else len(col)
+
+
+def _on_device(x):
+    return isinstance(x, torch.Tensor) and x.is_cuda
+
+
+class FocalLoss(nn.Module):
+
+    def __init__(self, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0):
+        super().__init__()
+        self.alpha, self.gamma, self.cls_weight, self.reg_weight = alpha, gamma, cls_weight, reg_weight
+
+    def forward(self, pi, ni, gi, gts, score, reg, anchors, anchorsPerLoc):
+        raise NotImplementedError('FocalLoss needs the logits of the heads, not their probabilities (a focal loss from '
+                                  'probabilities saturated in f32 is not computable): call heads_loss_frames, or pass the '
+                                  'criterion to pipeline.train_step_full')
+
+    @staticmethod
+    def pack_targets(targets, dev):
+        """Per-frame ``(pi, ni, gi, gts)`` or None, as pipeline.train_step_full receives them -> (PackedTargets on ``dev``,
+        has_reg): pos_idx / neg_idx i64 (F,3,cap), gi i64 (F,cap), counts i32 (F,2), gts f32 (max(1,n),7) of all frames
+        back to back, gt_off i32 (F+1,); has_reg = per frame "has a positive".  The three index tensors are slices of ONE
+        buffer, counts and gt_off of another.  Host lists reach the device with one copy per buffer; lists that are already
+        there (Calc.classifyAnchorsFrames) are gathered by one concatenation and one indexed write -- in both cases the number
+        of copies and launches does not depend on F."""
+        F = len(targets)
+        live = [t if t is not None else ((), (), (), None) for t in targets]
+        pis = [t[0] if t[0] is not None and len(t[0]) == 3 else None for t in live]
+        nis = [t[1] if t[1] is not None and len(t[1]) == 3 else None for t in live]
+        n_pos = [0 if p is None else _length(p[0]) for p in pis]
+        n_neg = [0 if n is None else _length(n[0]) for n in nis]
+        cap = max(1, max(n_pos + n_neg))
+        boxes = [t[3] for t in live]
+        meta = np.zeros((3 * F + 1,), np.int32)                    # counts (F,2) | gt_off (F+1,)
+        meta[0:2 * F:2], meta[1:2 * F:2] = n_pos, n_neg
+        meta[2 * F + 1:] = np.cumsum([0 if b is None else int(b.shape[0]) for b in boxes])
+        # one i64 buffer [pos (F,3,cap) | neg (F,3,cap) | gi (F,cap)]; its filled columns as (column, offset) pairs
+        neg0, gi0 = 3 * F * cap, 6 * F * cap
+        cols = []
+        for f in range(F):
+            if n_pos[f]:
+                cols += [(c, (f * 3 + j) * cap) for j, c in enumerate(pis[f])] + [(live[f][2], gi0 + f * cap)]
+            if n_neg[f]:
+                cols += [(c, neg0 + (f * 3 + j) * cap) for j, c in enumerate(nis[f])]
+        if not any(_on_device(c) for c, _ in cols):
+            host = np.zeros((7 * F * cap,), np.int64)
+            for c, off in cols:
+                a = np.asarray(c, dtype=np.int64).reshape(-1)
+                host[off:off + a.shape[0]] = a
+            idx = torch.from_numpy(host).to(dev)
+        else:
+            idx = torch.empty((7 * F * cap,), dtype=torch.int64, device=dev)          # beyond the counts: never read
+            dst = torch.from_numpy(np.concatenate([np.arange(off, off + _length(c), dtype=np.int64) for c, off in cols])).to(dev)
+            idx[dst] = torch.cat([torch.as_tensor(c).to(dev, torch.int64).reshape(-1) for c, _ in cols])
+        rows = [b.detach()[:, :7].float() for b in boxes if b is not None]
+        if not rows:
+            gts = torch.zeros((1, 7), dtype=torch.float32, device=dev)
+        elif any(_on_device(b) for b in rows):
+            gts = torch.cat([b.to(dev) for b in rows]).contiguous()
+        else:
+            gts = torch.cat(rows).contiguous().to(dev)
+        meta = torch.from_numpy(meta).to(dev)
+        packed = PackedTargets(idx[:neg0].view(F, 3, cap), idx[neg0:gi0].view(F, 3, cap), idx[gi0:].view(F, cap),
+                               meta[:2 * F].view(F, 2), gts, meta[2 * F:])
+        return packed, [n > 0 for n in n_pos]
+
+    def heads_loss_frames(self, heads, F, h1, w1, targets, anchors, want_grads=True):
+        """The loss of every frame on the channels-last head output (F*h1*w1, 8A) = [cls logits | reg] and its gradient, in
+        one library call.  Returns (losses (F,2) on the device = (clsLoss, regLoss or 0), per-frame bool "has a regression
+        loss", d_heads) -- the triple of pipeline.heads_loss."""
+        if not heads.is_cuda:
+            raise X.MvxHipError('FocalLoss runs on the GPU (no CPU fallback)')
+        dev = heads.device
+        A = heads.shape[1] // 8
+        packed, has_reg = self.pack_targets(targets, dev)
+        anc = anchors.detach().float().contiguous()
+        if not anc.is_cuda:
+            from modules import Calc
+            anc = Calc._anchors_on(anchors, dev)
+        losses, d_heads = _hip.focal_loss_frames(heads, F, h1, w1, A, packed.pos_idx, packed.neg_idx, packed.gi, packed.counts,
+                                                 packed.gts, packed.gt_off, anc, self.alpha, self.gamma, self.cls_weight,
+                                                 self.reg_weight, want_grads=want_grads)
+        return losses, has_reg, d_heads

@@ -4,6 +4,7 @@ loop, checkpoints and resume), running on this package's HIP modules.
     python train_like.py <dataroot> [-n EPOCHS] [-r LAST] [--steps K] [--mode module|fast] [--frames B] [--synthetic N]
                          [--augment [--gtdatabase DIR]] [--augment-geometry] [--extractor-weights FILE]
                          [--optimizer torch|hip [--clip-grad-norm X] [--lr-schedule constant|cosine --warmup-steps N --lr-min LR]]
+                         [--loss voxel|focal [--focal-alpha A --focal-gamma G --focal-reg-weight W]]
 
 What is the same as train.py: createDataset -> createAnchors / bbox3d2bev -> MVXNet, VoxelLoss, AdamW(lr 1e-3, eps) ->
 per frame lidar2Img + (row, col) swap + group + classifyAnchors -> forward -> clsLoss (+ regLoss) -> backward -> step ->
@@ -20,6 +21,9 @@ from torchvision).
 gradient bucket, the division by the frame count folded in), with global gradient-norm clipping (``--clip-grad-norm``), a guard
 that skips a step with a non-finite gradient on the device, and a warm-up + cosine learning-rate schedule.  Checkpoints keep
 torch.optim.AdamW's format: a run can resume with either optimizer from a checkpoint of the other.
+
+``--loss focal`` (--mode fast only) replaces VoxelLoss by the focal loss of modules/voxelnet/FocalLoss.py: one library call for
+all frames of a step on the logits of the heads; anchors between the two IoU thresholds are ignored.
 
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
@@ -72,7 +76,17 @@ def parse_args(argv=None):
     ap.add_argument('--lr-schedule', choices=['constant', 'cosine'], default='constant', help='--optimizer hip: cosine = linear warm-up, then cosine')
     ap.add_argument('--warmup-steps', type=int, default=0)
     ap.add_argument('--lr-min', type=float, default=0.0)
-    return ap.parse_args(argv)
+    ap.add_argument('--loss', choices=['voxel', 'focal'], default='voxel',
+                    help='voxel: the reference\'s VoxelLoss; focal: modules/voxelnet/FocalLoss.py on the logits of all frames of a '
+                         'step in one call (--mode fast only)')
+    ap.add_argument('--focal-alpha', type=float, default=0.25)
+    ap.add_argument('--focal-gamma', type=float, default=2.0)
+    ap.add_argument('--focal-reg-weight', type=float, default=2.0)
+    args = ap.parse_args(argv)
+    if args.loss == 'focal' and args.mode == 'module':
+        ap.error('--loss focal needs --mode fast: the focal loss reads the logits of the frame-set heads, --mode module hands the '
+                 'criterion probabilities')
+    return args
 
 
 def check_optimizer_args(args):
@@ -194,8 +208,15 @@ def train(args):
     anchorBevs = bbox3d2bev(anchors.reshape(anchors.shape[:2] + (-1, 7))).to(device).contiguous()
     torch.manual_seed(0)
     model = MVXNet().to(device)
-    criterion = VoxelLoss()
-    params = [p for p in model.parameters() if p.requires_grad]
+    if args.loss == 'focal':
+        from modules.voxelnet.FocalLoss import FocalLoss
+        criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight)
+        say('criterion: FocalLoss(alpha=%g, gamma=%g, cls_weight=%g, reg_weight=%g)'
+            % (criterion.alpha, criterion.gamma, criterion.cls_weight, criterion.reg_weight))
+    else:
+        criterion = VoxelLoss()
+        say('criterion: VoxelLoss(a=%g, b=%g)' % (criterion.a, criterion.b))
+    params =[p for p in model.parameters() if p.requires_grad]
     # train.py:64; on the GPU as one fused multi-tensor kernel per step (same update, ~10 launches fewer; bench.py has the numbers)
     hip_opt = args.optimizer == 'hip'
     bucket = parallel.GradBucket(params, late=[model.head.fusion.fcn1.fc.weight]) if args.mode == 'fast' else None
