@@ -656,6 +656,9 @@ int mvx_bn_finalize_frames(const double *stats, double count, double eps, float 
 int mvx_bn_apply_frames(const float *y, const float *mean_inv, float *out, int64_t rows, int32_t channels,
                         const mvx_frames_t *frames_host, int32_t row_kind, void *stream);
 size_t mvx_bn_backward_scratch_bytes_frames(int32_t channels, int32_t n_frames);
+/* A frame without voxels has no population.  Of the row layouts only MVX_ROWS_FUSION still stores a row for it (its shared
+ * padded row, weight 0).  Forward: the in-launch finalisations give such a frame mean 0 and inverse deviation 1/sqrt(eps).
+ * Backward: with finite mean_inv for that frame and zero dyhat on that row, its dz is exactly 0 and it adds nothing to dbias. */
 int mvx_bn_relu_backward_frames(const float *dyhat, const float *y, const float *mean_inv, double count, float *dz,
                                 float *dbias, double *scratch, const float *row_w, int64_t rows, int32_t channels,
                                 int32_t flags, const mvx_frames_t *frames_host, int32_t row_kind,

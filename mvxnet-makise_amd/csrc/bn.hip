@@ -45,7 +45,9 @@ __global__ void bn_apply(const float *__restrict__ y, const float *__restrict__ 
 }
 
 // per-channel sum / sum of squares of a [rows][C] matrix (used when the producer did not
-// already reduce them in its epilogue)
+// already reduce them in its epilogue).  f64 throughout, as row_stats_frames (rpn.hip): var = E[y^2] - mean^2 cancels, and with
+// f32 partials a channel of one constant value c came out with a variance of order 1e-7 c^2 instead of 0 (inverse deviation
+// 920 instead of 1000 at c = 3.7, eps = 1e-6)
 __global__ __launch_bounds__(256) void row_stats(const float *__restrict__ y, double *__restrict__ stats, size_t rows, int C) {
     __shared__ double red[2][256][4];
     const int c4 = C >> 2;
@@ -53,16 +55,17 @@ __global__ __launch_bounds__(256) void row_stats(const float *__restrict__ y, do
     const int ct = threadIdx.x % c4, rt = threadIdx.x / c4;
     for (int cb = 0; cb < c4; cb += 256) {             // C > 1024 -> several column blocks
         const int col = cb + ct;
-        float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
+        double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
         if (rt < rpi && col < c4) {
             for (size_t r = blockIdx.x * (size_t)rpi + rt; r < rows; r += (size_t)gridDim.x * rpi) {
                 const float4 v = *(const float4 *)(y + r * C + col * 4);
-                s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
-                s2.x += v.x * v.x; s2.y += v.y * v.y; s2.z += v.z * v.z; s2.w += v.w * v.w;
+                const double d[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { s1[j] += d[j]; s2[j] += d[j] * d[j]; }
             }
         }
-        red[0][threadIdx.x][0] = s1.x; red[0][threadIdx.x][1] = s1.y; red[0][threadIdx.x][2] = s1.z; red[0][threadIdx.x][3] = s1.w;
-        red[1][threadIdx.x][0] = s2.x; red[1][threadIdx.x][1] = s2.y; red[1][threadIdx.x][2] = s2.z; red[1][threadIdx.x][3] = s2.w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { red[0][threadIdx.x][j] = s1[j]; red[1][threadIdx.x][j] = s2[j]; }
         __syncthreads();
         if (rt == 0 && col < c4) {
             for (int k = 0; k < 2; ++k)
@@ -187,9 +190,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce(const float *__restrict__ d
 #pragma unroll
             for (int rp = 0; rp < 8; ++rp) { sa += v1[rp]; sb += v2[rp]; }
         }
+        // a frame without population (no voxels; MVX_ROWS_FUSION still stores its shared padded row, with weight 0): a = b = 0,
+        // not 0 / 0 -- pass 2 multiplies them by that row's weight, and 0 * NaN would reach dz and the bias gradient of ALL frames
         const double count = fm.count[f];
-        ab[(size_t)f * 2 * C + c] = (float)(sa / count);
-        ab[(size_t)f * 2 * C + C + c] = (float)(sb / count);
+        ab[(size_t)f * 2 * C + c] = count > 0.0 ? (float)(sa / count) : 0.f;
+        ab[(size_t)f * 2 * C + C + c] = count > 0.0 ? (float)(sb / count) : 0.f;
     }
 }
 
@@ -507,6 +512,9 @@ static int bn_relu_backward_impl(const float *dyhat, const float *y, const float
     return MVX_OK;
 }
 
+// Contract for a frame without population (a frame set may hold a frame without voxels; of the row layouts only MVX_ROWS_FUSION
+// then still stores a row for it, its shared padded row, whose weight is 0): mean_inv of that frame must be finite and dyhat of
+// that row zero; the row's dz is then exactly 0 and the frame adds nothing to dbias.  Its sums are not divided by the population.
 extern "C" int mvx_bn_relu_backward_frames(const float *dyhat, const float *y, const float *mean_inv, double count,
                                            float *dz, float *dbias, double *scratch, const float *row_w, int64_t rows,
                                            int32_t channels, int32_t flags, const mvx_frames_t *frames_host,

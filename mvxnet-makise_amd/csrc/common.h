@@ -236,9 +236,11 @@ __device__ __forceinline__ void bn_finalize_core(unsigned *done_counter, unsigne
 #pragma unroll
             for (int rp = 0; rp < CH; ++rp) { s1 += v1[rp]; s2 += v2[rp]; }
         }
+        // a frame without population (no voxels): mean 0 and variance 0, not 0 / 0 -- the shared padded row that MVX_ROWS_FUSION
+        // still stores for it is normalised with these, and a NaN there would reach the next layer's weight gradient
         const double count = count_of(f);
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
+        const double mean = count > 0.0 ? s1 / count : 0.0;
+        double var = count > 0.0 ? s2 / count - mean * mean : 0.0;
         if (var < 0.0) var = 0.0;
         mean_inv[(size_t)f * 2 * C + c] = (float)mean;
         mean_inv[(size_t)f * 2 * C + C + c] = (float)(1.0 / sqrt(var + eps));

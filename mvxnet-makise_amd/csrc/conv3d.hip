@@ -922,8 +922,11 @@ __global__ void wgrad_rank1(const float *__restrict__ T, const float *__restrict
 }
 
 // dW[co][ci][kd][kh][kw] = sum_strips slab[strip][kd][tap][ci][co]
+// zero_block > 0 (2-D, MVX_FLAG_TAPS2 with a parity block of zero_block channels that the weight-gradient kernel could not skip
+// because it is no whole input-channel block of its own, conv_set_taps2): the structurally zero (tap, parity) blocks were
+// executed, and what they hold is the gradient of entries that are zero by definition -- returned as zero, as the header says
 __global__ void wgrad_reduce(const float *__restrict__ slabs, float *__restrict__ dw, int nstrips, int Ci, int accumulate,
-                             int dst2d, Strips ks) {
+                             int dst2d, Strips ks, int zero_block) {
     const size_t per = (size_t)27 * Ci * BN;
     slabs += (size_t)blockIdx.y * nstrips * per;     // 64-channel block of the output channels
     dw += (size_t)blockIdx.y * (dst2d ? per / 3 : per);
@@ -938,6 +941,10 @@ __global__ void wgrad_reduce(const float *__restrict__ slabs, float *__restrict_
         float s = 0.f;
         for (int k = 0; k < nk; ++k) s += slabs[(size_t)k * per + e];
         if (dst2d && kd != 1) continue;             // 2-D kernel gradient: the middle depth slice only
+        if (zero_block > 0) {
+            const int ta = tap / 3, tb = tap % 3;
+            if (ta > 1 || tb > 1 || !((s2d_tap_mask(ci / zero_block) >> (ta * 2 + tb)) & 1u)) s = 0.f;
+        }
         float *dst = dst2d ? dw + (((size_t)co * Ci + ci) * 3 + tap / 3) * 3 + tap % 3
                            : dw + ((((size_t)co * Ci + ci) * 3 + kd) * 3 + tap / 3) * 3 + tap % 3;
         *dst = accumulate ? *dst + s : s;
@@ -1184,7 +1191,7 @@ extern "C" int mvx_conv3d_wgrad(const float *in, const float *dz, float *dw, int
     const size_t per_slab = (size_t)27 * cin * BN;
     hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256), nblk), dim3(256), 0, st, (const float *)workspace, dw,
                        nstrips, cin, flags & MVX_FLAG_ACCUMULATE, (flags & MVX_FLAG_CONV2D) ? 1 : 0,
-                       Strips{{nstrips, nstrips, nstrips}});
+                       Strips{{nstrips, nstrips, nstrips}}, 0);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -1296,7 +1303,7 @@ extern "C" int mvx_conv3d_wgrad_bg_frames(const float *in, const float *dz, floa
     MVX_LAUNCH_CHECK();
     const size_t per_slab = (size_t)27 * cin * BN;
     hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, (const float *)ws.slabs, dw, widest, cin,
-                       flags & MVX_FLAG_ACCUMULATE, 0, ks);
+                       flags & MVX_FLAG_ACCUMULATE, 0, ks, 0);
     MVX_LAUNCH_CHECK();
     hipLaunchKernelGGL(wgrad_rank1, dim3(mvx_cdiv(per_slab, 256)), dim3(256), 0, st, tap_sums, c_in, dw, g);
     MVX_LAUNCH_CHECK();
@@ -1395,7 +1402,7 @@ extern "C" int mvx_conv2d_wgrad_frames(const float *in, const float *dz, float *
     MVX_LAUNCH_CHECK();
     const size_t per_slab = (size_t)27 * cin * BN;
     hipLaunchKernelGGL(wgrad_reduce, dim3(mvx_cdiv(per_slab, 256), nblk), dim3(256), 0, st, (const float *)ws.slabs, dw, nstrips, cin,
-                       flags & MVX_FLAG_ACCUMULATE, 1, ks);
+                       flags & MVX_FLAG_ACCUMULATE, 1, ks, ((flags & MVX_FLAG_TAPS2) && g.s2d == 0 && cin % 4 == 0) ? cin / 4 : 0);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }

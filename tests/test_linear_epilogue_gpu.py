@@ -72,3 +72,45 @@ def test_shared_tile_epilogue(split, K, N):
         print('  frame %d: sums %.3e %.3e, mean %.3e, inverse std %.3e' % ((f,) + errs))
         assert errs[0] < 1e-12 and errs[1] < 1e-12
         assert errs[2] < 2e-5 and errs[3] < 2e-5
+
+
+@pytest.mark.parametrize('split,K,N', [(0, 24, 128), (3, 72, 128)])
+def test_frame_without_voxels_gets_finite_statistics(split, K, N):
+    """The middle frame has no voxels: MVX_ROWS_FUSION still stores its shared padded row (weight 0, population 0).  The
+    finalisation by the last workgroup gives that frame mean 0 and inverse deviation 1 / sqrt(eps) instead of 0 / 0; the live
+    frames keep their statistics."""
+    from modules import _hip
+    from modules import Extension as X
+    F = 3
+    real, vox = [0, 100, 100, 297], [0, 100, 100, 170]
+    g = torch.Generator().manual_seed(7 + split)
+    x = torch.randn((ROWS, K), generator=g).to(DEV)
+    w = (torch.randn((N, K), generator=g) * 0.2).to(DEV)
+    b = (torch.randn((N,), generator=g) * 0.1).to(DEV)
+    desc = X.FramesDesc.make(vox, real, T)
+    count = [float((vox[f + 1] - vox[f]) * T) for f in range(F)]
+    row_w = torch.ones((ROWS,), device=DEV)
+    row_w[-F:] = torch.tensor([count[f] - (real[f + 1] - real[f]) for f in range(F)])
+    assert count[1] == 0 and float(row_w[-2]) == 0
+    y = torch.full((ROWS, N), float('nan'), device=DEV)
+    st = torch.zeros((F, _hip.STATS_REPLICAS, 2, N), dtype=torch.float64, device=DEV)
+    cnt = torch.zeros((1,), dtype=torch.float64, device=DEV)
+    mi = torch.full((F, 2, N), float('nan'), device=DEV)
+    flags = _hip.split_flags(split, True) | _hip.FLAG_RELU
+    X.check(X.lib.mvx_linear_forward_bn_frames(X.ptr(x), K, X.ptr(w), K, 0, X.ptr(b), X.ptr(y), N, X.ptr(st), X.ptr(row_w),
+                                               ROWS, K, N, flags, X.ptr(cnt), EPS, X.ptr(mi), desc.ref(), X.ROWS_FUSION,
+                                               X.stream()), 'mvx_linear_forward_bn_frames')
+    torch.cuda.synchronize()
+    assert not torch.isnan(y).any() and not torch.isnan(mi).any(), 'NaN statistics for the frame without population'
+    assert (mi[1, 0] == 0).all() and rel(mi[1, 1], torch.full((N,), EPS ** -0.5, dtype=torch.float64, device=DEV)) < 1e-6
+    yw = y.double() * row_w.double()[:, None]
+    for f in (0, 2):
+        rows_f = torch.zeros((ROWS,), dtype=torch.bool, device=DEV)
+        rows_f[real[f]:real[f + 1]] = True
+        rows_f[ROWS - F + f] = True
+        s1, s2 = yw[rows_f].sum(0), (yw[rows_f] * y[rows_f].double()).sum(0)
+        mean = s1 / count[f]
+        inv = 1.0 / torch.sqrt((s2 / count[f] - mean * mean).clamp_min(0.0) + EPS)
+        errs = (rel(mi[f, 0], mean), rel(mi[f, 1], inv))
+        print('split %d frame %d: mean %.3e, inverse std %.3e' % ((split, f) + errs))
+        assert errs[0] < 2e-5 and errs[1] < 2e-5
