@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void anchor_window_walk(const float *__restric
     const LP gt = wk.q1, q = wk.q2;
     const float gt_area = load_oriented(gt, gts + (size_t)g * 8);
     load_quad(q, anchors);
-    const float anchor_area = shoelace(q, 4);         // of anchors[0], once, for every cell: the reference's arithmetic
+    const float anchor_area = fabsf(shoelace(q, 4));  // of anchors[0], once, for every cell: the reference's arithmetic
     // Bounding circles: boxes whose centres are further apart than the two half diagonals (+ 1 %) cannot touch.  Their
     // true IoU is 0 and the reference's origin-fan sum gives rounding noise of ~1e-6 there; either ends the walk
     // (iou < 0.1) the same way and neither value is ever output, so those cells skip the clipping.

@@ -103,11 +103,13 @@ __device__ __forceinline__ void load_quad(LP q, const float *src) {
     for (int k = 0; k < 4; ++k) { P2 v; v.x = src[2 * k]; v.y = src[2 * k + 1]; q[k] = v; }
 }
 
-// quad `src` (8 floats) into q (5 slots), oriented for quad_intersection; returns its SIGNED shoelace area, taken before
-// the re-orientation as the reference does (voxelutil.cpp:99-103)
+// quad `src` (8 floats) into q (5 slots), oriented for quad_intersection; returns its shoelace area, taken before the
+// re-orientation as the reference does (voxelutil.cpp:99-103) -- but its magnitude: the reference keeps the sign, which turns
+// the union of a clockwise quad negative (IoU -1 for a box against itself).  Counter-clockwise input, all the reference's own
+// callers produce, is unaffected bit for bit.
 __device__ __forceinline__ float load_oriented(LP q, const float *src) {
     load_quad(q, src);
-    const float area = shoelace(q, 4);
+    const float area = fabsf(shoelace(q, 4));
     orient_ccw(q);
     return area;
 }

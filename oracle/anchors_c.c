@@ -18,6 +18,11 @@
  *            right (v = 1,2,..) then left (v = -1,-2,..) until IoU < 0.1.  IoU >= posThr -> positive
  *            (also listed among the non-negatives), IoU >= negThr -> non-negative only.
  *
+ * One deliberate difference in the areas: the reference puts the SIGNED shoelace areas of the two boxes into the union
+ * (:105,110,112), so a clockwise quad makes the union negative and a box against itself scores -1.  This restatement and the
+ * HIP kernels take the magnitudes.  Counter-clockwise quads -- all that modules/Calc.py bbox3d2bev produces, and every
+ * fixture -- are unaffected bit for bit (fabsf of a positive float).
+ *
  * One call-history dependence of the reference is kept deliberately: the cut routine's scratch polygon is
  * a function-local static (:51), and when the crossing test fails (|s2 - s1| <= eps although the end points
  * classify differently, :44) the scratch slot is consumed without being written, i.e. it keeps the value of
@@ -122,10 +127,10 @@ void oracle_bbox_pairwise(const float *b1, int64_t n, const float *b2, int64_t m
     pt_t q1[5], q2[5];
     for (int64_t i = 0; i < n; i++) {
         load_quad(q1, b1 + i * 8);
-        float a1 = shoelace(q1, 4);
+        float a1 = fabsf(shoelace(q1, 4));     /* magnitude: see the header comment */
         for (int64_t j = 0; j < m; j++) {
             load_quad(q2, b2 + j * 8);
-            float a2 = shoelace(q2, 4);
+            float a2 = fabsf(shoelace(q2, 4));
             float inter = quad_intersection(q1, q2);
             out[i * m + j] = iou ? inter / (a1 + a2 - inter) : inter;
         }
@@ -174,11 +179,11 @@ void oracle_classify_anchors(const float *gts, int64_t G, const float *anchors, 
     lists_t o = {{px, py, pz}, {nx, ny_, nz}, gi, 0, 0};
     pt_t q[5], gt[5];
     load_quad(q, anchors);
-    float anchor_area = shoelace(q, 4);
+    float anchor_area = fabsf(shoelace(q, 4));
     for (int64_t g = 0; g < G; g++) {
         int64_t nl = nls[g], nw = nws[g];
         load_quad(gt, gts + g * 8);
-        float gt_area = shoelace(gt, 4);           /* signed, taken BEFORE any in-place reversal */
+        float gt_area = fabsf(shoelace(gt, 4));    /* taken BEFORE any in-place reversal */
         for (int64_t z = 0; z < A; z++) {
             for (int64_t h = 0; nl + h < L; h++) {
                 if (!visit(anchors, W, A, nl + h, nw, z, gt, gt_area, anchor_area, neg_thr, pos_thr, g, &o)) break;
