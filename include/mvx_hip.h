@@ -876,6 +876,29 @@ int mvx_classify_anchors_frames(const float *gts, const int32_t *gt_off_host, in
                                 float pos_thr, int32_t window_radius, int64_t *pos_idx, int64_t *neg_idx, int64_t *gi,
                                 int64_t cap, int32_t *counts, int32_t *status, void *workspace, size_t workspace_bytes,
                                 void *stream);
+/* Max-IoU anchor assignment (csrc/assign.hip).  The reference has none: its rule is mvx_classify_anchors.
+ * Per frame, iou(g, a) = mvx_bbox_pairwise(gts, anchors, 1)[g][a], or 0 where the two bounding circles are apart:
+ *   positive: max_g iou(g, a) >= pos_thr, matched to the lowest g attaining it; or a = the best anchor (lowest flat index
+ *     (x * w + y) * anchors_per_loc + z) of a ground truth whose best IoU is >= force_thr -- several ground truths on one
+ *     anchor: the largest IoU, ties the lowest g; a forced match overrides the threshold match.  force_thr > 1.5: no forcing.
+ *   not negative: max_g iou(g, a) >= neg_thr, plus every positive.
+ * mvx_assign_anchors_frames: gts f32 [G_total][4][2] of all frames back to back, gt_off_host i32 [n_frames + 1] (HOST memory),
+ *   anchors f32 [l][w][anchors_per_loc][4][2], a regular grid.  No centre cells: they are found on the device, and a centre
+ *   outside the grid only clips the window.  0 < neg_thr <= pos_thr, force_thr > 0, window_radius 1..55.  Output per frame f, every
+ *   anchor at most once per list, in ascending flat index: pos_idx i64 [f][3][cap], gi i64 [f][cap] (local to the frame),
+ *   neg_idx i64 [f][3][cap] (the NOT-negative anchors), counts i32 [f][2]; gt_best f32 [G_total] = the best IoU of every
+ *   ground truth.  status i32 [1], zero on entry, OR-ed: 1 = for some box the window could not be shown to give the result of
+ *   all anchors against all boxes (raise window_radius and replay; the lists are then not to be used), 2 = a list is longer
+ *   than cap (counts clipped, nothing written past cap).  Five launches and one memset for any n_frames and G_total; bitwise
+ *   reproducible.  G_total = 0: counts are zeroed, nothing else is touched.
+ */
+size_t mvx_assign_anchors_frames_workspace_bytes(int32_t n_gt_total, int32_t n_frames, int32_t l, int32_t w,
+                                                 int32_t anchors_per_loc);
+int mvx_assign_anchors_frames(const float *gts, const int32_t *gt_off_host, int32_t n_frames, const float *anchors, int32_t l,
+                              int32_t w, int32_t anchors_per_loc, float neg_thr, float pos_thr, float force_thr,
+                              int32_t window_radius, int64_t *pos_idx, int64_t *neg_idx, int64_t *gi, int64_t cap,
+                              int32_t *counts, float *gt_best, int32_t *status, void *workspace, size_t workspace_bytes,
+                              void *stream);
 int mvx_voxel_loss(const float *score, int64_t score_sl, int64_t score_sw, int64_t score_sa, const float *reg,
                    int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const int64_t *pos_idx, int64_t pos_ld,
                    const int64_t *neg_idx, int64_t neg_ld, const int64_t *gi, const int32_t *counts_dev, int32_t n_pos,

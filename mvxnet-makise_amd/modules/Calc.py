@@ -143,6 +143,99 @@ def classifyAnchorsFrames(frames, anchors: torch.Tensor, velorange: Sequence[flo
     return out
 
 
+_RADIUS_CACHE = {}
+
+
+def _anchor_radius(anchors: torch.Tensor) -> int:
+    """First window radius of assignAnchorsFrames from the anchor table alone (a constant of the run, read once): the
+    anchor's diagonal for both boxes, plus 2 cells, at most 55.  A larger box makes the kernel report status 1 and the call
+    is replayed with twice the radius."""
+    key = (anchors.data_ptr(), tuple(anchors.shape), str(anchors.device))
+    hit = _RADIUS_CACHE.get(key)
+    if hit is None or hit[0]() is not anchors:
+        import weakref
+        corner = anchors[:2, :2].detach().float().cpu()
+        hit = (weakref.ref(anchors), _window_radius(corner[0, 0], corner))
+        _RADIUS_CACHE.clear()
+        _RADIUS_CACHE[key] = hit
+    return hit[1]
+
+
+def assignAnchorsFrames(frames, anchors: torch.Tensor, negThr: float = 0.45, posThr: float = 0.6, forceThr: float = 0.1,
+                        device=None, info=None):
+    """Max-IoU assignment (csrc/assign.hip) for the frames of a step: an anchor is positive when its best IoU
+    over the frame's boxes is >= posThr, or when it is the best anchor of a box whose best IoU is >= forceThr (forceThr > 1.5:
+    thresholds only); not negative from negThr.  Every anchor at most once per list, in ascending (x, y, z) order.
+
+    ``frames`` and the result are those of classifyAnchorsFrames: per frame ``(gts (G,4,2), gtCenters)`` or None in (the centres
+    are not used: the kernel finds the centre cells, and a centre outside the grid is no error), ``(pi, ni, gi)`` or None out.
+    Boxes that are device tensors stay on the device.  One host read per group of MAX_FRAMES frames (counts, status and the
+    best IoU of every box together).  ``info`` (a dict) receives 'gt_best': per frame the best IoU of every box (CPU f32) or
+    None, 'forced_only': the boxes whose best IoU lies in [forceThr, posThr) -- they owe their positive to the forced match --
+    and 'none': the boxes below both (a box whose anchors all went to a box with an equal or better claim is not counted)."""
+    if not (0.0 < negThr <= posThr):
+        raise ValueError('assignAnchors: need 0 < negThr <= posThr, got %r, %r' % (negThr, posThr))
+    if not forceThr > 0.0:
+        raise ValueError('assignAnchors: need forceThr > 0 (above 1.5 = no forced match), got %r' % (forceThr,))
+    live = [k for k, fr in enumerate(frames) if fr is not None and fr[0].shape[0] > 0]
+    out = [None] * len(frames)
+    if info is not None:
+        info.update(gt_best=[None] * len(frames), forced_only=0, none=0)
+    if not live:
+        return out
+    dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
+    a_dev = anchors if anchors.is_cuda else _anchors_on(anchors, dev)
+    boxes = [frames[k][0].detach().float().reshape(-1, 4, 2) for k in live]
+    if any(b.is_cuda for b in boxes):
+        g_dev = torch.cat([b.to(dev) for b in boxes]).contiguous()
+    else:
+        g_dev = torch.cat(boxes).contiguous().to(dev)
+    off = [0]
+    for b in boxes:
+        off.append(off[-1] + b.shape[0])
+    radius = _anchor_radius(anchors)
+    step = X.MAX_FRAMES
+    for lo in range(0, len(live), step):
+        ids = live[lo:lo + step]
+        sub_off = [o - off[lo] for o in off[lo:lo + len(ids) + 1]]
+        sl = slice(off[lo], off[lo + len(ids)])
+        while True:
+            pos, neg, gi, host_dev = _hip.assign_anchors_frames(g_dev[sl], sub_off, a_dev, negThr, posThr, forceThr, radius)
+            host = host_dev.cpu()                                            # the one host read of the group
+            st = int(host[2 * len(ids)])
+            if st & 1 and radius < 55:              # a box much larger than an anchor: widen the window and replay
+                radius = min(55, radius * 2)
+                continue
+            break
+        if st & 1:
+            raise X.MvxHipError('assignAnchors: a ground truth overlaps anchors more than 55 cells from its centre '
+                                '(or the anchor table is no regular grid)')
+        counts = host[:2 * len(ids)].tolist()
+        best = host[2 * len(ids) + 1:].view(torch.float32)
+        for j, k in enumerate(ids):
+            n_pos, n_neg = counts[2 * j], counts[2 * j + 1]
+            out[k] = ((pos[j, 0, :n_pos], pos[j, 1, :n_pos], pos[j, 2, :n_pos]),
+                      (neg[j, 0, :n_neg], neg[j, 1, :n_neg], neg[j, 2, :n_neg]), gi[j, :n_pos])
+            if info is not None:
+                b = best[sub_off[j]:sub_off[j + 1]].clone()
+                forced = (b >= forceThr) & (b < posThr) if forceThr <= 1.5 else torch.zeros_like(b, dtype=torch.bool)
+                info['gt_best'][k] = b
+                info['forced_only'] += int(forced.sum())
+                info['none'] += int(((b < posThr) & ~forced).sum())
+    return out
+
+
+def assignAnchors(gts: torch.Tensor, anchors: torch.Tensor, negThr: float = 0.45, posThr: float = 0.6, forceThr: float = 0.1,
+                  device=None, info=None):
+    """assignAnchorsFrames for one frame: ``(pi, ni, gi)``, three empty lists for a frame without boxes."""
+    res = assignAnchorsFrames([(gts, None)], anchors, negThr, posThr, forceThr, device, info)[0]
+    if res is None:
+        dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
+        e = torch.empty((0,), dtype=torch.int64, device=dev)
+        return (e, e, e), (e, e, e), e
+    return res
+
+
 _ANCHOR_CACHE = {}
 
 

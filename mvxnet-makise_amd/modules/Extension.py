@@ -167,6 +167,9 @@ PROTOTYPES = {
     'mvx_classify_anchors_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'mvx_classify_anchors': (_i32, [_p, _i32, _p, _i32, _i32, _i32, _p, _p, _f32, _f32, _i32, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     'mvx_classify_anchors_frames': (_i32, [_p, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _f32, _f32, _i32, _p, _p, _p, _i64, _p, _p, _p, _sz, _p]),
+    'mvx_assign_anchors_frames_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    'mvx_assign_anchors_frames': (_i32, [_p, _p, _i32, _p, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _p, _p, _p, _i64, _p, _p, _p, _p,
+                                         _sz, _p]),
     'mvx_voxel_loss': (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _i32, _p,
                               _i32, _i32, _i32, _f32, _f32, _f32, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
     'mvx_focal_loss_frames_workspace_bytes': (_i64, [_i32, _i32, _i32, _i32]),

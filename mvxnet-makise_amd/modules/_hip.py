@@ -1912,6 +1912,32 @@ def classify_anchors_frames(gts, gt_off, anchor_bevs, nls, nws, neg_thr, pos_thr
     return pos, neg, gi, counts, status
 
 
+def assign_anchors_frames(gts, gt_off, anchor_bevs, neg_thr, pos_thr, force_thr, radius, cap=None):
+    """Max-IoU assignment (csrc/assign.hip) of the frames of a step: gts (G_total,4,2) of all frames back to back, ``gt_off`` host
+    list (F+1).  Returns (pos_idx i64 (F,3,cap), neg_idx i64 (F,3,cap), gi i64 (F,cap), host = i32 (2F + 1 + G_total): counts
+    (F,2), status, then the bits of gt_best f32 (G_total) -- ONE device tensor, so that the caller reads them together)."""
+    import ctypes
+    F = len(gt_off) - 1
+    G = int(gt_off[-1])
+    L, W, A = anchor_bevs.shape[:3]
+    dev = anchor_bevs.device
+    wn = 2 * radius + 1
+    gmax = max(gt_off[f + 1] - gt_off[f] for f in range(F))
+    cap = max(1, min(L * W * A, gmax * A * wn * wn)) if cap is None else int(cap)
+    pos = torch.empty((F, 3, cap), dtype=torch.int64, device=dev)
+    neg = torch.empty((F, 3, cap), dtype=torch.int64, device=dev)
+    gi = torch.empty((F, cap), dtype=torch.int64, device=dev)
+    host = torch.zeros((2 * F + 1 + G,), dtype=torch.int32, device=dev)
+    counts, status, best = host[:2 * F], host[2 * F:2 * F + 1], host[2 * F + 1:]
+    ws = workspace(X.lib.mvx_assign_anchors_frames_workspace_bytes(G, F, L, W, A), dev, 'anchors')
+    off = (ctypes.c_int32 * (F + 1))(*[int(v) for v in gt_off])
+    X.check(X.lib.mvx_assign_anchors_frames(X.ptr(gts), off, F, X.ptr(anchor_bevs), L, W, A, float(neg_thr), float(pos_thr),
+                                            float(force_thr), int(radius), X.ptr(pos), X.ptr(neg), X.ptr(gi), cap, X.ptr(counts),
+                                            X.ptr(best) if G else None, X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
+            'mvx_assign_anchors_frames')
+    return pos, neg, gi, host
+
+
 def voxel_loss(score, reg, pos_idx, neg_idx, gi, n_pos, n_neg, gts, anchors, A, a, b, eps, want_grads=True,
                dscore_out=None, dreg_out=None):
     """score (L,W,A) / reg (L,W,7A) f32 views with arbitrary strides; pos_idx / neg_idx i64 (3,cap) or None.

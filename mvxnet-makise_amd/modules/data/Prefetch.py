@@ -39,15 +39,18 @@ class _Staging:
 
 
 class PrefetchLoader:
-    def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1, augment=None, geometry=None):
+    def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1, augment=None, geometry=None,
+                 assigner=None):
         """``groups``: iterable of lists of frames as ``modules.data.Load.createDataset`` returns them; ``names_of(frame)``:
         the frame's name (for ``fpn_fn``); ``fpn_fn(name, device)``: the frame's FPN maps (the frozen extractor or its
-        stand-in); ``cap_points``: point capacity per frame of the resident batch."""
+        stand-in); ``cap_points``: point capacity per frame of the resident batch; ``assigner``: pipeline.batch_from_dataset's (None =
+        the reference's classifyAnchors, otherwise a callable ``frames -> lists``)."""
         self.groups = iter(groups)
         self.names_of, self.device, self.anchor_bevs, self.fpn_fn = names_of, device, anchor_bevs, fpn_fn
         self.cap = int(cap_points)
         self.augment = augment          # pipeline.batch_from_dataset's ``augment``: the GT paste then runs on the training stream
         self.geometry = geometry        # ... and its ``geometry``: the geometric augmentation, behind the paste or alone
+        self.assigner = assigner
         self.stream = torch.cuda.Stream(device=device, priority=priority)
         self.q = queue.Queue(maxsize=max(1, depth))
         self.slots = {}
@@ -69,6 +72,11 @@ class PrefetchLoader:
         elif st.free is not None:
             st.free.synchronize()                                # its previous copies have left the host buffers
         return st
+
+    def _assign(self, boxes):
+        if self.assigner is not None:
+            return self.assigner(boxes)
+        return Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)
 
     def _prepare(self, group):
         import time
@@ -94,7 +102,7 @@ class PrefetchLoader:
             targets = [None] * B
             if self.augment is None and self.geometry is None:          # with an augmentation the boxes are only known after it (__next__)
                 boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
-                lists = Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)      # one pass, one host read
+                lists = self._assign(boxes)                     # one pass, one host read
                 targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
             ev = torch.cuda.Event()
             ev.record(self.stream)
@@ -172,6 +180,6 @@ class PrefetchLoader:
             noise, glob, iou_thr = Geometry.geometry_draws(self.geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
             res = Geometry.augmentGeometryFrames(batch, [d[3] for d in group], noise, glob, iou_thr=iou_thr)
         if self.augment is not None or self.geometry is not None:
-            lists = Calc.classifyAnchorsFrames(res.boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)
+            lists = self._assign(res.boxes)
             targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, res.bbox3d)]
         return batch, targets

@@ -605,7 +605,7 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
 
 
 # ---- whole model on the fast path: frame sets up to the BEV map, RPN + VoxelLoss per frame ------------------------------
-def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None, geometry=None):
+def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None, geometry=None, assigner=None):
     """Frames of ``modules.data.Load.createDataset`` -> (FrameBatch resident on the GPU, per-frame targets).  Per frame, as
     train.py:26-49: lidar2Img on the torch path + (row, col) swap, the shuffle permutation drawn with np.random, and
     classifyAnchors for the 'Car' boxes; (pi, ni, gi, gt) or None when the frame has no box.
@@ -618,7 +618,9 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     ``geometry`` (default None: off): a Geometry.GeomParams, or ``{'params': GeomParams, 'rng': np.random.Generator}`` (optional
     keys 'noise', 'glob': the draws themselves, 'keep': a dict that receives the GeomResult): the geometric augmentation
     (modules/augment/Geometry.py: per-object noise, global rotation / scaling / flip, range filter) after the projection --
-    behind the paste inside its one host read with ``augment``, three launches and one host read of its own without."""
+    behind the paste inside its one host read with ``augment``, three launches and one host read of its own without.
+    ``assigner`` (default None: the reference's classifyAnchors at 0.45 / 0.6): a callable ``frames -> lists`` in its place, such
+    as ``lambda frames: Calc.assignAnchorsFrames(frames, anchorBevs)``."""
     import numpy as np
     extractor = augment.get('extractor') if augment is not None else None
     from modules import Calc
@@ -669,7 +671,7 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     if geo is not None and isinstance(geometry, dict) and geometry.get('keep') is not None:
         geometry['keep']['result'] = geo
     # target assignment of all frames in one kernel pass / one host read
-    lists = Calc.classifyAnchorsFrames(boxes, anchorBevs, cfg.velorange, 0.45, 0.6)
+    lists = Calc.classifyAnchorsFrames(boxes, anchorBevs, cfg.velorange, 0.45, 0.6) if assigner is None else assigner(boxes)
     targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, gts)]
     return batch.mark_created(), targets
 

@@ -79,6 +79,11 @@ def parse_args(argv=None):
     ap.add_argument('--loss', choices=['voxel', 'focal'], default='voxel',
                     help='voxel: the reference\'s VoxelLoss; focal: modules/voxelnet/FocalLoss.py on the logits of all frames of a '
                          'step in one call (--mode fast only)')
+    ap.add_argument('--targets', choices=['reference', 'maxiou'], default='reference',
+                    help='reference: the reference\'s classifyAnchors; maxiou: Calc.assignAnchorsFrames (thresholds 0.45 / 0.6 on the '
+                         'best box of every anchor, plus the best anchor of every box)')
+    ap.add_argument('--force-iou', type=float, default=0.1,
+                    help='--targets maxiou: a box whose best IoU reaches this gets its best anchor as a positive (2 = thresholds only)')
     ap.add_argument('--focal-alpha', type=float, default=0.25)
     ap.add_argument('--focal-gamma', type=float, default=2.0)
     ap.add_argument('--focal-reg-weight', type=float, default=2.0)
@@ -86,6 +91,8 @@ def parse_args(argv=None):
     if args.loss == 'focal' and args.mode == 'module':
         ap.error('--loss focal needs --mode fast: the focal loss reads the logits of the frame-set heads, --mode module hands the '
                  'criterion probabilities')
+    if args.force_iou <= 0:
+        ap.error('--force-iou must be positive (2 = thresholds only)')
     return args
 
 
@@ -124,10 +131,11 @@ def have_torchvision():
         return False
 
 
-def cputask(data, anchorBevs, cfg, gtwithinfo=None, geometry=None):
+def cputask(data, anchorBevs, cfg, gtwithinfo=None, geometry=None, assigner=None):
     """train.py:26-49: (GT-paste augmentation when ``gtwithinfo`` is given,) projection, (row, col) swap, voxelization,
     target assignment.  ``geometry`` = {'params', 'rng'}: the geometric augmentation between the projection and the grouping,
-    so that every point keeps the pixel it was seen at."""
+    so that every point keeps the pixel it was seen at.  ``assigner`` (``frames -> lists``, --targets maxiou) takes the place of
+    classifyAnchors, as one frame."""
     from modules.Calc import classifyAnchors
     from modules.data import Preprocessing as pre
     from modules.utils import lidar2Img
@@ -150,7 +158,10 @@ def cputask(data, anchorBevs, cfg, gtwithinfo=None, geometry=None):
         pcd6, bbox3d, bev = augmentGeometry(pcd6, bbox3d, params=geometry.get('params'), rng=geometry['rng'])
     voxel, idx = pre.group(pcd6, cfg.velorange, cfg.voxelsize, cfg.samplenum)
     if bev is not None and bev.shape[0] != 0:
-        pi, ni, gi = classifyAnchors(bev, bbox3d[:, [0, 1]], anchorBevs, cfg.velorange, 0.45, 0.6)
+        if assigner is not None:
+            pi, ni, gi = assigner([(bev, bbox3d[:, [0, 1]])])[0]
+        else:
+            pi, ni, gi = classifyAnchors(bev, bbox3d[:, [0, 1]], anchorBevs, cfg.velorange, 0.45, 0.6)
     else:
         pi, ni, gi = None, None, None
     return voxel, idx, img, bbox3d, bev, pi, ni, gi, calib
@@ -206,6 +217,17 @@ def train(args):
 
     anchors = pre.createAnchors(cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2, cfg.velorange, cfg.carsize)
     anchorBevs = bbox3d2bev(anchors.reshape(anchors.shape[:2] + (-1, 7))).to(device).contiguous()
+    assigner, assign_stats = None, {'boxes': 0, 'forced_only': 0, 'none': 0}
+    if args.targets == 'maxiou':
+        from modules.Calc import assignAnchorsFrames
+
+        def assigner(frames):
+            info = {}
+            lists = assignAnchorsFrames(frames, anchorBevs, 0.45, 0.6, args.force_iou, info=info)
+            assign_stats['boxes'] += sum(b.numel() for b in info['gt_best'] if b is not None)
+            assign_stats['forced_only'] += info['forced_only']
+            assign_stats['none'] += info['none']
+            return lists
     torch.manual_seed(0)
     model = MVXNet().to(device)
     if args.loss == 'focal':
@@ -272,7 +294,7 @@ def train(args):
         clsCnt = regCnt = 0
         if args.mode == 'module':
             for i, data in enumerate(mine):
-                voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo, geo)
+                voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo, geo, assigner)
                 calib = {k: torch.Tensor(calibCpu[k]).to(device) for k in calibCpu}
                 idx4 = np.concatenate([np.zeros((idx.shape[0], 1)), idx], axis=1)
                 opt.zero_grad()
@@ -332,14 +354,15 @@ def train(args):
                             yield None, None
                         else:
                             yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_fn, cap_points=cap,
-                                                        augment=aug, geometry=geo)
+                                                        augment=aug, geometry=geo, assigner=assigner)
                 loader = batches()
             else:
                 # batch k+1 is prepared by a worker thread on its own stream while step k runs (the reference overlaps its CPU
                 # preparation with a process pool, train.py:185-187)
                 from modules.data.Prefetch import PrefetchLoader
                 loader = PrefetchLoader(groups, lambda d: names[id(d)], device, anchorBevs, fpn_fn, cap,
-                                        depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug, geometry=geo)
+                                        depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug, geometry=geo,
+                                        assigner=assigner)
             pending = None                        # the losses of a step are read one step later: the host never waits for
                                                   # the step it has just enqueued
 
@@ -395,6 +418,10 @@ def train(args):
             say('Epoch%d: %d frames in %.2f s = %.1f frames/s (all ranks, %s)'
                 % (epoch + args.lastiter + 1, frames_epoch, loop_s, frames_epoch / max(loop_s, 1e-9),
                    'prefetch thread' if args.prefetch else 'batches prepared inside the step'))
+        if assigner is not None:
+            say('Epoch%d targets: %d boxes, %d with only a forced positive, %d with none'
+                % (epoch + args.lastiter + 1, assign_stats['boxes'], assign_stats['forced_only'], assign_stats['none']))
+            assign_stats.update(boxes=0, forced_only=0, none=0)
         report_optimizer(epoch + args.lastiter + 1)
         if rank == 0:
             n = epoch + args.lastiter + 1
