@@ -899,6 +899,51 @@ int mvx_assign_anchors_frames(const float *gts, const int32_t *gt_off_host, int3
                               int32_t window_radius, int64_t *pos_idx, int64_t *neg_idx, int64_t *gi, int64_t cap,
                               int32_t *counts, float *gt_best, int32_t *status, void *workspace, size_t workspace_bytes,
                               void *stream);
+/* Ignore regions for anchor targets (csrc/ignore.hip).  The reference has none.  Both losses give an anchor that
+ * neg_idx (the NOT-negative anchors) lists and pos_idx does not no classification loss; these two calls put more anchors there.
+ *
+ * mvx_box_point_counts_frames: counts i32 [n_boxes_total] = the points inside every box, all frames in one launch and one memset.
+ *   points6 f32 [n_frames][cap_points][ld >= 3] (x y z first), n_points i32 [n_frames] on the device (taken as
+ *   min(max(n, 0), cap_points); rows at or beyond it are never read), boxes f32 [n_boxes_total][7] xyzlwhr (z = bottom face) of
+ *   all frames back to back, gt_off i32 [n_frames + 1] on the DEVICE.  The decision is the f64 one of the GT-database crop and
+ *   the per-object augmentation (csrc/box3d.h, edges inclusive; cos / sin of the yaw in f64).  Integer sums: bitwise
+ *   reproducible.  No host read.  n_boxes_total = 0: nothing is touched.
+ *
+ * mvx_ignore_anchors_frames: rewrites the lists of mvx_assign_anchors_frames (pos_idx / neg_idx i64 [n_frames][3][cap], gi i64
+ *   [n_frames][cap], counts i32 [n_frames][2], all on the device, every anchor at most once per list; entries beyond a frame's
+ *   count are never read, an entry outside the grid is skipped).  Per frame f, anchors_per_loc 1..4:
+ *     sparse:    a box g of the frame with gt_points[gt_off[f] + g] < min_points (gt_points i32 [G_total] and gt_off i32
+ *                [n_frames + 1] on the device; gt_points NULL: no box is sparse).
+ *     demotion:  a pos_idx entry whose gi names a sparse box leaves the positive list and stays not negative; no rematch.
+ *     rectangle: an anchor not yet not negative becomes not negative when its centre (x, y, z + h/2) of anchors f32
+ *                [l][w][A][7], through M = img_from_lidar f64 [n_frames][3][4] as
+ *                    row_r = ((M[r][0] * x + M[r][1] * y) + M[r][2] * (z + h / 2)) + M[r][3]      (f64, no fused multiply-add)
+ *                has row_2 > 0 and (row_0 / row_2, row_1 / row_2) inside one of rects f32 [R_total][4] = (x1, y1, x2, y2) pixels
+ *                of the frame (rect_off i32 [n_frames + 1] on the device), edges inclusive.  rects NULL: none.
+ *     box:       an anchor still not not negative becomes not negative when, for a quad b of ign_quads f32 [B_total][4][2] of the
+ *                frame (ign_off i32 [n_frames + 1] on the device), inter(b, a) >= ioa_thr * area(a) in f32: inter =
+ *                mvx_bbox_pairwise(b, a, 0) on anchor_quads f32 [l][w][A][4][2], or 0 where the two bounding circles are apart;
+ *                area(a) = the magnitude of the f32 shoelace area.  Intersection over the ANCHOR's area.  ign_quads NULL: none.
+ *   Out: pos_out / neg_out i64 [n_frames][3][cap_out], gi_out i64 [n_frames][cap_out] (local to the unchanged box array),
+ *   counts_out i32 [n_frames][2]: the kept positives and the union of the not-negative anchors, every anchor at most once, in
+ *   ascending flat index; stats i32 [n_frames][4] = (demoted positives, anchors newly ignored by a rectangle, newly ignored by a
+ *   box only, sparse boxes); status i32 [1], OR-ed: 2 = a list is longer than cap_out (counts clipped, nothing written past it).
+ *   With no source at all the output lists equal the input lists.  Four launches and one memset for any n_frames; integer
+ *   atomics only: bitwise reproducible.  MVX_EINVAL before any launch: a NULL required pointer (gt_off with gt_points, rect_off
+ *   and img_from_lidar with rects, ign_off with ign_quads), n_frames outside 1..MVX_MAX_FRAMES, anchors_per_loc outside 1..4,
+ *   cap or cap_out < 1, ioa_thr outside (0, 1], min_points < 0, a workspace smaller than
+ *   mvx_ignore_anchors_frames_workspace_bytes(n_frames, l, w, anchors_per_loc).
+ */
+int mvx_box_point_counts_frames(const float *points6, int32_t n_frames, int32_t cap_points, int32_t ld, const int32_t *n_points,
+                                const float *boxes, const int32_t *gt_off, int32_t n_boxes_total, int32_t *counts, void *stream);
+size_t mvx_ignore_anchors_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc);
+int mvx_ignore_anchors_frames(const int64_t *pos_idx, const int64_t *neg_idx, const int64_t *gi, int64_t cap,
+                              const int32_t *counts, int32_t n_frames, const int32_t *gt_off, const int32_t *gt_points,
+                              int32_t min_points, const float *anchors, const float *anchor_quads, int32_t l, int32_t w,
+                              int32_t anchors_per_loc, const float *rects, const int32_t *rect_off,
+                              const double *img_from_lidar, const float *ign_quads, const int32_t *ign_off, float ioa_thr,
+                              int64_t *pos_out, int64_t *neg_out, int64_t *gi_out, int64_t cap_out, int32_t *counts_out,
+                              int32_t *stats, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 int mvx_voxel_loss(const float *score, int64_t score_sl, int64_t score_sw, int64_t score_sa, const float *reg,
                    int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const int64_t *pos_idx, int64_t pos_ld,
                    const int64_t *neg_idx, int64_t neg_ld, const int64_t *gi, const int32_t *counts_dev, int32_t n_pos,

@@ -161,8 +161,162 @@ def _anchor_radius(anchors: torch.Tensor) -> int:
     return hit[1]
 
 
+class IgnoreRegions:
+    """The ignore sources of the frames of a step (csrc/ignore.hip), per frame and each optional (None or empty):
+    ``rects`` (R,4) = (x1, y1, x2, y2) pixels -- DontCare rectangles -- with ``matrix`` (3,4) float64, LiDAR -> image;
+    ``quads`` (B,4,2) BEV corners of look-alike boxes; ``boxes3d`` (G,7) the frame's Car boxes, whose points ``count_points``
+    counts: a box with fewer than ``min_points`` (0 = off) is sparse.  ``anchors`` (l,w,A,7): the table whose BEV corners the
+    assigner gets (needed by the rectangle rule: the anchor's centre).  ``ioa_thr``: intersection over the ANCHOR's area from which
+    a look-alike box shields an anchor.  ``gt_points``: per frame i32 (G,) on the device or None, set by ``count_points``."""
+
+    def __init__(self, n_frames, anchors=None, rects=None, matrix=None, quads=None, boxes3d=None, min_points=0, ioa_thr=0.5):
+        def per_frame(v):
+            v = [None] * n_frames if v is None else list(v)
+            if len(v) != n_frames:
+                raise ValueError('IgnoreRegions: %d entries for %d frames' % (len(v), n_frames))
+            return v
+        if not 0.0 < float(ioa_thr) <= 1.0:
+            raise ValueError('IgnoreRegions: need 0 < ioa_thr <= 1, got %r' % (ioa_thr,))
+        if int(min_points) < 0:
+            raise ValueError('IgnoreRegions: need min_points >= 0, got %r' % (min_points,))
+        self.n_frames, self.anchors = n_frames, anchors
+        self.rects, self.matrix, self.quads, self.boxes3d = per_frame(rects), per_frame(matrix), per_frame(quads), per_frame(boxes3d)
+        self.min_points, self.ioa_thr = int(min_points), float(ioa_thr)
+        self.gt_points = [None] * n_frames
+        for k in range(n_frames):
+            if _rows(self.rects[k]) and self.matrix[k] is None:
+                raise ValueError('IgnoreRegions: frame %d has rectangles and no matrix' % k)
+        if any(_rows(r) for r in self.rects) and anchors is None:
+            raise ValueError('IgnoreRegions: the rectangle rule needs the anchors (l,w,A,7)')
+
+    def has_source(self, k):
+        return bool(_rows(self.rects[k]) or _rows(self.quads[k]))
+
+    def count_points(self, points6, n_points):
+        """Counts the points of ``points6`` f32 (F, cap, ld) / ``n_points`` i32 (F,) (device) inside ``boxes3d``: one launch and
+        one memset per MAX_FRAMES frames, no host read.  Nothing to do with ``min_points`` = 0."""
+        self.gt_points = [None] * self.n_frames
+        if self.min_points <= 0 or not any(_rows(b) for b in self.boxes3d):
+            return self
+        dev = points6.device
+        for lo in range(0, self.n_frames, X.MAX_FRAMES):
+            ids = list(range(lo, min(self.n_frames, lo + X.MAX_FRAMES)))
+            sizes = [_rows(self.boxes3d[k]) for k in ids]
+            if not any(sizes):
+                continue
+            off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+            b = torch.cat([torch.as_tensor(self.boxes3d[k]).detach().float()[:, :7].to(dev) for k in ids if _rows(self.boxes3d[k])])
+            counts = _hip.box_point_counts_frames(points6[lo:lo + len(ids)], n_points[lo:lo + len(ids)], b.contiguous(),
+                                                  torch.from_numpy(off).to(dev))
+            for j, k in enumerate(ids):
+                if sizes[j]:
+                    self.gt_points[k] = counts[int(off[j]):int(off[j + 1])]
+        return self
+
+
+def _rows(t):
+    return 0 if t is None else int(t.shape[0])
+
+
+def _cat_rows(items, shape, dtype, dev):
+    """Per-frame tensors / arrays / None -> (their rows back to back on ``dev`` or None when there is none, offsets i32 on ``dev``)."""
+    sizes = [_rows(t) for t in items]
+    if not any(sizes):
+        return None, None
+    parts = [torch.as_tensor(t).detach().to(dtype).reshape((-1,) + shape).to(dev) for t in items if _rows(t)]
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    return torch.cat(parts).contiguous(), off
+
+
+def _assign_with_ignore(frames, anchors, negThr, posThr, forceThr, device, info, ignore):
+    """assignAnchorsFrames with an IgnoreRegions: the ignore pass runs on the raw device lists of the assigner and its counts,
+    stats and status ride in the group's one host read."""
+    if ignore.n_frames != len(frames):
+        raise ValueError('assignAnchors: the IgnoreRegions hold %d frames, the call %d' % (ignore.n_frames, len(frames)))
+    n_box = [0 if fr is None else int(fr[0].shape[0]) for fr in frames]
+    live = [k for k in range(len(frames)) if n_box[k] > 0 or ignore.has_source(k)]
+    out = [None] * len(frames)
+    if info is not None:
+        info.update(gt_best=[None] * len(frames), forced_only=0, none=0, ignore_stats=[0, 0, 0, 0])
+    if not live:
+        return out
+    dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
+    a_dev = anchors if anchors.is_cuda else _anchors_on(anchors, dev)
+    an7 = None
+    if ignore.anchors is not None:
+        an7 = ignore.anchors.detach().float().contiguous() if ignore.anchors.is_cuda else _anchors7_on(ignore.anchors, dev)
+        if an7.numel() != a_dev.numel() // 8 * 7:
+            raise ValueError('assignAnchors: the IgnoreRegions hold another anchor table')
+    else:
+        an7 = torch.zeros((a_dev.numel() // 8 * 7,), dtype=torch.float32, device=dev)       # never read: no rectangle
+    radius = _anchor_radius(anchors)
+    step = X.MAX_FRAMES
+    for lo in range(0, len(live), step):
+        ids = live[lo:lo + step]
+        F = len(ids)
+        sub_off = [0]
+        for k in ids:
+            sub_off.append(sub_off[-1] + n_box[k])
+        boxes = [frames[k][0].detach().float().reshape(-1, 4, 2).to(dev) for k in ids if n_box[k] > 0]
+        g_dev = torch.cat(boxes).contiguous() if boxes else torch.zeros((0, 4, 2), dtype=torch.float32, device=dev)
+        # the sources of the group, on the device once (a replay reuses them)
+        rects, rect_off = _cat_rows([ignore.rects[k] for k in ids], (4,), torch.float32, dev)
+        quads, quad_off = _cat_rows([ignore.quads[k] for k in ids], (4, 2), torch.float32, dev)
+        mats = None
+        if rects is not None:
+            m = np.zeros((F, 3, 4), np.float64)
+            for j, k in enumerate(ids):
+                if ignore.matrix[k] is not None:
+                    m[j] = np.asarray(ignore.matrix[k], np.float64).reshape(3, 4)
+            mats = torch.from_numpy(m).to(dev)
+        gt_points = gt_off = None
+        if ignore.min_points > 0 and any(ignore.gt_points[k] is not None for k in ids):
+            parts = []
+            for k in ids:
+                p = ignore.gt_points[k]
+                if n_box[k] and (p is None or p.shape[0] != n_box[k]):
+                    raise ValueError('assignAnchors: frame %d holds %d boxes, its point counts are for %s'
+                                     % (k, n_box[k], None if p is None else p.shape[0]))
+                if n_box[k]:
+                    parts.append(p.to(dev))
+            gt_points = torch.cat(parts).contiguous()
+            gt_off = torch.tensor(sub_off, dtype=torch.int32).to(dev)
+        while True:
+            pos, neg, gi, host_dev = _hip.assign_anchors_frames(g_dev, sub_off, a_dev, negThr, posThr, forceThr, radius)
+            pos, neg, gi, words = _hip.ignore_anchors_frames(pos, neg, gi, host_dev[:2 * F], an7, a_dev, gt_off, gt_points,
+                                                             ignore.min_points, rects, rect_off, mats, quads, quad_off, ignore.ioa_thr)
+            host = torch.cat([host_dev, words]).cpu()                        # the one host read of the group
+            st = int(host[2 * F])
+            if st & 1 and radius < 55:              # a box much larger than an anchor: widen the window and replay both passes
+                radius = min(55, radius * 2)
+                continue
+            break
+        if st & 1:
+            raise X.MvxHipError('assignAnchors: a ground truth overlaps anchors more than 55 cells from its centre '
+                                '(or the anchor table is no regular grid)')
+        n_assign = 2 * F + 1 + sub_off[-1]
+        best = host[2 * F + 1:n_assign].view(torch.float32)
+        counts = host[n_assign:n_assign + 2 * F].tolist()
+        stats = host[n_assign + 2 * F:n_assign + 6 * F].view(F, 4)
+        if int(host[n_assign + 6 * F]):
+            raise X.MvxHipError('assignAnchors: the ignore pass reports status %d' % int(host[n_assign + 6 * F]))
+        for j, k in enumerate(ids):
+            n_pos, n_neg = counts[2 * j], counts[2 * j + 1]
+            out[k] = ((pos[j, 0, :n_pos], pos[j, 1, :n_pos], pos[j, 2, :n_pos]),
+                      (neg[j, 0, :n_neg], neg[j, 1, :n_neg], neg[j, 2, :n_neg]), gi[j, :n_pos])
+            if info is not None:
+                info['ignore_stats'] = [a + int(b) for a, b in zip(info['ignore_stats'], stats[j])]
+                if n_box[k]:
+                    b = best[sub_off[j]:sub_off[j + 1]].clone()
+                    forced = (b >= forceThr) & (b < posThr) if forceThr <= 1.5 else torch.zeros_like(b, dtype=torch.bool)
+                    info['gt_best'][k] = b
+                    info['forced_only'] += int(forced.sum())
+                    info['none'] += int(((b < posThr) & ~forced).sum())
+    return out
+
+
 def assignAnchorsFrames(frames, anchors: torch.Tensor, negThr: float = 0.45, posThr: float = 0.6, forceThr: float = 0.1,
-                        device=None, info=None):
+                        device=None, info=None, ignore=None):
     """Max-IoU assignment (csrc/assign.hip) for the frames of a step: an anchor is positive when its best IoU
     over the frame's boxes is >= posThr, or when it is the best anchor of a box whose best IoU is >= forceThr (forceThr > 1.5:
     thresholds only); not negative from negThr.  Every anchor at most once per list, in ascending (x, y, z) order.
@@ -172,12 +326,21 @@ def assignAnchorsFrames(frames, anchors: torch.Tensor, negThr: float = 0.45, pos
     Boxes that are device tensors stay on the device.  One host read per group of MAX_FRAMES frames (counts, status and the
     best IoU of every box together).  ``info`` (a dict) receives 'gt_best': per frame the best IoU of every box (CPU f32) or
     None, 'forced_only': the boxes whose best IoU lies in [forceThr, posThr) -- they owe their positive to the forced match --
-    and 'none': the boxes below both (a box whose anchors all went to a box with an equal or better claim is not counted)."""
+    and 'none': the boxes below both (a box whose anchors all went to a box with an equal or better claim is not counted).
+
+    ``ignore`` (default None: off, the code path of before): an IgnoreRegions for these frames.  The ignore pass (csrc/ignore.hip,
+    DESIGN.md 3.30) then rewrites the raw device lists before the host read -- positives of sparse boxes are demoted, anchors
+    over a DontCare rectangle or a look-alike box become not negative -- and its counts, status and stats ride in that same
+    read; it is enqueued again on a radius replay.  A frame without boxes but with rectangles or look-alike boxes is live: it
+    returns ``((e, e, e), ni, e)``.  ``info`` gains 'ignore_stats': [demoted positives, anchors newly ignored by a rectangle,
+    newly ignored by a box only, sparse boxes], summed over the frames."""
     if not (0.0 < negThr <= posThr):
         raise ValueError('assignAnchors: need 0 < negThr <= posThr, got %r, %r' % (negThr, posThr))
     if not forceThr > 0.0:
         raise ValueError('assignAnchors: need forceThr > 0 (above 1.5 = no forced match), got %r' % (forceThr,))
-    live = [k for k, fr in enumerate(frames) if fr is not None and fr[0].shape[0] > 0]
+    if ignore is not None:
+        return _assign_with_ignore(frames, anchors, negThr, posThr, forceThr, device, info, ignore)
+    live =[k for k, fr in enumerate(frames) if fr is not None and fr[0].shape[0] > 0]
     out = [None] * len(frames)
     if info is not None:
         info.update(gt_best=[None] * len(frames), forced_only=0, none=0)
@@ -248,6 +411,21 @@ def _anchors_on(anchors, dev):
         hit = (weakref.ref(anchors), anchors.detach().float().contiguous().to(dev))
         _ANCHOR_CACHE.clear()
         _ANCHOR_CACHE[key] = hit
+    return hit[1]
+
+
+_ANCHOR7_CACHE = {}
+
+
+def _anchors7_on(anchors7, dev):
+    """... and so is the (l,w,A,7) table of IgnoreRegions."""
+    key = (anchors7.data_ptr(), tuple(anchors7.shape), str(dev))
+    hit = _ANCHOR7_CACHE.get(key)
+    if hit is None or hit[0]() is not anchors7:
+        import weakref
+        hit = (weakref.ref(anchors7), anchors7.detach().float().contiguous().to(dev))
+        _ANCHOR7_CACHE.clear()
+        _ANCHOR7_CACHE[key] = hit
     return hit[1]
 
 

@@ -170,6 +170,10 @@ PROTOTYPES = {
     'mvx_assign_anchors_frames_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32]),
     'mvx_assign_anchors_frames': (_i32, [_p, _p, _i32, _p, _i32, _i32, _i32, _f32, _f32, _f32, _i32, _p, _p, _p, _i64, _p, _p, _p, _p,
                                          _sz, _p]),
+    'mvx_box_point_counts_frames': (_i32, [_p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p]),
+    'mvx_ignore_anchors_frames_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
+    'mvx_ignore_anchors_frames': (_i32, [_p, _p, _p, _i64, _p, _i32, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _f32,
+                                         _p, _p, _p, _i64, _p, _p, _p, _p, _sz, _p]),
     'mvx_voxel_loss': (_i32, [_p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _p, _i64, _p, _p, _i32, _i32, _p, _i32, _p,
                               _i32, _i32, _i32, _f32, _f32, _f32, _p, _i64, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p]),
     'mvx_focal_loss_frames_workspace_bytes': (_i64, [_i32, _i32, _i32, _i32]),

@@ -1938,6 +1938,58 @@ def assign_anchors_frames(gts, gt_off, anchor_bevs, neg_thr, pos_thr, force_thr,
     return pos, neg, gi, host
 
 
+def box_point_counts_frames(points6, n_points, boxes, gt_off):
+    """Points inside every box (csrc/ignore.hip), all frames in one launch and one memset: points6 f32 (F, cap_points, ld),
+    n_points i32 (F,), boxes f32 (G_total, 7) xyzlwhr of all frames back to back, gt_off i32 (F+1,), all on the device.
+    Returns counts i32 (G_total,).  No host read."""
+    F, cap_points, ld = points6.shape
+    G = boxes.shape[0]
+    assert points6.dtype == boxes.dtype == torch.float32 and n_points.dtype == gt_off.dtype == torch.int32
+    assert tuple(n_points.shape) == (F,) and tuple(gt_off.shape) == (F + 1,) and (G == 0 or tuple(boxes.shape) == (G, 7))
+    counts = torch.empty((G,), dtype=torch.int32, device=points6.device)
+    X.check(X.lib.mvx_box_point_counts_frames(X.ptr(points6), F, cap_points, ld, X.ptr(n_points), X.ptr(boxes) if G else None,
+                                              X.ptr(gt_off), G, X.ptr(counts) if G else None, X.stream()),
+            'mvx_box_point_counts_frames')
+    return counts
+
+
+def ignore_anchors_frames(pos, neg, gi, counts, anchors, anchor_bevs, gt_off=None, gt_points=None, min_points=0, rects=None,
+                          rect_off=None, img_from_lidar=None, ign_quads=None, ign_off=None, ioa_thr=0.5, cap_out=None, out=None):
+    """The ignore pass (csrc/ignore.hip) on the lists of ``assign_anchors_frames``: pos / neg i64 (F,3,cap), gi i64
+    (F,cap), counts i32 (2F,) or (F,2); anchors f32 (l,w,A,7) and anchor_bevs f32 (l,w,A,4,2); the sources are optional device
+    tensors: gt_points i32 (G_total,) with gt_off i32 (F+1,); rects f32 (R_total,4) with rect_off i32 (F+1,) and img_from_lidar
+    f64 (F,3,4); ign_quads f32 (B_total,4,2) with ign_off i32 (F+1,).  ``out``: an i32 device tensor of 6F + 1 words that receives
+    counts' (2F), stats (4F) and the status word (zero on entry) -- a slice of the caller's host-read tensor; made here when None.
+    Returns (pos' i64 (F,3,cap_out), neg' i64 (F,3,cap_out), gi' i64 (F,cap_out), out).  No host read."""
+    F, cap = gi.shape
+    L, W, A = anchor_bevs.shape[:3]
+    dev = gi.device
+    cap_out = L * W * A if cap_out is None else int(cap_out)
+    assert pos.dtype == neg.dtype == gi.dtype == torch.int64 and counts.dtype == torch.int32 and counts.numel() == 2 * F
+    assert tuple(pos.shape) == tuple(neg.shape) == (F, 3, cap) and anchors.numel() == L * W * A * 7
+    assert anchors.dtype == anchor_bevs.dtype == torch.float32
+    for t, dt, n in ((gt_off, torch.int32, F + 1), (rect_off, torch.int32, F + 1), (ign_off, torch.int32, F + 1),
+                     (img_from_lidar, torch.float64, F * 12)):
+        assert t is None or (t.dtype == dt and t.numel() == n)
+    assert gt_points is None or gt_points.dtype == torch.int32
+    assert (rects is None or rects.dtype == torch.float32) and (ign_quads is None or ign_quads.dtype == torch.float32)
+    pos_o = torch.empty((F, 3, cap_out), dtype=torch.int64, device=dev)
+    neg_o = torch.empty((F, 3, cap_out), dtype=torch.int64, device=dev)
+    gi_o = torch.empty((F, cap_out), dtype=torch.int64, device=dev)
+    if out is None:
+        out = torch.zeros((6 * F + 1,), dtype=torch.int32, device=dev)
+    assert out.dtype == torch.int32 and out.numel() == 6 * F + 1 and out.is_contiguous()
+    nbytes = X.lib.mvx_ignore_anchors_frames_workspace_bytes(F, L, W, A)
+    ws = workspace(nbytes, dev, 'ignore')
+    X.check(X.lib.mvx_ignore_anchors_frames(X.ptr(pos), X.ptr(neg), X.ptr(gi), cap, X.ptr(counts), F, X.ptr(gt_off), X.ptr(gt_points),
+                                            int(min_points), X.ptr(anchors), X.ptr(anchor_bevs), L, W, A, X.ptr(rects),
+                                            X.ptr(rect_off), X.ptr(img_from_lidar), X.ptr(ign_quads), X.ptr(ign_off), float(ioa_thr),
+                                            X.ptr(pos_o), X.ptr(neg_o), X.ptr(gi_o), cap_out, X.ptr(out[:2 * F]),
+                                            X.ptr(out[2 * F:6 * F]), X.ptr(out[6 * F:]), X.ptr(ws), ws.numel(), X.stream()),
+            'mvx_ignore_anchors_frames')
+    return pos_o, neg_o, gi_o, out
+
+
 def voxel_loss(score, reg, pos_idx, neg_idx, gi, n_pos, n_neg, gts, anchors, A, a, b, eps, want_grads=True,
                dscore_out=None, dreg_out=None):
     """score (L,W,A) / reg (L,W,7A) f32 views with arbitrary strides; pos_idx / neg_idx i64 (3,cap) or None.

@@ -67,6 +67,40 @@ def geometry_draws(geometry, F, B):
     return noise, glob, geometry.get('iou_thr', params.iou_thr)
 
 
+def global_matrix(glob_row):
+    """The global step of a frame as a 4x4 float64 matrix G on column vectors (x, y, z, 1): ``glob_row`` = (phi, s, flip, 0) as
+    drawn (f32).  Exactly what geom_points / geom_place apply: p_xy <- s (p_xy @ R(phi)) with R of Calc.getRotationMatrices on row
+    vectors, p_z <- s p_z, then y <- -y with the flip.  Points keep the pixel they were seen at, so a LiDAR -> image matrix M of
+    the frame before the augmentation becomes M @ inv(G) behind it."""
+    g = np.asarray(glob_row, np.float32).astype(np.float64)
+    c, s, k = math.cos(g[0]), math.sin(g[0]), g[1]
+    sy = -1.0 if g[2] != 0.0 else 1.0
+    m = np.eye(4)
+    m[0, :2] = [k * c, k * s]
+    m[1, :2] = [-sy * k * s, sy * k * c]
+    m[2, 2] = k
+    return m
+
+
+def transform_boxes(boxes7, glob_row):
+    """Boxes (n, 7) xyzlwhr through the global step of ``glob_row``, as geom_place moves the frame's own boxes (without its
+    per-object noise and range filter): the centre through ``global_matrix``, the sizes scaled, the yaw + phi, negated by the
+    flip, wrapped into [-pi, pi).  Returns f32 (n, 7) of the input's kind (numpy or host tensor)."""
+    is_t = isinstance(boxes7, torch.Tensor)
+    b = (boxes7.detach().cpu().numpy() if is_t else np.asarray(boxes7)).astype(np.float32).astype(np.float64).reshape(-1, 7)
+    g = np.asarray(glob_row, np.float32).astype(np.float64)
+    G = global_matrix(glob_row)
+    out = np.empty_like(b)
+    out[:, :3] = (np.concatenate([b[:, :3], np.ones((b.shape[0], 1))], axis=1) @ G.T)[:, :3]
+    out[:, 3:6] = g[1] * b[:, 3:6]
+    r = b[:, 6] + g[0]
+    if g[2] != 0.0:
+        r = -r
+    out[:, 6] = r - 2.0 * math.pi * np.floor((r + math.pi) / (2.0 * math.pi))
+    out = out.astype(np.float32)
+    return torch.from_numpy(out) if is_t else out
+
+
 class GeomLaunched:
     """The enqueued launches of a frame set: device outputs, and the int32 words the host needs (``words``) so that a caller
     with a read of its own can carry them in it; ``finish`` turns the words into the per-frame result."""

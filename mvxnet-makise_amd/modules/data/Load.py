@@ -72,6 +72,35 @@ def _read_class_labels(path, classes=('Car', 'Pedestrian', 'Cyclist')):
     return names, np.asarray(rows, dtype=np.float64).reshape(-1, 14)
 
 
+def readIgnoreLabels(names: List[str], root=None, classes=('Van',)):
+    """The ignore regions of the frames ``names`` (csrc/ignore.hip), which createDataset drops: per frame
+    ``(rects, boxes)`` -- the 'DontCare' rectangles f32 (R,4) = (x1, y1, x2, y2) pixels and the rows of the look-alike
+    ``classes`` as LiDAR boxes f32 (B,7) xyzlwhr (bboxCam2Lidar with the frame's calibration, as createDataset converts the
+    Cars; no range filter: a box half outside the range still shields the anchors it covers), both possibly empty."""
+    root = dataroot if root is None else root
+    _, _, labelroot, calibroot, _ = _roots(root)
+    out = []
+    for s in names:
+        rects, rows = [], []
+        with open(os.path.join(labelroot, s + '.txt'), 'r') as f:
+            for line in f:
+                tok = line.split(' ')
+                if not tok:
+                    continue
+                if tok[0] == 'DontCare':
+                    rects.append([float(v) for v in tok[4:8]])
+                elif tok[0] in classes:
+                    rows.append([float(v) for v in tok[8:15]])
+        rects = torch.Tensor(np.asarray(rects, dtype=np.float64).reshape(-1, 4))
+        boxes = torch.Tensor(np.asarray(rows, dtype=np.float64).reshape(-1, 7))
+        if len(boxes):
+            calib = readCalib(os.path.join(calibroot, s + '.txt'))
+            c2v = torch.linalg.inv(torch.Tensor(calib['Tr_velo_to_cam']))
+            boxes = Calc.bboxCam2Lidar(boxes, c2v, True)
+        out.append((rects, boxes))
+    return out
+
+
 def createDataset(splitSet: List[str], needCrop=False, root=None) -> \
         List[Tuple[np.ndarray, np.ndarray, torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]]:
     """Read KITTI frames ``splitSet`` (e.g. ['000000', ...]) from ``root`` (reference Load.py:43-95)."""

@@ -40,11 +40,18 @@ class _Staging:
 
 class PrefetchLoader:
     def __init__(self, groups, names_of, device, anchor_bevs, fpn_fn, cap_points, depth=2, priority=-1, augment=None, geometry=None,
-                 assigner=None):
+                 assigner=None, ignore=None):
         """``groups``: iterable of lists of frames as ``modules.data.Load.createDataset`` returns them; ``names_of(frame)``:
         the frame's name (for ``fpn_fn``); ``fpn_fn(name, device)``: the frame's FPN maps (the frozen extractor or its
         stand-in); ``cap_points``: point capacity per frame of the resident batch; ``assigner``: pipeline.batch_from_dataset's (None =
-        the reference's classifyAnchors, otherwise a callable ``frames -> lists``)."""
+        the reference's classifyAnchors, otherwise a callable ``frames -> lists``); ``ignore`` (default None: off): the settings of
+        pipeline.ignore_regions_of with ``'labels_of': name -> (rects, boxes)`` (a row of Load.readIgnoreLabels) in place of
+        'labels' -- the ignore regions of csrc/ignore.hip; the assigner must then take the keyword ``ignore``."""
+        from modules import pipeline
+        if ignore is not None and not pipeline.assigner_takes_ignore(assigner):
+            raise ValueError('PrefetchLoader: ignore regions need an assigner with a keyword `ignore` '
+                             '(Calc.assignAnchorsFrames; the reference assigner has no ignore pass)')
+        self.ignore = ignore
         self.groups = iter(groups)
         self.names_of, self.device, self.anchor_bevs, self.fpn_fn = names_of, device, anchor_bevs, fpn_fn
         self.cap = int(cap_points)
@@ -78,6 +85,16 @@ class PrefetchLoader:
             return self.assigner(boxes)
         return Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)
 
+    def _assign_ignoring(self, group, boxes, gts, glob, points6, n_points):
+        """Targets of a group with the ignore regions: the points are counted on the cloud as the network sees it."""
+        from modules import pipeline
+        settings = dict(self.ignore)
+        settings['labels'] = [self.ignore['labels_of'](self.names_of(d)) for d in group]
+        regions = pipeline.ignore_regions_of(group, settings, gts, glob, self.device).count_points(points6, n_points)
+        lists = self.assigner(boxes, ignore=regions)
+        empty = torch.zeros((0, 7), dtype=torch.float32, device=self.device)
+        return [None if t is None else (t[0], t[1], t[2], empty if gt is None else gt) for t, gt in zip(lists, gts)]
+
     def _prepare(self, group):
         import time
         t0 = time.perf_counter()
@@ -102,8 +119,11 @@ class PrefetchLoader:
             targets = [None] * B
             if self.augment is None and self.geometry is None:          # with an augmentation the boxes are only known after it (__next__)
                 boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
-                lists = self._assign(boxes)                     # one pass, one host read
-                targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
+                if self.ignore is not None:
+                    targets = self._assign_ignoring(group, boxes, [None if d[3] is None else d[3].to(dev) for d in group], None, pts6, n)
+                else:
+                    lists = self._assign(boxes)                 # one pass, one host read
+                    targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
             ev = torch.cuda.Event()
             ev.record(self.stream)
         t2 = time.perf_counter()
@@ -170,15 +190,24 @@ class PrefetchLoader:
             _hip.lidar2img(pts6[k, :P], m, p2, math_f32=True, out=pts6[k, :P], col_offset=4, swap_rc=True)    # reads x y z, writes cols 4:6
             fpn.append(self.fpn_fn(self.names_of(d), self.device))
         batch = FrameBatch(pts6, perms, n, fpn)
+        geometry, glob = self.geometry, None
+        if self.ignore is not None and geometry is not None:    # the global draws, which the frames' matrices need, made first
+            from modules.augment import Geometry
+            noise, glob, _ = Geometry.geometry_draws(geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
+            geometry = dict(geometry) if isinstance(geometry, dict) else {'params': geometry}
+            geometry.update(noise=noise, glob=glob)
+            glob = np.asarray(glob.cpu() if isinstance(glob, torch.Tensor) else glob, np.float32)
         if self.augment is not None:
             from modules.augment import Augment
             a = self.augment
             res = Augment.augmentFrames(batch, None, [None if d[3] is None else (d[2], d[3], d[4]) for d in group], a['db'],
-                                        lim=a.get('lim', 12), rng=a.get('rng'), geometry=self.geometry)
-        elif self.geometry is not None:
+                                        lim=a.get('lim', 12), rng=a.get('rng'), geometry=geometry)
+        elif geometry is not None:
             from modules.augment import Geometry
-            noise, glob, iou_thr = Geometry.geometry_draws(self.geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
-            res = Geometry.augmentGeometryFrames(batch, [d[3] for d in group], noise, glob, iou_thr=iou_thr)
+            noise, glob_d, iou_thr = Geometry.geometry_draws(geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
+            res = Geometry.augmentGeometryFrames(batch, [d[3] for d in group], noise, glob_d, iou_thr=iou_thr)
+        if (self.augment is not None or self.geometry is not None) and self.ignore is not None:
+            return batch, self._assign_ignoring(group, res.boxes, res.bbox3d, glob, batch.points6, batch.n_points)
         if self.augment is not None or self.geometry is not None:
             lists = self._assign(res.boxes)
             targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, res.bbox3d)]

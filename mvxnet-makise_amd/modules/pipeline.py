@@ -605,7 +605,7 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
 
 
 # ---- whole model on the fast path: frame sets up to the BEV map, RPN + VoxelLoss per frame ------------------------------
-def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None, geometry=None, assigner=None):
+def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, augment=None, geometry=None, assigner=None, ignore=None):
     """Frames of ``modules.data.Load.createDataset`` -> (FrameBatch resident on the GPU, per-frame targets).  Per frame, as
     train.py:26-49: lidar2Img on the torch path + (row, col) swap, the shuffle permutation drawn with np.random, and
     classifyAnchors for the 'Car' boxes; (pi, ni, gi, gt) or None when the frame has no box.
@@ -620,8 +620,23 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     (modules/augment/Geometry.py: per-object noise, global rotation / scaling / flip, range filter) after the projection --
     behind the paste inside its one host read with ``augment``, three launches and one host read of its own without.
     ``assigner`` (default None: the reference's classifyAnchors at 0.45 / 0.6): a callable ``frames -> lists`` in its place, such
-    as ``lambda frames: Calc.assignAnchorsFrames(frames, anchorBevs)``."""
+    as ``lambda frames: Calc.assignAnchorsFrames(frames, anchorBevs)``.
+    ``ignore`` (default None: off): the settings of ``ignore_regions_of`` -- DontCare rectangles, look-alike boxes and a lowest
+    point count per Car (csrc/ignore.hip).  The points are counted on ``batch.points6`` AFTER paste and geometry,
+    so the count sees what the network sees; the regions go to ``assigner(frames, ignore=regions)``, which must take that keyword
+    (ValueError otherwise).  A frame without Car boxes that has an ignore region then gets targets with an empty (0, 7) box
+    tensor.  With ``geometry`` the global draws are made here, in front of the paste's."""
     import numpy as np
+    if ignore is not None and not assigner_takes_ignore(assigner):
+        raise ValueError('batch_from_dataset: ignore regions need an assigner with a keyword `ignore` '
+                         '(Calc.assignAnchorsFrames; the reference assigner has no ignore pass)')
+    glob_pre = None
+    if ignore is not None and geometry is not None:
+        from modules.augment import Geometry
+        noise, glob_pre, _ = Geometry.geometry_draws(geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
+        geometry = dict(geometry) if isinstance(geometry, dict) else {'params': geometry}
+        geometry.update(noise=noise, glob=glob_pre)
+        glob_pre = np.asarray(glob_pre.cpu() if isinstance(glob_pre, torch.Tensor) else glob_pre, np.float32)
     extractor = augment.get('extractor') if augment is not None else None
     from modules import Calc
     from modules.data.Preprocessing import _calib_products
@@ -671,9 +686,67 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     if geo is not None and isinstance(geometry, dict) and geometry.get('keep') is not None:
         geometry['keep']['result'] = geo
     # target assignment of all frames in one kernel pass / one host read
+    if ignore is not None:
+        regions = ignore_regions_of(group, ignore, gts, glob_pre, device).count_points(batch.points6, batch.n_points)
+        if ignore.get('keep') is not None:
+            ignore['keep']['regions'] = regions
+        lists = assigner(boxes, ignore=regions)
+        empty = torch.zeros((0, 7), dtype=torch.float32, device=device)
+        targets = [None if t is None else (t[0], t[1], t[2], empty if gt is None else gt) for t, gt in zip(lists, gts)]
+        return batch.mark_created(), targets
     lists = Calc.classifyAnchorsFrames(boxes, anchorBevs, cfg.velorange, 0.45, 0.6) if assigner is None else assigner(boxes)
     targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, gts)]
     return batch.mark_created(), targets
+
+
+def assigner_takes_ignore(assigner):
+    """Whether the callable ``assigner`` has a keyword ``ignore`` (or takes any keyword)."""
+    import inspect
+    if assigner is None:
+        return False
+    try:
+        params = inspect.signature(assigner).parameters.values()
+    except (TypeError, ValueError):
+        return False
+    return any(p.name == 'ignore' or p.kind is inspect.Parameter.VAR_KEYWORD for p in params)
+
+
+def ignore_regions_of(group, ignore, gts, glob, device):
+    """The Calc.IgnoreRegions of the frames ``group`` from the settings ``ignore``: ``{'labels': per frame (rects (R,4), boxes (B,7))
+    as Load.readIgnoreLabels returns them, 'anchors': the (l,w,A,7) anchor table}`` and optionally 'dontcare' (default True: use
+    the rectangles), 'ioa' (default 0.5), 'min_points' (default 0 = off), 'keep' (a dict that receives the regions).  ``gts``: the
+    frames' Car boxes as the network sees them; ``glob``: the global draws (F,4) of the geometric augmentation or None -- the
+    frame's matrix is then P2 R0 Tr inv(G), because points keep the pixel they were seen at, and the look-alike boxes move with G."""
+    import numpy as np
+    from modules import Calc
+    from modules.augment import Geometry
+    from modules.data.Preprocessing import _calib_products
+    labels = ignore['labels']
+    if len(labels) != len(group):
+        raise ValueError('ignore: %d label entries for %d frames' % (len(labels), len(group)))
+    use_rects = ignore.get('dontcare', True)
+    rects, mats, quads = [], [], []
+    for k, d in enumerate(group):
+        r, b = labels[k]
+        r = r if use_rects and r is not None and r.shape[0] else None
+        b = b if b is not None and b.shape[0] else None
+        G = None if glob is None else Geometry.global_matrix(glob[k])
+        m = None
+        if r is not None:
+            tr, p2 = _calib_products(d[5], True)
+            m = (p2 @ tr)[:3]
+            if G is not None:
+                m = m @ np.linalg.inv(G)
+        if b is not None:
+            b = torch.as_tensor(b).detach().float().cpu()[:, :7]
+            if G is not None:
+                b = Geometry.transform_boxes(b, glob[k])
+            b = Calc.bbox3d2bev(b)
+        rects.append(r)
+        mats.append(m)
+        quads.append(b)
+    return Calc.IgnoreRegions(len(group), anchors=ignore.get('anchors'), rects=rects, matrix=mats, quads=quads, boxes3d=gts,
+                              min_points=ignore.get('min_points', 0), ioa_thr=ignore.get('ioa', 0.5))
 
 
 def heads_loss(heads, F, h1, w1, targets, criterion, anchors):

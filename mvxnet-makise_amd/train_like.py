@@ -84,6 +84,17 @@ def parse_args(argv=None):
                          'best box of every anchor, plus the best anchor of every box)')
     ap.add_argument('--force-iou', type=float, default=0.1,
                     help='--targets maxiou: a box whose best IoU reaches this gets its best anchor as a positive (2 = thresholds only)')
+    ap.add_argument('--ignore-dontcare', action='store_true',
+                    help='--targets maxiou --mode fast: anchors whose centre projects into a DontCare rectangle leave the classification loss')
+    ap.add_argument('--ignore-classes', nargs='+', default=[], metavar='CLASS',
+                    help='--targets maxiou --mode fast: anchors covered by a box of these classes (Van, Truck, Tram ...) leave the '
+                         'classification loss')
+    ap.add_argument('--ignore-ioa', type=float, default=0.5,
+                    help='--ignore-classes: share of the ANCHOR\'s area that such a box must cover, in (0, 1] (0.5 is a design choice, '
+                         'not a measured optimum)')
+    ap.add_argument('--min-gt-points', type=int, default=0,
+                    help='--targets maxiou --mode fast: a Car with fewer points than this, counted after crop and augmentation, gives no '
+                         'positive; its anchors are ignored (0 = off: a design choice, not a measured optimum)')
     ap.add_argument('--focal-alpha', type=float, default=0.25)
     ap.add_argument('--focal-gamma', type=float, default=2.0)
     ap.add_argument('--focal-reg-weight', type=float, default=2.0)
@@ -93,6 +104,16 @@ def parse_args(argv=None):
                  'criterion probabilities')
     if args.force_iou <= 0:
         ap.error('--force-iou must be positive (2 = thresholds only)')
+    args.ignore = bool(args.ignore_dontcare or args.ignore_classes or args.min_gt_points)
+    if (args.ignore or args.ignore_ioa != 0.5) and args.targets != 'maxiou':
+        ap.error('--ignore-dontcare / --ignore-classes / --ignore-ioa / --min-gt-points need --targets maxiou: the ignore pass '
+                 'rewrites the lists of the max-IoU assigner')
+    if args.ignore and args.mode != 'fast':
+        ap.error('--ignore-dontcare / --ignore-classes / --min-gt-points need --mode fast: the pass runs on the frame set of a step')
+    if not 0.0 < args.ignore_ioa <= 1.0:
+        ap.error('--ignore-ioa must lie in (0, 1]')
+    if args.min_gt_points < 0:
+        ap.error('--min-gt-points must not be negative')
     return args
 
 
@@ -221,13 +242,24 @@ def train(args):
     if args.targets == 'maxiou':
         from modules.Calc import assignAnchorsFrames
 
-        def assigner(frames):
+        def assigner(frames, ignore=None):
             info = {}
-            lists = assignAnchorsFrames(frames, anchorBevs, 0.45, 0.6, args.force_iou, info=info)
+            lists = assignAnchorsFrames(frames, anchorBevs, 0.45, 0.6, args.force_iou, info=info, ignore=ignore)
             assign_stats['boxes'] += sum(b.numel() for b in info['gt_best'] if b is not None)
             assign_stats['forced_only'] += info['forced_only']
             assign_stats['none'] += info['none']
+            if ignore is not None:
+                ignore_stats[:] = [a + b for a, b in zip(ignore_stats, info['ignore_stats'])]
             return lists
+    ign, ignore_stats = None, [0, 0, 0, 0]
+    if args.ignore:
+        rows = load.readIgnoreLabels(trainSet, root=args.dataroot, classes=tuple(args.ignore_classes))
+        ign_labels = dict(zip(trainSet, rows))
+        ign = {'anchors': anchors.reshape(anchors.shape[:2] + (-1, 7)), 'dontcare': args.ignore_dontcare, 'ioa': args.ignore_ioa,
+               'min_points': args.min_gt_points, 'labels_of': lambda name: ign_labels[name]}
+        say('ignore regions: %d DontCare rectangle(s)%s, %d box(es) of %s, Cars below %d point(s)'
+            % (sum(r.shape[0] for r, _ in rows), '' if args.ignore_dontcare else ' (not used)', sum(b.shape[0] for _, b in rows),
+               '/'.join(args.ignore_classes) or 'no class', args.min_gt_points))
     torch.manual_seed(0)
     model = MVXNet().to(device)
     if args.loss == 'focal':
@@ -353,8 +385,10 @@ def train(args):
                         if not group:
                             yield None, None
                         else:
-                            yield pl.batch_from_dataset(group, [names[id(d)] for d in group], device, anchorBevs, fpn_fn, cap_points=cap,
-                                                        augment=aug, geometry=geo, assigner=assigner)
+                            gnames = [names[id(d)] for d in group]
+                            ig = None if ign is None else dict(ign, labels=[ign_labels[n] for n in gnames])
+                            yield pl.batch_from_dataset(group, gnames, device, anchorBevs, fpn_fn, cap_points=cap,
+                                                        augment=aug, geometry=geo, assigner=assigner, ignore=ig)
                 loader = batches()
             else:
                 # batch k+1 is prepared by a worker thread on its own stream while step k runs (the reference overlaps its CPU
@@ -362,8 +396,8 @@ def train(args):
                 from modules.data.Prefetch import PrefetchLoader
                 loader = PrefetchLoader(groups, lambda d: names[id(d)], device, anchorBevs, fpn_fn, cap,
                                         depth=args.prefetch_depth, priority=args.prefetch_priority, augment=aug, geometry=geo,
-                                        assigner=assigner)
-            pending = None                        # the losses of a step are read one step later: the host never waits for
+                                        assigner=assigner, ignore=ign)
+            pending = None                       # the losses of a step are read one step later: the host never waits for
                                                   # the step it has just enqueued
 
             def account(p):
@@ -422,6 +456,10 @@ def train(args):
             say('Epoch%d targets: %d boxes, %d with only a forced positive, %d with none'
                 % (epoch + args.lastiter + 1, assign_stats['boxes'], assign_stats['forced_only'], assign_stats['none']))
             assign_stats.update(boxes=0, forced_only=0, none=0)
+        if ign is not None:
+            say('Epoch%d ignored: %d positive(s) demoted, %d anchor(s) by a DontCare rectangle, %d by a look-alike box, %d sparse box(es)'
+                % ((epoch + args.lastiter + 1,) + tuple(ignore_stats)))
+            ignore_stats[:] = [0, 0, 0, 0]
         report_optimizer(epoch + args.lastiter + 1)
         if rank == 0:
             n = epoch + args.lastiter + 1
