@@ -12,6 +12,7 @@
 // (2R+1)^2 window around the centre in parallel into LDS, then one lane replays the reference's walk over the
 // window (rows up, rows down; inside a row right, then left) -- same visiting order, same break conditions -- and
 // a second single-workgroup launch concatenates the per-pair lists in (ground truth, orientation) order.
+#include "anchor_lists.h"
 #include "bev_iou.h"
 
 namespace {
@@ -109,10 +110,8 @@ __global__ __launch_bounds__(256) void anchor_window_walk(const float *__restric
 // One workgroup per FRAME: concatenates the per-pair lists of the frame's ground truths in pair order into the i64 index
 // triples of the reference.  ``goff`` = ground-truth offsets of the frames (a single frame: {0, n_gt}); frame f writes
 // pos_idx[f][3][cap], neg_idx[f][3][cap], gi[f][cap] (ground-truth ids LOCAL to the frame) and counts[f][2].
-struct GtOffsets { int off[MVX_MAX_FRAMES + 1]; };
-
 __global__ void anchor_concat(const int *__restrict__ pair_counts, const int *__restrict__ pos_list,
-                              const int *__restrict__ neg_list, GtOffsets goff, int A, int W, int cap_pair,
+                              const int *__restrict__ neg_list, FrameOffsets goff, int A, int W, int cap_pair,
                               long long *__restrict__ pos_idx, long long *__restrict__ neg_idx, long long *__restrict__ gi,
                               long long cap, int *__restrict__ counts, int *__restrict__ status) {
     __shared__ int s_scan[17];
@@ -190,10 +189,8 @@ extern "C" int mvx_classify_anchors_frames(const float *gts, const int32_t *gt_o
     MVX_CHECK_ARG(l > 0 && w > 0 && anchors_per_loc > 0 && window_radius >= 1 && window_radius <= 55);
     MVX_CHECK_ARG(counts && status && cap >= 0);
     MVX_CHECK_ARG((long long)l * w < (1ll << 31));
-    GtOffsets goff;
-    for (int f = 0; f <= MVX_MAX_FRAMES; ++f) goff.off[f] = gt_off_host[f < n_frames ? f : n_frames];
-    MVX_CHECK_ARG(goff.off[0] == 0);
-    for (int f = 0; f < n_frames; ++f) MVX_CHECK_ARG(goff.off[f + 1] >= goff.off[f]);
+    FrameOffsets goff;
+    MVX_CHECK_ARG(frame_offsets(gt_off_host, n_frames, goff));
     const int n_gt = goff.off[n_frames];
     hipStream_t st = (hipStream_t)stream;
     const int pairs = n_gt * anchors_per_loc;

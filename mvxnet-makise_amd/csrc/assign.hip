@@ -37,12 +37,10 @@
 //     true IoU by `ub`; the f32 IoU is within 3e-4 of the truth (targets_cases.IOU_BOUND).  If ub + 1e-3 is below both neg_thr
 //     and b(g), no anchor outside can enter a list, be c(g) or change b(g): exact.  If not: status bit 1, replay with a
 //     larger radius.
+#include "anchor_lists.h"
 #include "bev_iou.h"
-#include "compact.h"
 
 namespace {
-
-struct AssignOffsets { int off[MVX_MAX_FRAMES + 1]; };
 
 constexpr unsigned long long FORCED = 1ull << 63;
 constexpr float NOISE = 1e-3f;              // > IOU_BOUND = 3e-4, the largest |f32 IoU - truth|
@@ -53,7 +51,7 @@ __device__ __forceinline__ unsigned long long make_key(float iou, int g_local) {
 __device__ __forceinline__ float key_iou(unsigned long long k) { return __uint_as_float((unsigned)(k >> 32) & 0x7fffffffu); }
 __device__ __forceinline__ int key_g(unsigned long long k) { return (int)(~(unsigned)k); }
 
-__device__ __forceinline__ int frame_of(const AssignOffsets &o, int F, int g) {
+__device__ __forceinline__ int frame_of(const FrameOffsets &o, int F, int g) {
     int f = 0;
     for (int k = 1; k < F; ++k) f += (g >= o.off[k]);
     return f;
@@ -94,7 +92,7 @@ __device__ __forceinline__ long long cells_outside(long long n, int R, int len) 
 
 // pair_best: per pair [iou f32, lowest flat anchor index i32, ub f32, 1 if anchors of the grid lie outside the window]
 __global__ __launch_bounds__(256) void assign_window(const float *__restrict__ gts, const float *__restrict__ anchors, int L, int W,
-                                                     int A, AssignOffsets goff, int F, float neg_thr, int R,
+                                                     int A, FrameOffsets goff, int F, float neg_thr, int R,
                                                      unsigned long long *__restrict__ keymap, float *__restrict__ pair_iou,
                                                      int *__restrict__ pair_idx, float *__restrict__ pair_ub,
                                                      int *__restrict__ pair_outside, int *__restrict__ status) {
@@ -191,7 +189,7 @@ __global__ __launch_bounds__(256) void assign_window(const float *__restrict__ g
     }
 }
 
-__global__ __launch_bounds__(256) void assign_boxes(int G, int A, long long N, AssignOffsets goff, int F, float neg_thr, float force_thr,
+__global__ __launch_bounds__(256) void assign_boxes(int G, int A, long long N, FrameOffsets goff, int F, float neg_thr, float force_thr,
                                                     const float *__restrict__ pair_iou, const int *__restrict__ pair_idx,
                                                     const float *__restrict__ pair_ub, const int *__restrict__ pair_outside,
                                                     unsigned long long *__restrict__ keymap, float *__restrict__ gt_best,
@@ -226,19 +224,12 @@ __device__ __forceinline__ int key_flags(unsigned long long k, float pos_thr) {
     return 1 | (((k & FORCED) || key_iou(k) >= pos_thr) ? 2 : 0);
 }
 
-// bcount i32 [2F][nblocks]: row 2f = positives, row 2f + 1 = not negatives of frame f
 __global__ __launch_bounds__(256) void assign_count(const unsigned long long *__restrict__ keymap, long long N, int nblocks, float pos_thr,
                                                     int *__restrict__ bcount) {
     __shared__ int s[2][4];
     const int f = blockIdx.y;
     const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int fl = a < N ? key_flags(keymap[(size_t)f * N + a], pos_thr) : 0;
-    const int np = block_kept_count<4>((fl & 2) != 0, s[0]);
-    const int nn = block_kept_count<4>((fl & 1) != 0, s[1]);
-    if (threadIdx.x == 0) {
-        bcount[(size_t)(2 * f) * nblocks + blockIdx.x] = np;
-        bcount[(size_t)(2 * f + 1) * nblocks + blockIdx.x] = nn;
-    }
+    list_block_counts(a < N ? key_flags(keymap[(size_t)f * N + a], pos_thr) : 0, f, nblocks, s, bcount);
 }
 
 __global__ __launch_bounds__(256) void assign_write(const unsigned long long *__restrict__ keymap, long long N, int W, int A, int nblocks,
@@ -250,29 +241,8 @@ __global__ __launch_bounds__(256) void assign_write(const unsigned long long *__
     const int f = blockIdx.y;
     const long long a = (long long)blockIdx.x * 256 + threadIdx.x;
     const unsigned long long k = a < N ? keymap[(size_t)f * N + a] : 0ull;
-    const int fl = key_flags(k, pos_thr);
-    int tp, tn;
-    const long long op = boff[(size_t)(2 * f) * nblocks + blockIdx.x] + block_kept_rank<4>((fl & 2) != 0, s[0], tp);
-    const long long on = boff[(size_t)(2 * f + 1) * nblocks + blockIdx.x] + block_kept_rank<4>((fl & 1) != 0, s[1], tn);
-    const long long x = a / ((long long)W * A), y = (a / A) % W, z = a % A;
-    if ((fl & 2) && op < cap) {
-        long long *p = pos_idx + (size_t)f * 3 * cap;
-        p[op] = x; p[cap + op] = y; p[2 * cap + op] = z;
-        gi[(size_t)f * cap + op] = key_g(k);
-    }
-    if ((fl & 1) && on < cap) {
-        long long *n = neg_idx + (size_t)f * 3 * cap;
-        n[on] = x; n[cap + on] = y; n[2 * cap + on] = z;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const long long np = totals[2 * f], nn = totals[2 * f + 1];
-        counts[2 * f] = (int)(np < cap ? np : cap);
-        counts[2 * f + 1] = (int)(nn < cap ? nn : cap);
-        if (np > cap || nn > cap) atomicOr(status, 2);
-    }
+    list_write(key_flags(k, pos_thr), key_g(k), f, a, W, A, nblocks, s, boff, totals, pos_idx, neg_idx, gi, cap, counts, status);
 }
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -294,10 +264,8 @@ extern "C" int mvx_assign_anchors_frames(const float *gts, const int32_t *gt_off
     MVX_CHECK_ARG(neg_thr > 0.f && neg_thr <= pos_thr && force_thr > 0.f);
     MVX_CHECK_ARG(counts && status && cap >= 0);
     MVX_CHECK_ARG((long long)l * w * anchors_per_loc < (1ll << 31));
-    AssignOffsets goff;
-    for (int f = 0; f <= MVX_MAX_FRAMES; ++f) goff.off[f] = gt_off_host[f < n_frames ? f : n_frames];
-    MVX_CHECK_ARG(goff.off[0] == 0);
-    for (int f = 0; f < n_frames; ++f) MVX_CHECK_ARG(goff.off[f + 1] >= goff.off[f]);
+    FrameOffsets goff;
+    MVX_CHECK_ARG(frame_offsets(gt_off_host, n_frames, goff));
     const int n_gt = goff.off[n_frames];
     hipStream_t st = (hipStream_t)stream;
     if (n_gt == 0) {

@@ -23,9 +23,9 @@
 //
 // mvx_box_point_counts_frames -- one launch and one memset: a workgroup takes 1024 rows of one frame's cloud, holds the frame's
 // boxes in LDS 64 at a time (box3d.h, f64), counts per box in LDS integers and adds the sums to counts with integer atomics.
+#include "anchor_lists.h"
 #include "bev_iou.h"
 #include "box3d.h"
-#include "compact.h"
 
 namespace {
 
@@ -217,12 +217,7 @@ __global__ __launch_bounds__(256) void ignore_dense(IgnoreArgs a) {
     }
     if (in && m != m_in) *slot = m;
     __syncthreads();
-    const int np = block_kept_count<4>(in && (m & 2u), s[0]);
-    const int nn = block_kept_count<4>(in && (m & 1u), s[1]);
-    if (tid == 0) {
-        a.bcount[(size_t)(2 * f) * a.nblocks + blockIdx.x] = np;
-        a.bcount[(size_t)(2 * f + 1) * a.nblocks + blockIdx.x] = nn;
-    }
+    list_block_counts(in ? (int)(m & 3u) : 0, f, a.nblocks, s, a.bcount);
     const int by_rect = __popcll(__ballot(in && (m & 4u))), by_box = __popcll(__ballot(in && (m & 8u)));
     if ((tid & 63) == 0) {
         if (by_rect) atomicAdd(a.wstats + 4 * f + 1, by_rect);
@@ -239,29 +234,10 @@ __global__ __launch_bounds__(256) void ignore_write(const unsigned *__restrict__
     const int f = blockIdx.y;
     const long long at = (long long)blockIdx.x * 256 + threadIdx.x;
     const unsigned m = at < N ? map[(size_t)f * N + at] : 0u;
-    int tp, tn;
-    const long long op = boff[(size_t)(2 * f) * nblocks + blockIdx.x] + block_kept_rank<4>((m & 2u) != 0, s[0], tp);
-    const long long on = boff[(size_t)(2 * f + 1) * nblocks + blockIdx.x] + block_kept_rank<4>((m & 1u) != 0, s[1], tn);
-    const long long x = at / ((long long)W * A), y = (at / A) % W, z = at % A;
-    if ((m & 2u) && op < cap) {
-        long long *p = pos_out + (size_t)f * 3 * cap;
-        p[op] = x; p[cap + op] = y; p[2 * cap + op] = z;
-        gi_out[(size_t)f * cap + op] = (long long)(m >> GI_SHIFT) - 1;
-    }
-    if ((m & 1u) && on < cap) {
-        long long *n = neg_out + (size_t)f * 3 * cap;
-        n[on] = x; n[cap + on] = y; n[2 * cap + on] = z;
-    }
+    list_write((int)(m & 3u), (long long)(m >> GI_SHIFT) - 1, f, at, W, A, nblocks, s, boff, totals, pos_out, neg_out, gi_out, cap,
+               counts, status);
     if (blockIdx.x == 0 && threadIdx.x < 4) stats[4 * f + threadIdx.x] = wstats[4 * f + threadIdx.x];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const long long np = totals[2 * f], nn = totals[2 * f + 1];
-        counts[2 * f] = (int)(np < cap ? np : cap);
-        counts[2 * f + 1] = (int)(nn < cap ? nn : cap);
-        if (np > cap || nn > cap) atomicOr(status, 2);
-    }
 }
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 

@@ -5,6 +5,8 @@ reference's ``(pi, ni, gi)`` with the same members in the same order; the box co
 operations on a handful of boxes (label preparation) and stay plain torch, as in the reference.
 """
 import math
+import types
+import weakref
 from typing import Sequence, Tuple, Union
 
 import numpy as np
@@ -66,99 +68,126 @@ def _window_radius(gts: torch.Tensor, anchors: torch.Tensor) -> int:
     return max(2, min(55, int(math.ceil((diag(gts) + diag(anchors[0, 0])) / 2 / cell)) + 2))
 
 
-def classifyAnchors(gts: torch.Tensor, gtCenters: torch.Tensor, anchors: torch.Tensor, velorange: Sequence[float],
-                    negThr: float, posThr: float, device=None) -> Tuple[index3d, index3d, torch.Tensor]:
-    """Reference Calc.py:88-96 (-> cpp/voxelutil.cpp:138-316).  gts (G,4,2) BEV corners, gtCenters (G,2), anchors
-    (L,W,A,4,2) BEV corners.  Returns ``(pi, ni, gi)``: index triples (LongTensors on the GPU) of the positive and of
-    the not-negative anchors and the ground-truth id of every positive, in the reference's order.  One host read
-    (the two list lengths)."""
-    dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
-    nls, nws = anchorCenterCells(gtCenters.float().cpu(), anchors.shape, velorange)
-    a_dev = anchors if anchors.is_cuda else _anchors_on(anchors, dev)
-    g_dev = gts.detach().float().contiguous().to(dev)
-    radius = _window_radius(gts.detach().float().cpu(), anchors[:2, :2].detach().float().cpu())
+_CONSTANTS = {}             # name -> (key, weak reference to the tensor, value): ONE entry per name
+
+
+def _constant(name, t, tag, make):
+    """``make()`` for the tensor ``t``, a constant of the run (the anchor tables, train.py:59-60): kept while the same tensor
+    object comes back."""
+    key = (t.data_ptr(), tuple(t.shape), tag)
+    hit = _CONSTANTS.get(name)
+    if hit is None or hit[0] != key or hit[1]() is not t:
+        hit = (key, weakref.ref(t), make())
+        _CONSTANTS[name] = hit
+    return hit[2]
+
+
+def _anchors_on(anchors, dev, name='anchors'):
+    """The device copy of the anchor grid; ``name`` 'anchors7': that of the (l,w,A,7) table of IgnoreRegions, kept beside it."""
+    return _constant(name, anchors, str(dev), lambda: anchors.detach().float().contiguous().to(dev))
+
+
+def _anchor_radius(anchors: torch.Tensor) -> int:
+    """First window radius of assignAnchorsFrames from the anchor table alone (read once): the anchor's diagonal for both boxes,
+    plus 2 cells, at most 55.  A larger box makes the kernel report status 1 and the call is replayed with twice the radius."""
+    def make():
+        corner = anchors[:2, :2].detach().float().cpu()
+        return _window_radius(corner[0, 0], corner)
+    return _constant('radius', anchors, str(anchors.device), make)
+
+
+def _device_of(anchors, device):
+    return torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
+
+
+def replay_wider(radius, run):
+    """``run(radius) -> (result, status word)`` until status bit 1 (a box reaches beyond the window) is clear or the radius is 55,
+    with twice the radius each time.  Returns (result, status word, the radius that gave them)."""
     while True:
-        pos, neg, gi, counts, status = _hip.classify_anchors(g_dev, a_dev, nls.to(dev), nws.to(dev), negThr, posThr, radius)
-        n_pos, n_neg, st = counts.tolist() + status.tolist()
-        if st & 1 and radius < 55:              # a box much larger than estimated: widen the window and replay
-            radius = min(55, radius * 2)
-            continue
-        break
-    if st & 4:
-        raise X.MvxHipError('classifyAnchors: a ground-truth centre lies outside the anchor grid '
-                            '(the reference reads out of bounds there)')
-    if st & 1:
-        raise X.MvxHipError('classifyAnchors: a ground truth overlaps anchors more than 55 cells from its centre')
-    pi = (pos[0, :n_pos], pos[1, :n_pos], pos[2, :n_pos])
-    ni = (neg[0, :n_neg], neg[1, :n_neg], neg[2, :n_neg])
-    return pi, ni, gi[:n_pos]
+        res, st = run(radius)
+        if not (st & 1 and radius < 55):
+            return res, st, radius
+        radius = min(55, 2 * radius)
+
+
+def _frame_groups(out, live, boxes, radius_of, enqueue, decode, dev):
+    """The one driver of target assignment: the frames ``live`` with their ``boxes`` ((n,4,2) each, n = 0 allowed) in groups of
+    MAX_FRAMES.  Boxes that are device tensors stay on the device; host boxes are joined on the host and copied once;
+    ``radius_of(the joined boxes)`` is the first window radius.
+    ``enqueue(group, radius) -> (pos, neg, gi, words)`` launches a group -- ``group.ids`` its frames, ``group.gts`` their boxes back
+    to back on the device, ``group.off`` the host offsets (F+1), ``group.first`` its first box among all -- and returns the raw
+    device lists with ONE i32 device tensor, word 2F the status; it is read once per enqueue, and enqueued again through
+    replay_wider (a widened radius stays for the groups that follow).  ``decode(host, group, status) -> counts`` (2F) gets the
+    words as a list and raises what they report.  Fills and returns ``out``: out[frame] = ((x,y,z), (x,y,z), gi)."""
+    boxes = [b.detach().float().reshape(-1, 4, 2) for b in boxes]
+    joined = torch.cat([b.to(dev) for b in boxes] if any(b.is_cuda for b in boxes) else boxes).contiguous()
+    radius, gts = radius_of(joined), joined.to(dev)
+    off = [0]
+    for b in boxes:
+        off.append(off[-1] + b.shape[0])
+    for lo in range(0, len(live), X.MAX_FRAMES):
+        grp = types.SimpleNamespace(ids=live[lo:lo + X.MAX_FRAMES], first=off[lo])
+        F = len(grp.ids)
+        grp.off = [o - grp.first for o in off[lo:lo + F + 1]]
+        grp.gts = gts[grp.first:grp.first + grp.off[-1]]
+
+        def run(r):
+            pos, neg, gi, words = enqueue(grp, r)
+            host = words.tolist()                                            # the one host read of the group
+            return (pos, neg, gi, host), host[2 * F]
+        (pos, neg, gi, host), st, radius = replay_wider(radius, run)
+        counts = decode(host, grp, st)
+        for j, k in enumerate(grp.ids):
+            n_pos, n_neg = counts[2 * j], counts[2 * j + 1]
+            out[k] = ((pos[j, 0, :n_pos], pos[j, 1, :n_pos], pos[j, 2, :n_pos]),
+                      (neg[j, 0, :n_neg], neg[j, 1, :n_neg], neg[j, 2, :n_neg]), gi[j, :n_pos])
+    return out
 
 
 def classifyAnchorsFrames(frames, anchors: torch.Tensor, velorange: Sequence[float], negThr: float, posThr: float, device=None):
     """classifyAnchors (train.py:46) for the frames of a step with ONE kernel pass and ONE host read: ``frames`` = per frame
     ``(gts (G,4,2), gtCenters (G,2))`` or None (no box).  Returns per frame ``(pi, ni, gi)`` exactly as classifyAnchors
     would (ground-truth ids local to the frame), or None."""
-    dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
+    dev = _device_of(anchors, device)
     live = [k for k, fr in enumerate(frames) if fr is not None and fr[0].shape[0] > 0]
     out = [None] * len(frames)
     if not live:
         return out
     a_dev = anchors if anchors.is_cuda else _anchors_on(anchors, dev)
-    gts = torch.cat([frames[k][0].detach().float().cpu().reshape(-1, 4, 2) for k in live])
     cen = torch.cat([frames[k][1].detach().float().cpu().reshape(-1, 2) for k in live])
-    off = [0]
-    for k in live:
-        off.append(off[-1] + frames[k][0].shape[0])
-    nls, nws = anchorCenterCells(cen, anchors.shape, velorange)
-    radius = _window_radius(gts, anchors[:2, :2].detach().float().cpu())
-    g_dev = gts.contiguous().to(dev)
-    nls_d, nws_d = nls.to(dev), nws.to(dev)
-    # frame sets hold at most MVX_MAX_FRAMES frames: larger batches go in groups
-    res = {}
-    step = X.MAX_FRAMES
-    for lo in range(0, len(live), step):
-        ids = live[lo:lo + step]
-        sub_off = [o - off[lo] for o in off[lo:lo + len(ids) + 1]]
-        sl = slice(off[lo], off[lo + len(ids)])
-        while True:
-            pos, neg, gi, counts, status = _hip.classify_anchors_frames(g_dev[sl], sub_off, a_dev, nls_d[sl], nws_d[sl], negThr,
-                                                                        posThr, radius)
-            host = torch.cat([counts.reshape(-1), status]).tolist()          # the one host read of the group
-            st = host[-1]
-            if st & 1 and radius < 55:              # a box much larger than estimated: widen the window and replay
-                radius = min(55, radius * 2)
-                continue
-            break
+    nls, nws = (t.to(dev) for t in anchorCenterCells(cen, anchors.shape, velorange))
+
+    def enqueue(grp, r):
+        sl = slice(grp.first, grp.first + grp.off[-1])
+        pos, neg, gi, counts, status = _hip.classify_anchors_frames(grp.gts, grp.off, a_dev, nls[sl], nws[sl], negThr, posThr, r)
+        return pos, neg, gi, torch.cat([counts.reshape(-1), status])
+
+    def decode(host, grp, st):
         if st & 4:
             raise X.MvxHipError('classifyAnchors: a ground-truth centre lies outside the anchor grid '
                                 '(the reference reads out of bounds there)')
         if st & 1:
             raise X.MvxHipError('classifyAnchors: a ground truth overlaps anchors more than 55 cells from its centre')
-        for j, k in enumerate(ids):
-            n_pos, n_neg = host[2 * j], host[2 * j + 1]
-            res[k] = ((pos[j, 0, :n_pos], pos[j, 1, :n_pos], pos[j, 2, :n_pos]),
-                      (neg[j, 0, :n_neg], neg[j, 1, :n_neg], neg[j, 2, :n_neg]), gi[j, :n_pos])
-    for k in live:
-        out[k] = res[k]
-    return out
+        return host[:2 * len(grp.ids)]
+
+    def radius_of(gts):
+        return _window_radius(gts.cpu(), anchors[:2, :2].detach().float().cpu())
+    return _frame_groups(out, live, [frames[k][0] for k in live], radius_of, enqueue, decode, dev)
 
 
-_RADIUS_CACHE = {}
+def classifyAnchors(gts: torch.Tensor, gtCenters: torch.Tensor, anchors: torch.Tensor, velorange: Sequence[float],
+                    negThr: float, posThr: float, device=None) -> Tuple[index3d, index3d, torch.Tensor]:
+    """Reference Calc.py:88-96 (-> cpp/voxelutil.cpp:138-316).  gts (G,4,2) BEV corners, gtCenters (G,2), anchors
+    (L,W,A,4,2) BEV corners.  Returns ``(pi, ni, gi)``: index triples (LongTensors on the GPU) of the positive and of
+    the not-negative anchors and the ground-truth id of every positive, in the reference's order.  One host read
+    (the two list lengths and the status word).  classifyAnchorsFrames for one frame; three empty lists without a box."""
+    res = classifyAnchorsFrames([(gts, gtCenters)], anchors, velorange, negThr, posThr, device)[0]
+    return _empty_lists(_device_of(anchors, device)) if res is None else res
 
 
-def _anchor_radius(anchors: torch.Tensor) -> int:
-    """First window radius of assignAnchorsFrames from the anchor table alone (a constant of the run, read once): the
-    anchor's diagonal for both boxes, plus 2 cells, at most 55.  A larger box makes the kernel report status 1 and the call
-    is replayed with twice the radius."""
-    key = (anchors.data_ptr(), tuple(anchors.shape), str(anchors.device))
-    hit = _RADIUS_CACHE.get(key)
-    if hit is None or hit[0]() is not anchors:
-        import weakref
-        corner = anchors[:2, :2].detach().float().cpu()
-        hit = (weakref.ref(anchors), _window_radius(corner[0, 0], corner))
-        _RADIUS_CACHE.clear()
-        _RADIUS_CACHE[key] = hit
-    return hit[1]
+def _empty_lists(dev):
+    e = torch.empty((0,), dtype=torch.int64, device=dev)
+    return (e, e, e), (e, e, e), e
 
 
 class IgnoreRegions:
@@ -228,91 +257,28 @@ def _cat_rows(items, shape, dtype, dev):
     return torch.cat(parts).contiguous(), off
 
 
-def _assign_with_ignore(frames, anchors, negThr, posThr, forceThr, device, info, ignore):
-    """assignAnchorsFrames with an IgnoreRegions: the ignore pass runs on the raw device lists of the assigner and its counts,
-    stats and status ride in the group's one host read."""
-    if ignore.n_frames != len(frames):
-        raise ValueError('assignAnchors: the IgnoreRegions hold %d frames, the call %d' % (ignore.n_frames, len(frames)))
-    n_box = [0 if fr is None else int(fr[0].shape[0]) for fr in frames]
-    live = [k for k in range(len(frames)) if n_box[k] > 0 or ignore.has_source(k)]
-    out = [None] * len(frames)
-    if info is not None:
-        info.update(gt_best=[None] * len(frames), forced_only=0, none=0, ignore_stats=[0, 0, 0, 0])
-    if not live:
-        return out
-    dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
-    a_dev = anchors if anchors.is_cuda else _anchors_on(anchors, dev)
-    an7 = None
-    if ignore.anchors is not None:
-        an7 = ignore.anchors.detach().float().contiguous() if ignore.anchors.is_cuda else _anchors7_on(ignore.anchors, dev)
-        if an7.numel() != a_dev.numel() // 8 * 7:
-            raise ValueError('assignAnchors: the IgnoreRegions hold another anchor table')
-    else:
-        an7 = torch.zeros((a_dev.numel() // 8 * 7,), dtype=torch.float32, device=dev)       # never read: no rectangle
-    radius = _anchor_radius(anchors)
-    step = X.MAX_FRAMES
-    for lo in range(0, len(live), step):
-        ids = live[lo:lo + step]
-        F = len(ids)
-        sub_off = [0]
-        for k in ids:
-            sub_off.append(sub_off[-1] + n_box[k])
-        boxes = [frames[k][0].detach().float().reshape(-1, 4, 2).to(dev) for k in ids if n_box[k] > 0]
-        g_dev = torch.cat(boxes).contiguous() if boxes else torch.zeros((0, 4, 2), dtype=torch.float32, device=dev)
-        # the sources of the group, on the device once (a replay reuses them)
-        rects, rect_off = _cat_rows([ignore.rects[k] for k in ids], (4,), torch.float32, dev)
-        quads, quad_off = _cat_rows([ignore.quads[k] for k in ids], (4, 2), torch.float32, dev)
-        mats = None
-        if rects is not None:
-            m = np.zeros((F, 3, 4), np.float64)
-            for j, k in enumerate(ids):
-                if ignore.matrix[k] is not None:
-                    m[j] = np.asarray(ignore.matrix[k], np.float64).reshape(3, 4)
-            mats = torch.from_numpy(m).to(dev)
-        gt_points = gt_off = None
-        if ignore.min_points > 0 and any(ignore.gt_points[k] is not None for k in ids):
-            parts = []
-            for k in ids:
-                p = ignore.gt_points[k]
-                if n_box[k] and (p is None or p.shape[0] != n_box[k]):
-                    raise ValueError('assignAnchors: frame %d holds %d boxes, its point counts are for %s'
-                                     % (k, n_box[k], None if p is None else p.shape[0]))
-                if n_box[k]:
-                    parts.append(p.to(dev))
-            gt_points = torch.cat(parts).contiguous()
-            gt_off = torch.tensor(sub_off, dtype=torch.int32).to(dev)
-        while True:
-            pos, neg, gi, host_dev = _hip.assign_anchors_frames(g_dev, sub_off, a_dev, negThr, posThr, forceThr, radius)
-            pos, neg, gi, words = _hip.ignore_anchors_frames(pos, neg, gi, host_dev[:2 * F], an7, a_dev, gt_off, gt_points,
-                                                             ignore.min_points, rects, rect_off, mats, quads, quad_off, ignore.ioa_thr)
-            host = torch.cat([host_dev, words]).cpu()                        # the one host read of the group
-            st = int(host[2 * F])
-            if st & 1 and radius < 55:              # a box much larger than an anchor: widen the window and replay both passes
-                radius = min(55, radius * 2)
-                continue
-            break
-        if st & 1:
-            raise X.MvxHipError('assignAnchors: a ground truth overlaps anchors more than 55 cells from its centre '
-                                '(or the anchor table is no regular grid)')
-        n_assign = 2 * F + 1 + sub_off[-1]
-        best = host[2 * F + 1:n_assign].view(torch.float32)
-        counts = host[n_assign:n_assign + 2 * F].tolist()
-        stats = host[n_assign + 2 * F:n_assign + 6 * F].view(F, 4)
-        if int(host[n_assign + 6 * F]):
-            raise X.MvxHipError('assignAnchors: the ignore pass reports status %d' % int(host[n_assign + 6 * F]))
+def _ignore_sources(ignore, grp, dev):
+    """The sources of a group for _hip.ignore_anchors_frames, on the device: (gt_off, gt_points, rects, rect_off, mats, quads,
+    quad_off), each None where the group has none."""
+    ids = grp.ids
+    rects, rect_off = _cat_rows([ignore.rects[k] for k in ids], (4,), torch.float32, dev)
+    quads, quad_off = _cat_rows([ignore.quads[k] for k in ids], (4, 2), torch.float32, dev)
+    mats = gt_points = gt_off = None
+    if rects is not None:
+        m = [np.zeros((3, 4)) if ignore.matrix[k] is None else np.asarray(ignore.matrix[k], np.float64).reshape(3, 4) for k in ids]
+        mats = torch.from_numpy(np.stack(m)).to(dev)
+    if ignore.min_points > 0 and any(ignore.gt_points[k] is not None for k in ids):
+        parts = []
         for j, k in enumerate(ids):
-            n_pos, n_neg = counts[2 * j], counts[2 * j + 1]
-            out[k] = ((pos[j, 0, :n_pos], pos[j, 1, :n_pos], pos[j, 2, :n_pos]),
-                      (neg[j, 0, :n_neg], neg[j, 1, :n_neg], neg[j, 2, :n_neg]), gi[j, :n_pos])
-            if info is not None:
-                info['ignore_stats'] = [a + int(b) for a, b in zip(info['ignore_stats'], stats[j])]
-                if n_box[k]:
-                    b = best[sub_off[j]:sub_off[j + 1]].clone()
-                    forced = (b >= forceThr) & (b < posThr) if forceThr <= 1.5 else torch.zeros_like(b, dtype=torch.bool)
-                    info['gt_best'][k] = b
-                    info['forced_only'] += int(forced.sum())
-                    info['none'] += int(((b < posThr) & ~forced).sum())
-    return out
+            p, n = ignore.gt_points[k], grp.off[j + 1] - grp.off[j]
+            if n and (p is None or p.shape[0] != n):
+                raise ValueError('assignAnchors: frame %d holds %d boxes, its point counts are for %s'
+                                 % (k, n, None if p is None else p.shape[0]))
+            if n:
+                parts.append(p.to(dev))
+        gt_points = torch.cat(parts).contiguous()
+        gt_off = torch.tensor(grp.off, dtype=torch.int32).to(dev)
+    return gt_off, gt_points, rects, rect_off, mats, quads, quad_off
 
 
 def assignAnchorsFrames(frames, anchors: torch.Tensor, negThr: float = 0.45, posThr: float = 0.6, forceThr: float = 0.1,
@@ -328,105 +294,79 @@ def assignAnchorsFrames(frames, anchors: torch.Tensor, negThr: float = 0.45, pos
     None, 'forced_only': the boxes whose best IoU lies in [forceThr, posThr) -- they owe their positive to the forced match --
     and 'none': the boxes below both (a box whose anchors all went to a box with an equal or better claim is not counted).
 
-    ``ignore`` (default None: off, the code path of before): an IgnoreRegions for these frames.  The ignore pass (csrc/ignore.hip,
-    DESIGN.md 3.30) then rewrites the raw device lists before the host read -- positives of sparse boxes are demoted, anchors
-    over a DontCare rectangle or a look-alike box become not negative -- and its counts, status and stats ride in that same
-    read; it is enqueued again on a radius replay.  A frame without boxes but with rectangles or look-alike boxes is live: it
-    returns ``((e, e, e), ni, e)``.  ``info`` gains 'ignore_stats': [demoted positives, anchors newly ignored by a rectangle,
-    newly ignored by a box only, sparse boxes], summed over the frames."""
+    ``ignore`` (default None: off, no ignore kernel and no ignore buffer): an IgnoreRegions for these frames.  The ignore pass
+    (csrc/ignore.hip) then rewrites the raw device lists before the host read -- positives of sparse boxes are
+    demoted, anchors over a DontCare rectangle or a look-alike box become not negative -- and its counts, status and stats ride
+    in that same read; it is enqueued again on a radius replay.  A frame without boxes but with rectangles or look-alike boxes is
+    live: it returns ``((e, e, e), ni, e)``.  ``info`` gains 'ignore_stats': [demoted positives, anchors newly ignored by a
+    rectangle, newly ignored by a box only, sparse boxes], summed over the frames."""
     if not (0.0 < negThr <= posThr):
         raise ValueError('assignAnchors: need 0 < negThr <= posThr, got %r, %r' % (negThr, posThr))
     if not forceThr > 0.0:
         raise ValueError('assignAnchors: need forceThr > 0 (above 1.5 = no forced match), got %r' % (forceThr,))
-    if ignore is not None:
-        return _assign_with_ignore(frames, anchors, negThr, posThr, forceThr, device, info, ignore)
-    live =[k for k, fr in enumerate(frames) if fr is not None and fr[0].shape[0] > 0]
+    if ignore is not None and ignore.n_frames != len(frames):
+        raise ValueError('assignAnchors: the IgnoreRegions hold %d frames, the call %d' % (ignore.n_frames, len(frames)))
+    n_box = [0 if fr is None else int(fr[0].shape[0]) for fr in frames]
+    live = [k for k in range(len(frames)) if n_box[k] > 0 or (ignore is not None and ignore.has_source(k))]
     out = [None] * len(frames)
     if info is not None:
         info.update(gt_best=[None] * len(frames), forced_only=0, none=0)
+        if ignore is not None:
+            info['ignore_stats'] = [0, 0, 0, 0]
     if not live:
         return out
-    dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
+    dev = _device_of(anchors, device)
     a_dev = anchors if anchors.is_cuda else _anchors_on(anchors, dev)
-    boxes = [frames[k][0].detach().float().reshape(-1, 4, 2) for k in live]
-    if any(b.is_cuda for b in boxes):
-        g_dev = torch.cat([b.to(dev) for b in boxes]).contiguous()
-    else:
-        g_dev = torch.cat(boxes).contiguous().to(dev)
-    off = [0]
-    for b in boxes:
-        off.append(off[-1] + b.shape[0])
-    radius = _anchor_radius(anchors)
-    step = X.MAX_FRAMES
-    for lo in range(0, len(live), step):
-        ids = live[lo:lo + step]
-        sub_off = [o - off[lo] for o in off[lo:lo + len(ids) + 1]]
-        sl = slice(off[lo], off[lo + len(ids)])
-        while True:
-            pos, neg, gi, host_dev = _hip.assign_anchors_frames(g_dev[sl], sub_off, a_dev, negThr, posThr, forceThr, radius)
-            host = host_dev.cpu()                                            # the one host read of the group
-            st = int(host[2 * len(ids)])
-            if st & 1 and radius < 55:              # a box much larger than an anchor: widen the window and replay
-                radius = min(55, radius * 2)
-                continue
-            break
+    if ignore is not None and ignore.anchors is not None:
+        an7 = ignore.anchors.detach().float().contiguous() if ignore.anchors.is_cuda else _anchors_on(ignore.anchors, dev, 'anchors7')
+        if an7.numel() != a_dev.numel() // 8 * 7:
+            raise ValueError('assignAnchors: the IgnoreRegions hold another anchor table')
+    elif ignore is not None:
+        an7 = torch.zeros((a_dev.numel() // 8 * 7,), dtype=torch.float32, device=dev)       # never read: no rectangle
+    sources = []                # [group, its sources on the device]: made once, a replay reuses them
+
+    def enqueue(grp, r):
+        if ignore is not None and (not sources or sources[0] is not grp):
+            sources[:] = [grp, _ignore_sources(ignore, grp, dev)]
+        pos, neg, gi, words = _hip.assign_anchors_frames(grp.gts, grp.off, a_dev, negThr, posThr, forceThr, r)
+        if ignore is None:
+            return pos, neg, gi, words
+        gt_off, gt_points, rects, rect_off, mats, quads, quad_off = sources[1]
+        pos, neg, gi, more = _hip.ignore_anchors_frames(pos, neg, gi, words[:2 * len(grp.ids)], an7, a_dev, gt_off, gt_points,
+                                                        ignore.min_points, rects, rect_off, mats, quads, quad_off, ignore.ioa_thr)
+        return pos, neg, gi, torch.cat([words, more])
+
+    def decode(host, grp, st):
+        """Words of the assigner: counts (2F), status, gt_best (G); of the ignore pass behind them: counts (2F), stats (4F), status."""
         if st & 1:
             raise X.MvxHipError('assignAnchors: a ground truth overlaps anchors more than 55 cells from its centre '
                                 '(or the anchor table is no regular grid)')
-        counts = host[:2 * len(ids)].tolist()
-        best = host[2 * len(ids) + 1:].view(torch.float32)
-        for j, k in enumerate(ids):
-            n_pos, n_neg = counts[2 * j], counts[2 * j + 1]
-            out[k] = ((pos[j, 0, :n_pos], pos[j, 1, :n_pos], pos[j, 2, :n_pos]),
-                      (neg[j, 0, :n_neg], neg[j, 1, :n_neg], neg[j, 2, :n_neg]), gi[j, :n_pos])
-            if info is not None:
-                b = best[sub_off[j]:sub_off[j + 1]].clone()
-                forced = (b >= forceThr) & (b < posThr) if forceThr <= 1.5 else torch.zeros_like(b, dtype=torch.bool)
-                info['gt_best'][k] = b
-                info['forced_only'] += int(forced.sum())
-                info['none'] += int(((b < posThr) & ~forced).sum())
-    return out
+        F, n_assign = len(grp.ids), 2 * len(grp.ids) + 1 + grp.off[-1]
+        if ignore is not None and host[n_assign + 6 * F]:
+            raise X.MvxHipError('assignAnchors: the ignore pass reports status %d' % host[n_assign + 6 * F])
+        if info is not None:
+            best = torch.tensor(host[2 * F + 1:n_assign], dtype=torch.int32).view(torch.float32)
+            for j, k in enumerate(grp.ids):
+                if ignore is not None:
+                    stats = host[n_assign + 2 * F + 4 * j:n_assign + 2 * F + 4 * j + 4]
+                    info['ignore_stats'] = [a + b for a, b in zip(info['ignore_stats'], stats)]
+                if n_box[k]:
+                    b = best[grp.off[j]:grp.off[j + 1]].clone()
+                    forced = (b >= forceThr) & (b < posThr) if forceThr <= 1.5 else torch.zeros_like(b, dtype=torch.bool)
+                    info['gt_best'][k] = b
+                    info['forced_only'] += int(forced.sum())
+                    info['none'] += int(((b < posThr) & ~forced).sum())
+        return host[n_assign:n_assign + 2 * F] if ignore is not None else host[:2 * F]
+    none = torch.zeros((0, 4, 2), dtype=torch.float32)
+    return _frame_groups(out, live, [frames[k][0] if n_box[k] else none for k in live], lambda g: _anchor_radius(anchors), enqueue,
+                         decode, dev)
 
 
 def assignAnchors(gts: torch.Tensor, anchors: torch.Tensor, negThr: float = 0.45, posThr: float = 0.6, forceThr: float = 0.1,
                   device=None, info=None):
     """assignAnchorsFrames for one frame: ``(pi, ni, gi)``, three empty lists for a frame without boxes."""
     res = assignAnchorsFrames([(gts, None)], anchors, negThr, posThr, forceThr, device, info)[0]
-    if res is None:
-        dev = torch.device(device) if device is not None else (anchors.device if anchors.is_cuda else X.device())
-        e = torch.empty((0,), dtype=torch.int64, device=dev)
-        return (e, e, e), (e, e, e), e
-    return res
-
-
-_ANCHOR_CACHE = {}
-
-
-def _anchors_on(anchors, dev):
-    """The anchor grid is a constant of the run (train.py:59-60): keep its device copy."""
-    key = (anchors.data_ptr(), tuple(anchors.shape), str(dev))
-    hit = _ANCHOR_CACHE.get(key)
-    if hit is None or hit[0]() is not anchors:
-        import weakref
-        hit = (weakref.ref(anchors), anchors.detach().float().contiguous().to(dev))
-        _ANCHOR_CACHE.clear()
-        _ANCHOR_CACHE[key] = hit
-    return hit[1]
-
-
-_ANCHOR7_CACHE = {}
-
-
-def _anchors7_on(anchors7, dev):
-    """... and so is the (l,w,A,7) table of IgnoreRegions."""
-    key = (anchors7.data_ptr(), tuple(anchors7.shape), str(dev))
-    hit = _ANCHOR7_CACHE.get(key)
-    if hit is None or hit[0]() is not anchors7:
-        import weakref
-        hit = (weakref.ref(anchors7), anchors7.detach().float().contiguous().to(dev))
-        _ANCHOR7_CACHE.clear()
-        _ANCHOR7_CACHE[key] = hit
-    return hit[1]
+    return _empty_lists(_device_of(anchors, device)) if res is None else res
 
 
 def bboxCam2Lidar(camBoxes: Union[torch.Tensor, np.ndarray], c2v: Union[torch.Tensor, np.ndarray], inplace: bool = False):

@@ -337,14 +337,12 @@ class _Cpp:
         g = _Cpp._boxes(gts, dev)
         a = _Cpp._boxes(anchors, dev)
         to_i64 = lambda v: torch.as_tensor(np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v, dtype=np.int64)).to(dev)
-        radius = Calc._window_radius(g.cpu(), a[:2, :2].cpu()) if g.shape[0] else 2
-        while True:
+
+        def run(radius):
             pos, neg, gi, counts, status = _hip.classify_anchors(g, a, to_i64(nls), to_i64(nws), negThr, posThr, radius)
             n_pos, n_neg, st = counts.tolist() + status.tolist()
-            if st & 1 and radius < 55:
-                radius = min(55, 2 * radius)
-                continue
-            break
+            return (pos, neg, gi, n_pos, n_neg), st
+        (pos, neg, gi, n_pos, n_neg), st, _ = Calc.replay_wider(Calc._window_radius(g.cpu(), a[:2, :2].cpu()) if g.shape[0] else 2, run)
         if st:
             raise MvxHipError('_classifyAnchors: status %d (1 = window too small, 4 = centre outside the grid)' % st)
         pos, neg, gi = pos.cpu().numpy(), neg.cpu().numpy(), gi.cpu().numpy()

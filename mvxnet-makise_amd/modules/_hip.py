@@ -1868,44 +1868,38 @@ def bbox_pairwise(b1, b2, want_iou):
     return out
 
 
+def _anchor_lists(F, cap, dev):
+    """The list buffers of F frames: pos_idx i64 (F,3,cap), neg_idx i64 (F,3,cap), gi i64 (F,cap)."""
+    return (torch.empty((F, 3, cap), dtype=torch.int64, device=dev), torch.empty((F, 3, cap), dtype=torch.int64, device=dev),
+            torch.empty((F, cap), dtype=torch.int64, device=dev))
+
+
+def _gt_offsets(gt_off):
+    """The host list (F+1) as the C entries take it."""
+    return (ctypes.c_int32 * len(gt_off))(*[int(v) for v in gt_off])
+
+
 def classify_anchors(gts, anchor_bevs, nls, nws, neg_thr, pos_thr, radius, cap=None):
-    """Device tensors in, capacity-sized device tensors out: (pos_idx i64 (3,cap), neg_idx i64 (3,cap), gi i64 (cap,),
-    counts i32 (2,), status i32 (1,))."""
-    G = gts.shape[0]
-    L, W, A = anchor_bevs.shape[:3]
-    dev = anchor_bevs.device
-    wn = 2 * radius + 1
-    cap = max(1, G * A * wn * wn) if cap is None else int(cap)
-    pos = torch.empty((3, cap), dtype=torch.int64, device=dev)
-    neg = torch.empty((3, cap), dtype=torch.int64, device=dev)
-    gi = torch.empty((cap,), dtype=torch.int64, device=dev)
-    counts = torch.empty((2,), dtype=torch.int32, device=dev)
-    status = torch.zeros((1,), dtype=torch.int32, device=dev)
-    ws = workspace(X.lib.mvx_classify_anchors_workspace_bytes(G, A, radius), dev, 'anchors')
-    X.check(X.lib.mvx_classify_anchors(X.ptr(gts), G, X.ptr(anchor_bevs), L, W, A, X.ptr(nls), X.ptr(nws), float(neg_thr),
-                                       float(pos_thr), int(radius), X.ptr(pos), X.ptr(neg), X.ptr(gi), cap, X.ptr(counts),
-                                       X.ptr(status), X.ptr(ws), ws.numel(), X.stream()), 'mvx_classify_anchors')
-    return pos, neg, gi, counts, status
+    """One frame of classify_anchors_frames: (pos_idx i64 (3,cap), neg_idx i64 (3,cap), gi i64 (cap,), counts i32 (2,),
+    status i32 (1,))."""
+    pos, neg, gi, counts, status = classify_anchors_frames(gts, [0, gts.shape[0]], anchor_bevs, nls, nws, neg_thr, pos_thr, radius, cap)
+    return pos[0], neg[0], gi[0], counts[0], status
 
 
-def classify_anchors_frames(gts, gt_off, anchor_bevs, nls, nws, neg_thr, pos_thr, radius):
+def classify_anchors_frames(gts, gt_off, anchor_bevs, nls, nws, neg_thr, pos_thr, radius, cap=None):
     """The frames of a step in one walk launch: gts (G_total,4,2) of all frames back to back, ``gt_off`` host list (F+1).
     Returns (pos_idx i64 (F,3,cap), neg_idx i64 (F,3,cap), gi i64 (F,cap), counts i32 (F,2), status i32 (1,))."""
-    import ctypes
     F = len(gt_off) - 1
     L, W, A = anchor_bevs.shape[:3]
     dev = anchor_bevs.device
     wn = 2 * radius + 1
     gmax = max(gt_off[f + 1] - gt_off[f] for f in range(F))
-    cap = max(1, gmax * A * wn * wn)
-    pos = torch.empty((F, 3, cap), dtype=torch.int64, device=dev)
-    neg = torch.empty((F, 3, cap), dtype=torch.int64, device=dev)
-    gi = torch.empty((F, cap), dtype=torch.int64, device=dev)
+    cap = max(1, gmax * A * wn * wn) if cap is None else int(cap)
+    pos, neg, gi = _anchor_lists(F, cap, dev)
     counts = torch.empty((F, 2), dtype=torch.int32, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     ws = workspace(X.lib.mvx_classify_anchors_workspace_bytes(int(gt_off[-1]), A, radius), dev, 'anchors')
-    off = (ctypes.c_int32 * (F + 1))(*[int(v) for v in gt_off])
-    X.check(X.lib.mvx_classify_anchors_frames(X.ptr(gts), off, F, X.ptr(anchor_bevs), L, W, A, X.ptr(nls), X.ptr(nws),
+    X.check(X.lib.mvx_classify_anchors_frames(X.ptr(gts), _gt_offsets(gt_off), F, X.ptr(anchor_bevs), L, W, A, X.ptr(nls), X.ptr(nws),
                                               float(neg_thr), float(pos_thr), int(radius), X.ptr(pos), X.ptr(neg), X.ptr(gi), cap,
                                               X.ptr(counts), X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
             'mvx_classify_anchors_frames')
@@ -1916,7 +1910,6 @@ def assign_anchors_frames(gts, gt_off, anchor_bevs, neg_thr, pos_thr, force_thr,
     """Max-IoU assignment (csrc/assign.hip) of the frames of a step: gts (G_total,4,2) of all frames back to back, ``gt_off`` host
     list (F+1).  Returns (pos_idx i64 (F,3,cap), neg_idx i64 (F,3,cap), gi i64 (F,cap), host = i32 (2F + 1 + G_total): counts
     (F,2), status, then the bits of gt_best f32 (G_total) -- ONE device tensor, so that the caller reads them together)."""
-    import ctypes
     F = len(gt_off) - 1
     G = int(gt_off[-1])
     L, W, A = anchor_bevs.shape[:3]
@@ -1924,14 +1917,11 @@ def assign_anchors_frames(gts, gt_off, anchor_bevs, neg_thr, pos_thr, force_thr,
     wn = 2 * radius + 1
     gmax = max(gt_off[f + 1] - gt_off[f] for f in range(F))
     cap = max(1, min(L * W * A, gmax * A * wn * wn)) if cap is None else int(cap)
-    pos = torch.empty((F, 3, cap), dtype=torch.int64, device=dev)
-    neg = torch.empty((F, 3, cap), dtype=torch.int64, device=dev)
-    gi = torch.empty((F, cap), dtype=torch.int64, device=dev)
+    pos, neg, gi = _anchor_lists(F, cap, dev)
     host = torch.zeros((2 * F + 1 + G,), dtype=torch.int32, device=dev)
     counts, status, best = host[:2 * F], host[2 * F:2 * F + 1], host[2 * F + 1:]
     ws = workspace(X.lib.mvx_assign_anchors_frames_workspace_bytes(G, F, L, W, A), dev, 'anchors')
-    off = (ctypes.c_int32 * (F + 1))(*[int(v) for v in gt_off])
-    X.check(X.lib.mvx_assign_anchors_frames(X.ptr(gts), off, F, X.ptr(anchor_bevs), L, W, A, float(neg_thr), float(pos_thr),
+    X.check(X.lib.mvx_assign_anchors_frames(X.ptr(gts), _gt_offsets(gt_off), F, X.ptr(anchor_bevs), L, W, A, float(neg_thr), float(pos_thr),
                                             float(force_thr), int(radius), X.ptr(pos), X.ptr(neg), X.ptr(gi), cap, X.ptr(counts),
                                             X.ptr(best) if G else None, X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
             'mvx_assign_anchors_frames')

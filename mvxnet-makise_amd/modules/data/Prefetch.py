@@ -24,8 +24,7 @@ import threading
 import numpy as np
 import torch
 
-import modules.config as cfg
-from modules import Calc, _hip
+from modules import _hip
 
 
 class _Staging:
@@ -80,20 +79,12 @@ class PrefetchLoader:
             st.free.synchronize()                                # its previous copies have left the host buffers
         return st
 
-    def _assign(self, boxes):
-        if self.assigner is not None:
-            return self.assigner(boxes)
-        return Calc.classifyAnchorsFrames(boxes, self.anchor_bevs, cfg.velorange, 0.45, 0.6)
-
-    def _assign_ignoring(self, group, boxes, gts, glob, points6, n_points):
-        """Targets of a group with the ignore regions: the points are counted on the cloud as the network sees it."""
+    def _targets(self, group, boxes, gts, glob, points6, n_points):
         from modules import pipeline
-        settings = dict(self.ignore)
-        settings['labels'] = [self.ignore['labels_of'](self.names_of(d)) for d in group]
-        regions = pipeline.ignore_regions_of(group, settings, gts, glob, self.device).count_points(points6, n_points)
-        lists = self.assigner(boxes, ignore=regions)
-        empty = torch.zeros((0, 7), dtype=torch.float32, device=self.device)
-        return [None if t is None else (t[0], t[1], t[2], empty if gt is None else gt) for t, gt in zip(lists, gts)]
+        settings = None
+        if self.ignore is not None:
+            settings = dict(self.ignore, labels=[self.ignore['labels_of'](self.names_of(d)) for d in group], keep=None)
+        return pipeline.targets_of_group(group, boxes, gts, self.assigner, self.anchor_bevs, settings, glob, points6, n_points, self.device)
 
     def _prepare(self, group):
         import time
@@ -119,11 +110,8 @@ class PrefetchLoader:
             targets = [None] * B
             if self.augment is None and self.geometry is None:          # with an augmentation the boxes are only known after it (__next__)
                 boxes = [(d[4], d[3][:, [0, 1]]) if (d[4] is not None and d[4].shape[0] != 0) else None for d in group]
-                if self.ignore is not None:
-                    targets = self._assign_ignoring(group, boxes, [None if d[3] is None else d[3].to(dev) for d in group], None, pts6, n)
-                else:
-                    lists = self._assign(boxes)                 # one pass, one host read
-                    targets = [None if t is None else (t[0], t[1], t[2], d[3].to(dev)) for t, d in zip(lists, group)]
+                gts = [None if d[3] is None else d[3].to(dev) for d in group]
+                targets = self._targets(group, boxes, gts, None, pts6, n)      # one pass, one host read
             ev = torch.cuda.Event()
             ev.record(self.stream)
         t2 = time.perf_counter()
@@ -172,7 +160,7 @@ class PrefetchLoader:
         if raw is None:
             return None, None
         from modules.data.Preprocessing import _calib_products
-        from modules.pipeline import FrameBatch
+        from modules import pipeline
         pts6, perms, n, group = raw
         main = torch.cuda.current_stream(self.device)
         main.wait_event(ev)
@@ -189,14 +177,8 @@ class PrefetchLoader:
             m, p2 = _calib_products(d[5], True)
             _hip.lidar2img(pts6[k, :P], m, p2, math_f32=True, out=pts6[k, :P], col_offset=4, swap_rc=True)    # reads x y z, writes cols 4:6
             fpn.append(self.fpn_fn(self.names_of(d), self.device))
-        batch = FrameBatch(pts6, perms, n, fpn)
-        geometry, glob = self.geometry, None
-        if self.ignore is not None and geometry is not None:    # the global draws, which the frames' matrices need, made first
-            from modules.augment import Geometry
-            noise, glob, _ = Geometry.geometry_draws(geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
-            geometry = dict(geometry) if isinstance(geometry, dict) else {'params': geometry}
-            geometry.update(noise=noise, glob=glob)
-            glob = np.asarray(glob.cpu() if isinstance(glob, torch.Tensor) else glob, np.float32)
+        batch = pipeline.FrameBatch(pts6, perms, n, fpn)
+        geometry, glob = pipeline.global_draws_first(self.geometry, self.ignore, len(group))    # the frames' matrices need them
         if self.augment is not None:
             from modules.augment import Augment
             a = self.augment
@@ -206,9 +188,6 @@ class PrefetchLoader:
             from modules.augment import Geometry
             noise, glob_d, iou_thr = Geometry.geometry_draws(geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
             res = Geometry.augmentGeometryFrames(batch, [d[3] for d in group], noise, glob_d, iou_thr=iou_thr)
-        if (self.augment is not None or self.geometry is not None) and self.ignore is not None:
-            return batch, self._assign_ignoring(group, res.boxes, res.bbox3d, glob, batch.points6, batch.n_points)
         if self.augment is not None or self.geometry is not None:
-            lists = self._assign(res.boxes)
-            targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, res.bbox3d)]
+            targets = self._targets(group, res.boxes, res.bbox3d, glob, batch.points6, batch.n_points)
         return batch, targets

@@ -630,15 +630,8 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
     if ignore is not None and not assigner_takes_ignore(assigner):
         raise ValueError('batch_from_dataset: ignore regions need an assigner with a keyword `ignore` '
                          '(Calc.assignAnchorsFrames; the reference assigner has no ignore pass)')
-    glob_pre = None
-    if ignore is not None and geometry is not None:
-        from modules.augment import Geometry
-        noise, glob_pre, _ = Geometry.geometry_draws(geometry, len(group), _hip.GT_PASTE_MAX_BOXES)
-        geometry = dict(geometry) if isinstance(geometry, dict) else {'params': geometry}
-        geometry.update(noise=noise, glob=glob_pre)
-        glob_pre = np.asarray(glob_pre.cpu() if isinstance(glob_pre, torch.Tensor) else glob_pre, np.float32)
+    geometry, glob_pre = global_draws_first(geometry, ignore, len(group))
     extractor = augment.get('extractor') if augment is not None else None
-    from modules import Calc
     from modules.data.Preprocessing import _calib_products
     B = len(group)
     pts6 = torch.zeros((B, cap_points, 6), dtype=torch.float32, device=device)
@@ -685,18 +678,39 @@ def batch_from_dataset(group, names, device, anchorBevs, fpn_fn, cap_points, aug
         gts = [None if d[3] is None else d[3].to(device) for d in group]
     if geo is not None and isinstance(geometry, dict) and geometry.get('keep') is not None:
         geometry['keep']['result'] = geo
-    # target assignment of all frames in one kernel pass / one host read
-    if ignore is not None:
-        regions = ignore_regions_of(group, ignore, gts, glob_pre, device).count_points(batch.points6, batch.n_points)
-        if ignore.get('keep') is not None:
-            ignore['keep']['regions'] = regions
-        lists = assigner(boxes, ignore=regions)
-        empty = torch.zeros((0, 7), dtype=torch.float32, device=device)
-        targets = [None if t is None else (t[0], t[1], t[2], empty if gt is None else gt) for t, gt in zip(lists, gts)]
-        return batch.mark_created(), targets
-    lists = Calc.classifyAnchorsFrames(boxes, anchorBevs, cfg.velorange, 0.45, 0.6) if assigner is None else assigner(boxes)
-    targets = [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, gts)]
-    return batch.mark_created(), targets
+    return batch.mark_created(), targets_of_group(group, boxes, gts, assigner, anchorBevs, ignore, glob_pre, batch.points6, batch.n_points,
+                                                  device)
+
+
+def global_draws_first(geometry, ignore, n_frames):
+    """With ignore regions and the geometric augmentation both on, the frames' matrices need the global draws: they are made
+    here, in front of every other draw of the batch, and travel inside ``geometry``.  Returns (geometry, the global draws (F,4)
+    f32 on the host or None)."""
+    if ignore is None or geometry is None:
+        return geometry, None
+    import numpy as np
+    from modules.augment import Geometry
+    noise, glob, _ = Geometry.geometry_draws(geometry, n_frames, _hip.GT_PASTE_MAX_BOXES)
+    geometry = dict(geometry) if isinstance(geometry, dict) else {'params': geometry}
+    geometry.update(noise=noise, glob=glob)
+    return geometry, np.asarray(glob.cpu() if isinstance(glob, torch.Tensor) else glob, np.float32)
+
+
+def targets_of_group(group, boxes, gts, assigner, anchor_bevs, ignore, glob, points6, n_points, device):
+    """Target assignment of the frames ``group`` in one kernel pass / one host read: ``boxes`` per frame (BEV corners, centres) or
+    None, ``gts`` the frames' Car boxes or None, ``assigner`` / ``ignore`` those of batch_from_dataset, ``glob`` the global draws
+    of global_draws_first, ``points6`` / ``n_points`` the resident cloud as the network sees it (the ignore regions count its
+    points).  Returns per frame (pi, ni, gi, gt boxes) or None; a live frame without Car boxes gets an empty (0, 7) tensor."""
+    if ignore is None:
+        from modules import Calc
+        lists = Calc.classifyAnchorsFrames(boxes, anchor_bevs, cfg.velorange, 0.45, 0.6) if assigner is None else assigner(boxes)
+        return [None if t is None else (t[0], t[1], t[2], gt) for t, gt in zip(lists, gts)]
+    regions = ignore_regions_of(group, ignore, gts, glob, device).count_points(points6, n_points)
+    if ignore.get('keep') is not None:
+        ignore['keep']['regions'] = regions
+    lists = assigner(boxes, ignore=regions)
+    empty = torch.zeros((0, 7), dtype=torch.float32, device=device)
+    return [None if t is None else (t[0], t[1], t[2], empty if gt is None else gt) for t, gt in zip(lists, gts)]
 
 
 def assigner_takes_ignore(assigner):

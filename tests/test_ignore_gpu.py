@@ -394,6 +394,43 @@ def test_ignore_none_is_the_direct_assigner_result():
             assert np.array_equal(a, b)
 
 
+def test_regions_without_a_source_change_nothing_but_the_launches():
+    """Calc.assignAnchorsFrames on (boxes, None, boxes): ``ignore=None`` launches the assigner's five kernels per enqueue and no
+    other; an IgnoreRegions without any source and min_points = 0 adds the ignore pass's four behind every one of them and returns
+    the same lists and the same ``info`` (the rule, tests/ignore_ref.py, is the identity on them), with all-zero stats."""
+    from modules import Calc
+    from modules import Extension as X
+    g = IC.grid('24x20x2')
+    cars, _ = IC.base_boxes()
+    bevs = _dev(g['bevs'])
+    frames = [(torch.from_numpy(C.bev(cars[:4])), None), None, (torch.from_numpy(C.bev(cars[4:])), None)]
+    runs = []
+    for ignore in (None, Calc.IgnoreRegions(3, min_points=0)):
+        info = {}
+        n0 = X.lib.mvx_launch_count()
+        out = Calc.assignAnchorsFrames(frames, bevs, IC.NEG, IC.POS, IC.FORCE, info=info, ignore=ignore)
+        runs.append((out, info, X.lib.mvx_launch_count() - n0))
+    (plain, info_p, n_p), (ign, info_i, n_i) = runs
+    enqueues = n_p // 5
+    print('launches: %d without regions, %d with (%d enqueue(s))' % (n_p, n_i, enqueues))
+    assert enqueues >= 1 and n_p == 5 * enqueues and n_i == (5 + 4) * enqueues
+    assert plain[1] is None and ign[1] is None
+    N = g['l'] * g['w'] * g['A']
+    for k in (0, 2):
+        a, b = _calc_lists(plain[k]), _calc_lists(ign[k])
+        assert len(a[0]) > 0 and len(a[3]) > len(a[0])
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y)
+        rule = IR.ignore_rule(N, AC.flat(a[0], a[1], a[2], g), a[6], AC.flat(a[3], a[4], a[5], g))
+        for x, y in zip(a, _triples(rule['pos'], g) + _triples(rule['notneg'], g) + [rule['gi']]):
+            assert np.array_equal(x, y)
+        assert rule['stats'] == [0, 0, 0, 0]
+        assert torch.equal(info_p['gt_best'][k], info_i['gt_best'][k])
+    assert info_p['gt_best'][1] is None and info_i['gt_best'][1] is None
+    assert (info_p['forced_only'], info_p['none']) == (info_i['forced_only'], info_i['none'])
+    assert 'ignore_stats' not in info_p and info_i['ignore_stats'] == [0, 0, 0, 0]
+
+
 def test_calc_with_ignore_regions_and_a_frame_without_cars(monkeypatch):
     """Through Calc: the regions of three frames, one without a Car but with rectangles (live: empty positives, a not-negative
     list), one with nothing (None); the stats in ``info``; and a radius replay enqueues the ignore pass again."""
