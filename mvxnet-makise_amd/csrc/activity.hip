@@ -13,10 +13,11 @@
 //              remaining c (x) sum(dz) term in closed form,
 // both exact rewrites of the dense arithmetic (differences at fp32 rounding level).
 #include "common.h"
+#include "quad.h"
 
 namespace {
 
-constexpr int ATH = 8, ATW = 16;        // tile of the convolution kernels (conv3d.hip TH x TW)
+constexpr int ATH = QTH, ATW = QTW;     // tile of the convolution kernels (conv3d.hip TH x TW)
 
 // dst[d][y][x] = 1 iff any source site in the 3x3x3 receptive field is active, or (mark_border and the
 // in-plane window leaves the image).  Source: int32 index grid (voxel id, -1 = empty) or uint8 mask.
@@ -205,28 +206,20 @@ __global__ __launch_bounds__(256) void bn_apply_tiles(const float *__restrict__ 
                                                       const float *__restrict__ c_bg, const int *__restrict__ tile_flags,
                                                       float *__restrict__ out, int D, int H, int W, int C, int ntiles,
                                                       const int *__restrict__ read_flags) {
-    const int tiles_x = (W + ATW - 1) / ATW;
     const int t = blockIdx.x, d = blockIdx.y, frame = d / D;
     // read_flags (may be NULL): the tiles some consumer reads (tile_read_flags below); a background tile outside that set is not
     // written -- its constant would never be looked at
     if (read_flags && !read_flags[(size_t)d * ntiles + t] && !tile_flags[(size_t)d * ntiles + t]) return;
-    const int c4n = C >> 2, ct = threadIdx.x % c4n, st = threadIdx.x / c4n, spb = 256 / c4n;
-    const int ty0 = (t / tiles_x) * ATH, tx0 = (t % tiles_x) * ATW;
+    const TileThreads tt(C, t, W);
     const bool on = tile_flags[(size_t)d * ntiles + t] != 0;          // block-uniform
-    const float4 cb = *(const float4 *)(c_bg + (size_t)d * C + ct * 4);
+    const float4 cb = ld4(c_bg + (size_t)d * C + tt.ct * 4);
     const float *fmi = mi + (size_t)frame * 2 * C;
-    const float4 m = *(const float4 *)(fmi + ct * 4), iv = *(const float4 *)(fmi + C + ct * 4);
-    for (int sidx = st; sidx < ATH * ATW; sidx += spb) {
-        const int gy = ty0 + sidx / ATW, gx = tx0 + sidx % ATW;
-        if (gy >= H || gx >= W) continue;
-        const size_t off = (((size_t)d * H + gy) * W + gx) * C + ct * 4;
-        float4 o = cb;
-        if (on) {
-            const float4 v = *(const float4 *)(y + off);
-            o = make_float4((v.x - m.x) * iv.x, (v.y - m.y) * iv.y, (v.z - m.z) * iv.z, (v.w - m.w) * iv.w);
-        }
-        *(float4 *)(out + off) = o;
-    }
+    const float4 m = ld4(fmi + tt.ct * 4), iv = ld4(fmi + C + tt.ct * 4);
+    tt.for_each_site([&](int, int gy, int gx) {
+        if (gy >= H || gx >= W) return;
+        const size_t off = (((size_t)d * H + gy) * W + gx) * C + tt.ct * 4;
+        st4(out + off, on ? bn4(ld4(y + off), m, iv) : cb);
+    });
 }
 
 // ---- which tiles of a layer's INPUT does the background-aware gather of that layer read?  The gather computes output tile T of
@@ -270,23 +263,17 @@ __global__ __launch_bounds__(256) void bn_apply_tiles_bev(const float *__restric
                                                           const float *__restrict__ c_bg, const int *__restrict__ tile_flags,
                                                           float *__restrict__ bev, int D, int H, int W, int C, int ntiles) {
     __shared__ float s_t[ATH * ATW][64 + 1];
-    const int tiles_x = (W + ATW - 1) / ATW;
     const int t = blockIdx.x, d = blockIdx.y, frame = d / D, dd = d - frame * D;
-    const int c4n = C >> 2, ct = threadIdx.x % c4n, st = threadIdx.x / c4n, spb = 256 / c4n;
-    const int ty0 = (t / tiles_x) * ATH, tx0 = (t % tiles_x) * ATW;
+    const TileThreads tt(C, t, W);
+    const int ct = tt.ct, ty0 = tt.ty0, tx0 = tt.tx0;
     const bool on = tile_flags[(size_t)d * ntiles + t] != 0;          // block-uniform
-    const float4 cb = *(const float4 *)(c_bg + (size_t)d * C + ct * 4);
+    const float4 cb = ld4(c_bg + (size_t)d * C + ct * 4);
     const float *fmi = mi + (size_t)frame * 2 * C;
-    const float4 m = *(const float4 *)(fmi + ct * 4), iv = *(const float4 *)(fmi + C + ct * 4);
-    for (int sidx = st; sidx < ATH * ATW; sidx += spb) {
-        const int gy = ty0 + sidx / ATW, gx = tx0 + sidx % ATW;
-        float4 o = cb;
-        if (on && gy < H && gx < W) {
-            const float4 v = *(const float4 *)(y + (((size_t)d * H + gy) * W + gx) * C + ct * 4);
-            o = make_float4((v.x - m.x) * iv.x, (v.y - m.y) * iv.y, (v.z - m.z) * iv.z, (v.w - m.w) * iv.w);
-        }
+    const float4 m = ld4(fmi + ct * 4), iv = ld4(fmi + C + ct * 4);
+    tt.for_each_site([&](int sidx, int gy, int gx) {
+        const float4 o = (on && gy < H && gx < W) ? bn4(ld4(y + (((size_t)d * H + gy) * W + gx) * C + ct * 4), m, iv) : cb;
         s_t[sidx][ct * 4 + 0] = o.x; s_t[sidx][ct * 4 + 1] = o.y; s_t[sidx][ct * 4 + 2] = o.z; s_t[sidx][ct * 4 + 3] = o.w;
-    }
+    });
     __syncthreads();
     // (tile row, channel, group of four columns): lanes walk the four groups of a 64-byte row piece, then the channels (LDS
     // banks: site + channel mod 32 with the 65-float pitch -- 28 distinct banks per wave)
@@ -372,52 +359,34 @@ __global__ __launch_bounds__(256) void bnb_tiles(const float *__restrict__ dyh, 
                                                  unsigned *__restrict__ amax_slot) {
     __shared__ float red[2][256][4];
     float mx = 0.f;                                   // MODE 1: max |dz| this thread wrote (-> amax_slot, see mvx_wave_amax_to)
-    const int tiles_x = (W + ATW - 1) / ATW;
-    const int c4n = C >> 2, ct = threadIdx.x % c4n, st = threadIdx.x / c4n, spb = 256 / c4n;
+    TileThreads tt(C, 0, W);
+    const int ct = tt.ct, st = tt.st, spb = tt.spb;
     const int nact = *n_act;
     const int per = (nact + (int)gridDim.x - 1) / (int)gridDim.x;
     const int j0 = (int)blockIdx.x * per, j1 = min(nact, j0 + per);
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-    float4 m = s1, iv = s1, cb = s1, a = s1, b = s1;
+    float4 s[2] = {zero4(), zero4()};
+    float4 m = zero4(), iv = m, cb = m, a = m, b = m;
     int cur = -1;                                     // plane the running sums belong to
     auto flush = [&](int d) {                         // block-uniform
         const int frame = d / D, dl = d - frame * D;
-        double *sums = sums_all + (size_t)frame * BREP * (D + 2) * C;
-        __syncthreads();
-        red[0][threadIdx.x][0] = s1.x; red[0][threadIdx.x][1] = s1.y; red[0][threadIdx.x][2] = s1.z; red[0][threadIdx.x][3] = s1.w;
-        red[1][threadIdx.x][0] = s2.x; red[1][threadIdx.x][1] = s2.y; red[1][threadIdx.x][2] = s2.z; red[1][threadIdx.x][3] = s2.w;
-        __syncthreads();
-        if (st == 0) {
-            const unsigned rep = blockIdx.x % BREP;
-            double *base = sums + (size_t)rep * (D + 2) * C;        // layout per replica: [D planes of P1][Q1][Z1]
-            for (int q4 = 0; q4 < 4; ++q4) {
-                double t1 = 0.0, t2 = 0.0;
-                for (int q = 0; q < spb; ++q) { t1 += (double)red[0][q * c4n + ct][q4]; t2 += (double)red[1][q * c4n + ct][q4]; }
-                const int n = ct * 4 + q4;
-                if (MODE == 0) {
-                    atomicAdd(base + (size_t)dl * C + n, t1);
-                    atomicAdd(base + (size_t)D * C + n, t2);
-                } else {
-                    atomicAdd(base + (size_t)(D + 1) * C + n, t1);
-                }
-            }
-        }
-        s1 = make_float4(0.f, 0.f, 0.f, 0.f); s2 = s1;
+        // layout per frame and replica: [D planes of P1][Q1][Z1]
+        double *base = sums_all + ((size_t)frame * BREP + blockIdx.x % BREP) * (D + 2) * C;
+        fold_quads<2>(s, red, C >> 2, spb, ct, false, [&](int k, int n, double t) {
+            if (MODE == 0) atomicAdd(base + (size_t)(k == 0 ? dl : D) * C + n, t);
+            else if (k == 0) atomicAdd(base + (size_t)(D + 1) * C + n, t);
+        });
+        s[0] = zero4(); s[1] = zero4();
     };
     auto site = [&](const float4 g, const float4 v, size_t off) __attribute__((always_inline)) {
-        const float4 yh = make_float4((v.x - m.x) * iv.x, (v.y - m.y) * iv.y, (v.z - m.z) * iv.z, (v.w - m.w) * iv.w);
+        const float4 yh = bn4(v, m, iv);
         if (MODE == 0) {
-            s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
-            s2.x += g.x * (yh.x - cb.x); s2.y += g.y * (yh.y - cb.y); s2.z += g.z * (yh.z - cb.z); s2.w += g.w * (yh.w - cb.w);
+            acc4(s[0], g);
+            acc4(s[1], mul4(g, make_float4(yh.x - cb.x, yh.y - cb.y, yh.z - cb.z, yh.w - cb.w)));
         } else {
-            float4 o;
-            o.x = v.x > 0.f ? iv.x * (g.x - (a.x + yh.x * b.x)) : 0.f;
-            o.y = v.y > 0.f ? iv.y * (g.y - (a.y + yh.y * b.y)) : 0.f;
-            o.z = v.z > 0.f ? iv.z * (g.z - (a.z + yh.z * b.z)) : 0.f;
-            o.w = v.w > 0.f ? iv.w * (g.w - (a.w + yh.w * b.w)) : 0.f;
-            *(float4 *)(dz + off) = o;
-            s1.x += o.x; s1.y += o.y; s1.z += o.z; s1.w += o.w;
-            mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+            const float4 o = dz4<false>(g, v, yh, iv, a, b);
+            st4(dz + off, o);
+            acc4(s[0], o);
+            mx = amax4(mx, o);
         }
     };
     for (int j = j0; j < j1; ++j) {
@@ -428,29 +397,28 @@ __global__ __launch_bounds__(256) void bnb_tiles(const float *__restrict__ dyh, 
             cur = d;
             const int frame = d / D;
             const float *fmi = mi + (size_t)frame * 2 * C;
-            m = *(const float4 *)(fmi + ct * 4); iv = *(const float4 *)(fmi + C + ct * 4);
-            cb = *(const float4 *)(c_bg + (size_t)d * C + ct * 4);
-            if (MODE == 1) { a = *(const float4 *)(ab + (size_t)frame * 2 * C + ct * 4); b = *(const float4 *)(ab + (size_t)frame * 2 * C + C + ct * 4); }
+            m = ld4(fmi + ct * 4); iv = ld4(fmi + C + ct * 4);
+            cb = ld4(c_bg + (size_t)d * C + ct * 4);
+            if (MODE == 1) { a = ld4(ab + (size_t)frame * 2 * C + ct * 4); b = ld4(ab + (size_t)frame * 2 * C + C + ct * 4); }
         }
-        const int ty0 = (t / tiles_x) * ATH, tx0 = (t % tiles_x) * ATW;
-        if (spb == ATW && ty0 + ATH <= H && tx0 + ATW <= W) {
+        tt.at(t, W);
+        if (spb == ATW && tt.ty0 + ATH <= H && tt.tx0 + ATW <= W) {
             // full tile, 64 channels: thread = (column st, quad ct), the eight rows' loads in flight together
             float4 gq[ATH], vq[ATH];
-            const size_t off0 = (((size_t)d * H + ty0) * W + tx0 + st) * C + ct * 4;
+            const size_t off0 = (((size_t)d * H + tt.ty0) * W + tt.tx0 + st) * C + ct * 4;
 #pragma unroll
             for (int r = 0; r < ATH; ++r) {
-                gq[r] = *(const float4 *)(dyh + off0 + (size_t)r * W * C);
-                vq[r] = *(const float4 *)(y + off0 + (size_t)r * W * C);
+                gq[r] = ld4(dyh + off0 + (size_t)r * W * C);
+                vq[r] = ld4(y + off0 + (size_t)r * W * C);
             }
 #pragma unroll
             for (int r = 0; r < ATH; ++r) site(gq[r], vq[r], off0 + (size_t)r * W * C);
         } else {
-            for (int sidx = st; sidx < ATH * ATW; sidx += spb) {
-                const int gy = ty0 + sidx / ATW, gx = tx0 + sidx % ATW;
-                if (gy >= H || gx >= W) continue;
+            tt.for_each_site([&](int, int gy, int gx) {
+                if (gy >= H || gx >= W) return;
                 const size_t off = (((size_t)d * H + gy) * W + gx) * C + ct * 4;
-                site(*(const float4 *)(dyh + off), *(const float4 *)(y + off), off);
-            }
+                site(ld4(dyh + off), ld4(y + off), off);
+            });
         }
     }
     if (cur >= 0) flush(cur);

@@ -6,6 +6,7 @@
 // partials per thread, f64 across the block and f64 atomics across blocks, so the batch
 // statistics do not depend on the launch geometry beyond f64 rounding.
 #include "common.h"
+#include "quad.h"
 #include "split_common.h"
 
 namespace {
@@ -36,46 +37,33 @@ __global__ void bn_apply(const float *__restrict__ y, const float *__restrict__ 
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < n4; e += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(e % c4) * 4;
         const float *fmi = mi + (size_t)fm_frame_of(fm, (long long)(e / c4)) * 2 * C;
-        const float4 v = ((const float4 *)y)[e];
-        const float4 m = *(const float4 *)(fmi + c), s = *(const float4 *)(fmi + C + c);
-        float4 o;
-        o.x = (v.x - m.x) * s.x; o.y = (v.y - m.y) * s.y; o.z = (v.z - m.z) * s.z; o.w = (v.w - m.w) * s.w;
-        ((float4 *)out)[e] = o;
+        ((float4 *)out)[e] = bn4(((const float4 *)y)[e], ld4(fmi + c), ld4(fmi + C + c));
     }
 }
 
-// per-channel sum / sum of squares of a [rows][C] matrix (used when the producer did not
-// already reduce them in its epilogue).  f64 throughout, as row_stats_frames (rpn.hip): var = E[y^2] - mean^2 cancels, and with
-// f32 partials a channel of one constant value c came out with a variance of order 1e-7 c^2 instead of 0 (inverse deviation
-// 920 instead of 1000 at c = 3.7, eps = 1e-6)
+// per-channel sum / sum of squares of a [F][rows][C] tensor, frame = blockIdx.y (used when the producer did not already reduce
+// them in its epilogue).  f64 throughout: var = E[y^2] - mean^2 cancels, and with f32 partials a channel of one constant value c
+// came out with a variance of order 1e-7 c^2 instead of 0 (inverse deviation 920 instead of 1000 at c = 3.7, eps = 1e-6)
 __global__ __launch_bounds__(256) void row_stats(const float *__restrict__ y, double *__restrict__ stats, size_t rows, int C) {
     __shared__ double red[2][256][4];
     const int c4 = C >> 2;
     const int rpi = max(1, 256 / c4);                 // rows per block iteration
     const int ct = threadIdx.x % c4, rt = threadIdx.x / c4;
+    y += (size_t)blockIdx.y * rows * C;
+    stats += (size_t)blockIdx.y * MVX_REP * 2 * C;
     for (int cb = 0; cb < c4; cb += 256) {             // C > 1024 -> several column blocks
         const int col = cb + ct;
-        double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+        double4 s[2] = {make_double4(0.0, 0.0, 0.0, 0.0), make_double4(0.0, 0.0, 0.0, 0.0)};
         if (rt < rpi && col < c4) {
             for (size_t r = blockIdx.x * (size_t)rpi + rt; r < rows; r += (size_t)gridDim.x * rpi) {
-                const float4 v = *(const float4 *)(y + r * C + col * 4);
-                const double d[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { s1[j] += d[j]; s2[j] += d[j] * d[j]; }
+                const float4 v = ld4(y + r * C + col * 4);
+                const double4 d = make_double4((double)v.x, (double)v.y, (double)v.z, (double)v.w);
+                acc4(s[0], d);
+                acc4(s[1], mul4(d, d));
             }
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { red[0][threadIdx.x][j] = s1[j]; red[1][threadIdx.x][j] = s2[j]; }
-        __syncthreads();
-        if (rt == 0 && col < c4) {
-            for (int k = 0; k < 2; ++k)
-                for (int j = 0; j < 4; ++j) {
-                    double t = 0.0;
-                    for (int r = 0; r < rpi; ++r) t += red[k][r * c4 + ct][j];
-                    atomicAdd(stats + ((size_t)(blockIdx.x % MVX_REP) * 2 + k) * C + col * 4 + j, t);
-                }
-        }
-        __syncthreads();
+        fold_quads<2>(s, red, c4, rpi, col, false,
+                      [&](int k, int c, double t) { atomicAdd(stats + ((size_t)(blockIdx.x % MVX_REP) * 2 + k) * C + c, t); });
     }
 }
 
@@ -110,9 +98,9 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce(const float *__restrict__ d
         double *fsums = sums + (size_t)f * REP * 3 * C;
         for (int cb = 0; cb < c4; cb += 256) {
             const int col = cb + ct;
-            float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
+            float4 s[2] = {zero4(), zero4()};
             if (rt < rpi && col < c4) {
-                const float4 m = *(const float4 *)(fmi + col * 4), iv = *(const float4 *)(fmi + C + col * 4);
+                const float4 m = ld4(fmi + col * 4), iv = ld4(fmi + C + col * 4);
                 const size_t stride = (size_t)rpi;
                 for (size_t r = lo + rt; r < hi; r += TRIP * stride) {
                     float4 g[TRIP], v[TRIP];
@@ -120,52 +108,20 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce(const float *__restrict__ d
                     for (int j = 0; j < TRIP; ++j) {
                         const size_t rr = r + j * stride;
                         const bool ok = rr < hi;
-                        g[j] = ok ? *(const float4 *)(dyh + rr * C + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                        v[j] = ok ? *(const float4 *)(y + rr * C + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        g[j] = ok ? ld4(dyh + rr * C + col * 4) : zero4();
+                        v[j] = ok ? ld4(y + rr * C + col * 4) : zero4();
                     }
 #pragma unroll
                     for (int j = 0; j < TRIP; ++j) {
-                        s1.x += g[j].x; s1.y += g[j].y; s1.z += g[j].z; s1.w += g[j].w;
-                        s2.x += g[j].x * ((v[j].x - m.x) * iv.x); s2.y += g[j].y * ((v[j].y - m.y) * iv.y);
-                        s2.z += g[j].z * ((v[j].z - m.z) * iv.z); s2.w += g[j].w * ((v[j].w - m.w) * iv.w);
+                        acc4(s[0], g[j]);
+                        acc4(s[1], mul4(g[j], bn4(v[j], m, iv)));
                     }
                 }
             }
-            if (64 % c4 == 0) {
-                // few channels (c4 divides the wave): the threads of a wave that share a channel quad are folded with shuffles, the
-                // four waves through LDS.  (The serial form below walks rpi = 256 / c4 partials per quad with ONE thread per quad:
-                // 64 dependent f64 LDS reads x 8 values at C = 16, which made the two 16-channel fusion layers' reduce pass take
-                // 94 us for 5 MB.)
-                double v[8] = {s1.x, s1.y, s1.z, s1.w, s2.x, s2.y, s2.z, s2.w};
-                for (int off = c4; off < 64; off <<= 1)
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] += __shfl_xor(v[i], off, 64);
-                const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-                if (lane < c4)
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) red[i >> 2][wave * c4 + lane][i & 3] = v[i];
-                __syncthreads();
-                if ((int)threadIdx.x < c4)
-                    for (int k = 0; k < 2; ++k)
-                        for (int j = 0; j < 4; ++j) {
-                            const double t = (red[k][ct][j] + red[k][c4 + ct][j]) + (red[k][2 * c4 + ct][j] + red[k][3 * c4 + ct][j]);
-                            atomicAdd(fsums + ((size_t)(blockIdx.x % REP) * 3 + k) * C + col * 4 + j, t);
-                        }
-                __syncthreads();
-            } else {
-            red[0][threadIdx.x][0] = s1.x; red[0][threadIdx.x][1] = s1.y; red[0][threadIdx.x][2] = s1.z; red[0][threadIdx.x][3] = s1.w;
-            red[1][threadIdx.x][0] = s2.x; red[1][threadIdx.x][1] = s2.y; red[1][threadIdx.x][2] = s2.z; red[1][threadIdx.x][3] = s2.w;
-            __syncthreads();
-            if (rt == 0 && col < c4) {
-                for (int k = 0; k < 2; ++k)
-                    for (int j = 0; j < 4; ++j) {
-                        double t = 0.0;
-                        for (int r = 0; r < rpi; ++r) t += red[k][r * c4 + ct][j];
-                        atomicAdd(fsums + ((size_t)(blockIdx.x % REP) * 3 + k) * C + col * 4 + j, t);
-                    }
-            }
-            __syncthreads();
-            }
+            // few channels (c4 divides the wave): the shuffle order.  (The serial order made the two 16-channel fusion layers'
+            // reduce pass take 94 us for 5 MB.)
+            fold_quads<2>(s, red, c4, rpi, col, 64 % c4 == 0,
+                          [&](int k, int c, double t) { atomicAdd(fsums + ((size_t)(blockIdx.x % REP) * 3 + k) * C + c, t); });
         }
     }
     }
@@ -213,8 +169,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float *__restrict__ dy
                                                     unsigned total_blocks) {
     // block_base / total_blocks: the pass may be enqueued in several launches over consecutive block ranges (the consumer of
     // the first rows starts while the rest is still being written); the bias gradient is folded by the last block of ALL
-    __shared__ double red[256][4];
-    float mx = 0.f;                                  // max |dz| this thread wrote (-> amax_slot: the fp16-piece kernels scale dz by it)
+    __shared__ double red[1][256][4];
+    float mx = 0.f;                                 // max |dz| this thread wrote (-> amax_slot: the fp16-piece kernels scale dz by it)
     const int c4 = C >> 2;
     const int rpi = max(1, 256 / c4);
     const int ct = threadIdx.x % c4, rt = threadIdx.x / c4;
@@ -225,18 +181,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float *__restrict__ dy
     const int s_lo = live ? fm_seg_at(fm, (long long)blk_lo) : 0, s_hi = live ? fm_seg_at(fm, (long long)blk_hi - 1) : 0;
     for (int cb = 0; cb < c4; cb += 256) {
         const int col = cb + ct;
-        float4 sb = make_float4(0, 0, 0, 0);
+        float4 sb[1] = {zero4()};
         for (int sg = s_lo; sg <= s_hi && live; ++sg) {
             const int f = fm_seg_frame(fm, sg);
             const size_t lo = max(blk_lo, (size_t)fm_seg_lo(fm, sg));
             const size_t hi = min(blk_hi, fm_seg_hi(fm, sg, blk_hi));
             const float *fmi = mi + (size_t)f * 2 * C;
             if (rt < rpi && col < c4) {
-                const float4 m = *(const float4 *)(fmi + col * 4), iv = *(const float4 *)(fmi + C + col * 4);
+                const float4 m = ld4(fmi + col * 4), iv = ld4(fmi + C + col * 4);
                 // written by the last workgroup of pass 1 (an earlier kernel of this stream): plain loads
-                const float4 av = *(const float4 *)(ab + (size_t)f * 2 * C + col * 4);
-                const float4 bv = *(const float4 *)(ab + (size_t)f * 2 * C + C + col * 4);
-                const float a[4] = {av.x, av.y, av.z, av.w}, b[4] = {bv.x, bv.y, bv.z, bv.w};
+                const float4 a = ld4(ab + (size_t)f * 2 * C + col * 4), b = ld4(ab + (size_t)f * 2 * C + C + col * 4);
                 const size_t stride = (size_t)rpi;
                 for (size_t r = lo + rt; r < hi; r += TRIP * stride) {
                     float4 g[TRIP], v[TRIP];
@@ -245,19 +199,15 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float *__restrict__ dy
                     for (int j = 0; j < TRIP; ++j) {
                         const size_t rr = r + j * stride;
                         const bool ok = rr < hi;
-                        g[j] = ok ? *(const float4 *)(dyh + rr * C + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-                        v[j] = ok ? *(const float4 *)(y + rr * C + col * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+                        g[j] = ok ? ld4(dyh + rr * C + col * 4) : zero4();
+                        v[j] = ok ? ld4(y + rr * C + col * 4) : zero4();
                         rw[j] = (ok && row_w) ? row_w[rr] : 1.f;   // a compact row standing for rw dense rows
                     }
 #pragma unroll
                     for (int j = 0; j < TRIP; ++j) {
                         const size_t rr = r + j * stride;
                         if (rr >= hi) break;
-                        float4 o;
-                        o.x = v[j].x > 0.f ? iv.x * (g[j].x - rw[j] * (a[0] + ((v[j].x - m.x) * iv.x) * b[0])) : 0.f;
-                        o.y = v[j].y > 0.f ? iv.y * (g[j].y - rw[j] * (a[1] + ((v[j].y - m.y) * iv.y) * b[1])) : 0.f;
-                        o.z = v[j].z > 0.f ? iv.z * (g[j].z - rw[j] * (a[2] + ((v[j].z - m.z) * iv.z) * b[2])) : 0.f;
-                        o.w = v[j].w > 0.f ? iv.w * (g[j].w - rw[j] * (a[3] + ((v[j].w - m.w) * iv.w) * b[3])) : 0.f;
+                        const float4 o = dz4<true>(g[j], v[j], bn4(v[j], m, iv), iv, a, b, rw[j]);
                         if constexpr (PL) {
                             uint2 pc[3];
                             split_n<3, 0>(o.x, o.y, o.z, o.w, pc);
@@ -265,41 +215,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply(const float *__restrict__ dy
 #pragma unroll
                             for (int q = 0; q < 3; ++q) *(uint2 *)(pl + ((size_t)q * rows + rr) * C + col * 4) = pc[q];
                         } else {
-                            *(float4 *)(dz + rr * C + col * 4) = o;
+                            st4(dz + rr * C + col * 4, o);
                         }
-                        sb.x += o.x; sb.y += o.y; sb.z += o.z; sb.w += o.w;
-                        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+                        acc4(sb[0], o);
+                        mx = amax4(mx, o);
                     }
                 }
             }
         }
-        if (dbias && 64 % c4 == 0) {                  // see bn_bwd_reduce: shuffles within the wave, four partials through LDS
-            double v[4] = {sb.x, sb.y, sb.z, sb.w};
-            for (int off = c4; off < 64; off <<= 1)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] += __shfl_xor(v[i], off, 64);
-            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-            if (lane < c4)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) red[wave * c4 + lane][i] = v[i];
-            __syncthreads();
-            if ((int)threadIdx.x < c4)
-                for (int j = 0; j < 4; ++j)
-                    atomicAdd(dbias + (size_t)(gblock % REP) * 3 * C + col * 4 + j,
-                              (red[ct][j] + red[c4 + ct][j]) + (red[2 * c4 + ct][j] + red[3 * c4 + ct][j]));
-            __syncthreads();
-        } else if (dbias) {
-            red[threadIdx.x][0] = sb.x; red[threadIdx.x][1] = sb.y; red[threadIdx.x][2] = sb.z; red[threadIdx.x][3] = sb.w;
-            __syncthreads();
-            if (rt == 0 && col < c4) {
-                for (int j = 0; j < 4; ++j) {
-                    double t = 0.0;
-                    for (int r = 0; r < rpi; ++r) t += red[r * c4 + ct][j];
-                    atomicAdd(dbias + (size_t)(gblock % REP) * 3 * C + col * 4 + j, t);
-                }
-            }
-            __syncthreads();
-        }
+        if (dbias)                                    // the fold orders of bn_bwd_reduce
+            fold_quads<1>(sb, red, c4, rpi, col, 64 % c4 == 0,
+                          [&](int, int c, double t) { atomicAdd(dbias + (size_t)(gblock % REP) * 3 * C + c, t); });
     }
     if (amax_slot) mvx_wave_amax_to(amax_slot, mx);
     if (dbias && done_counter) {
@@ -337,9 +263,20 @@ __global__ void dbias_finish(const double *__restrict__ scratch, float *__restri
 constexpr int BWD_TRIP = 4;            // rows per thread in flight in the two BatchNorm-backward passes
 
 inline unsigned row_grid(size_t rows, int C) {
-    const int rpi = (256 / (C / 4)) > 1 ? 256 / (C / 4) : 1;
-    size_t b = (rows + 4 * (size_t)rpi - 1) / (4 * (size_t)rpi);   // kernels take 4 rows per thread and trip
+    const size_t rpi = quad_rows_per_trip(C);
+    size_t b = (rows + 4 * rpi - 1) / (4 * rpi);   // kernels take 4 rows per thread and trip
     return (unsigned)(b > 768 ? 768 : (b ? b : 1));
+}
+
+// the statistics of `n_frames` equal shares of the rows, `blocks` workgroups per frame: the partition of the rows over the
+// workgroups decides the f64 rounding of the sums, so each entry point keeps its own
+int row_stats_launch(const float *y, double *stats, size_t rows_per_frame, int C, int n_frames, unsigned blocks, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * C * n_frames, st);
+    if (e != hipSuccess) return (int)e;
+    if (rows_per_frame == 0) return MVX_OK;
+    hipLaunchKernelGGL(row_stats, dim3(blocks, n_frames), dim3(256), 0, st, y, stats, rows_per_frame, C);
+    MVX_LAUNCH_CHECK();
+    return MVX_OK;
 }
 
 }  // namespace
@@ -378,13 +315,16 @@ extern "C" int mvx_bn_apply(const float *y, const float *mean_inv, float *out, i
 
 extern "C" int mvx_row_stats(const float *y, double *stats, int64_t rows, int32_t channels, void *stream) {
     MVX_CHECK_ARG(y && stats && rows >= 0 && channels > 0 && channels % 4 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * channels, st);
-    if (e != hipSuccess) return (int)e;
-    if (rows == 0) return MVX_OK;
-    hipLaunchKernelGGL(row_stats, dim3(row_grid(rows, channels)), dim3(256), 0, st, y, stats, (size_t)rows, channels);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
+    return row_stats_launch(y, stats, (size_t)rows, channels, 1, row_grid(rows, channels), (hipStream_t)stream);
+}
+
+extern "C" int mvx_row_stats_frames(const float *y, double *stats, int64_t rows, int32_t channels, int32_t n_frames,
+                                    void *stream) {
+    MVX_CHECK_ARG(y && stats && rows >= 0 && channels > 0 && channels % 4 == 0 && channels <= 1024);
+    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES && rows % n_frames == 0);
+    const size_t per = (size_t)(rows / n_frames), rpi = quad_rows_per_trip(channels);
+    const size_t b = (per + rpi - 1) / rpi;
+    return row_stats_launch(y, stats, per, channels, n_frames, (unsigned)(b > 512 ? 512 : b), (hipStream_t)stream);
 }
 
 extern "C" size_t mvx_bn_backward_scratch_bytes(int32_t channels) {
@@ -405,8 +345,7 @@ __global__ __launch_bounds__(256) void tensor_amax(const float *__restrict__ x, 
     float mx = 0.f;
     const size_t n4 = n >> 2;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const float4 v = ((const float4 *)x)[i];
-        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+        mx = amax4(mx, ((const float4 *)x)[i]);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) mx = fmaxf(mx, fabsf(x[(n4 << 2) + threadIdx.x]));
     mvx_wave_amax_to(slot, mx);
@@ -468,7 +407,7 @@ static int bn_relu_backward_impl(const float *dyhat, const float *y, const float
     }
     if (part_rows) part_rows[0] = part_rows[1] = 0;
     if (rows > 0) {
-        const int rpi = (256 / (channels / 4)) > 1 ? 256 / (channels / 4) : 1;
+        const int rpi = quad_rows_per_trip(channels);
         // up to 4 workgroups per CU, each with at least two trips of BWD_TRIP x rpi rows
         size_t want = ((size_t)rows + 2 * BWD_TRIP * rpi - 1) / (2 * (size_t)BWD_TRIP * rpi);
         const unsigned grid = (unsigned)(want > 1024 ? 1024 : (want ? want : 1));

@@ -16,6 +16,7 @@
 // sampled; row_map sends a dense row to its compact row (or -1), and one shared zero row stands
 // for every padded row downstream.
 #include "compact.h"
+#include "quad.h"
 #include "split_common.h"
 
 namespace {
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void feature_sample_rows(const float *__restri
 #pragma unroll
             for (int q = 0; q < 3; ++q) *(uint2 *)(planes + ((size_t)q * plane_rows + j) * ldo + lv * C + c) = pc[q];
         }
-        mx = fmaxf(fmaxf(mx, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        mx = amax4(mx, o);
     }
     if (amax_slot) mvx_wave_amax_to(amax_slot, mx);
 }

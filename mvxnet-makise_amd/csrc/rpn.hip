@@ -14,6 +14,7 @@
 //   s2d_gather       the inverse read (gradient of the concat slice back into GEMM layout).
 //   bn_apply_strided BatchNorm apply of a dense [rows][C] tensor into a channel slice of a wider buffer.
 #include "common.h"
+#include "quad.h"
 
 namespace {
 
@@ -59,8 +60,7 @@ __global__ void d2s_rows(float *__restrict__ t, const float *__restrict__ mi, fl
         float4 v = ((const float4 *)t)[e];
         if (mi) {
             const float *fmi = mi + (size_t)f * 2 * C;
-            const float4 m = *(const float4 *)(fmi + c), iv = *(const float4 *)(fmi + C + c);
-            v.x = (v.x - m.x) * iv.x; v.y = (v.y - m.y) * iv.y; v.z = (v.z - m.z) * iv.z; v.w = (v.w - m.w) * iv.w;
+            v = bn4(v, ld4(fmi + c), ld4(fmi + C + c));
         }
         *(float4 *)o = v;
     }
@@ -83,46 +83,9 @@ __global__ void bn_apply_strided(float *__restrict__ y, const float *__restrict_
         float4 v = ((const float4 *)y)[e];
         if (mi) {
             const float *fmi = mi + (row / rows_per_frame) * 2 * C;
-            const float4 m = *(const float4 *)(fmi + c), iv = *(const float4 *)(fmi + C + c);
-            v.x = (v.x - m.x) * iv.x; v.y = (v.y - m.y) * iv.y; v.z = (v.z - m.z) * iv.z; v.w = (v.w - m.w) * iv.w;
+            v = bn4(v, ld4(fmi + c), ld4(fmi + C + c));
         }
         *(float4 *)o = v;
-    }
-}
-
-// per-channel (sum, sum of squares) of a [F][rows_per_frame][C] tensor, per frame (replicated accumulators)
-__global__ __launch_bounds__(256) void row_stats_frames(const float *__restrict__ y, double *__restrict__ stats,
-                                                        size_t rows_per_frame, int C) {
-    __shared__ double red[2][256][4];
-    const int c4 = C >> 2;
-    const int rpi = max(1, 256 / c4);
-    const int ct = threadIdx.x % c4, rt = threadIdx.x / c4;
-    const int f = blockIdx.y;
-    y += (size_t)f * rows_per_frame * C;
-    stats += (size_t)f * MVX_REP * 2 * C;
-    for (int cb = 0; cb < c4; cb += 256) {
-        const int col = cb + ct;
-        double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};      // f64 throughout (var = E[y^2] - mean^2 cancels)
-        if (rt < rpi && col < c4) {
-            for (size_t r = blockIdx.x * (size_t)rpi + rt; r < rows_per_frame; r += (size_t)gridDim.x * rpi) {
-                const float4 v = *(const float4 *)(y + r * C + col * 4);
-                const double d[4] = {(double)v.x, (double)v.y, (double)v.z, (double)v.w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { s1[j] += d[j]; s2[j] += d[j] * d[j]; }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { red[0][threadIdx.x][j] = s1[j]; red[1][threadIdx.x][j] = s2[j]; }
-        __syncthreads();
-        if (rt == 0 && col < c4) {
-            for (int k = 0; k < 2; ++k)
-                for (int j = 0; j < 4; ++j) {
-                    double t = 0.0;
-                    for (int r = 0; r < rpi; ++r) t += red[k][r * c4 + ct][j];
-                    atomicAdd(stats + ((size_t)(blockIdx.x % MVX_REP) * 2 + k) * C + col * 4 + j, t);
-                }
-        }
-        __syncthreads();
     }
 }
 
@@ -162,23 +125,6 @@ extern "C" int mvx_bn_apply_strided_frames(float *y, const float *mean_inv, floa
     if (rows == 0) return MVX_OK;
     hipLaunchKernelGGL(bn_apply_strided, dim3(ew_grid((size_t)rows * channels / 4)), dim3(256), 0, (hipStream_t)stream, y,
                        mean_inv, out, (size_t)rows, (size_t)(rows / n_frames), channels, ld_out, col_offset, reverse);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
-}
-
-extern "C" int mvx_row_stats_frames(const float *y, double *stats, int64_t rows, int32_t channels, int32_t n_frames,
-                                    void *stream) {
-    MVX_CHECK_ARG(y && stats && rows >= 0 && channels > 0 && channels % 4 == 0 && channels <= 1024);
-    MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES && rows % n_frames == 0);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * MVX_REP * 2 * channels * n_frames, st);
-    if (e != hipSuccess) return (int)e;
-    if (rows == 0) return MVX_OK;
-    const size_t per = (size_t)(rows / n_frames);
-    const int rpi = (256 / (channels / 4)) > 1 ? 256 / (channels / 4) : 1;
-    size_t b = (per + (size_t)rpi - 1) / rpi;
-    if (b > 512) b = 512;
-    hipLaunchKernelGGL(row_stats_frames, dim3((unsigned)b, n_frames), dim3(256), 0, st, y, stats, per, channels);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }

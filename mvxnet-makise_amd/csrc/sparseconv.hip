@@ -17,6 +17,7 @@
 // Sums run in a fixed order (k inside the GEMM, then taps in ascending order): deterministic, and
 // equal to the dense convolution up to fp32 summation order.
 #include "common.h"
+#include "quad.h"
 
 namespace {
 
@@ -134,46 +135,36 @@ __global__ __launch_bounds__(256) void sparse_conv_output(const float *__restric
                 if (site[k] >= 0) {                    // the nine taps of one entry go to nine different sites
                     float4 *q = (float4 *)(s_acc + ((size_t)site[k] * c4n + ct) * 4);
                     float4 t = *q;
-                    t.x += p[k].x; t.y += p[k].y; t.z += p[k].z; t.w += p[k].w;
+                    acc4(t, p[k]);
                     *q = t;
                 }
                 __syncthreads();                       // the next entry may add into the same sites
             }
         }
     }
-    float4 bs = bias ? *(const float4 *)(bias + ct * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 bs = bias ? ld4(bias + ct * 4) : zero4();
+    float4 s[2] = {zero4(), zero4()};
     const bool col_live = st < OTW && x < g.W;
     int live_sites = 0;
     for (int r = 0; r < OTH; ++r) {
         const int y = tcy * OTH + r;
         if (y >= g.H || !col_live) continue;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (any) acc = *(const float4 *)(s_acc + ((size_t)(r * OTW + st) * c4n + ct) * 4);
-        acc.x += bs.x; acc.y += bs.y; acc.z += bs.z; acc.w += bs.w;
+        float4 acc = zero4();
+        if (any) acc = ld4(s_acc + ((size_t)(r * OTW + st) * c4n + ct) * 4);
+        acc4(acc, bs);
         if (relu) { acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f); }
-        *(float4 *)(out + (((size_t)d * g.H + y) * g.W + x) * g.Cout + ct * 4) = acc;
-        s1.x += acc.x; s1.y += acc.y; s1.z += acc.z; s1.w += acc.w;
-        s2.x += acc.x * acc.x; s2.y += acc.y * acc.y; s2.z += acc.z * acc.z; s2.w += acc.w * acc.w;
+        st4(out + (((size_t)d * g.H + y) * g.W + x) * g.Cout + ct * 4, acc);
+        acc4(s[0], acc);
+        acc4(s[1], mul4(acc, acc));
         ++live_sites;
     }
     // Tiles without any source voxel wrote ReLU(bias) everywhere: their share of the BatchNorm sums
     // is added in closed form by sparse_stats_fix, so only the few active tiles touch the atomics.
     if (stats && any) {
-        red[0][threadIdx.x][0] = s1.x; red[0][threadIdx.x][1] = s1.y; red[0][threadIdx.x][2] = s1.z; red[0][threadIdx.x][3] = s1.w;
-        red[1][threadIdx.x][0] = s2.x; red[1][threadIdx.x][1] = s2.y; red[1][threadIdx.x][2] = s2.z; red[1][threadIdx.x][3] = s2.w;
-        __syncthreads();
-        const int spb = 256 / c4n;
         if (ct == 0) atomicAdd(active_sites, live_sites);
-        if (st == 0) {
-            const unsigned rep = (blockIdx.x + blockIdx.y * gridDim.x) % MVX_REP;
-            for (int k = 0; k < 2; ++k)
-                for (int j = 0; j < 4; ++j) {
-                    double t = 0.0;
-                    for (int q = 0; q < spb; ++q) t += (double)red[k][q * c4n + ct][j];
-                    atomicAdd(stats + ((size_t)rep * 2 + k) * g.Cout + ct * 4 + j, t);
-                }
-        }
+        const unsigned rep = (blockIdx.x + blockIdx.y * gridDim.x) % MVX_REP;
+        fold_quads<2, false>(s, red, c4n, 256 / c4n, ct, false,
+                             [&](int k, int c, double t) { atomicAdd(stats + ((size_t)rep * 2 + k) * g.Cout + c, t); });
     }
 }
 

@@ -16,212 +16,149 @@
 // the max only if T - vcnt[v] > 0, and its gradient is the SUM over the rows it stands for.
 // argmax holds the local row (0..vcnt-1) or vcnt[v] for the padded row.
 #include "common.h"
+#include "quad.h"
 
 namespace {
 
-struct Rows {            // row addressing of one voxel
-    const int *voff, *vcnt;
-    int T, n_real;
-    __device__ __forceinline__ int count(int v) const { return vcnt ? vcnt[v] : T; }
-    __device__ __forceinline__ bool has_pad(int v) const { return vcnt && vcnt[v] < T; }
-    // row index of local row t (t == count -> the padded row)
-    __device__ __forceinline__ size_t row(int v, int t) const {
-        if (!vcnt) return (size_t)v * T + t;
-        return t < vcnt[v] ? (size_t)voff[v] + t : (size_t)n_real + v;
-    }
-};
-
-__global__ __launch_bounds__(256) void vfe_bn_max_concat(const float *__restrict__ y, const float *__restrict__ mi,
-                                                         float *__restrict__ out, int *__restrict__ argmax,
-                                                         int V, int C, Rows R, FrameMap fm) {
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * C) return;
-    const int v = (int)(e / C), c = (int)(e % C);
-    mi += (size_t)fm_frame_of(fm, v) * 2 * C;             // per-frame BatchNorm (frames = voxel segments)
-    const float m = mi[c], iv = mi[C + c];
-    const int n = R.count(v) + (R.has_pad(v) ? 1 : 0);
-    float best = -INFINITY;
-    int bi = 0;
-    for (int t = 0; t < n; ++t) {
-        const float val = (y[R.row(v, t) * C + c] - m) * iv;
-        if (val > best) { best = val; bi = t; }
-    }
-    const int nw = R.vcnt ? R.count(v) + 1 : n;          // the padded row is always written
-    for (int t = 0; t < nw; ++t) {
-        const size_t r = R.row(v, t);
-        out[r * 2 * C + c] = (y[r * C + c] - m) * iv;
-        out[r * 2 * C + C + c] = best;
-    }
-    argmax[e] = bi;
-}
-
-__global__ __launch_bounds__(256) void vfe_max_concat_bwd(const float *__restrict__ g, const int *__restrict__ argmax,
-                                                          float *__restrict__ dyh, int V, int C, Rows R) {
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * C) return;
-    const int v = (int)(e / C), c = (int)(e % C);
-    const int nw = R.vcnt ? R.count(v) + 1 : R.T;        // rows stored for this voxel
-    float s = 0.f;
-    for (int t = 0; t < nw; ++t) s += g[R.row(v, t) * 2 * C + C + c];   // padded row: already summed
-    const int am = argmax[e];
-    for (int t = 0; t < nw; ++t) {
-        const size_t r = R.row(v, t);
-        dyh[r * C + c] = g[r * 2 * C + c] + (t == am ? s : 0.f);
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_segmax(const float *__restrict__ y, const float *__restrict__ mi,
-                                                 float *__restrict__ out, int *__restrict__ argmax, int V, int C, Rows R,
-                                                 FrameMap fm) {
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * C) return;
-    const int v = (int)(e / C), c = (int)(e % C);
-    mi += (size_t)fm_frame_of(fm, v) * 2 * C;
-    const float m = mi[c], iv = mi[C + c];
-    const int n = R.count(v) + (R.has_pad(v) ? 1 : 0);
-    float best = -INFINITY;
-    int bi = 0;
-    for (int t = 0; t < n; ++t) {
-        const float val = (y[R.row(v, t) * C + c] - m) * iv;
-        if (val > best) { best = val; bi = t; }
-    }
-    out[e] = best;
-    argmax[e] = bi;
-}
-
-__global__ __launch_bounds__(256) void segmax_bwd(const float *__restrict__ dfeat, const int *__restrict__ argmax,
-                                                  float *__restrict__ dyh, int V, int C, Rows R) {
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * C) return;
-    const int v = (int)(e / C), c = (int)(e % C);
-    const float gval = dfeat[e];
-    const int am = argmax[e];
-    const int nw = R.vcnt ? R.count(v) + 1 : R.T;
-    for (int t = 0; t < nw; ++t) dyh[R.row(v, t) * C + c] = (t == am) ? gval : 0.f;
-}
-
-
-// ---- float4 forms (channels a multiple of 4, 16-byte aligned tensors): one thread owns one (voxel, channel QUAD) and keeps FOUR
-// rows of its voxel in flight per trip.  The scalar kernels above move 4 bytes per lane with one dependent row at a time and
-// ran at 0.9-1.9 TB/s (config 2: 1.0 of 2.5 ms per step in these four kernels); the arithmetic and its order per channel -- first
-// maximum wins, gradient sums in row order -- are unchanged, so results are bit-equal to the scalar forms.
-constexpr int VU = 4;       // rows in flight per thread
-
-__device__ __forceinline__ float4 ld4(const float *p) { return *(const float4 *)p; }
-__device__ __forceinline__ void st4(float *p, const float4 v) { *(float4 *)p = v; }
-__device__ __forceinline__ float4 bn4(const float4 y, const float4 m, const float4 iv) {
-    return make_float4((y.x - m.x) * iv.x, (y.y - m.y) * iv.y, (y.z - m.z) * iv.z, (y.w - m.w) * iv.w);
-}
-#define MVX_ARGMAX4(val, t)                                                                                   \
-    do {                                                                                                      \
-        if (val.x > best.x) { best.x = val.x; bi.x = (t); }                                                   \
-        if (val.y > best.y) { best.y = val.y; bi.y = (t); }                                                   \
-        if (val.z > best.z) { best.z = val.z; bi.z = (t); }                                                   \
-        if (val.w > best.w) { best.w = val.w; bi.w = (t); }                                                   \
-    } while (0)
+// One thread owns VEC neighbouring channels of one voxel and moves them as one load / store.  VEC = 4 is the form of the workload
+// (channels a multiple of 4, 16-byte aligned tensors); VEC = 1 serves every other call.  Both keep VU rows of the voxel in flight
+// per trip (one dependent 4-byte row at a time ran at 0.9-1.9 TB/s), and the arithmetic and its order per channel -- first maximum
+// wins, gradient sums in stored-row order -- do not depend on VEC: the two instantiations give the same bits.
+constexpr int VU = 4;
+template <typename T, int VEC>
+struct alignas(sizeof(T) * VEC) Pack { T c[VEC]; };
+template <int VEC, typename T>
+__device__ __forceinline__ Pack<T, VEC> ldv(const T *p) { return *(const Pack<T, VEC> *)p; }
+template <int VEC, typename T>
+__device__ __forceinline__ void stv(T *p, const Pack<T, VEC> &v) { *(Pack<T, VEC> *)p = v; }
 
 // rows of voxel v in compact or dense layout, resolved once per thread (voff / vcnt are the same for all lanes of a voxel)
 struct VoxRows {
-    size_t first, pad;      // first real row, the padded row (compact) -- dense: first row, unused
-    int count, n, nw;       // real rows; rows that take part in the max; rows that are stored
-    bool compact;
-    __device__ __forceinline__ size_t row(int t) const { return (!compact || t < count) ? first + t : pad; }
+    size_t first, pad;      // first real row, the padded row (dense: first row, unused)
+    int count, n, nw;       // real rows (dense: all T); rows that take part in the max; rows that are stored
+    __device__ __forceinline__ VoxRows(const int *voff, const int *vcnt, int T, int n_real, int v) {
+        count = vcnt ? vcnt[v] : T;
+        first = vcnt ? (size_t)voff[v] : (size_t)v * T;
+        pad = (size_t)n_real + v;
+        n = count + (count < T ? 1 : 0);
+        nw = vcnt ? count + 1 : T;                        // the padded row is always written
+    }
+    __device__ __forceinline__ size_t row(int t) const { return t < count ? first + t : pad; }
+    // row t of a trip that loads VU rows whatever is left: the rows past the last of `rows` read that last one again
+    __device__ __forceinline__ size_t row_of(int t, int rows) const { return row(t < rows ? t : rows - 1); }
 };
-__device__ __forceinline__ VoxRows vox_rows(const Rows &R, int v) {
-    VoxRows w;
-    w.compact = R.vcnt != nullptr;
-    if (!w.compact) { w.first = (size_t)v * R.T; w.pad = 0; w.count = R.T; w.n = R.T; w.nw = R.T; return w; }
-    w.count = R.vcnt[v];
-    w.first = (size_t)R.voff[v];
-    w.pad = (size_t)R.n_real + v;
-    w.n = w.count + (w.count < R.T ? 1 : 0);
-    w.nw = w.count + 1;                                   // the padded row is always written
-    return w;
+#define VOX_ROWS_PARAMS const int *__restrict__ voff, const int *__restrict__ vcnt, int T, int n_real
+
+// this thread's voxel and first channel, or false past the end
+template <int VEC>
+__device__ __forceinline__ bool vfe_thread(int V, int C, int &v, int &c) {
+    const int cv = C / VEC;
+    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    v = (int)(e / cv); c = (int)(e % cv) * VEC;
+    return e < (long long)V * cv;
 }
 
-template <bool CONCAT>
-__global__ __launch_bounds__(256) void vfe_bn_max4(const float *__restrict__ y, const float *__restrict__ mi,
-                                                   float *__restrict__ out, int *__restrict__ argmax, int V, int C, Rows R,
-                                                   FrameMap fm) {
-    const int c4 = C >> 2;
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * c4) return;
-    const int v = (int)(e / c4), c = (int)(e % c4) * 4;
-    mi += (size_t)fm_frame_of(fm, v) * 2 * C;
-    const float4 m = ld4(mi + c), iv = ld4(mi + C + c);
-    const VoxRows w = vox_rows(R, v);
-    float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    int4 bi = make_int4(0, 0, 0, 0);
-    for (int t0 = 0; t0 < w.n; t0 += VU) {
-        float4 q[VU];
+// out = BN(y) and its max over the voxel's rows: CONCAT [row][2C] = (BN(y), max), else [voxel][C] = max alone
+template <int VEC, bool CONCAT>
+__global__ __launch_bounds__(256) void vfe_bn_max(const float *__restrict__ y, const float *__restrict__ mi,
+                                                  float *__restrict__ out, int *__restrict__ argmax, int V, int C,
+                                                  VOX_ROWS_PARAMS, FrameMap fm) {
+    int v, c;
+    if (!vfe_thread<VEC>(V, C, v, c)) return;
+    mi += (size_t)fm_frame_of(fm, v) * 2 * C;             // per-frame BatchNorm (frames = voxel segments)
+    const Pack<float, VEC> m = ldv<VEC>(mi + c), iv = ldv<VEC>(mi + C + c);
+    const VoxRows w(voff, vcnt, T, n_real, v);
+    auto bn = [&](const Pack<float, VEC> &q) {
+        Pack<float, VEC> r;
 #pragma unroll
-        for (int u = 0; u < VU; ++u) q[u] = ld4(y + w.row(t0 + u < w.n ? t0 + u : w.n - 1) * C + c);
+        for (int i = 0; i < VEC; ++i) r.c[i] = bn1(q.c[i], m.c[i], iv.c[i]);
+        return r;
+    };
+    Pack<float, VEC> best;
+    Pack<int, VEC> bi;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) { best.c[i] = -INFINITY; bi.c[i] = 0; }
+    for (int t0 = 0; t0 < w.n; t0 += VU) {
+        Pack<float, VEC> q[VU];
+#pragma unroll
+        for (int u = 0; u < VU; ++u) q[u] = ldv<VEC>(y + w.row_of(t0 + u, w.n) * C + c);
 #pragma unroll
         for (int u = 0; u < VU; ++u)
-            if (t0 + u < w.n) { const float4 val = bn4(q[u], m, iv); MVX_ARGMAX4(val, t0 + u); }
+            if (t0 + u < w.n) {
+                const Pack<float, VEC> val = bn(q[u]);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i)
+                    if (val.c[i] > best.c[i]) { best.c[i] = val.c[i]; bi.c[i] = t0 + u; }       // the first maximum wins
+            }
     }
     if (CONCAT) {
         for (int t0 = 0; t0 < w.nw; t0 += VU) {
-            float4 q[VU];
+            Pack<float, VEC> q[VU];
 #pragma unroll
-            for (int u = 0; u < VU; ++u) q[u] = ld4(y + w.row(t0 + u < w.nw ? t0 + u : w.nw - 1) * C + c);
+            for (int u = 0; u < VU; ++u) q[u] = ldv<VEC>(y + w.row_of(t0 + u, w.nw) * C + c);
 #pragma unroll
             for (int u = 0; u < VU; ++u)
                 if (t0 + u < w.nw) {
                     float *o = out + w.row(t0 + u) * 2 * C;
-                    st4(o + c, bn4(q[u], m, iv));
-                    st4(o + C + c, best);
+                    stv<VEC>(o + c, bn(q[u]));
+                    stv<VEC>(o + C + c, best);
                 }
         }
     } else {
-        st4(out + (size_t)v * C + c, best);
+        stv<VEC>(out + (size_t)v * C + c, best);
     }
-    *(int4 *)(argmax + (size_t)v * C + c) = bi;
+    stv<VEC>(argmax + (size_t)v * C + c, bi);
 }
 
-__global__ __launch_bounds__(256) void vfe_max_concat_bwd4(const float *__restrict__ g, const int *__restrict__ argmax,
-                                                           float *__restrict__ dyh, int V, int C, Rows R) {
-    const int c4 = C >> 2;
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * c4) return;
-    const int v = (int)(e / c4), c = (int)(e % c4) * 4;
-    const VoxRows w = vox_rows(R, v);
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t0 = 0; t0 < w.nw; t0 += VU) {                // the gradient of the max: summed in row order
-        float4 q[VU];
+template <int VEC>
+__global__ __launch_bounds__(256) void vfe_max_concat_bwd(const float *__restrict__ g, const int *__restrict__ argmax,
+                                                          float *__restrict__ dyh, int V, int C, VOX_ROWS_PARAMS) {
+    int v, c;
+    if (!vfe_thread<VEC>(V, C, v, c)) return;
+    const VoxRows w(voff, vcnt, T, n_real, v);
+    Pack<float, VEC> s;
 #pragma unroll
-        for (int u = 0; u < VU; ++u) q[u] = ld4(g + w.row(t0 + u < w.nw ? t0 + u : w.nw - 1) * 2 * C + C + c);
+    for (int i = 0; i < VEC; ++i) s.c[i] = 0.f;
+    for (int t0 = 0; t0 < w.nw; t0 += VU) {                // the gradient of the max: summed in row order (padded row: already summed)
+        Pack<float, VEC> q[VU];
+#pragma unroll
+        for (int u = 0; u < VU; ++u) q[u] = ldv<VEC>(g + w.row_of(t0 + u, w.nw) * 2 * C + C + c);
 #pragma unroll
         for (int u = 0; u < VU; ++u)
-            if (t0 + u < w.nw) { s.x += q[u].x; s.y += q[u].y; s.z += q[u].z; s.w += q[u].w; }
-    }
-    const int4 am = *(const int4 *)(argmax + (size_t)v * C + c);
-    for (int t0 = 0; t0 < w.nw; t0 += VU) {
-        float4 q[VU];
+            if (t0 + u < w.nw)
 #pragma unroll
-        for (int u = 0; u < VU; ++u) q[u] = ld4(g + w.row(t0 + u < w.nw ? t0 + u : w.nw - 1) * 2 * C + c);
+                for (int i = 0; i < VEC; ++i) s.c[i] += q[u].c[i];
+    }
+    const Pack<int, VEC> am = ldv<VEC>(argmax + (size_t)v * C + c);
+    for (int t0 = 0; t0 < w.nw; t0 += VU) {
+        Pack<float, VEC> q[VU];
+#pragma unroll
+        for (int u = 0; u < VU; ++u) q[u] = ldv<VEC>(g + w.row_of(t0 + u, w.nw) * 2 * C + c);
 #pragma unroll
         for (int u = 0; u < VU; ++u) {
             const int t = t0 + u;
-            if (t < w.nw)
-                st4(dyh + w.row(t) * C + c, make_float4(q[u].x + (t == am.x ? s.x : 0.f), q[u].y + (t == am.y ? s.y : 0.f),
-                                                         q[u].z + (t == am.z ? s.z : 0.f), q[u].w + (t == am.w ? s.w : 0.f)));
+            if (t >= w.nw) break;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) q[u].c[i] += t == am.c[i] ? s.c[i] : 0.f;
+            stv<VEC>(dyh + w.row(t) * C + c, q[u]);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void segmax_bwd4(const float *__restrict__ dfeat, const int *__restrict__ argmax,
-                                                   float *__restrict__ dyh, int V, int C, Rows R) {
-    const int c4 = C >> 2;
-    const long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (e >= (long long)V * c4) return;
-    const int v = (int)(e / c4), c = (int)(e % c4) * 4;
-    const VoxRows w = vox_rows(R, v);
-    const float4 gv = ld4(dfeat + (size_t)v * C + c);
-    const int4 am = *(const int4 *)(argmax + (size_t)v * C + c);
-    for (int t = 0; t < w.nw; ++t)
-        st4(dyh + w.row(t) * C + c, make_float4(t == am.x ? gv.x : 0.f, t == am.y ? gv.y : 0.f, t == am.z ? gv.z : 0.f,
-                                                 t == am.w ? gv.w : 0.f));
+template <int VEC>
+__global__ __launch_bounds__(256) void segmax_bwd(const float *__restrict__ dfeat, const int *__restrict__ argmax,
+                                                  float *__restrict__ dyh, int V, int C, VOX_ROWS_PARAMS) {
+    int v, c;
+    if (!vfe_thread<VEC>(V, C, v, c)) return;
+    const VoxRows w(voff, vcnt, T, n_real, v);
+    const Pack<float, VEC> gv = ldv<VEC>(dfeat + (size_t)v * C + c);
+    const Pack<int, VEC> am = ldv<VEC>(argmax + (size_t)v * C + c);
+    for (int t = 0; t < w.nw; ++t) {
+        Pack<float, VEC> o;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) o.c[i] = t == am.c[i] ? gv.c[i] : 0.f;
+        stv<VEC>(dyh + w.row(t) * C + c, o);
+    }
 }
 
 // ---- compact row bookkeeping --------------------------------------------------------------------
@@ -351,10 +288,8 @@ __global__ void vfe_compact_pad_finish(const double *__restrict__ padsum, float 
 }  // namespace
 
 #define VFE_ARGS_OK (n_voxels >= 0 && t > 0 && channels > 0)
-#define VFE_GRID dim3(mvx_cdiv((long long)n_voxels * channels, 256)), dim3(256), 0, (hipStream_t)stream
-
-#define VFE_ROWS Rows{voff, vcnt, t, n_real}
-#define VFE_GRID4 dim3(mvx_cdiv((long long)n_voxels * (channels / 4), 256)), dim3(256), 0, (hipStream_t)stream
+#define VFE_GRID(vec) dim3(mvx_cdiv((long long)n_voxels * (channels / (vec)), 256)), dim3(256), 0, (hipStream_t)stream
+#define VFE_ROWS voff, vcnt, t, n_real
 static inline bool vfe_vec4(int channels, const void *a, const void *b, const void *c) {
     return channels % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
@@ -369,9 +304,9 @@ extern "C" int mvx_vfe_bn_max_concat_frames(const float *y, const float *mean_in
     if (n_voxels == 0) return MVX_OK;
     VFE_FRAMES(fm);
     if (vfe_vec4(channels, y, out, argmax) && ((uintptr_t)mean_inv & 15) == 0)
-        hipLaunchKernelGGL(vfe_bn_max4<true>, VFE_GRID4, y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
+        hipLaunchKernelGGL((vfe_bn_max<4, true>), VFE_GRID(4), y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
     else
-        hipLaunchKernelGGL(vfe_bn_max_concat, VFE_GRID, y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
+        hipLaunchKernelGGL((vfe_bn_max<1, true>), VFE_GRID(1), y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -388,9 +323,9 @@ extern "C" int mvx_vfe_max_concat_backward(const float *grad_out, const int32_t 
     MVX_CHECK_ARG(grad_out && argmax && dyhat && VFE_ARGS_OK && VFE_ROWS_OK);
     if (n_voxels == 0) return MVX_OK;
     if (vfe_vec4(channels, grad_out, dyhat, argmax))
-        hipLaunchKernelGGL(vfe_max_concat_bwd4, VFE_GRID4, grad_out, argmax, dyhat, n_voxels, channels, VFE_ROWS);
+        hipLaunchKernelGGL(vfe_max_concat_bwd<4>, VFE_GRID(4), grad_out, argmax, dyhat, n_voxels, channels, VFE_ROWS);
     else
-        hipLaunchKernelGGL(vfe_max_concat_bwd, VFE_GRID, grad_out, argmax, dyhat, n_voxels, channels, VFE_ROWS);
+        hipLaunchKernelGGL(vfe_max_concat_bwd<1>, VFE_GRID(1), grad_out, argmax, dyhat, n_voxels, channels, VFE_ROWS);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -403,9 +338,9 @@ extern "C" int mvx_bn_segment_max_frames(const float *y, const float *mean_inv, 
     if (n_voxels == 0) return MVX_OK;
     VFE_FRAMES(fm);
     if (vfe_vec4(channels, y, out, argmax) && ((uintptr_t)mean_inv & 15) == 0)
-        hipLaunchKernelGGL(vfe_bn_max4<false>, VFE_GRID4, y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
+        hipLaunchKernelGGL((vfe_bn_max<4, false>), VFE_GRID(4), y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
     else
-        hipLaunchKernelGGL(bn_segmax, VFE_GRID, y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
+        hipLaunchKernelGGL((vfe_bn_max<1, false>), VFE_GRID(1), y, mean_inv, out, argmax, n_voxels, channels, VFE_ROWS, fm);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -422,9 +357,9 @@ extern "C" int mvx_segment_max_backward(const float *dfeat, const int32_t *argma
     MVX_CHECK_ARG(dfeat && argmax && dyhat && VFE_ARGS_OK && VFE_ROWS_OK);
     if (n_voxels == 0) return MVX_OK;
     if (vfe_vec4(channels, dfeat, dyhat, argmax))
-        hipLaunchKernelGGL(segmax_bwd4, VFE_GRID4, dfeat, argmax, dyhat, n_voxels, channels, VFE_ROWS);
+        hipLaunchKernelGGL(segmax_bwd<4>, VFE_GRID(4), dfeat, argmax, dyhat, n_voxels, channels, VFE_ROWS);
     else
-        hipLaunchKernelGGL(segmax_bwd, VFE_GRID, dfeat, argmax, dyhat, n_voxels, channels, VFE_ROWS);
+        hipLaunchKernelGGL(segmax_bwd<1>, VFE_GRID(1), dfeat, argmax, dyhat, n_voxels, channels, VFE_ROWS);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
