@@ -985,6 +985,32 @@ int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32_t l, int32
                           const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight,
                           float *d_heads, float *losses, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* mvx_focal_loss_dir_frames: mvx_focal_loss_frames with a direction classifier (SECOND / PointPillars), the
+ * same three launches and memset.  Rows carry explicit strides: heads f32 rows of heads_ld >= 8A floats (a multiple of 4, base
+ * 16-byte aligned) whose first 8A columns are mvx_focal_loss_frames's; d_heads (optional) rows of d_heads_ld floats, written
+ * in full: every column beyond 8A is zero unless the direction gradient lives there.  The direction logits and their gradient
+ * come as pointer + row stride, dir[row*dir_ld + a] for anchor a < A of BEV cell row: columns of the head rows (dir = heads +
+ * 8A, dir_ld = heads_ld) or a tensor of their own; d_dir likewise (given exactly when d_heads is; outside the d_heads rows its
+ * A columns per row are zeroed first, further columns are left alone).  Per pos_idx entry (anchor a, box g, direction logit x;
+ * entries the regression term skips are skipped, duplicates count every time):
+ *   angle column:  SmoothL1(sin D) with D = r6 - (g6 - an6) in place of SmoothL1(D), same mean and reg_weight; gradient
+ *                  reg_weight / (n_pos*7) * SmoothL1'(sin D) * cos D;
+ *   direction bit: b = floor(mod(g6 - dir_offset, 2 pi) / pi) in {0, 1};
+ *   dir_f = dir_weight / max(1, n_pos) * sum (b ? softplus(-x) : softplus(x)), gradient dir_weight / max(1, n_pos) * (sigmoid(x) - b).
+ * The classification term and regression columns 0..5 are mvx_focal_loss_frames's (the cls loss and gradient bit for bit).
+ * losses f32 [n_frames][3] = (cls_f, reg_f, dir_f).  workspace: mvx_focal_loss_dir_frames_workspace_bytes(n_frames, l, w,
+ * anchors_per_loc, d_heads_ld) bytes (pass heads_ld without d_heads).  Reproducibility as mvx_focal_loss_frames.
+ */
+int64_t mvx_focal_loss_dir_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                                  int32_t d_heads_ld);
+int mvx_focal_loss_dir_frames(const float *heads, int32_t heads_ld, const float *dir, int32_t dir_ld, int32_t n_frames, int32_t l,
+                              int32_t w, int32_t anchors_per_loc, const int64_t *pos_idx, const int64_t *neg_idx,
+                              const int64_t *gi, int64_t cap, const int32_t *counts, const float *gts, int32_t gt_ld,
+                              const int32_t *gt_off, const float *anchors, float alpha, float gamma, float cls_weight,
+                              float reg_weight, float dir_weight, float dir_offset, float *d_heads, int32_t d_heads_ld,
+                              float *d_dir, int32_t d_dir_ld, float *losses, void *workspace, int64_t workspace_bytes,
+                              void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Detection output (csrc/detect.hip): score selection, top-K, box decoding and rotated BEV NMS for the frames of a step.
  * The reference has none of it (its Calc.decodeRegression is never called).
@@ -1030,6 +1056,20 @@ int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t 
                       int32_t post_max, int32_t decode, float *boxes, float *scores, int32_t *anchor_idx, int32_t *counts,
                       int32_t *n_candidates, int32_t *status, int32_t *dbg_idx, float *dbg_boxes, float *dbg_corners,
                       void *workspace, size_t workspace_bytes, void *stream);
+/* mvx_detect_frames_dir: mvx_detect_frames plus a fourth head, the direction logit of anchor a at dir[f*dir_sf + x*dir_sl +
+ * y*dir_sw + a*dir_sa] (what mvx_focal_loss_dir_frames trains), and dir_offset.  After yaw = r6 + yaw_a the decode computes
+ *   base = (yaw - dir_offset) - floor((yaw - dir_offset) / pi) * pi,  yaw' = base + dir_offset + pi * [logit > 0],
+ * wraps yaw' into [-pi, pi) and uses it for the corners, the NMS and the output: for a perfect regression and a correct bit
+ * yaw' = g6 (mod 2 pi), also when the regression is half a turn off.  A non-finite yaw is left as it is and sets
+ * MVX_DETECT_NONFINITE.  dir = NULL is mvx_detect_frames bit for bit (which calls this).
+ */
+int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+                          int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *dir, int64_t dir_sf,
+                          int64_t dir_sl, int64_t dir_sw, int64_t dir_sa, float dir_offset, const float *anchors,
+                          int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc, float score_thr, float iou_thr,
+                          int32_t pre_max, int32_t post_max, int32_t decode, float *boxes, float *scores, int32_t *anchor_idx,
+                          int32_t *counts, int32_t *n_candidates, int32_t *status, int32_t *dbg_idx, float *dbg_boxes,
+                          float *dbg_corners, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * KITTI object evaluation (csrc/kitti_eval.hip): AP for 2D bbox, BEV and 3D, plus AOS, in the semantics of the widely used

@@ -20,10 +20,11 @@ def initWeights(m):
 
 class MVXNet(nn.Module):
 
-    def __init__(self):
+    def __init__(self, direction=False):
+        """``direction``: the RPN carries the direction classifier ``backbone.rpn.dir`` (voxelnet/Pipe.py RPN)."""
         super().__init__()
         self.head = ImageHead()
-        self.backbone = VoxelNet()
+        self.backbone = VoxelNet(direction=direction)
         self.backbone.apply(initWeights)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -90,6 +91,7 @@ class MVXNet(nn.Module):
         """Boxes of one frame, with forward's inputs (MVXNet.py:21-27) and the anchor grid (h1, w1, 14)
         (Preprocessing.createAnchors): the forward on the single HIP node up to the raw head logits, then
         ``modules.detect.postprocess`` (keyword arguments as there: score_thr, iou_thr, pre_max, post_max, decode).
+        A model with the direction head decodes through it (``direction`` / ``dir_offset`` of postprocess): yaws in [-pi, pi).
         Returns ``{boxes (n,7) xyzlwhr LiDAR frame, scores (n,), anchor_idx (n,), n_candidates, status}``."""
         from modules import detect, whole
         from modules import Extension as X

@@ -14,6 +14,11 @@
 //   4. detect_scan    (one wave per frame): the greedy scan, the removed bitmap one u64 per lane, mask rows streamed through
 //                     LDS 64 rows at a time; writes the kept boxes.
 // No float atomics and no host synchronisation: every output is bitwise reproducible.
+//
+// mvx_detect_frames_dir adds a fourth head, one direction logit x per anchor (the classifier mvx_focal_loss_dir_frames trains):
+// detect_select folds the decoded yaw t = r6 + an6 into the half turn the bit names,
+//   base = (t - dir_offset) - floor((t - dir_offset) / pi) pi,  t' = base + dir_offset + pi [x > 0],  wrapped into [-pi, pi),
+// before the corners are formed, so the circle, the NMS and the output all see t'.  A null head is mvx_detect_frames.
 #include "bev_iou.h"
 
 namespace {
@@ -75,7 +80,8 @@ __global__ __launch_bounds__(256) void detect_keys(Head cls, int F, int L, int W
 }
 
 // 2. one workgroup per frame
-__global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg, const float *__restrict__ anchors, int L, int W, int A,
+__global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg, Head dir, float dir_offset,
+                                                             const float *__restrict__ anchors, int L, int W, int A,
                                                              int decode, Layout lay, unsigned char *__restrict__ ws,
                                                              int *__restrict__ n_candidates, int *__restrict__ status,
                                                              int *__restrict__ dbg_idx, float *__restrict__ dbg_boxes,
@@ -202,6 +208,15 @@ __global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg,
         bool ok = true;
 #pragma unroll
         for (int k = 0; k < 7; ++k) ok = ok && isfinite(b[k]);
+        if (dir.p && isfinite(b[6])) {              // the half turn the direction bit names; a non-finite yaw stays as it is
+            const float PI = 3.14159265358979323846f, PI_BELOW = 3.14159250f;      // PI rounds above pi, PI_BELOW is the float under it
+            const float v = b[6] - dir_offset;
+            const float base = v - floorf(v / PI) * PI;
+            float t = base + dir_offset + (dir.p[head_off(dir, f, x, y, a)] > 0.f ? PI : 0.f);
+            t -= floorf((t + PI) / (2.f * PI)) * (2.f * PI);
+            if (t > PI_BELOW) t -= 2.f * PI;
+            b[6] = fmaxf(t, -PI_BELOW);             // [-pi, pi) as real numbers too
+        }
         // unit-square corners scaled by (l, w), times [[cos, -sin], [sin, cos]] from the right, shifted by (x, y)
         const float cs = cosf(b[6]), sn = sinf(b[6]);
         const float ux[4] = {0.5f, -0.5f, -0.5f, 0.5f}, uy[4] = {0.5f, 0.5f, -0.5f, -0.5f};
@@ -359,12 +374,15 @@ extern "C" size_t mvx_detect_workspace_bytes(int32_t n_frames, int32_t n_anchors
     return Layout(pre_max > 0 ? pre_max : 0, n_anchors > 0 ? n_anchors : 0, F).total(F);
 }
 
-extern "C" int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
-                                 int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *anchors,
-                                 int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc, float score_thr, float iou_thr,
-                                 int32_t pre_max, int32_t post_max, int32_t decode, float *boxes, float *scores,
-                                 int32_t *anchor_idx, int32_t *counts, int32_t *n_candidates, int32_t *status, int32_t *dbg_idx,
-                                 float *dbg_boxes, float *dbg_corners, void *workspace, size_t workspace_bytes, void *stream) {
+extern "C" int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+                                     int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *dir,
+                                     int64_t dir_sf, int64_t dir_sl, int64_t dir_sw, int64_t dir_sa, float dir_offset,
+                                     const float *anchors, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                     float score_thr, float iou_thr, int32_t pre_max, int32_t post_max, int32_t decode, float *boxes,
+                                     float *scores, int32_t *anchor_idx, int32_t *counts, int32_t *n_candidates, int32_t *status,
+                                     int32_t *dbg_idx, float *dbg_boxes, float *dbg_corners, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+    MVX_CHECK_ARG(!dir || dir_offset == dir_offset);
     MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
     MVX_CHECK_ARG(pre_max >= 1 && pre_max <= MVX_DETECT_MAX_PRE && post_max >= 1 && post_max <= pre_max);
     MVX_CHECK_ARG(iou_thr >= 1e-3f && iou_thr < 1.f && score_thr >= 0.f && score_thr < 1.f);
@@ -380,12 +398,13 @@ extern "C" int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_s
     hipStream_t st = (hipStream_t)stream;
     unsigned char *ws = (unsigned char *)workspace;
     const Head hc = {cls, cls_sf, cls_sl, cls_sw, cls_sa}, hr = {reg, reg_sf, reg_sl, reg_sw, reg_sc};
+    const Head hd = {dir, dir_sf, dir_sl, dir_sw, dir_sa};
     const long long tot = (long long)n_frames * lay.npad;
     hipLaunchKernelGGL(detect_keys, dim3(mvx_cdiv(tot, 256)), dim3(256), 0, st, hc, n_frames, l, w, anchors_per_loc, score_thr,
                        (unsigned *)(ws + lay.keys), lay.npad);
     MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(detect_select, dim3(n_frames), dim3(SEL_THREADS), 0, st, hc, hr, anchors, l, w, anchors_per_loc, decode, lay,
-                       ws, n_candidates, status, dbg_idx, dbg_boxes, dbg_corners);
+    hipLaunchKernelGGL(detect_select, dim3(n_frames), dim3(SEL_THREADS), 0, st, hc, hr, hd, dir_offset, anchors, l, w, anchors_per_loc,
+                       decode, lay, ws, n_candidates, status, dbg_idx, dbg_boxes, dbg_corners);
     MVX_LAUNCH_CHECK();
     const unsigned nb = (unsigned)lay.NW;
     hipLaunchKernelGGL(detect_mask, dim3(nb * MASK_SPLIT, nb, n_frames), dim3(MASK_THREADS), 0, st, lay, ws, iou_thr);
@@ -393,4 +412,16 @@ extern "C" int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_s
     hipLaunchKernelGGL(detect_scan, dim3(n_frames), dim3(64), 0, st, lay, ws, post_max, boxes, scores, anchor_idx, counts);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
+}
+
+extern "C" int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+                                 int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *anchors,
+                                 int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc, float score_thr, float iou_thr,
+                                 int32_t pre_max, int32_t post_max, int32_t decode, float *boxes, float *scores,
+                                 int32_t *anchor_idx, int32_t *counts, int32_t *n_candidates, int32_t *status, int32_t *dbg_idx,
+                                 float *dbg_boxes, float *dbg_corners, void *workspace, size_t workspace_bytes, void *stream) {
+    return mvx_detect_frames_dir(cls, cls_sf, cls_sl, cls_sw, cls_sa, reg, reg_sf, reg_sl, reg_sw, reg_sc, nullptr, 0, 0, 0, 0, 0.f,
+                                 anchors, n_frames, l, w, anchors_per_loc, score_thr, iou_thr, pre_max, post_max, decode, boxes,
+                                 scores, anchor_idx, counts, n_candidates, status, dbg_idx, dbg_boxes, dbg_corners, workspace,
+                                 workspace_bytes, stream);
 }

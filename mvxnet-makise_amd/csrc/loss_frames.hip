@@ -19,6 +19,15 @@
 //                    entries that name the same anchor collide there), then the frame's partials summed in index order
 // No f64 atomic, no atomic across workgroups on a sum: the losses are bitwise reproducible, and so is the gradient whenever
 // no anchor is listed twice in pos_idx.  counts and gt_off are read on the device: the host reads nothing.
+//
+// mvx_focal_loss_dir_frames is the same three launches with a direction classifier (SECOND, PointPillars): rows of any stride
+// (heads / d_heads may carry further columns), and per pos_idx entry of anchor a, box g and direction logit x, in focal_lists:
+//   angle column   SmoothL1(sin D), D = r6 - (g6 - an6), in place of SmoothL1(D): blind to half turns; gradient
+//                  reg_scale * SmoothL1'(sin D) * cos D
+//   direction bit  b = floor(mod(g6 - dir_offset, 2 pi) / pi) = floor((g6 - dir_offset) / pi) mod 2
+//   dir_f = dir_weight / max(1, n_pos) * sum (b ? softplus(-x) : softplus(x)),  gradient dir_weight / max(1, n_pos) * (sigmoid(x) - b)
+// The direction logits and their gradient come as pointer + row stride: columns of the head rows (the dense pass zeroes them
+// with the rest of the row) or a tensor of their own (the dense pass zeroes its A columns).  losses is (F,3) = (cls, reg, dir).
 #include "common.h"
 
 namespace {
@@ -33,11 +42,13 @@ struct Layout {
     long long flag_bytes;     // all frames, one byte per anchor, rounded up to 256
     int nb;                   // workgroups of the dense pass per frame
     bool ok;
-    Layout(int F, int l, int w, int A) {
-        ok = F >= 1 && F <= MVX_MAX_FRAMES && l > 0 && w > 0 && A >= 1 && A <= 4 && (long long)F * l * w * A * 8 < (1ll << 31);
+    // ld: floats per row of the gradient the dense pass writes (8A for the plain rows)
+    Layout(int F, int l, int w, int A, int ld) {
+        ok = F >= 1 && F <= MVX_MAX_FRAMES && l > 0 && w > 0 && A >= 1 && A <= 4 && ld >= 8 * A && ld % 4 == 0 &&
+             (long long)F * l * w * ld < (1ll << 31);
         n_anchors = ok ? (long long)l * w * A : 0;
         flag_bytes = ((long long)F * n_anchors + 255) & ~255ll;
-        const long long chunks = (long long)l * w * 2 * A;      // float4 pieces of a frame's rows
+        const long long chunks = (long long)l * w * (ld / 4);   // float4 pieces of a frame's rows
         const long long want = ok ? (chunks + DENSE_THREADS * 4 - 1) / (DENSE_THREADS * 4) : 0;
         nb = (int)(want > DENSE_MAX_BLOCKS ? DENSE_MAX_BLOCKS : want);
     }
@@ -91,15 +102,17 @@ __device__ __forceinline__ double block_sum_f64(double v, double *s_part) {
     return t;
 }
 
-// One thread per float4 of a row; the first float4 of a row holds its A <= 4 logits.
+// One thread per float4 of a gradient row (ldd floats); the first float4 of a row holds its A <= 4 logits.  zero / ldz: a
+// direction gradient outside the head rows, whose A columns per row are zeroed here for the list pass to add into.
 __global__ void __launch_bounds__(DENSE_THREADS)
-focal_dense(const float *__restrict__ heads, int rows, int A, const unsigned char *__restrict__ flags, Lists ls, float alpha,
-            float gamma, float cls_weight, float *__restrict__ d_heads, double *__restrict__ partials) {
+focal_dense(const float *__restrict__ heads, int ld, int rows, int A, const unsigned char *__restrict__ flags, Lists ls, float alpha,
+            float gamma, float cls_weight, float *__restrict__ d_heads, int ldd, float *__restrict__ zero, int ldz,
+            double *__restrict__ partials) {
     const int f = blockIdx.y;
-    const int cpr = 2 * A;                                   // float4 pieces per row
+    const int cpr = ldd >> 2, cpr_in = ld >> 2;              // float4 pieces per row
     const long long chunks = (long long)rows * cpr;
-    const float4 *src = (const float4 *)(heads + (size_t)f * rows * 8 * A);
-    float4 *dst = d_heads ? (float4 *)(d_heads + (size_t)f * rows * 8 * A) : nullptr;
+    const float4 *src = (const float4 *)(heads + (size_t)f * rows * ld);
+    float4 *dst = d_heads ? (float4 *)(d_heads + (size_t)f * rows * ldd) : nullptr;
     const unsigned char *fl = flags + (size_t)f * rows * A;
     const int n_pos = list_count(ls, f, 0);
     const float scale = cls_weight / (float)(n_pos > 1 ? n_pos : 1);
@@ -108,7 +121,7 @@ focal_dense(const float *__restrict__ heads, int rows, int A, const unsigned cha
         const long long row = i / cpr;
         float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i - row * cpr == 0) {
-            const float4 in = src[i];
+            const float4 in = src[row * cpr_in];
             const float xs[4] = {in.x, in.y, in.z, in.w};
             float g[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -137,22 +150,38 @@ focal_dense(const float *__restrict__ heads, int rows, int A, const unsigned cha
         }
         if (dst) dst[i] = out;
     }
+    if (zero)
+        for (long long i = (long long)blockIdx.x * DENSE_THREADS + threadIdx.x; i < (long long)rows * A; i += (long long)gridDim.x * DENSE_THREADS)
+            zero[((size_t)f * rows + i / A) * ldz + i % A] = 0.f;
     __shared__ double s_part[DENSE_THREADS / 64];
     const double t = block_sum_f64(part, s_part);
     if (threadIdx.x == 0) partials[(size_t)f * gridDim.x + blockIdx.x] = t;
 }
 
+// The direction classifier of mvx_focal_loss_dir_frames: logits x and their gradient d as pointer + row stride.
+struct Dir {
+    const float *x;
+    float *d;
+    int ldx, ldd;
+    float weight, offset;
+};
+
+constexpr float PI_F = 3.14159265358979323846f;
+
+template <bool DIR>
 __global__ void __launch_bounds__(LIST_THREADS)
-focal_lists(const float *__restrict__ heads, Lists ls, const float *__restrict__ gts, int gt_ld, const int *__restrict__ gt_off,
-            const float *__restrict__ anchors, int L, int W, int A, float cls_weight, float reg_weight,
-            float *__restrict__ d_heads, const double *__restrict__ partials, int nb, float *__restrict__ losses) {
+focal_lists(const float *__restrict__ heads, int ld, Lists ls, const float *__restrict__ gts, int gt_ld,
+            const int *__restrict__ gt_off, const float *__restrict__ anchors, int L, int W, int A, float cls_weight,
+            float reg_weight, float *__restrict__ d_heads, int ldd, const double *__restrict__ partials, int nb, Dir dir,
+            float *__restrict__ losses) {
     const int f = blockIdx.x;
     const int n_pos = list_count(ls, f, 0);
     const long long *pos = ls.pos + (size_t)f * 3 * ls.cap, *gi = ls.gi + (size_t)f * ls.cap;
     const int g_lo = gt_off[f], n_gt = gt_off[f + 1] - g_lo;
-    const size_t frame = (size_t)f * L * W * 8 * A;
+    const size_t cell0 = (size_t)f * L * W;
     const float reg_scale = n_pos > 0 ? reg_weight / (float)(n_pos * 7) : 0.f;
-    double s_reg = 0.0;
+    const float dir_scale = DIR ? dir.weight / (float)(n_pos > 1 ? n_pos : 1) : 0.f;
+    double s_reg = 0.0, s_dir = 0.0;
     for (int k = threadIdx.x; k < n_pos; k += blockDim.x) {
         const long long a = list_anchor(pos, ls.cap, k, L, W, A);
         const long long gk = gi[k];
@@ -169,31 +198,76 @@ focal_lists(const float *__restrict__ heads, Lists ls, const float *__restrict__
         t[4] = logf(g[4] / an[4]);
         t[5] = logf(g[5] / an[5]);
         t[6] = g[6] - an[6];
-        const size_t col0 = frame + (size_t)(a / A) * 8 * A + A + z * 7;
+        const size_t cell = cell0 + (size_t)(a / A);
+        const size_t col0 = cell * ld + A + z * 7, dcol0 = cell * ldd + A + z * 7;
 #pragma unroll
         for (int c = 0; c < 7; ++c) {
-            const float diff = heads[col0 + c] - t[c];
+            float diff = heads[col0 + c] - t[c];
+            float chain = 1.f;
+            if (DIR && c == 6) {                         // the angle through its sine: d/dD SmoothL1(sin D) = SmoothL1'(sin D) cos D
+                const float delta = diff;
+                sincosf(delta, &diff, &chain);
+            }
             const float ad = fabsf(diff);
             s_reg += (double)(ad < 1.f ? 0.5f * diff * diff : ad - 0.5f);
-            if (d_heads) atomicAdd(d_heads + col0 + c, reg_scale * (ad < 1.f ? diff : (diff > 0.f ? 1.f : -1.f)));
+            const float slope = ad < 1.f ? diff : (diff > 0.f ? 1.f : -1.f);
+            if (d_heads) atomicAdd(d_heads + dcol0 + c, DIR && c == 6 ? reg_scale * slope * chain : reg_scale * slope);
+        }
+        if (DIR) {
+            const int bit = (int)floorf((g[6] - dir.offset) / PI_F) & 1;
+            const float x = dir.x[cell * dir.ldx + z];
+            const float e = expf(-fabsf(x));
+            const float l1p = log1pf(e);
+            s_dir += (double)((bit ? fmaxf(-x, 0.f) : fmaxf(x, 0.f)) + l1p);      // softplus(-x) : softplus(x)
+            const float inv = 1.f / (1.f + e);
+            if (dir.d) atomicAdd(dir.d + cell * dir.ldd + z, dir_scale * ((x >= 0.f ? inv : e * inv) - (float)bit));
         }
     }
     __shared__ double s_part[LIST_THREADS / 64];
+    __shared__ double s_part_dir[DIR ? LIST_THREADS / 64 : 1];
     __shared__ double s_cls[DENSE_MAX_BLOCKS];
     for (int k = threadIdx.x; k < nb; k += blockDim.x) s_cls[k] = partials[(size_t)f * nb + k];
     const double tr = block_sum_f64(s_reg, s_part);      // its barrier also publishes s_cls
+    const double td = DIR ? block_sum_f64(s_dir, s_part_dir) : 0.0;
     if (threadIdx.x == 0) {
         double tc = 0.0;
         for (int k = 0; k < nb; ++k) tc += s_cls[k];
-        losses[2 * f] = (float)((double)cls_weight * tc / (double)(n_pos > 1 ? n_pos : 1));
-        losses[2 * f + 1] = n_pos > 0 ? (float)((double)reg_weight * tr / (double)(n_pos * 7)) : 0.f;
+        float *out = losses + (DIR ? 3 : 2) * f;
+        out[0] = (float)((double)cls_weight * tc / (double)(n_pos > 1 ? n_pos : 1));
+        out[1] = n_pos > 0 ? (float)((double)reg_weight * tr / (double)(n_pos * 7)) : 0.f;
+        if (DIR) out[2] = (float)((double)dir.weight * td / (double)(n_pos > 1 ? n_pos : 1));
     }
+}
+
+// The three launches of both entry points.  dir.x == nullptr: the plain loss, losses (F,2).
+int focal_launch(const float *heads, int ld, int n_frames, int l, int w, int A, const Lists &ls, const float *gts, int gt_ld,
+                 const int *gt_off, const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight, float *d_heads,
+                 int ldd, const Dir &dir, float *losses, const Layout &lay, void *workspace, hipStream_t st) {
+    unsigned char *ws = (unsigned char *)workspace;
+    double *partials = (double *)(ws + lay.partials());
+    hipError_t e = hipMemsetAsync(ws, 0, (size_t)lay.flag_bytes, st);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(focal_flags, dim3(LIST_BLOCKS, n_frames), dim3(256), 0, st, ls, l, w, A, (unsigned *)ws);
+    MVX_LAUNCH_CHECK();
+    // a direction gradient that is not a column range of the d_heads rows is zeroed by the dense pass too
+    const bool inside = dir.d && d_heads && dir.ldd == ldd && dir.d >= d_heads && dir.d + A <= d_heads + ldd;
+    hipLaunchKernelGGL(focal_dense, dim3(lay.nb, n_frames), dim3(DENSE_THREADS), 0, st, heads, ld, l * w, A, ws, ls, alpha, gamma,
+                       cls_weight, d_heads, ldd, dir.d && !inside ? dir.d : nullptr, dir.ldd, partials);
+    MVX_LAUNCH_CHECK();
+    if (dir.x)
+        hipLaunchKernelGGL(focal_lists<true>, dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off, anchors, l,
+                           w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, losses);
+    else
+        hipLaunchKernelGGL(focal_lists<false>, dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off, anchors, l,
+                           w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, losses);
+    MVX_LAUNCH_CHECK();
+    return MVX_OK;
 }
 
 }  // namespace
 
 extern "C" int64_t mvx_focal_loss_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc) {
-    return Layout(n_frames, l, w, anchors_per_loc).total(n_frames);
+    return Layout(n_frames, l, w, anchors_per_loc, 8 * anchors_per_loc).total(n_frames);
 }
 
 extern "C" int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
@@ -201,7 +275,8 @@ extern "C" int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32
                                      const int32_t *counts, const float *gts, int32_t gt_ld, const int32_t *gt_off,
                                      const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight,
                                      float *d_heads, float *losses, void *workspace, int64_t workspace_bytes, void *stream) {
-    const Layout lay(n_frames, l, w, anchors_per_loc);
+    const int ld = 8 * anchors_per_loc;
+    const Layout lay(n_frames, l, w, anchors_per_loc, ld);
     MVX_CHECK_ARG(lay.ok);
     MVX_CHECK_ARG(heads && pos_idx && neg_idx && gi && counts && gts && gt_off && anchors && losses && workspace);
     MVX_CHECK_ARG(cap >= 1 && cap < (1ll << 31) && gt_ld >= 7);
@@ -209,19 +284,38 @@ extern "C" int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32
     MVX_CHECK_ARG(workspace_bytes >= lay.total(n_frames));
     // rows are read and written as float4; the flag words and the f64 partials sit in the workspace
     MVX_CHECK_ARG(((uintptr_t)heads & 15) == 0 && ((uintptr_t)d_heads & 15) == 0 && ((uintptr_t)workspace & 7) == 0);
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char *ws = (unsigned char *)workspace;
-    double *partials = (double *)(ws + lay.partials());
-    hipError_t e = hipMemsetAsync(ws, 0, (size_t)lay.flag_bytes, st);
-    if (e != hipSuccess) return (int)e;
     const Lists ls = {(const long long *)pos_idx, (const long long *)neg_idx, (const long long *)gi, (long long)cap, counts};
-    hipLaunchKernelGGL(focal_flags, dim3(LIST_BLOCKS, n_frames), dim3(256), 0, st, ls, l, w, anchors_per_loc, (unsigned *)ws);
-    MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(focal_dense, dim3(lay.nb, n_frames), dim3(DENSE_THREADS), 0, st, heads, l * w, anchors_per_loc, ws, ls, alpha,
-                       gamma, cls_weight, d_heads, partials);
-    MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(focal_lists, dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ls, gts, gt_ld, gt_off, anchors, l, w,
-                       anchors_per_loc, cls_weight, reg_weight, d_heads, partials, lay.nb, losses);
-    MVX_LAUNCH_CHECK();
-    return MVX_OK;
+    const Dir none = {nullptr, nullptr, 0, 0, 0.f, 0.f};
+    return focal_launch(heads, ld, n_frames, l, w, anchors_per_loc, ls, gts, gt_ld, gt_off, anchors, alpha, gamma, cls_weight,
+                        reg_weight, d_heads, ld, none, losses, lay, workspace, (hipStream_t)stream);
+}
+
+extern "C" int64_t mvx_focal_loss_dir_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                                             int32_t d_heads_ld) {
+    return Layout(n_frames, l, w, anchors_per_loc, d_heads_ld).total(n_frames);
+}
+
+extern "C" int mvx_focal_loss_dir_frames(const float *heads, int32_t heads_ld, const float *dir, int32_t dir_ld, int32_t n_frames,
+                                         int32_t l, int32_t w, int32_t anchors_per_loc, const int64_t *pos_idx,
+                                         const int64_t *neg_idx, const int64_t *gi, int64_t cap, const int32_t *counts,
+                                         const float *gts, int32_t gt_ld, const int32_t *gt_off, const float *anchors, float alpha,
+                                         float gamma, float cls_weight, float reg_weight, float dir_weight, float dir_offset,
+                                         float *d_heads, int32_t d_heads_ld, float *d_dir, int32_t d_dir_ld, float *losses,
+                                         void *workspace, int64_t workspace_bytes, void *stream) {
+    const Layout lay(n_frames, l, w, anchors_per_loc, d_heads_ld);
+    MVX_CHECK_ARG(lay.ok);
+    MVX_CHECK_ARG(heads && dir && pos_idx && neg_idx && gi && counts && gts && gt_off && anchors && losses && workspace);
+    MVX_CHECK_ARG(heads_ld >= 8 * anchors_per_loc && heads_ld % 4 == 0 && (long long)n_frames * l * w * heads_ld < (1ll << 31));
+    MVX_CHECK_ARG(dir_ld >= anchors_per_loc && (long long)n_frames * l * w * dir_ld < (1ll << 31));
+    MVX_CHECK_ARG((d_heads == nullptr) == (d_dir == nullptr));
+    MVX_CHECK_ARG(!d_dir || (d_dir_ld >= anchors_per_loc && (long long)n_frames * l * w * d_dir_ld < (1ll << 31)));
+    MVX_CHECK_ARG(cap >= 1 && cap < (1ll << 31) && gt_ld >= 7);
+    MVX_CHECK_ARG(alpha >= 0.f && alpha <= 1.f && gamma >= 0.f && dir_weight >= 0.f && dir_offset == dir_offset);
+    MVX_CHECK_ARG(workspace_bytes >= lay.total(n_frames));
+    MVX_CHECK_ARG(((uintptr_t)heads & 15) == 0 && ((uintptr_t)d_heads & 15) == 0 && ((uintptr_t)workspace & 7) == 0);
+    MVX_CHECK_ARG(((uintptr_t)dir & 3) == 0 && ((uintptr_t)d_dir & 3) == 0);
+    const Lists ls = {(const long long *)pos_idx, (const long long *)neg_idx, (const long long *)gi, (long long)cap, counts};
+    const Dir d = {dir, d_dir, dir_ld, d_dir_ld, dir_weight, dir_offset};
+    return focal_launch(heads, heads_ld, n_frames, l, w, anchors_per_loc, ls, gts, gt_ld, gt_off, anchors, alpha, gamma, cls_weight,
+                        reg_weight, d_heads, d_heads_ld, d, losses, lay, workspace, (hipStream_t)stream);
 }

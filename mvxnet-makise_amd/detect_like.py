@@ -11,6 +11,7 @@ GPU).  The feature maps come from the same stand-in as train_like.py when torchv
     python detect_like.py <dataroot> --render pictures      # and a bird's-eye and a camera picture of every frame (visualize_like.py)
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -35,6 +36,8 @@ def parse_args(argv=None):
     ap.add_argument('--pre-max', type=int, default=1000)
     ap.add_argument('--post-max', type=int, default=100)
     ap.add_argument('--decode', choices=['loss', 'reference'], default='loss')
+    ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
+                    help='a checkpoint of train_like.py --direction (it holds backbone.rpn.dir.weight): the --dir-offset it was trained with')
     ap.add_argument('--eval', action='store_true', help='score the written files against the split\'s label_2 (KITTI AP on the GPU)')
     ap.add_argument('--classes', nargs='+', default=['Car'], help='classes scored by --eval')
     ap.add_argument('--extractor-weights', default=None,
@@ -69,14 +72,18 @@ def main(args):
     anchorBevs = bbox3d2bev(anchors.reshape(anchors.shape[:2] + (-1, 7))).to(device).contiguous()
     anchors = anchors.to(device)
     torch.manual_seed(0)
-    model = MVXNet().to(device)
-    if args.checkpoint:
-        model.load_state_dict(torch.load(args.checkpoint, map_location=device))
+    state = torch.load(args.checkpoint, map_location=device) if args.checkpoint else None
+    direction = state is not None and 'backbone.rpn.dir.weight' in state      # written by train_like.py --direction
+    model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
+    if state is not None:
+        model.load_state_dict(state)
     fpn_fn = fpn_maps_for
     if args.extractor_weights:
         model.head.extractor.load_weights(args.extractor_weights).to(device)
         fpn_fn = extractor_fpn_fn(model.head.extractor, {n: d[1] for d, n in zip(data, names)})
     kw = dict(score_thr=args.score_thr, iou_thr=args.iou_thr, pre_max=args.pre_max, post_max=args.post_max, decode=args.decode)
+    if direction:
+        kw['dir_offset'] = args.dir_offset
     cap = max(args.points, max(d[0].shape[0] for d in data))
     t0, n_boxes = time.perf_counter(), 0
     for lo in range(0, len(data), args.frames):

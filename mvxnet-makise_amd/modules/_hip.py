@@ -1,6 +1,7 @@
 """Typed torch-tensor wrappers over the C ABI (plumbing only: allocation, pointers, stream)."""
 import collections
 import ctypes
+import math
 import os
 
 import torch
@@ -1314,7 +1315,10 @@ def linear_wgrad_pre(x_planes, dz_planes, accumulate_into=None, rows=None):
     pieces, plane_rows, K = x_planes.shape
     N = dz_planes.shape[2]
     lo, hi = rows if rows is not None else (0, plane_rows)
-    if accumulate_into is not None:
+    # the kernel adds through 16-byte vectors: a gradient view that starts elsewhere (a GradBucket lays parameters back to back,
+    # and a model with the direction head has 18 bias floats in front of the late part) gets the product through a buffer
+    via = accumulate_into is not None and accumulate_into.data_ptr() % 16 != 0
+    if accumulate_into is not None and not via:
         assert accumulate_into.is_contiguous() and accumulate_into.numel() == N * K
         dw, flags = accumulate_into, FLAG_ACCUMULATE
     else:
@@ -1326,6 +1330,11 @@ def linear_wgrad_pre(x_planes, dz_planes, accumulate_into=None, rows=None):
         with _Timed('linear_wgrad', 2.0 * (hi - lo) * K * N if KERNEL_TIMERS is not None else 0):
             X.check(X.lib.mvx_linear_wgrad_pre_rows(X.ptr(x_planes), X.ptr(dz_planes), X.ptr(dw), plane_rows, lo, hi, K, N, flags,
                                                     1.0, X.ptr(ws), ws.numel(), X.stream()), 'mvx_linear_wgrad_pre_rows')
+        if via:
+            if isinstance(scope, _SideStream):       # the buffer lives until the owning stream has joined (see _SideStream)
+                _KEEP.setdefault(dw.device.index, []).append(dw)
+            assert accumulate_into.is_contiguous() and accumulate_into.numel() == N * K
+            accumulate_into.view(N, K).add_(dw)
     return None if accumulate_into is not None else dw
 
 
@@ -2035,18 +2044,70 @@ def focal_loss_frames(heads, F, l, w, A, pos_idx, neg_idx, gi, counts, gts, gt_o
     return losses, d_heads
 
 
+def focal_loss_dir_frames(heads, dir_logits, F, l, w, A, pos_idx, neg_idx, gi, counts, gts, gt_off, anchors, alpha, gamma, cls_weight,
+                          reg_weight, dir_weight, dir_offset, want_grads=True, d_heads=None, d_dir=None):
+    """Focal loss with the direction classifier and the sine angle term (csrc/loss_frames.hip), the three
+    launches and one memset of ``focal_loss_frames``.  ``heads`` f32 (F*l*w, ld) with ld >= 8A a multiple of 4, unit column
+    stride: the first 8A columns are [A cls logits | 7A regression]; ``dir_logits`` f32 (F*l*w, A) with any row stride and unit
+    column stride -- columns of ``heads`` (``heads[:, 8A:9A]``) or a tensor of its own.  Lists, boxes and anchors as
+    ``focal_loss_frames``.  Returns (losses f32 (F,3) = (cls, reg, dir) per frame, d_heads in the layout of ``heads``, d_dir a
+    view like ``dir_logits``) -- the gradients None without ``want_grads``.  When ``dir_logits`` is a column range of ``heads``,
+    d_dir is the same range of d_heads and every other column beyond 8A is zero; otherwise d_dir is a tensor shaped like
+    ``dir_logits``'s storage rows whose A columns are written.  ``d_heads`` / ``d_dir`` (tests): buffers to write instead."""
+    dev = heads.device
+    rows = F * l * w
+    assert heads.dtype == dir_logits.dtype == torch.float32 and heads.dim() == 2 and heads.shape[0] == rows
+    assert heads.stride(1) == 1 and heads.shape[1] >= 8 * A and (rows == 1 or heads.stride(0) % 4 == 0)
+    assert tuple(dir_logits.shape) == (rows, A) and dir_logits.stride(1) == 1
+    assert tuple(pos_idx.shape) == tuple(neg_idx.shape) == (F, 3, gi.shape[1]) and tuple(gi.shape) == (F, gi.shape[1])
+    assert pos_idx.dtype == neg_idx.dtype == gi.dtype == torch.int64 and counts.dtype == gt_off.dtype == torch.int32
+    assert tuple(counts.shape) == (F, 2) and tuple(gt_off.shape) == (F + 1,) and gts.dtype == anchors.dtype == torch.float32
+    assert gts.dim() == 2 and gts.shape[0] >= 1 and anchors.numel() == l * w * A * 7
+    ld, dir_ld = heads.stride(0), dir_logits.stride(0)
+    losses = torch.empty((F, 3), dtype=torch.float32, device=dev)
+    ldd = ld
+    if want_grads:
+        inside = (dir_ld == ld and 0 <= dir_logits.data_ptr() - heads.data_ptr() <= 4 * (heads.shape[1] - A)
+                  and dir_logits.untyped_storage().data_ptr() == heads.untyped_storage().data_ptr())
+        if d_heads is None:
+            d_heads = torch.empty((rows, heads.shape[1]), dtype=torch.float32, device=dev)
+        if d_dir is None:
+            if inside:
+                c0 = (dir_logits.data_ptr() - heads.data_ptr()) // 4
+                d_dir = d_heads[:, c0:c0 + A]
+            else:
+                d_dir = torch.empty((rows, A), dtype=torch.float32, device=dev)
+        assert d_heads.stride(1) == 1 and d_dir.stride(1) == 1 and tuple(d_dir.shape) == (rows, A)
+        ldd = d_heads.stride(0)
+    else:
+        d_heads = d_dir = None
+    nbytes = X.lib.mvx_focal_loss_dir_frames_workspace_bytes(int(F), int(l), int(w), int(A), int(ldd))
+    ws = workspace(nbytes, dev, 'focal_loss')
+    X.check(X.lib.mvx_focal_loss_dir_frames(_vptr(heads), int(ld), _vptr(dir_logits), int(dir_ld), int(F), int(l), int(w), int(A),
+                                            X.ptr(pos_idx), X.ptr(neg_idx), X.ptr(gi), gi.shape[1], X.ptr(counts), X.ptr(gts),
+                                            gts.shape[1], X.ptr(gt_off), X.ptr(anchors), float(alpha), float(gamma),
+                                            float(cls_weight), float(reg_weight), float(dir_weight), float(dir_offset),
+                                            _vptr(d_heads) if want_grads else None, int(ldd),
+                                            _vptr(d_dir) if want_grads else None, int(d_dir.stride(0)) if want_grads else 0,
+                                            X.ptr(losses), X.ptr(ws), ws.numel(), X.stream()), 'mvx_focal_loss_dir_frames')
+    return losses, d_heads, d_dir
+
+
 # ---------------------------------------------------------------------------------------------
 # detection output (csrc/detect.hip)
 # ---------------------------------------------------------------------------------------------
 DECODE_MODES = {'loss': 0, 'reference': 1}
 
 
-def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, post_max, decode='loss', debug=False):
+def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, post_max, decode='loss', debug=False, dir_logits=None,
+                  dir_offset=math.pi / 4):
     """Selection, decoding and rotated BEV NMS of F frames in four launches.  ``cls`` / ``reg``: f32 views (F, l, w, A) and
     (F, l, w, 7A) with arbitrary element strides (the frame-set heads or NCHW maps, read in place); anchors f32 [l][w][A][7]
     contiguous on the device.  Returns (boxes (F,post_max,7), scores (F,post_max), anchor_idx i32 (F,post_max), meta i32 (3,F) =
     (kept count, candidates above score_thr, status)) on the device, plus (candidate anchor indices i32 (F,pre_max), decoded
-    boxes (F,pre_max,7), corners (F,pre_max,4,2)) with ``debug``."""
+    boxes (F,pre_max,7), corners (F,pre_max,4,2)) with ``debug``.  ``dir_logits``: f32 view (F, l, w, A) of the direction head:
+    the decoded yaw is folded into the half turn its sign names, around ``dir_offset``, and wrapped into [-pi, pi)
+    (mvx_detect_frames_dir); None is the plain decode (mvx_detect_frames)."""
     if decode not in DECODE_MODES:
         raise X.MvxHipError("decode must be 'loss' or 'reference', not %r" % (decode,))
     dev = cls.device
@@ -2064,6 +2125,17 @@ def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, po
     nbytes = X.lib.mvx_detect_workspace_bytes(F, l * w * A, pre_max)
     ws = workspace(nbytes, dev, 'detect')
     cs, rs = cls.stride(), reg.stride()
+    if dir_logits is not None:
+        assert dir_logits.shape == (F, l, w, A) and dir_logits.dtype == torch.float32 and dir_logits.device == dev
+        ds = dir_logits.stride()
+        X.check(X.lib.mvx_detect_frames_dir(_vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3],
+                                            _vptr(dir_logits), ds[0], ds[1], ds[2], ds[3], float(dir_offset), X.ptr(anchors),
+                                            int(F), int(l), int(w), int(A), float(score_thr), float(iou_thr), int(pre_max),
+                                            int(post_max), DECODE_MODES[decode], X.ptr(boxes), X.ptr(scores), X.ptr(idx),
+                                            X.ptr(meta[0]), X.ptr(meta[1]), X.ptr(meta[2]), X.ptr(dbg[0]), X.ptr(dbg[1]),
+                                            X.ptr(dbg[2]), X.ptr(ws), ws.numel(), X.stream()), 'mvx_detect_frames_dir')
+        out = (boxes, scores, idx, meta)
+        return out + dbg if debug else out
     X.check(X.lib.mvx_detect_frames(_vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3], X.ptr(anchors),
                                     int(F), int(l), int(w), int(A), float(score_thr), float(iou_thr), int(pre_max), int(post_max),
                                     DECODE_MODES[decode], X.ptr(boxes), X.ptr(scores), X.ptr(idx), X.ptr(meta[0]),

@@ -28,20 +28,23 @@ def _anchors_dev(anchors, h1, w1, dev):
 
 
 def _views(heads_or_maps, F, h1, w1):
-    """(cls (F,h1,w1,A), reg (F,h1,w1,7A)) views of the channels-last heads (F*h1*w1, 16) or of NCHW maps (cls, reg)."""
+    """(cls (F,h1,w1,A), reg (F,h1,w1,7A), dir (F,h1,w1,A) or None) views of the channels-last heads (F*h1*w1, 16), of the
+    direction model's (F*h1*w1, 20) = [cls | reg | dir | 0 0] (rpn_frames.head_layout), or of NCHW maps (cls, reg[, dir])."""
     if isinstance(heads_or_maps, (tuple, list)):
-        cls, reg = heads_or_maps
+        cls, reg = heads_or_maps[:2]
         assert cls.dim() == 4 and cls.shape[0] == F and cls.shape[2:] == (h1, w1), tuple(cls.shape)
         assert reg.shape == (F, 7 * cls.shape[1], h1, w1), tuple(reg.shape)
-        return cls.permute(0, 2, 3, 1), reg.permute(0, 2, 3, 1)
+        dirm = heads_or_maps[2] if len(heads_or_maps) > 2 else None
+        assert dirm is None or dirm.shape == cls.shape, tuple(dirm.shape)
+        return cls.permute(0, 2, 3, 1), reg.permute(0, 2, 3, 1), None if dirm is None else dirm.permute(0, 2, 3, 1)
+    from modules import rpn_frames as rf
     v = heads_or_maps.view(F, h1, w1, -1)
-    A = v.shape[-1] // 8
-    assert v.shape[-1] == 8 * A, tuple(heads_or_maps.shape)
-    return v[..., :A], v[..., A:]
+    A, has_dir = rf.head_layout(v.shape[-1])
+    return v[..., :A], v[..., A:8 * A], v[..., 8 * A:9 * A] if has_dir else None
 
 
 def postprocess(heads_or_maps, anchors, F, h1, w1, *, score_thr=0.05, iou_thr=0.01, pre_max=1000, post_max=100, decode='loss',
-                read=True, debug=False):
+                read=True, debug=False, direction=None, dir_offset=math.pi / 4):
     """Boxes of F frames from the raw head output, read in place: the frame-set heads (F*h1*w1, 16) = [cls logits | reg] of
     ``rpn_frames.rpn_forward``, or NCHW maps ``(cls logits (F,2,h1,w1), reg (F,14,h1,w1))``.  ``anchors`` (h1, w1, 14) =
     [l][w][A][7] (Preprocessing.createAnchors), on the host or the device.
@@ -50,19 +53,31 @@ def postprocess(heads_or_maps, anchors, F, h1, w1, *, score_thr=0.05, iou_thr=0.
     ascending), decoded (``decode='loss'``: the inverse of VoxelLoss's targets; ``'reference'``: Calc.decodeRegression as the
     reference wrote it, diagonal from anchor columns 0:2), greedy NMS at BEV IoU > iou_thr, at most ``post_max`` kept.
 
+    ``direction``: fold every decoded yaw into the half turn its direction logit names (the classifier that
+    ``FocalLoss(direction=True)`` trains, with the same ``dir_offset``) and wrap it into [-pi, pi), before the corners and the
+    NMS.  None (default) = when the heads carry direction columns (the 20-wide rows of a direction model, or a third map);
+    True without them is an error, False ignores them.
+
     Returns a list of F dicts ``{boxes (n,7) xyzlwhr, scores (n,), anchor_idx (n,) i32, n_candidates, status}`` (device
     tensors) after ONE device->host read; ``read=False`` returns the padded device tensors instead
     ``{boxes (F,post_max,7), scores, anchor_idx, meta i32 (3,F) = (counts, n_candidates, status)}`` for a caller that
     pipelines (``unpack`` reads them later).  ``debug`` adds the sorted candidates ('cand_idx', 'cand_boxes',
     'cand_corners', padded to pre_max) to the device dict."""
-    cls, reg = _views(heads_or_maps, F, h1, w1)
+    cls, reg, dirv = _views(heads_or_maps, F, h1, w1)
+    if direction is None:
+        direction = dirv is not None
+    if direction and dirv is None:
+        raise X.MvxHipError('postprocess(direction=True) needs heads with direction columns (MVXNet(direction=True))')
+    if direction and dirv.dtype != torch.float32:
+        raise X.MvxHipError('postprocess reads f32 head outputs')
     if cls.dtype != torch.float32 or reg.dtype != torch.float32:
         raise X.MvxHipError('postprocess reads f32 head outputs')
     A = cls.shape[-1]
     anc = _anchors_dev(anchors, h1, w1, cls.device)
     if anc.shape[2] != A:
         raise X.MvxHipError('anchors hold %d orientations per cell, the heads %d' % (anc.shape[2], A))
-    res = _hip.detect_frames(cls, reg, anc, F, h1, w1, A, score_thr, iou_thr, pre_max, post_max, decode, debug=debug)
+    res = _hip.detect_frames(cls, reg, anc, F, h1, w1, A, score_thr, iou_thr, pre_max, post_max, decode, debug=debug,
+                             dir_logits=dirv if direction else None, dir_offset=dir_offset)
     out = dict(boxes=res[0], scores=res[1], anchor_idx=res[2], meta=res[3])
     if debug:
         out.update(cand_idx=res[4], cand_boxes=res[5], cand_corners=res[6])

@@ -770,6 +770,9 @@ def heads_loss(heads, F, h1, w1, targets, criterion, anchors):
     Returns (losses (F,2) on the device = (clsLoss, regLoss or 0), per-frame bool "has a regression loss", d_heads)."""
     from modules.voxelnet.Loss import _index_block
     dev = heads.device
+    if heads.shape[1] != 16:
+        raise _hip.X.MvxHipError('the direction head is trained by FocalLoss(direction=True) only: VoxelLoss reads 16-wide heads, '
+                                 'these are %d wide' % heads.shape[1])
     v = heads.view(F, h1, w1, 16)
     score = torch.sigmoid(v[..., :2])
     d = torch.zeros_like(v)
@@ -804,7 +807,10 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     ``targets``: per frame (pi, ni, gi, gt boxes) or None.  Gradients are ADDED into the existing .grad buffers
     (GradBucket).  ``rpn_hip=False`` runs the RPN + loss through the torch modules under autograd instead (comparison).
     A ``criterion`` that has ``heads_loss_frames`` (voxelnet/FocalLoss.py) computes the loss of all frames in one call on the
-    raw head output, in place of the per-frame VoxelLoss; it needs ``rpn_hip=True``.
+    raw head output, in place of the per-frame VoxelLoss; it needs ``rpn_hip=True``.  With ``FocalLoss(direction=True)`` on a
+    model with the direction head (``MVXNet(direction=True)``) the losses are (F,3) and out['dir'] holds the direction loss of
+    every frame with a positive, out['loss'] includes it; a direction criterion on a model without ``rpn.dir``, or any other
+    criterion on a model with it, raises MvxHipError before anything is launched.
     ``prepare_next`` = (next batch, callable returning its targets): voxelized, mapped and target-assigned on the
     preparation stream after this step has been enqueued; returned as out['next'] = (ready, targets) for the next call.
     ``read=False`` leaves the losses on the device (out['losses_dev'] (F,2)) and skips the status read: the caller reads
@@ -818,6 +824,10 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     frames_loss = hasattr(criterion, 'heads_loss_frames')
     if frames_loss and not rpn_hip:
         raise _hip.X.MvxHipError('a criterion with heads_loss_frames reads the logits of the frame-set heads: it needs rpn_hip=True')
+    if bool(getattr(criterion, 'direction', False)) != hasattr(model.backbone.rpn, 'dir'):
+        raise _hip.X.MvxHipError('the direction head is trained by FocalLoss(direction=True) on MVXNet(direction=True): the model %s '
+                                 'rpn.dir, the criterion is %s' % ('has' if hasattr(model.backbone.rpn, 'dir') else 'has no',
+                                                                   type(criterion).__name__ + ('(direction=True)' if getattr(criterion, 'direction', False) else '')))
     target_tensors =(x for t in targets if t is not None for x in tuple(t[0]) + tuple(t[1]) + (t[2], t[3])
                       if isinstance(x, torch.Tensor) and x.is_cuda)      # written on the preparation stream too (target_fn)
     fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev), also=target_tensors)
@@ -883,6 +893,15 @@ def read_losses(out):
         return out
     _check_statuses(out['statuses'])
     vals = out['losses_dev'].tolist()
+    if vals and len(vals[0]) == 3:                  # a direction criterion: (cls, reg, dir) per frame
+        out.setdefault('dir', [])
+        for (c, r, d), hr in zip(vals, out['has_reg']):
+            out['cls'].append(c)
+            if hr:
+                out['reg'].append(r)
+                out['dir'].append(d)
+            out['loss'].append(c + r + d if hr else c)
+        return out
     for (c, r), hr in zip(vals, out['has_reg']):
         out['cls'].append(c)
         if hr:

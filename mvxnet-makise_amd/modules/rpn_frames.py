@@ -15,7 +15,9 @@ every CRB2d / DeCRB2d = conv -> ReLU -> BatchNorm with per-frame batch statistic
     VoxelNet.py:36 is never materialised on this path;
   * deconv2 / deconv3 (kernel = stride): row GEMMs (csrc/linear.hip) whose output is normalised and pixel-shuffled into
     its channel slice of the 768-channel concat buffer by one pass (csrc/rpn.hip);
-  * the two heads: one row GEMM with 16 output columns.
+  * the two heads: one row GEMM with 16 output columns; with the optional direction head (``RPN(direction=True)``) the same
+    GEMM with 20: [cls 2 | reg 14 | dir 2 | two zero columns], so that rows stay multiples of 16 bytes and the 768-channel
+    concat buffer is read once.
 Maps are channels-last [F][h][w][c].  Parameter gradients are ADDED into the existing .grad buffers, weight-gradient
 kernels run on the side stream.
 """
@@ -177,7 +179,8 @@ def _d2s(xs, F, planes, h, w, C):
 
 def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
     """x_cl: the normalised CML output, channels-last planes [F*planes][H][W][Cp] (BEV channel c*planes + d).
-    Returns (heads (F*H/2*W/2, 16) = [cls logits (2) | reg (14)] per BEV cell, saved state)."""
+    Returns (heads (F*H/2*W/2, 16) = [cls logits (2) | reg (14)] per BEV cell, saved state); with a direction head the rows
+    are 20 wide, [cls (2) | reg (14) | dir logits (2) | 0 0] (``head_layout``)."""
     dev = x_cl.device
     eps = cfg.eps
     _hip.require_plain_batchnorm()
@@ -226,17 +229,36 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
         _hip.d2s_bn_apply(t, mi, up, F, hk, wk, s, cout, 768, off)
         S['dk'].append(dict(x=xr, t=t, mi=mi, m=m, s=s, off=off, h=hk, w=wk, w_all=w_all, cin=cin, cout=cout))
     # heads (Pipe.py:64-65,74): one GEMM, 16 columns
-    w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768)]).contiguous()
-    b_heads = torch.cat([rpn.cls.bias, rpn.reg.bias])
+    dirh = getattr(rpn, 'dir', None)
+    if dirh is None:
+        w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768)]).contiguous()
+        b_heads = torch.cat([rpn.cls.bias, rpn.reg.bias])
+    else:                                           # + the direction logits and two zero rows: 20 columns
+        w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768), dirh.weight.view(2, 768),
+                             torch.zeros((2, 768), dtype=torch.float32, device=dev)]).contiguous()
+        b_heads = torch.cat([rpn.cls.bias, rpn.reg.bias, dirh.bias, torch.zeros((2,), dtype=torch.float32, device=dev)])
     heads, _ = _hip.linear_forward(up, w_heads, b_heads, relu=False, want_stats=False)
     S.update(up=up, w_heads=w_heads, h1=h1, w1=w1)
     return heads, S
 
 
+def head_layout(width):
+    """Row width of a head output -> (A, has_dir): 8A columns [A cls | 7A reg], or with the direction head 9A rounded up to a
+    multiple of 4, [A cls | 7A reg | A dir | zeros] (8, 16, 24, 32 against 12, 20, 28, 36: never ambiguous for A <= 4)."""
+    if width % 8 == 0 and 1 <= width // 8 <= 4:
+        return width // 8, False
+    A = width // 9
+    if 1 <= A <= 4 and (9 * A + 3) // 4 * 4 == width:
+        return A, True
+    raise X.MvxHipError('a head row of %d columns is neither [A cls | 7A reg] nor that plus A direction logits' % width)
+
+
 def split_heads(heads, F, h1, w1):
-    """(score (F,2,h1,w1) = sigmoid(cls), reg (F,14,h1,w1)) as views of the channels-last head output (no copies of reg)."""
-    v = heads.view(F, h1, w1, 16)
-    return torch.sigmoid(v[..., :2]).permute(0, 3, 1, 2), v[..., 2:].permute(0, 3, 1, 2)
+    """(score (F,2,h1,w1) = sigmoid(cls), reg (F,14,h1,w1)) as views of the channels-last head output (no copies of reg), of
+    either width."""
+    A, _ = head_layout(heads.shape[-1])
+    v = heads.view(F, h1, w1, heads.shape[-1])
+    return torch.sigmoid(v[..., :A]).permute(0, 3, 1, 2), v[..., A:8 * A].permute(0, 3, 1, 2)
 
 
 _MUTATE = {}        # TESTS ONLY (tests/test_rpn_gpu.py): name -> factor applied to one term of the RPN backward, to prove that the
@@ -248,7 +270,7 @@ def _mut(name, t):
 
 
 def rpn_backward(rpn, S, d_heads):
-    """Backward from dL/d(heads) (F*h1*w1, 16); returns dL/d(x_cl) in the layout of rpn_forward's input.
+    """Backward from dL/d(heads) (F*h1*w1, 16 or 20, as rpn_forward returned them); returns dL/d(x_cl) in the layout of rpn_forward's input.
     Needs _hip.ASYNC_WGRAD semantics: weight gradients are produced on the side stream (join before the optimizer)."""
     F = S['F']
     planes, H, W, Cp = S['geom']
@@ -264,13 +286,16 @@ def rpn_backward(rpn, S, d_heads):
     # (the row-GEMM weight gradients of the heads and of deconv2 / deconv3 run on the side stream like the convolutions': they
     # were 0.41 ms of main-queue time per --mode full step)
     with _hip._SideStream(up, d_heads):
-        dwh = _hip.linear_wgrad(up, d_heads)                               # (16, 768)
+        dwh = _hip.linear_wgrad(up, d_heads)                               # (16 or 20, 768)
     with _hip._SideStream(dwh, d_heads):
         _grad_of(rpn.cls.weight).view(2, 768).add_(dwh[:2])
-        _grad_of(rpn.reg.weight).view(14, 768).add_(dwh[2:])
+        _grad_of(rpn.reg.weight).view(14, 768).add_(dwh[2:16])
         db = d_heads.sum(0)
         _grad_of(rpn.cls.bias).add_(db[:2])
-        _grad_of(rpn.reg.bias).add_(db[2:])
+        _grad_of(rpn.reg.bias).add_(db[2:16])
+        if w_heads.shape[0] == 20:                  # the direction head (its two pad columns of d_heads are zero)
+            _grad_of(rpn.dir.weight).view(2, 768).add_(dwh[16:18])
+            _grad_of(rpn.dir.bias).add_(db[16:18])
     g_up, _ = _hip.linear_forward(d_heads, w_heads, None, relu=False, want_stats=False, w_transposed=True)      # (rows, 768)
     g_up = _mut('heads_dgrad', g_up)
     # deconv2 / deconv3

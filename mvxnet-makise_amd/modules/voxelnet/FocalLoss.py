@@ -8,8 +8,20 @@ PointPillars and mmdetection3d's MVXNet), for all frames of a step in one HIP ca
 with p = sigmoid(logit).  It reads the raw head output -- logits, not probabilities: a focal loss from probabilities that
 have saturated to 0 or 1 in f32 cannot be computed -- so it is used through ``heads_loss_frames`` on the frame-set path
 (``pipeline.train_step_full(..., criterion=FocalLoss())``) and not through the reference's per-frame ``forward``.
+
+``direction=True`` trains the heading the way those three detectors do, on a model built with
+``MVXNet(direction=True)``.  Per ``pi`` entry, with D = reg[6] - (gt[6] - anchor[6]) and x the anchor's direction logit:
+
+    the angle column of regLoss is SmoothL1(sin D) in place of SmoothL1(D): blind to half turns of the box
+    b       = floor(mod(gt[6] - dir_offset, 2 pi) / pi)                       the half turn that is meant, 0 or 1
+    dirLoss = dir_weight / max(1, len(pi)) * sum (b ? -log sigmoid(x) : -log(1 - sigmoid(x)))
+
+and the decode (modules/detect.py) folds the regressed yaw into the half turn the logit names.  ``dir_weight=0.2`` and
+``dir_offset=pi/4`` are the values of SECOND's and mmdetection3d's KITTI configurations: design choices taken over from
+there, not optima measured on this model.
 """
 import collections
+import math
 
 import numpy as np
 import torch
@@ -31,9 +43,10 @@ def _on_device(x):
 
 class FocalLoss(nn.Module):
 
-    def __init__(self, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0):
+    def __init__(self, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0, direction=False, dir_weight=0.2, dir_offset=math.pi / 4):
         super().__init__()
         self.alpha, self.gamma, self.cls_weight, self.reg_weight = alpha, gamma, cls_weight, reg_weight
+        self.direction, self.dir_weight, self.dir_offset = bool(direction), dir_weight, dir_offset
 
     def forward(self, pi, ni, gi, gts, score, reg, anchors, anchorsPerLoc):
         raise NotImplementedError('FocalLoss needs the logits of the heads, not their probabilities (a focal loss from '
@@ -92,16 +105,30 @@ class FocalLoss(nn.Module):
     def heads_loss_frames(self, heads, F, h1, w1, targets, anchors, want_grads=True):
         """The loss of every frame on the channels-last head output (F*h1*w1, 8A) = [cls logits | reg] and its gradient, in
         one library call.  Returns (losses (F,2) on the device = (clsLoss, regLoss or 0), per-frame bool "has a regression
-        loss", d_heads) -- the triple of pipeline.heads_loss."""
+        loss", d_heads) -- the triple of pipeline.heads_loss.  With ``direction`` the rows are those of a direction model,
+        [cls | reg | dir logits | zeros] (rpn_frames.head_layout), losses is (F,3) = (clsLoss, regLoss or 0, dirLoss) and
+        d_heads carries the direction gradient in its columns, zeros in the pad columns.  A criterion and rows that do not
+        match raise MvxHipError before anything is launched."""
+        from modules import rpn_frames as rf
         if not heads.is_cuda:
             raise X.MvxHipError('FocalLoss runs on the GPU (no CPU fallback)')
         dev = heads.device
-        A = heads.shape[1] // 8
+        A, has_dir = rf.head_layout(heads.shape[1])
+        if has_dir != self.direction:
+            raise X.MvxHipError('FocalLoss(direction=True) needs the heads of a direction model (MVXNet(direction=True)), and a '
+                                'direction model needs FocalLoss(direction=True): the criterion has direction=%s, the heads are '
+                                '%d wide' % (self.direction, heads.shape[1]))
         packed, has_reg = self.pack_targets(targets, dev)
         anc = anchors.detach().float().contiguous()
         if not anc.is_cuda:
             from modules import Calc
             anc = Calc._anchors_on(anchors, dev)
+        if self.direction:
+            losses, d_heads, _ = _hip.focal_loss_dir_frames(heads, heads[:, 8 * A:9 * A], F, h1, w1, A, packed.pos_idx, packed.neg_idx,
+                                                            packed.gi, packed.counts, packed.gts, packed.gt_off, anc, self.alpha,
+                                                            self.gamma, self.cls_weight, self.reg_weight, self.dir_weight,
+                                                            self.dir_offset, want_grads=want_grads)
+            return losses, has_reg, d_heads
         losses, d_heads = _hip.focal_loss_frames(heads, F, h1, w1, A, packed.pos_idx, packed.neg_idx, packed.gi, packed.counts,
                                                  packed.gts, packed.gt_off, anc, self.alpha, self.gamma, self.cls_weight,
                                                  self.reg_weight, want_grads=want_grads)

@@ -174,9 +174,14 @@ class RPN(nn.Module):
     backward run on this library's kernels as one autograd node (RPNFunction over modules/rpn_frames.py: the MFMA gather /
     weight-gradient kernels for the 3x3 layers, row GEMMs for the kernel = stride deconvolutions and the heads; per-frame
     BatchNorm statistics); ``rpn_hip: False`` in config.yml (or a CPU tensor, or batch > 1) takes the torch modules
-    (CRB2d / DeCRB2d -> MIOpen), which remain as the comparison path of the tests."""
+    (CRB2d / DeCRB2d -> MIOpen), which remain as the comparison path of the tests.
 
-    def __init__(self):
+    ``direction=True`` adds a third head ``dir``, one logit per anchor: the two-way direction classifier of SECOND /
+    PointPillars that says which half turn of the box is meant (voxelnet/FocalLoss.py).  It is trained on the
+    frame-set path only; ``forward`` / ``forward_cl`` / ``forward_torch`` return (score, reg) for both kinds of model.  Without
+    it the module tree and the state dict are the reference's."""
+
+    def __init__(self, direction=False):
         super().__init__()
         self.blk1 = nn.Sequential(CRB2d(128, 128, 3, 2, 1), *[CRB2d(128, 128, 3, 1, 1) for _ in range(3)])
         self.blk2 = nn.Sequential(CRB2d(128, 128, 3, 2, 1), *[CRB2d(128, 128, 3, 1, 1) for _ in range(5)])
@@ -186,6 +191,8 @@ class RPN(nn.Module):
         self.deconv3 = DeCRB2d(256, 256, 4, 4, 0)
         self.cls = nn.Conv2d(768, 2, 1, 1, 0)
         self.reg = nn.Conv2d(768, 14, 1, 1, 0)
+        if direction:
+            self.dir = nn.Conv2d(768, 2, 1, 1, 0)
 
     def _hip_ok(self, x, H, W):
         return bool(cfg.config.get('rpn_hip', True)) and x.is_cuda and x.dtype == torch.float32 and H % 8 == 0 and W % 8 == 0
@@ -195,8 +202,8 @@ class RPN(nn.Module):
         of VoxelNet.py:36 folded into the first layer's weight): (score (1,2,H/2,W/2), reg (1,14,H/2,W/2))."""
         params = [p for p in self.parameters()]
         heads = RPNFunction.apply(x_cl, self, planes, H, W, Cp, *params)
-        v = heads.view(1, H // 2, W // 2, 16)
-        return torch.sigmoid(v[..., :2]).permute(0, 3, 1, 2), v[..., 2:].permute(0, 3, 1, 2)
+        from modules import rpn_frames as rf
+        return rf.split_heads(heads, 1, H // 2, W // 2)
 
     def forward_torch(self, x):
         """The per-module path: every block through its own forward.  On the torch modules (MIOpen) this is the comparison

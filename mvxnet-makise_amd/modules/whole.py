@@ -141,7 +141,8 @@ def _all_params(model):
 
 
 def forward_heads(model, voxels, imgs, idx, imsize):
-    """The single node's raw output: heads (H/2 * W/2, 16) = [cls logits (2) | reg (14)] per BEV cell.  The data-dependent
+    """The single node's raw output: heads (H/2 * W/2, 16) = [cls logits (2) | reg (14)] per BEV cell (20 wide with the
+    direction head: rpn_frames.head_layout).  The data-dependent
     status words of the sampling / scatter kernels stand for the reference's assert (imhead/Pipe.py:71); they are collected
     on the model and read without stalling the training stream (take_status), at once for a no-grad call."""
     hw = _imsize_hw(imsize)
@@ -157,5 +158,5 @@ def forward(model, voxels, imgs, idx, imsize):
     """MVXNet.forward on the single node: (score (1,2,H/2,W/2) = sigmoid of the logits, reg (1,14,H/2,W/2))."""
     heads = forward_heads(model, voxels, imgs, idx, imsize)
     h1, w1 = cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2
-    v = heads.view(1, h1, w1, 16)
-    return torch.sigmoid(v[..., :2]).permute(0, 3, 1, 2), v[..., 2:].permute(0, 3, 1, 2)
+    from modules import rpn_frames as rf
+    return rf.split_heads(heads, 1, h1, w1)

@@ -25,12 +25,18 @@ torch.optim.AdamW's format: a run can resume with either optimizer from a checkp
 ``--loss focal`` (--mode fast only) replaces VoxelLoss by the focal loss of modules/voxelnet/FocalLoss.py: one library call for
 all frames of a step on the logits of the heads; anchors between the two IoU thresholds are ignored.
 
+``--direction`` (--mode fast --loss focal only) trains the heading as SECOND / PointPillars do: the model gets a two-way
+direction classifier per anchor (``backbone.rpn.dir``), the angle is regressed through the sine of its residual, and the
+decode of detect_like.py folds the yaw back with the classifier's bit.  ``--dir-weight`` / ``--dir-offset`` are FocalLoss's;
+pass the same ``--dir-offset`` to detect_like.py / visualize_like.py (the checkpoint is the bare state dict).
+
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
                 frames), RPN + VoxelLoss per frame (per-frame BatchNorm statistics, as B reference forwards), one AdamW
                 step per B frames on the summed gradient / B; data-parallel over ranks when launched with torchrun.
 """
 import argparse
+import math
 import os
 import random
 import sys
@@ -98,7 +104,16 @@ def parse_args(argv=None):
     ap.add_argument('--focal-alpha', type=float, default=0.25)
     ap.add_argument('--focal-gamma', type=float, default=2.0)
     ap.add_argument('--focal-reg-weight', type=float, default=2.0)
+    ap.add_argument('--direction', action='store_true',
+                    help='--mode fast --loss focal: a direction classifier per anchor and the sine angle loss (MVXNet(direction=True), '
+                         'FocalLoss(direction=True))')
+    ap.add_argument('--dir-weight', type=float, default=0.2, help='--direction: weight of the direction loss (SECOND\'s value)')
+    ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
+                    help='--direction: yaw at which the direction bit flips (SECOND\'s pi/4); detect_like.py takes the same value')
     args = ap.parse_args(argv)
+    if args.direction and (args.mode != 'fast' or args.loss != 'focal'):
+        ap.error('--direction needs --mode fast --loss focal: the direction head is trained by the focal loss of the frame-set '
+                 'heads only')
     if args.loss == 'focal' and args.mode == 'module':
         ap.error('--loss focal needs --mode fast: the focal loss reads the logits of the frame-set heads, --mode module hands the '
                  'criterion probabilities')
@@ -261,12 +276,18 @@ def train(args):
             % (sum(r.shape[0] for r, _ in rows), '' if args.ignore_dontcare else ' (not used)', sum(b.shape[0] for _, b in rows),
                '/'.join(args.ignore_classes) or 'no class', args.min_gt_points))
     torch.manual_seed(0)
-    model = MVXNet().to(device)
+    model = (MVXNet(direction=True) if args.direction else MVXNet()).to(device)
     if args.loss == 'focal':
         from modules.voxelnet.FocalLoss import FocalLoss
-        criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight)
+        if args.direction:
+            criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight, direction=True,
+                                  dir_weight=args.dir_weight, dir_offset=args.dir_offset)
+        else:
+            criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight)
         say('criterion: FocalLoss(alpha=%g, gamma=%g, cls_weight=%g, reg_weight=%g)'
             % (criterion.alpha, criterion.gamma, criterion.cls_weight, criterion.reg_weight))
+        if args.direction:
+            say('direction head: dir_weight=%g, dir_offset=%g, sine angle loss' % (criterion.dir_weight, criterion.dir_offset))
     else:
         criterion = VoxelLoss()
         say('criterion: VoxelLoss(a=%g, b=%g)' % (criterion.a, criterion.b))
@@ -322,8 +343,8 @@ def train(args):
     for epoch in range(args.numepochs):
         random.Random(epoch + args.lastiter).shuffle(trainDataSet)
         mine = trainDataSet
-        clsLossSum = regLossSum = 0.0
-        clsCnt = regCnt = 0
+        clsLossSum = regLossSum = dirLossSum = 0.0
+        clsCnt = regCnt = dirCnt = 0
         if args.mode == 'module':
             for i, data in enumerate(mine):
                 voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo, geo, assigner)
@@ -401,7 +422,7 @@ def train(args):
                                                   # the step it has just enqueued
 
             def account(p):
-                nonlocal clsLossSum, clsCnt, regLossSum, regCnt
+                nonlocal clsLossSum, clsCnt, regLossSum, regCnt, dirLossSum, dirCnt
                 if p is None:
                     return
                 pl.read_losses(p)
@@ -410,6 +431,8 @@ def train(args):
                 clsCnt += len(p['cls'])
                 regLossSum += sum(p['reg'])
                 regCnt += len(p['reg'])
+                dirLossSum += sum(p.get('dir', ()))
+                dirCnt += len(p.get('dir', ()))
 
             t_epoch = time.perf_counter()
             frames_epoch = 0
@@ -437,8 +460,9 @@ def train(args):
                 pending = out
                 frames_epoch += hi - lo
                 steps_done += 1
-                say('Epoch%d %d/%d  average classification loss %.6f, average regression loss %.6f'
-                    % (epoch + args.lastiter + 1, hi, len(trainDataSet), clsLossSum / max(1, clsCnt), regLossSum / max(1, regCnt)))
+                say('Epoch%d %d/%d  average classification loss %.6f, average regression loss %.6f%s'
+                    % (epoch + args.lastiter + 1, hi, len(trainDataSet), clsLossSum / max(1, clsCnt), regLossSum / max(1, regCnt),
+                       ', average direction loss %.6f' % (dirLossSum / max(1, dirCnt)) if args.direction else ''))
                 if args.steps and steps_done >= args.steps:
                     break
             account(pending)

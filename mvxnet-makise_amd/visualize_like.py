@@ -9,6 +9,7 @@ Detections come from KITTI result files (``--results DIR``, as detect_like.py wr
     python visualize_like.py /tmp/kitti --synthetic 3          # a synthetic tree, ground truth only
 """
 import argparse
+import math
 import os
 import sys
 
@@ -25,6 +26,8 @@ def parse_args(argv=None):
     ap.add_argument('dataroot')
     ap.add_argument('--results', default=None, help='directory of KITTI result files (<name>.txt) to draw as detections')
     ap.add_argument('--checkpoint', default=None, help='state dict written by train_like.py: detections from running the model')
+    ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
+                    help='a checkpoint of train_like.py --direction (it holds backbone.rpn.dir.weight): the --dir-offset it was trained with')
     ap.add_argument('--split', default='train', help='ImageSets/<split>.txt')
     ap.add_argument('--out', default=None, help='picture directory (default <dataroot>/pictures)')
     ap.add_argument('--view', choices=['bev', 'camera', 'both'], default='both')
@@ -63,13 +66,16 @@ def _model_detector(args, device, data, names):
     anchor_bevs = bbox3d2bev(anchors.reshape(anchors.shape[:2] + (-1, 7))).to(device).contiguous()
     anchors = anchors.to(device)
     torch.manual_seed(0)
-    model = MVXNet().to(device)
-    model.load_state_dict(torch.load(args.checkpoint, map_location=device))
+    state = torch.load(args.checkpoint, map_location=device)
+    direction = 'backbone.rpn.dir.weight' in state                            # written by train_like.py --direction
+    model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
+    model.load_state_dict(state)
+    kw = dict(dir_offset=args.dir_offset) if direction else {}
     cap = max(d[0].shape[0] for d in data)
 
     def run(group, gnames):
         batch, _ = pl.batch_from_dataset(group, gnames, device, anchor_bevs, fpn_maps_for, cap_points=cap)
-        return batch, detect_frame_set(model, batch, anchors, cfg.imsize)
+        return batch, detect_frame_set(model, batch, anchors, cfg.imsize, **kw)
     return run
 
 
