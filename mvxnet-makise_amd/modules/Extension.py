@@ -302,6 +302,29 @@ def stream():
     return ctypes.c_void_p(raw_stream())
 
 
+_Tensor = torch.Tensor
+# every entry point that launches on a stream and returns a status -> (foreign function, positions of its pointer parameters:
+# only there can a tensor stand); built once, so that a launch costs one lookup
+_LAUNCHES = {name: (getattr(lib, name), tuple(i for i, t in enumerate(args[:-1]) if t is _p))
+             for name, (res, args) in PROTOTYPES.items() if res is _i32 and args and args[-1] is _p}
+
+
+def call(name, *args):
+    """Launch entry point ``name`` of the library on the current stream: a tensor goes as ``ptr(t)``, everything else (None,
+    numbers, ctypes values) as it is, ``stream()`` last; a non-zero status raises through ``check``.  ptr's accepting path and
+    stream() are written out here, this being the per-launch host path; ptr words every refusal, and
+    tests/test_abi_call_gpu.py holds both to the functions."""
+    fn, pointers = _LAUNCHES[name]
+    argv = list(args)
+    for i in pointers:
+        a = argv[i]
+        if isinstance(a, _Tensor):
+            argv[i] = _p(a.data_ptr()) if a.is_cuda and a.is_contiguous() else ptr(a)
+    status = fn(*argv, _p(_raw_stream(_cur_device())))
+    if status != 0:
+        check(status, name)
+
+
 def device():
     if not torch.cuda.is_available():
         raise MvxHipError('no GPU visible: the MVXNet hot path has no CPU fallback')

@@ -52,7 +52,7 @@ def new_amax(device):
 def tensor_amax(t):
     """Measure max |t| on the device (one pass over t) and tag t with it."""
     am = torch.empty((1,), dtype=torch.float32, device=t.device)
-    X.check(X.lib.mvx_tensor_amax(X.ptr(t), t.numel(), X.ptr(am), 0, X.stream()), 'mvx_tensor_amax')
+    X.call('mvx_tensor_amax', t, t.numel(), am, 0)
     return tag_amax(t, am)
 
 
@@ -155,8 +155,7 @@ def guard_fp16_weight(w):
         seen[tuple(w.shape)] = tag
         wc = w.detach()
         wc = wc if wc.is_contiguous() else wc.contiguous()
-        X.check(X.lib.mvx_split_f16_weight_check(X.ptr(wc), wc.numel(), X.ptr(fp16_weight_status(w.device)), X.stream()),
-                'mvx_split_f16_weight_check')
+        X.call('mvx_split_f16_weight_check', wc, wc.numel(), fp16_weight_status(w.device))
 
 
 def raise_on_status(word):
@@ -566,8 +565,7 @@ def scatter_voxels(feat, coords, dhw, grid=None, zero=True, want_occupancy=False
     if want_occupancy:
         occ = torch.empty((D, -(-H // th), -(-W // tw)), dtype=torch.int32, device=feat.device)
         bits = torch.empty((D, H, -(-W // 32)), dtype=torch.int32, device=feat.device)
-    X.check(X.lib.mvx_scatter_voxels(X.ptr(feat), X.ptr(coords), X.ptr(grid), V, C, D, H, W, int(zero),
-                                     X.ptr(status), X.ptr(occ), th, tw, X.ptr(bits), X.stream()), 'mvx_scatter_voxels')
+    X.call('mvx_scatter_voxels', feat, coords, grid, V, C, D, H, W, int(zero), status, occ, th, tw, bits)
     if want_occupancy:
         return grid, status, (occ, bits)
     return grid, status
@@ -576,8 +574,7 @@ def scatter_voxels(feat, coords, dhw, grid=None, zero=True, want_occupancy=False
 def gather_voxels(grid, coords, V):
     D, H, W, C = grid.shape
     feat = torch.empty((V, C), dtype=torch.float32, device=grid.device)
-    X.check(X.lib.mvx_gather_voxels(X.ptr(grid), X.ptr(coords), X.ptr(feat), V, C, D, H, W, X.stream()),
-            'mvx_gather_voxels')
+    X.call('mvx_gather_voxels', grid, coords, feat, V, C, D, H, W)
     return feat
 
 
@@ -587,7 +584,7 @@ def cl_to_bev(cl, F=None):
     D = FD // (F or 1)
     bev = torch.empty(_per_frame(F, C * D, H, W), dtype=torch.float32, device=cl.device)
     with _timed_bytes('cl_bev_transpose', 2 * cl.numel() * 4):
-        X.check(X.lib.mvx_cl_to_bev_frames(X.ptr(cl), X.ptr(bev), D, H, W, C, 0, F or 1, X.stream()), 'mvx_cl_to_bev_frames')
+        X.call('mvx_cl_to_bev_frames', cl, bev, D, H, W, C, 0, F or 1)
     return bev
 
 
@@ -597,7 +594,7 @@ def bev_to_cl(bev, D):
     CD, H, W = bev.shape[-3:]
     C = CD // D
     cl = torch.empty((F * D, H, W, C), dtype=torch.float32, device=bev.device)
-    X.check(X.lib.mvx_cl_to_bev_frames(X.ptr(cl), X.ptr(bev), D, H, W, C, 1, F, X.stream()), 'mvx_cl_to_bev_frames')
+    X.call('mvx_cl_to_bev_frames', cl, bev, D, H, W, C, 1, F)
     return cl
 
 
@@ -606,7 +603,7 @@ def bev_to_cl_broadcast(bev, D, F):
     CD, H, W = bev.shape[-3:]
     C = CD // D
     cl = torch.empty((F * D, H, W, C), dtype=torch.float32, device=bev.device)
-    X.check(X.lib.mvx_bev_to_cl_broadcast(X.ptr(bev), X.ptr(cl), D, H, W, C, F, X.stream()), 'mvx_bev_to_cl_broadcast')
+    X.call('mvx_bev_to_cl_broadcast', bev, cl, D, H, W, C, F)
     return cl
 
 
@@ -616,14 +613,14 @@ def bev_to_cl_broadcast(bev, D, F):
 def row_stats(y2d):
     rows, C = y2d.shape
     stats = torch.empty((STATS_REPLICAS, 2, C), dtype=torch.float64, device=y2d.device)
-    X.check(X.lib.mvx_row_stats(X.ptr(y2d), X.ptr(stats), rows, C, X.stream()), 'mvx_row_stats')
+    X.call('mvx_row_stats', y2d, stats, rows, C)
     return stats
 
 
 def row_stats_frames(y, C, F):
     """BatchNorm sums f64 (F,R,2,C) of a frame set: y holds its rows of C channels frame after frame."""
     stats = torch.empty((F, STATS_REPLICAS, 2, C), dtype=torch.float64, device=y.device)
-    X.check(X.lib.mvx_row_stats_frames(X.ptr(y), X.ptr(stats), y.numel() // C, C, F, X.stream()), 'mvx_row_stats_frames')
+    X.call('mvx_row_stats_frames', y, stats, y.numel() // C, C, F)
     return stats
 
 
@@ -631,8 +628,7 @@ def bn_finalize(stats, count, eps, F=None):
     """(mean, 1/sqrt(var + eps)) f32 (2,C) from the sums of one frame; (F,2,C) from those of a frame set."""
     C = stats.shape[-1]
     mi = torch.empty(_per_frame(F, 2, C), dtype=torch.float32, device=stats.device)
-    X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(count), float(eps), X.ptr(mi), C, F or 1, X.stream()),
-            'mvx_bn_finalize_frames')
+    X.call('mvx_bn_finalize_frames', stats, float(count), float(eps), mi, C, F or 1)
     return mi
 
 
@@ -647,31 +643,27 @@ def bn_apply(y, mi, out=None, desc=None, kind=X.ROWS_SINGLE, timed=True):
     if out is None:
         out = torch.empty_like(y)
     with _timed_bytes('bn_apply', 2 * y.numel() * 4) if timed else _Inline():
-        X.check(X.lib.mvx_bn_apply_frames(X.ptr(y), X.ptr(mi), X.ptr(out), rows, C, _desc_ref(desc), kind, X.stream()),
-                'mvx_bn_apply_frames')
+        X.call('mvx_bn_apply_frames', y, mi, out, rows, C, _desc_ref(desc), kind)
     return out
 
 
 def bn_apply_strided(x, mi, buf, rows, C, ld, off, F, reverse=False):
     """x (rows,C) normalised per frame into columns off..off+C of the (rows,ld) buffer ``buf``; ``reverse``: that column slice of
     buf copied out into x (mi unused: the gradient of the concat)."""
-    X.check(X.lib.mvx_bn_apply_strided_frames(X.ptr(x), X.ptr(mi), X.ptr(buf), rows, C, ld, off, F, int(reverse), X.stream()),
-            'mvx_bn_apply_strided_frames')
+    X.call('mvx_bn_apply_strided_frames', x, mi, buf, rows, C, ld, off, F, int(reverse))
 
 
 def d2s_bn_apply(t, mi, buf, F, h, w, s, cout, ld, off, reverse=False):
     """t (F*h*w, s*s*cout) normalised per frame and pixel-shuffled into columns off..off+cout of the (F*h*s*w*s, ld) buffer
     ``buf``; ``reverse``: the inverse shuffle of that slice of buf into t (mi unused)."""
-    X.check(X.lib.mvx_d2s_bn_apply_frames(X.ptr(t), X.ptr(mi), X.ptr(buf), F, h, w, s, cout, ld, off, int(reverse), X.stream()),
-            'mvx_d2s_bn_apply_frames')
+    X.call('mvx_d2s_bn_apply_frames', t, mi, buf, F, h, w, s, cout, ld, off, int(reverse))
 
 
 def space_to_depth(x, F, planes, h, w, C, reverse=False):
     """[F*planes][h][w][C] -> [F][h/2][w/2][4*planes*C] (2x2 parity blocks side by side); ``reverse``: the way back."""
     shape = (F * planes, h, w, C) if reverse else (F, h // 2, w // 2, 4 * planes * C)
     out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    X.check(X.lib.mvx_space_to_depth_frames(X.ptr(x), X.ptr(out), F, planes, h, w, C, int(reverse), X.stream()),
-            'mvx_space_to_depth_frames')
+    X.call('mvx_space_to_depth_frames', x, out, F, planes, h, w, C, int(reverse))
     return out
 
 
@@ -691,9 +683,8 @@ def bn_relu_backward(dyhat, y, mi, count, want_dbias=True, dz=None, row_w=None, 
     scratch, fz = _bn_backward_scratch(C, desc, y.device)
     amax = new_amax(y.device)
     with _timed_bytes('bn_relu_backward', 5 * y.numel() * 4) if timed else _Inline():      # reduce reads 2 tensors, apply reads 2 + writes 1
-        X.check(X.lib.mvx_bn_relu_backward_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), float(count), X.ptr(dz),
-                                                  X.ptr(dbias), X.ptr(scratch), X.ptr(row_w), rows, C, flags | fz, _desc_ref(desc),
-                                                  kind, X.ptr(amax), X.stream()), 'mvx_bn_relu_backward_frames')
+        X.call('mvx_bn_relu_backward_frames', dyhat, y, mi, float(count), dz, dbias, scratch, row_w, rows, C, flags | fz,
+               _desc_ref(desc), kind, amax)
     tag_amax(dz, amax)                                   # max |dz|: the range the fp16x3 kernels scale dz by
     return dz, (None if dbias_out is not None else dbias)
 
@@ -710,9 +701,8 @@ def bn_relu_backward_planes(dyhat, y, mi, dbias_out, row_w, desc, kind):
     dzp = torch.empty((3, rows, C), dtype=torch.int16, device=y.device)
     scratch, fz = _bn_backward_scratch(C, desc, y.device)
     with _timed_bytes('bn_relu_backward', 5.5 * y.numel() * 4):
-        X.check(X.lib.mvx_bn_relu_backward_planes_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dzp), X.ptr(dbias_out),
-                                                         X.ptr(scratch), X.ptr(row_w), rows, C, FLAG_ACCUMULATE | fz,
-                                                         desc.ref(), kind, None, X.stream()), 'mvx_bn_relu_backward_planes_frames')
+        X.call('mvx_bn_relu_backward_planes_frames', dyhat, y, mi, 1.0, dzp, dbias_out, scratch, row_w, rows, C,
+               FLAG_ACCUMULATE | fz, desc.ref(), kind, None)
     return dzp
 
 
@@ -728,10 +718,8 @@ def bn_relu_backward_planes_parts(dyhat, y, mi, dbias_out, row_w, desc, kind, np
     rng = (ctypes.c_int64 * 2)()
     for part in range(nparts):
         with _timed_bytes('bn_relu_backward', 5.5 * y.numel() * 4 / nparts):
-            X.check(X.lib.mvx_bn_relu_backward_planes_part_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), 1.0, X.ptr(dzp),
-                                                                  X.ptr(dbias_out), X.ptr(scratch), X.ptr(row_w), rows, C,
-                                                                  FLAG_ACCUMULATE | fz, desc.ref(), kind, part, nparts, rng,
-                                                                  X.stream()), 'mvx_bn_relu_backward_planes_part_frames')
+            X.call('mvx_bn_relu_backward_planes_part_frames', dyhat, y, mi, 1.0, dzp, dbias_out, scratch, row_w, rows, C,
+                   FLAG_ACCUMULATE | fz, desc.ref(), kind, part, nparts, rng)
         if rng[1] > rng[0]:
             yield dzp, int(rng[0]), int(rng[1])
 
@@ -752,12 +740,10 @@ def conv3d_pack(weight, for_dgrad, split=False):
         if int(split) == 4:
             guard_fp16_weight(weight)
         wpk = torch.empty((X.lib.mvx_conv3d_packed_weight_bytes_split(cout, cin, sf) // 2,), dtype=torch.int16, device=weight.device)
-        X.check(X.lib.mvx_conv3d_pack_weights_split(X.ptr(weight.contiguous()), X.ptr(wpk), cout, cin, int(for_dgrad), sf, X.stream()),
-                'mvx_conv3d_pack_weights_split')
+        X.call('mvx_conv3d_pack_weights_split', weight.contiguous(), wpk, cout, cin, int(for_dgrad), sf)
         return wpk
     wpk = torch.empty((27 * cout * cin,), dtype=torch.float32, device=weight.device)
-    X.check(X.lib.mvx_conv3d_pack_weights(X.ptr(weight.contiguous()), X.ptr(wpk), cout, cin, int(for_dgrad) | (2 if two_d else 0),
-                                          X.stream()), 'mvx_conv3d_pack_weights')
+    X.call('mvx_conv3d_pack_weights', weight.contiguous(), wpk, cout, cin, int(for_dgrad) | (2 if two_d else 0))
     return wpk
 
 
@@ -774,14 +760,10 @@ def conv3d_forward(x, wpk, bias, cout, sd, pd, relu=True, want_stats=True, split
     flags = (FLAG_RELU if relu else 0) | fz | split_flags(split)
     if split:
         with _Timed('conv3d_gather_split', conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):
-            X.check(X.lib.mvx_conv3d_forward_split(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
-                                                   H, W, cin, cout, sd, pd, flags, X.stream()),
-                    'mvx_conv3d_forward_split')
+            X.call('mvx_conv3d_forward_split', x, wpk, bias, out, stats, din, dout, H, W, cin, cout, sd, pd, flags)
         return out, stats
     with _Timed('conv3d_gather', conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):
-        X.check(X.lib.mvx_conv3d_forward(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats),
-                                         din, dout, H, W, cin, cout, sd, pd, flags, X.ptr(_work_counter(x.device)),
-                                         X.stream()), 'mvx_conv3d_forward')
+        X.call('mvx_conv3d_forward', x, wpk, bias, out, stats, din, dout, H, W, cin, cout, sd, pd, flags, _work_counter(x.device))
     return out, stats
 
 
@@ -791,12 +773,10 @@ def conv3d_dgrad(dz, wpk_d, din, cin, sd, pd, split=False):
     if split:
         with _Timed('conv3d_gather_split', conv_flops(din, dout, H, W, cout, cin, sd, pd, True) if KERNEL_TIMERS is not None else 0):
             bind_amax(split, dz)
-            X.check(X.lib.mvx_conv3d_dgrad_split(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd, pd,
-                                                 split_flags(split), X.stream()), 'mvx_conv3d_dgrad_split')
+            X.call('mvx_conv3d_dgrad_split', dz, wpk_d, dx, din, dout, H, W, cin, cout, sd, pd, split_flags(split))
         return dx
     with _Timed('conv3d_gather', conv_flops(din, dout, H, W, cout, cin, sd, pd, True) if KERNEL_TIMERS is not None else 0):
-        X.check(X.lib.mvx_conv3d_dgrad(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd, pd,
-                                       X.ptr(_work_counter(dz.device)), X.stream()), 'mvx_conv3d_dgrad')
+        X.call('mvx_conv3d_dgrad', dz, wpk_d, dx, din, dout, H, W, cin, cout, sd, pd, _work_counter(dz.device))
     return dx
 
 
@@ -822,8 +802,7 @@ def conv3d_wgrad(x, dz, sd, pd, split=False, accumulate_into=None, two_d=False):
         ws = workspace(nbytes, x.device, 'wgrad_side' if isinstance(scope, _SideStream) else 'wgrad')
         with _Timed('conv3d_wgrad', conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):
             bind_amax(split, x, dz)
-            X.check(X.lib.mvx_conv3d_wgrad(X.ptr(x), X.ptr(dz), X.ptr(dw), din, dout, H, W, cin, cout, sd, pd, flags, X.ptr(ws),
-                                           ws.numel(), X.stream()), 'mvx_conv3d_wgrad')
+            X.call('mvx_conv3d_wgrad', x, dz, dw, din, dout, H, W, cin, cout, sd, pd, flags, ws, ws.numel())
     return None if accumulate_into is not None else dw
 
 
@@ -851,16 +830,13 @@ def conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, split=False):
     mi = torch.empty((F, 2, cout), dtype=torch.float32, device=dev)
     with _Timed('rpn_conv', _conv2d_flops(F, h, w, cin, cout, flags)):
         if split:                              # split arithmetic (bf16x3 / bf16x6), same window / structural-zero skipping
-            X.check(X.lib.mvx_conv2d_forward_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), X.ptr(stats), h, w, cin, cout,
-                                                          FLAG_RELU | fz | flags | split_flags(split), F, X.stream()),
-                    'mvx_conv2d_forward_split_frames')
+            X.call('mvx_conv2d_forward_split_frames', x, wpk, bias, y, stats, h, w, cin, cout,
+                   FLAG_RELU | fz | flags | split_flags(split), F)
         else:
-            X.check(X.lib.mvx_conv2d_forward_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), X.ptr(stats), h, w, cin, cout,
-                                                    FLAG_RELU | fz | flags, X.ptr(fin), float(eps), X.ptr(mi),
-                                                    X.ptr(_work_counter(dev)), F, X.stream()), 'mvx_conv2d_forward_frames')
+            X.call('mvx_conv2d_forward_frames', x, wpk, bias, y, stats, h, w, cin, cout, FLAG_RELU | fz | flags, fin, float(eps),
+                   mi, _work_counter(dev), F)
     if split:
-        X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), float(h * w), float(eps), X.ptr(mi), cout, F, X.stream()),
-                'mvx_bn_finalize_frames')
+        X.call('mvx_bn_finalize_frames', stats, float(h * w), float(eps), mi, cout, F)
     return y, mi
 
 
@@ -869,11 +845,9 @@ def conv2d_dgrad(dz, wpk_d, F, h, w, cin, cout, flags, split=False):
     with _Timed('rpn_conv', _conv2d_flops(F, h, w, cin, cout, flags)):
         if split:
             bind_amax(split, dz)
-            X.check(X.lib.mvx_conv2d_dgrad_split_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), h, w, cin, cout,
-                                                        flags | split_flags(split), F, X.stream()), 'mvx_conv2d_dgrad_split_frames')
+            X.call('mvx_conv2d_dgrad_split_frames', dz, wpk_d, dx, h, w, cin, cout, flags | split_flags(split), F)
         else:
-            X.check(X.lib.mvx_conv2d_dgrad_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), h, w, cin, cout, flags,
-                                                  X.ptr(_work_counter(dz.device)), F, X.stream()), 'mvx_conv2d_dgrad_frames')
+            X.call('mvx_conv2d_dgrad_frames', dz, wpk_d, dx, h, w, cin, cout, flags, _work_counter(dz.device), F)
     return dx
 
 
@@ -887,9 +861,8 @@ def conv2d_wgrad(x, dz, F, h, w, cin, cout, flags, accumulate_into=None, split=F
     with _SideStream(x, dz, dw), _Timed('rpn_wgrad', _conv2d_flops(F, h, w, cin, cout, flags)):
         ws = workspace(nbytes, dev, 'rpn_wgrad_side')
         bind_amax(split, None, dz)
-        X.check(X.lib.mvx_conv2d_wgrad_frames(X.ptr(x), X.ptr(dz), X.ptr(dw), h, w, cin, cout,
-                                              flags | sp | (FLAG_ACCUMULATE if accumulate_into is not None else 0), X.ptr(ws),
-                                              ws.numel(), F, X.stream()), 'mvx_conv2d_wgrad_frames')
+        X.call('mvx_conv2d_wgrad_frames', x, dz, dw, h, w, cin, cout,
+               flags | sp | (FLAG_ACCUMULATE if accumulate_into is not None else 0), ws, ws.numel(), F)
     return dw
 
 
@@ -936,9 +909,8 @@ def activity_dilate(src, src_is_index, din, H, W, sd, pd, mark_border, want_tile
     mask = torch.empty((F * dout, H, W), dtype=torch.uint8, device=src.device)
     hflag = torch.empty((F * dout, n_tiles(H, W)), dtype=torch.int32, device=src.device)
     tflag = torch.empty_like(hflag) if want_tile_flags else None
-    X.check(X.lib.mvx_activity_dilate_frames(X.ptr(src), 1 if src_is_index else 0, din, dout, H, W, sd, pd,
-                                             1 if mark_border else 0, X.ptr(mask), X.ptr(hflag), X.ptr(tflag), F, X.stream()),
-            'mvx_activity_dilate_frames')
+    X.call('mvx_activity_dilate_frames', src, 1 if src_is_index else 0, din, dout, H, W, sd, pd, 1 if mark_border else 0, mask,
+           hflag, tflag, F)
     return (mask, hflag, tflag) if want_tile_flags else (mask, hflag)
 
 
@@ -946,8 +918,7 @@ def conv3d_background(w, c_in, din, sd, pd):
     cout, cin = w.shape[0], w.shape[1]
     dout = conv_out_depth(din, sd, pd)
     bg_pre = torch.empty((dout, cout), dtype=torch.float32, device=w.device)
-    X.check(X.lib.mvx_conv3d_background(X.ptr(w.contiguous()), X.ptr(c_in), din, dout, cin, cout, sd, pd, X.ptr(bg_pre),
-                                        X.stream()), 'mvx_conv3d_background')
+    X.call('mvx_conv3d_background', w.contiguous(), c_in, din, dout, cin, cout, sd, pd, bg_pre)
     return bg_pre
 
 
@@ -957,16 +928,14 @@ def conv3d_background_taps(w, c_in, din, sd, pd, F=1):
     cout, cin = w.shape[0], w.shape[1]
     dout = conv_out_depth(din, sd, pd)
     bg_all = torch.empty((F * dout * 13, cout), dtype=torch.float32, device=w.device)
-    X.check(X.lib.mvx_conv3d_background_taps_frames(X.ptr(w), X.ptr(c_in), din, dout, cin, cout, sd, pd, X.ptr(bg_all), F,
-                                                    X.stream()), 'mvx_conv3d_background_taps_frames')
+    X.call('mvx_conv3d_background_taps_frames', w, c_in, din, dout, cin, cout, sd, pd, bg_all, F)
     return bg_all
 
 
 def bn_background(bg_pre, bias, mi, planes, channels, relu=True, want_y=False, F=1):
     c_out = torch.empty((F * planes, channels), dtype=torch.float32, device=mi.device)
     y_bg = torch.empty_like(c_out) if want_y else None
-    X.check(X.lib.mvx_bn_background_frames(X.ptr(bg_pre), X.ptr(bias), X.ptr(mi), planes, channels, FLAG_RELU if relu else 0,
-                                           X.ptr(y_bg), X.ptr(c_out), F, X.stream()), 'mvx_bn_background_frames')
+    X.call('mvx_bn_background_frames', bg_pre, bias, mi, planes, channels, FLAG_RELU if relu else 0, y_bg, c_out, F)
     return (c_out, y_bg) if want_y else c_out
 
 
@@ -982,11 +951,9 @@ def bn_apply_tiles(y, mi, c_bg, tflag, F=1, read=None, out=None):
               * (128 * C * 4)) if KERNEL_TIMERS is not None else 0
     with _timed_bytes('bn_apply', nbytes):
         if read is not None:
-            X.check(X.lib.mvx_bn_apply_tiles_read_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(read), X.ptr(out),
-                                                         FD // F, H, W, C, F, X.stream()), 'mvx_bn_apply_tiles_read_frames')
+            X.call('mvx_bn_apply_tiles_read_frames', y, mi, c_bg, tflag, read, out, FD // F, H, W, C, F)
         else:
-            X.check(X.lib.mvx_bn_apply_tiles_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(out), FD // F, H, W, C,
-                                                    F, X.stream()), 'mvx_bn_apply_tiles_frames')
+            X.call('mvx_bn_apply_tiles_frames', y, mi, c_bg, tflag, out, FD // F, H, W, C, F)
     return out
 
 
@@ -997,8 +964,7 @@ def bn_apply_tiles_bev(y, mi, c_bg, tflag, F=1):
     bev = torch.empty((F, C * D, H, W), dtype=torch.float32, device=y.device)
     nbytes = (lambda: (tflag.ne(0).sum() + tflag.numel()) * (128 * C * 4)) if KERNEL_TIMERS is not None else 0
     with _timed_bytes('bn_apply', nbytes):
-        X.check(X.lib.mvx_bn_apply_tiles_bev_frames(X.ptr(y), X.ptr(mi), X.ptr(c_bg), X.ptr(tflag), X.ptr(bev), D, H, W, C,
-                                                    F, X.stream()), 'mvx_bn_apply_tiles_bev_frames')
+        X.call('mvx_bn_apply_tiles_bev_frames', y, mi, c_bg, tflag, bev, D, H, W, C, F)
     return bev
 
 
@@ -1008,16 +974,14 @@ def plane_tap_sums(dz, tile_flags=None, inactive_sums=None):
     D, H, W, C = dz.shape
     T = torch.empty((D, 9, C), dtype=torch.float32, device=dz.device)
     ws = workspace(X.lib.mvx_plane_tap_sums_workspace_bytes(D, C), dz.device, 'tap_sums')
-    X.check(X.lib.mvx_plane_tap_sums(X.ptr(dz), D, H, W, C, X.ptr(tile_flags), X.ptr(inactive_sums), X.ptr(T), X.ptr(ws),
-                                     ws.numel(), X.stream()), 'mvx_plane_tap_sums')
+    X.call('mvx_plane_tap_sums', dz, D, H, W, C, tile_flags, inactive_sums, T, ws, ws.numel())
     return T
 
 
 def tile_dilate_flags(in_tflag, self_tflag, din, H, W, sd, pd, F=1):
     dout = conv_out_depth(din, sd, pd)
     out = torch.empty((F * dout, n_tiles(H, W)), dtype=torch.int32, device=in_tflag.device)
-    X.check(X.lib.mvx_tile_dilate_flags_frames(X.ptr(in_tflag), X.ptr(self_tflag), din, dout, H, W, sd, pd, X.ptr(out), F,
-                                               X.stream()), 'mvx_tile_dilate_flags_frames')
+    X.call('mvx_tile_dilate_flags_frames', in_tflag, self_tflag, din, dout, H, W, sd, pd, out, F)
     return out
 
 
@@ -1026,16 +990,14 @@ def tile_read_flags(hflag, din, H, W, sd, pd, F=1):
     neighbourhoods of the output tiles it computes), from the input's halo flags i32 (F*din, tiles)."""
     dout = conv_out_depth(din, sd, pd)
     out = torch.empty_like(hflag)
-    X.check(X.lib.mvx_tile_read_flags_frames(X.ptr(hflag), din, dout, H, W, sd, pd, X.ptr(out), F, X.stream()),
-            'mvx_tile_read_flags_frames')
+    X.call('mvx_tile_read_flags_frames', hflag, din, dout, H, W, sd, pd, out, F)
     return out
 
 
 def conv3d_input_grad_sums(w, T, din, sd, pd, F=1):
     cout, cin = w.shape[0], w.shape[1]
     A = torch.empty((F * din, cin), dtype=torch.float32, device=w.device)
-    X.check(X.lib.mvx_conv3d_input_grad_sums_frames(X.ptr(w.contiguous()), X.ptr(T), din, T.shape[0] // F, cin, cout, sd, pd,
-                                                    X.ptr(A), F, X.stream()), 'mvx_conv3d_input_grad_sums_frames')
+    X.call('mvx_conv3d_input_grad_sums_frames', w.contiguous(), T, din, T.shape[0] // F, cin, cout, sd, pd, A, F)
     return A
 
 
@@ -1048,13 +1010,11 @@ def conv3d_dgrad_tiles(dz, wpk_d, din, cin, sd, pd, tflag, split=False, F=1):
     with _Timed('conv3d_gather_tiles', F * conv_flops(din, dout, H, W, cout, cin, sd, pd, True) if KERNEL_TIMERS is not None else 0):   # dense-equivalent
         if split:
             bind_amax(split, dz)
-            X.check(X.lib.mvx_conv3d_dgrad_tiles_split_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd,
-                                                              pd, split_flags(split), X.ptr(tflag), X.ptr(counter), F, X.stream()),
-                    'mvx_conv3d_dgrad_tiles_split_frames')
+            X.call('mvx_conv3d_dgrad_tiles_split_frames', dz, wpk_d, dx, din, dout, H, W, cin, cout, sd, pd, split_flags(split),
+                   tflag, counter, F)
         else:
-            X.check(X.lib.mvx_conv3d_dgrad_tiles_frames(X.ptr(dz), X.ptr(wpk_d), X.ptr(dx), din, dout, H, W, cin, cout, sd, pd,
-                                                        X.ptr(tflag), X.ptr(counter), X.ptr(_work_counter(dz.device)), F,
-                                                        X.stream()), 'mvx_conv3d_dgrad_tiles_frames')
+            X.call('mvx_conv3d_dgrad_tiles_frames', dz, wpk_d, dx, din, dout, H, W, cin, cout, sd, pd, tflag, counter,
+                   _work_counter(dz.device), F)
     return dx
 
 
@@ -1074,10 +1034,8 @@ def bn_relu_backward_tiles(dyhat, y, mi, bg, plane_grad_sums, dbias_out=None, wa
     bflag = bg.bflag
     nbytes = (lambda: bflag.ne(0).sum() * (128 * C * 4 * 5)) if KERNEL_TIMERS is not None else 0
     with _timed_bytes('bn_relu_backward_tiles', nbytes):
-        X.check(X.lib.mvx_bn_relu_backward_tiles_frames(X.ptr(dyhat), X.ptr(y), X.ptr(mi), X.ptr(bg.c), X.ptr(bg.y_bg),
-                                                        X.ptr(plane_grad_sums), X.ptr(bflag), FD // F, H, W, C, X.ptr(dz),
-                                                        X.ptr(db), X.ptr(inact), X.ptr(amax), flags, X.ptr(ws), ws.numel(), F,
-                                                        X.stream()), 'mvx_bn_relu_backward_tiles_frames')
+        X.call('mvx_bn_relu_backward_tiles_frames', dyhat, y, mi, bg.c, bg.y_bg, plane_grad_sums, bflag, FD // F, H, W, C, dz, db,
+               inact, amax, flags, ws, ws.numel(), F)
     tag_amax(dz, amax)
     db = None if dbias_out is not None else db
     return (dz, db, inact) if want_inactive_sums else (dz, db)
@@ -1105,18 +1063,14 @@ def conv3d_forward_bg(x, wpk, bias, cout, sd, pd, bg_in, out_mask, bg_pre, relu=
     counter = _exec_stages(x.device)
     with _Timed('conv3d_gather_bg', nf * conv_flops(dout, din, H, W, cin, cout, sd, pd) if KERNEL_TIMERS is not None else 0):   # dense-equivalent
         if split:
-            X.check(X.lib.mvx_conv3d_forward_bg_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
-                                                             H, W, cin, cout, sd, pd, flags, X.ptr(bg_in.hflag), X.ptr(out_mask),
-                                                             X.ptr(bg_pre), 1, X.ptr(counter), nf, X.stream()),
-                    'mvx_conv3d_forward_bg_split_frames')
+            X.call('mvx_conv3d_forward_bg_split_frames', x, wpk, bias, out, stats, din, dout, H, W, cin, cout, sd, pd, flags,
+                   bg_in.hflag, out_mask, bg_pre, 1, counter, nf)
         else:
-            X.check(X.lib.mvx_conv3d_forward_bg_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout, H, W,
-                                                       cin, cout, sd, pd, flags, X.ptr(bg_in.hflag), X.ptr(out_mask), X.ptr(bg_pre),
-                                                       1, X.ptr(counter), X.ptr(fin), npos, float(finalize_eps or 0.0), X.ptr(mi),
-                                                       X.ptr(_work_counter(x.device)), nf, X.stream()), 'mvx_conv3d_forward_bg_frames')
+            X.call('mvx_conv3d_forward_bg_frames', x, wpk, bias, out, stats, din, dout, H, W, cin, cout, sd, pd, flags,
+                   bg_in.hflag, out_mask, bg_pre, 1, counter, fin, npos, float(finalize_eps or 0.0), mi, _work_counter(x.device),
+                   nf)
     if split and mi is not None:
-        X.check(X.lib.mvx_bn_finalize_frames(X.ptr(stats), npos, float(finalize_eps), X.ptr(mi), cout, nf, X.stream()),
-                'mvx_bn_finalize_frames')
+        X.call('mvx_bn_finalize_frames', stats, npos, float(finalize_eps), mi, cout, nf)
     return (out, mi) if mi is not None else (out, stats)
 
 
@@ -1140,9 +1094,8 @@ def conv3d_wgrad_bg(x, dz, sd, pd, bg_in, tap_sums=None, accumulate_into=None, s
         ws = workspace(nbytes, x.device, 'wgrad_bg_side' if isinstance(scope, _SideStream) else 'wgrad_bg')
         with _Timed('conv3d_wgrad_bg', flops):
             bind_amax(split, None, dz)
-            X.check(X.lib.mvx_conv3d_wgrad_bg_frames(X.ptr(x), X.ptr(dz), X.ptr(dw), din, dout, H, W, cin, cout, sd, pd, flags,
-                                                     X.ptr(bg_in.hflag), X.ptr(bg_in.c), X.ptr(tap_sums), X.ptr(ws), ws.numel(),
-                                                     F, X.stream()), 'mvx_conv3d_wgrad_bg_frames')
+            X.call('mvx_conv3d_wgrad_bg_frames', x, dz, dw, din, dout, H, W, cin, cout, sd, pd, flags, bg_in.hflag, bg_in.c,
+                   tap_sums, ws, ws.numel(), F)
     return None if accumulate_into is not None else dw
 
 
@@ -1280,7 +1233,7 @@ def split_rows(x, split, scale=1.0):
     rows, K = x.shape
     flags = split_flags(split, True)
     planes = torch.empty((3 if int(split) == 3 else 2, rows, K), dtype=torch.int16, device=x.device)
-    X.check(X.lib.mvx_split_rows(_vptr(x), _ld(x), rows, K, X.ptr(planes), flags, float(scale), X.stream()), 'mvx_split_rows')
+    X.call('mvx_split_rows', _vptr(x), _ld(x), rows, K, planes, flags, float(scale))
     return planes
 
 
@@ -1303,10 +1256,8 @@ def linear_forward_pre(x_planes, w_planes, bias, y, stats, row_w, flags, counter
     _, rows, K = x_planes.shape
     N = w_planes.shape[1]
     with _Timed('linear_fwd', 2.0 * rows * K * N if KERNEL_TIMERS is not None else 0):
-        X.check(X.lib.mvx_linear_forward_pre_frames(X.ptr(x_planes), X.ptr(w_planes), X.ptr(bias), _vptr(y), _ld(y), X.ptr(stats),
-                                                    X.ptr(row_w), rows, K, N, flags, 1.0, X.ptr(counter), float(eps), X.ptr(mi),
-                                                    desc.ref() if desc is not None else None, kind, X.stream()),
-                'mvx_linear_forward_pre_frames')
+        X.call('mvx_linear_forward_pre_frames', x_planes, w_planes, bias, _vptr(y), _ld(y), stats, row_w, rows, K, N, flags, 1.0,
+               counter, float(eps), mi, desc.ref() if desc is not None else None, kind)
 
 
 def linear_wgrad_pre(x_planes, dz_planes, accumulate_into=None, rows=None):
@@ -1328,8 +1279,7 @@ def linear_wgrad_pre(x_planes, dz_planes, accumulate_into=None, rows=None):
     with _wgrad_scope(accumulate_into, x_planes, dz_planes) as scope:
         ws = workspace(nbytes, x_planes.device, 'lwgrad_pre_side' if isinstance(scope, _SideStream) else 'lwgrad_pre')
         with _Timed('linear_wgrad', 2.0 * (hi - lo) * K * N if KERNEL_TIMERS is not None else 0):
-            X.check(X.lib.mvx_linear_wgrad_pre_rows(X.ptr(x_planes), X.ptr(dz_planes), X.ptr(dw), plane_rows, lo, hi, K, N, flags,
-                                                    1.0, X.ptr(ws), ws.numel(), X.stream()), 'mvx_linear_wgrad_pre_rows')
+            X.call('mvx_linear_wgrad_pre_rows', x_planes, dz_planes, dw, plane_rows, lo, hi, K, N, flags, 1.0, ws, ws.numel())
         if via:
             if isinstance(scope, _SideStream):       # the buffer lives until the owning stream has joined (see _SideStream)
                 _KEEP.setdefault(dw.device.index, []).append(dw)
@@ -1372,20 +1322,18 @@ def linear_forward(x, w, bias, relu=True, want_stats=True, w_transposed=False, r
             counter = torch.zeros((1,), dtype=torch.float64, device=x.device)
         mi = torch.empty((2, N), dtype=torch.float32, device=x.device)
         bind_amax(split, x)
-        X.check(X.lib.mvx_linear_forward_bn(_vptr(x), _ld(x), _vptr(w), _ld(w), int(w_transposed), X.ptr(bias),
-                                            _vptr(out), _ld(out), X.ptr(stats), X.ptr(row_w), R, K, N,
-                                            (FLAG_RELU if relu else 0) | fz | split_flags(split, True) | xfl, X.ptr(counter), float(finalize[0]),
-                                            float(finalize[1]), X.ptr(mi), X.stream()), 'mvx_linear_forward_bn')
+        X.call('mvx_linear_forward_bn', _vptr(x), _ld(x), _vptr(w), _ld(w), int(w_transposed), bias, _vptr(out), _ld(out), stats,
+               row_w, R, K, N, (FLAG_RELU if relu else 0) | fz | split_flags(split, True) | xfl, counter, float(finalize[0]),
+               float(finalize[1]), mi)
         return out, mi
     ws = None
     if bias is None and not relu and not want_stats and K >= 256 and R * N <= (1 << 22):
         ws = workspace(X.lib.mvx_linear_splitk_workspace_bytes(R, N), x.device, 'splitk')
     with _Timed(label or ('linear_dgrad' if w_transposed else 'linear_fwd'), 2.0 * R * K * N if KERNEL_TIMERS is not None else 0):
         bind_amax(split, x)
-        X.check(X.lib.mvx_linear_forward(_vptr(x), _ld(x), _vptr(w), _ld(w), int(w_transposed), X.ptr(bias),
-                                         _vptr(out), _ld(out), X.ptr(stats), X.ptr(row_w), R, K, N,
-                                         (FLAG_RELU if relu else 0) | fz | split_flags(split, True) | xfl,
-                                         X.ptr(ws), ws.numel() if ws is not None else 0, X.stream()), 'mvx_linear_forward')
+        X.call('mvx_linear_forward', _vptr(x), _ld(x), _vptr(w), _ld(w), int(w_transposed), bias, _vptr(out), _ld(out), stats,
+               row_w, R, K, N, (FLAG_RELU if relu else 0) | fz | split_flags(split, True) | xfl, ws,
+               ws.numel() if ws is not None else 0)
     if finalize is not None and want_stats:      # empty input: no launch happened, finalise the (zero) sums separately
         return out, bn_finalize(stats, finalize[0], finalize[1])
     return out, stats
@@ -1417,10 +1365,8 @@ def linear_forward_bn_frames(x, w2, bias, desc, kind, row_w, eps, split=False, f
         guard_fp16_weight(w2)                          # fp16x3: |w| < 255.9 (device-side status bit, checked once per step)
     with _Timed('linear_fwd', 2.0 * Rr * K * N if KERNEL_TIMERS is not None else 0):
         bind_amax(split, x)                            # fp16x3: the range tag of a foreign input (the sampled image features)
-        X.check(X.lib.mvx_linear_forward_bn_frames(_vptr(x), _ld(x), _vptr(w2), _ld(w2), 0, X.ptr(bias), _vptr(y), _ld(y),
-                                                   X.ptr(stats), X.ptr(row_w), Rr, K, N,
-                                                   FLAG_RELU | fz | split_flags(split, True) | xfl, X.ptr(counter), float(eps),
-                                                   X.ptr(mi), desc.ref(), kind, X.stream()), 'mvx_linear_forward_bn_frames')
+        X.call('mvx_linear_forward_bn_frames', _vptr(x), _ld(x), _vptr(w2), _ld(w2), 0, bias, _vptr(y), _ld(y), stats, row_w, Rr,
+               K, N, FLAG_RELU | fz | split_flags(split, True) | xfl, counter, float(eps), mi, desc.ref(), kind)
     return y, mi
 
 
@@ -1443,8 +1389,7 @@ def linear_wgrad(x, dz, accumulate_into=None, split=None, x_foreign=False):
         ws = workspace(nbytes, x.device, 'lwgrad_side' if isinstance(scope, _SideStream) else 'lwgrad')
         with _Timed('linear_wgrad', 2.0 * R * K * N if KERNEL_TIMERS is not None else 0):
             bind_amax(split, x, dz)
-            X.check(X.lib.mvx_linear_wgrad(_vptr(x), _ld(x), _vptr(dz), _ld(dz), X.ptr(dw), R, K, N, flags, X.ptr(ws),
-                                           ws.numel(), X.stream()), 'mvx_linear_wgrad')
+            X.call('mvx_linear_wgrad', _vptr(x), _ld(x), _vptr(dz), _ld(dz), dw, R, K, N, flags, ws, ws.numel())
     return None if accumulate_into is not None else dw
 
 
@@ -1479,8 +1424,7 @@ def voxel_row_offsets(row_map, V, T, n_real, desc=None):
     vcnt = torch.empty((V,), dtype=torch.int32, device=dev)
     row_w = torch.empty((n_real + V,), dtype=torch.float32, device=dev)
     fusion_row_w = torch.empty((n_real + desc.n_frames,), dtype=torch.float32, device=dev) if desc is not None else None
-    X.check(X.lib.mvx_voxel_row_offsets_frames(X.ptr(row_map), V, T, n_real, X.ptr(voff), X.ptr(vcnt), X.ptr(row_w),
-                                               X.ptr(fusion_row_w), _desc_ref(desc), X.stream()), 'mvx_voxel_row_offsets_frames')
+    X.call('mvx_voxel_row_offsets_frames', row_map, V, T, n_real, voff, vcnt, row_w, fusion_row_w, _desc_ref(desc))
     return (voff, vcnt, row_w) if desc is None else (voff, vcnt, row_w, fusion_row_w)
 
 
@@ -1497,8 +1441,7 @@ def vfe_bn_max_concat(y, mi, V, T, cr=None):
     am = torch.empty((V, C), dtype=torch.int32, device=y.device)
     vo, vc, nr, d = _rows_args(cr)
     with _timed_bytes('vfe_bn_max_concat', y.shape[0] * C * 4 * 3 + V * C * 4):      # read y, write [x | max] + argmax
-        X.check(X.lib.mvx_vfe_bn_max_concat_frames(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), V, T, C, vo, vc, nr, d, X.stream()),
-                'mvx_vfe_bn_max_concat_frames')
+        X.call('mvx_vfe_bn_max_concat_frames', y, mi, out, am, V, T, C, vo, vc, nr, d)
     return out, am
 
 
@@ -1507,8 +1450,7 @@ def vfe_max_concat_backward(g, am, V, T, cr=None):
     dyh = torch.empty((g.shape[0], C), dtype=torch.float32, device=g.device)
     vo, vc, nr, _ = _rows_args(cr)
     with _timed_bytes('vfe_max_concat_backward', g.shape[0] * C * 4 * 3 + V * C * 4):  # read [gx | gmax] + argmax, write dyhat
-        X.check(X.lib.mvx_vfe_max_concat_backward(X.ptr(g), X.ptr(am), X.ptr(dyh), V, T, C, vo, vc, nr, X.stream()),
-                'mvx_vfe_max_concat_backward')
+        X.call('mvx_vfe_max_concat_backward', g, am, dyh, V, T, C, vo, vc, nr)
     return dyh
 
 
@@ -1518,8 +1460,7 @@ def bn_segment_max(y, mi, V, T, cr=None):
     am = torch.empty((V, C), dtype=torch.int32, device=y.device)
     vo, vc, nr, d = _rows_args(cr)
     with _timed_bytes('vfe_bn_segment_max', y.shape[0] * C * 4 + V * C * 8):          # read y, write max + argmax
-        X.check(X.lib.mvx_bn_segment_max_frames(X.ptr(y), X.ptr(mi), X.ptr(out), X.ptr(am), V, T, C, vo, vc, nr, d, X.stream()),
-                'mvx_bn_segment_max_frames')
+        X.call('mvx_bn_segment_max_frames', y, mi, out, am, V, T, C, vo, vc, nr, d)
     return out, am
 
 
@@ -1528,8 +1469,7 @@ def segment_max_backward(dfeat, am, V, T, cr=None):
     rows = cr.rows if cr is not None else V * T
     dyh = torch.empty((rows, C), dtype=torch.float32, device=dfeat.device)
     vo, vc, nr, _ = _rows_args(cr)
-    X.check(X.lib.mvx_segment_max_backward(X.ptr(dfeat), X.ptr(am), X.ptr(dyh), V, T, C, vo, vc, nr, X.stream()),
-            'mvx_segment_max_backward')
+    X.call('mvx_segment_max_backward', dfeat, am, dyh, V, T, C, vo, vc, nr)
     return dyh
 
 
@@ -1539,9 +1479,8 @@ def vfe_compact_input(vox2d, imfeat_c, cr, pitch=None):
     F = imfeat_c.shape[1]
     pitch = 7 + F if pitch is None else pitch
     out = torch.empty((cr.rows, pitch), dtype=torch.float32, device=vox2d.device)
-    X.check(X.lib.mvx_vfe_compact_input_pitch_frames(X.ptr(vox2d), vox2d.shape[1], X.ptr(cr.rows_sel), X.ptr(imfeat_c), F,
-                                                     cr.n_real, cr.V, X.ptr(out), pitch, _desc_ref(cr.desc), X.stream()),
-            'mvx_vfe_compact_input_pitch_frames')
+    X.call('mvx_vfe_compact_input_pitch_frames', vox2d, vox2d.shape[1], cr.rows_sel, imfeat_c, F, cr.n_real, cr.V, out, pitch,
+           _desc_ref(cr.desc))
     return out
 
 
@@ -1550,8 +1489,7 @@ def vfe_compact_input_backward(g, F, cr):
     nf = cr.desc.n_frames if cr.desc is not None else 1
     d = torch.empty((cr.n_real + nf, F), dtype=torch.float32, device=g.device)
     scratch = torch.empty((nf * F,), dtype=torch.float64, device=g.device)
-    X.check(X.lib.mvx_vfe_compact_input_backward_frames(X.ptr(g), F, cr.n_real, cr.V, X.ptr(d), X.ptr(scratch),
-                                                        _desc_ref(cr.desc), X.stream()), 'mvx_vfe_compact_input_backward_frames')
+    X.call('mvx_vfe_compact_input_backward_frames', g, F, cr.n_real, cr.V, d, scratch, _desc_ref(cr.desc))
     return d
 
 
@@ -1569,8 +1507,7 @@ def row_compact_map(vox2d, desc=None):
     real_off = torch.empty((desc.n_frames + 1,), dtype=torch.int32, device=dev) if desc is not None else None
     nbytes = X.lib.mvx_row_compact_workspace_bytes(R)
     ws = workspace(nbytes, dev, 'compact')
-    X.check(X.lib.mvx_row_compact_map_frames(X.ptr(vox2d), vc, R, X.ptr(row_map), X.ptr(rows_sel), X.ptr(n_real), X.ptr(ws),
-                                             ws.numel(), _desc_ref(desc), X.ptr(real_off), X.stream()), 'mvx_row_compact_map_frames')
+    X.call('mvx_row_compact_map_frames', vox2d, vc, R, row_map, rows_sel, n_real, ws, ws.numel(), _desc_ref(desc), real_off)
     return (row_map, rows_sel, n_real) if desc is None else (row_map, rows_sel, n_real, real_off)
 
 
@@ -1590,9 +1527,8 @@ def feature_sample(vox2d, feats_cl, imsize_hw, eps, out, row_map=None, rows_sel=
     # algorithmic bytes: 4 taps x L levels x C floats gathered + L*C floats written per sampled row, + the voxel rows
     nrows = out.shape[0]
     with _timed_bytes('feature_sample', nrows * L * C * 4 * 5 + R * vc * 4):
-        X.check(X.lib.mvx_feature_sample(X.ptr(vox2d), vc, R, X.ptr(row_map), ptrs, hw, L, C,
-                                         float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
-                                         X.ptr(status), X.stream()), 'mvx_feature_sample')
+        X.call('mvx_feature_sample', vox2d, vc, R, row_map, ptrs, hw, L, C, float(imsize_hw[0]), float(imsize_hw[1]), float(eps),
+               out, status)
     return status
 
 
@@ -1610,15 +1546,11 @@ def feature_sample_rows(vox2d, rows_sel, n_real, feats_cl, imsize_hw, eps, out, 
     # algorithmic bytes: 4 taps x L levels x C floats gathered + L*C floats written per sampled row, + the voxel rows
     with _timed_bytes('feature_sample', n_real * L * C * 4 * 5 + n_real * vc * 4 + (n_real * L * C * 6 if planes is not None else 0)):
         if planes is not None:
-            X.check(X.lib.mvx_feature_sample_rows_planes_frames(X.ptr(vox2d), vc, X.ptr(rows_sel), n_real, ptrs, hw, L, C,
-                                                                float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
-                                                                X.ptr(status), _desc_ref(desc), X.ptr(amax), X.ptr(planes),
-                                                                planes.shape[1], X.stream()), 'mvx_feature_sample_rows_planes_frames')
+            X.call('mvx_feature_sample_rows_planes_frames', vox2d, vc, rows_sel, n_real, ptrs, hw, L, C, float(imsize_hw[0]),
+                   float(imsize_hw[1]), float(eps), out, status, _desc_ref(desc), amax, planes, planes.shape[1])
         else:
-            X.check(X.lib.mvx_feature_sample_rows_frames(X.ptr(vox2d), vc, X.ptr(rows_sel), n_real, ptrs, hw, L, C,
-                                                         float(imsize_hw[0]), float(imsize_hw[1]), float(eps), X.ptr(out),
-                                                         X.ptr(status), _desc_ref(desc), X.ptr(amax), X.stream()),
-                    'mvx_feature_sample_rows_frames')
+            X.call('mvx_feature_sample_rows_frames', vox2d, vc, rows_sel, n_real, ptrs, hw, L, C, float(imsize_hw[0]),
+                   float(imsize_hw[1]), float(eps), out, status, _desc_ref(desc), amax)
     return status
 
 
@@ -1626,8 +1558,7 @@ def expand_rows(compact, row_map, pad_row):
     R = row_map.shape[0]
     C = compact.shape[1]
     out = torch.empty((R, C), dtype=torch.float32, device=compact.device)
-    X.check(X.lib.mvx_expand_rows(X.ptr(compact), X.ptr(row_map), int(pad_row), X.ptr(out), R, C, X.stream()),
-            'mvx_expand_rows')
+    X.call('mvx_expand_rows', compact, row_map, int(pad_row), out, R, C)
     return out
 
 
@@ -1635,8 +1566,7 @@ def expand_rows_backward(g, row_map, pad_row, n_compact):
     R, C = g.shape
     dc = torch.empty((n_compact, C), dtype=torch.float32, device=g.device)
     scratch = torch.empty((C,), dtype=torch.float64, device=g.device)
-    X.check(X.lib.mvx_expand_rows_backward(X.ptr(g), X.ptr(row_map), int(pad_row), X.ptr(dc), X.ptr(scratch),
-                                           R, C, X.stream()), 'mvx_expand_rows_backward')
+    X.call('mvx_expand_rows_backward', g, row_map, int(pad_row), dc, scratch, R, C)
     return dc
 
 
@@ -1665,9 +1595,8 @@ def crop_points(pcd, n_in=None, range6=None, bounds_f32=False, cam_from_velo=Non
     k1, r_ptr = _host_f64(range6, 6)
     k2, m_ptr = _host_f64(cam_from_velo, 16)
     k3, p_ptr = _host_f64(p2, 16)
-    X.check(X.lib.mvx_crop_points(X.ptr(pcd), X.ptr(n_in), F, cap, ncol, r_ptr, int(bounds_f32), m_ptr, p_ptr,
-                                  float(imsize_wh[0]), float(imsize_wh[1]), int(math_f32), X.ptr(out), X.ptr(n_out),
-                                  X.ptr(src), X.ptr(ws), ws.numel(), X.stream()), 'mvx_crop_points')
+    X.call('mvx_crop_points', pcd, n_in, F, cap, ncol, r_ptr, int(bounds_f32), m_ptr, p_ptr, float(imsize_wh[0]),
+           float(imsize_wh[1]), int(math_f32), out, n_out, src, ws, ws.numel())
     return out, n_out, src
 
 
@@ -1685,9 +1614,8 @@ def crop_project(pcd, n_in, range6, cam_from_velo64, p2_64, imsize_wh, cam_from_
     k4, m32_ptr = _host_f64(cam_from_velo32, 16)
     k5, p32_ptr = _host_f64(p2_32, 16)
     with _timed_bytes('crop_project', F * cap * ncol * 4 * 2 + F * cap_out * (ncol + 2) * 4):
-        X.check(X.lib.mvx_crop_project_points(X.ptr(pcd), X.ptr(n_in), F, cap, ncol, r_ptr, m_ptr, p_ptr, float(imsize_wh[0]),
-                                              float(imsize_wh[1]), m32_ptr, p32_ptr, X.ptr(out), int(cap_out), X.ptr(n_out),
-                                              X.ptr(ws), ws.numel(), X.stream()), 'mvx_crop_project_points')
+        X.call('mvx_crop_project_points', pcd, n_in, F, cap, ncol, r_ptr, m_ptr, p_ptr, float(imsize_wh[0]), float(imsize_wh[1]),
+               m32_ptr, p32_ptr, out, int(cap_out), n_out, ws, ws.numel())
     return out, n_out
 
 
@@ -1699,8 +1627,7 @@ def lidar2img(pcd2d, cam_from_velo, p2, math_f32=True, out=None, col_offset=0, s
     z = torch.empty((n,), dtype=torch.float32, device=pcd2d.device) if want_z else None
     k2, m_ptr = _host_f64(cam_from_velo, 16)
     k3, p_ptr = _host_f64(p2, 16)
-    X.check(X.lib.mvx_lidar2img(X.ptr(pcd2d), ncol, n, m_ptr, p_ptr, int(math_f32), _vptr(out), _ld(out), col_offset,
-                                int(swap_rc), X.ptr(z), X.stream()), 'mvx_lidar2img')
+    X.call('mvx_lidar2img', pcd2d, ncol, n, m_ptr, p_ptr, int(math_f32), _vptr(out), _ld(out), col_offset, int(swap_rc), z)
     return out, z
 
 
@@ -1713,8 +1640,7 @@ def index_grid(coords, dhw, desc=None):
     nf = desc.n_frames if desc is not None else 1
     buf = torch.empty((X.lib.mvx_index_grid_bytes_frames(D, H, W, nf) // 4,), dtype=torch.int32, device=coords.device)
     status = torch.zeros((1,), dtype=torch.int32, device=coords.device)
-    X.check(X.lib.mvx_index_grid_frames(X.ptr(coords), coords.shape[0], D, H, W, X.ptr(buf), X.ptr(status), _desc_ref(desc),
-                                        X.stream()), 'mvx_index_grid_frames')
+    X.call('mvx_index_grid_frames', coords, coords.shape[0], D, H, W, buf, status, _desc_ref(desc))
     return buf, status
 
 
@@ -1724,9 +1650,8 @@ def sparse_conv_output(P, idx_grid, dhw, bias, cout, sd, pd, relu=True, want_sta
     out = torch.empty((dout, H, W, cout), dtype=torch.float32, device=P.device)
     stats, fz = _acc_f64((STATS_REPLICAS, 2, cout), P.device) if want_stats else (None, 0)
     with _timed_bytes('sparse_conv_output', out.numel() * 4 + din * H * W * 4):     # dense output written + index grid read
-        X.check(X.lib.mvx_sparse_conv_output(X.ptr(P), X.ptr(idx_grid), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
-                                             H, W, cout, sd, pd, (FLAG_RELU if relu else 0) | fz, X.stream()),
-                'mvx_sparse_conv_output')
+        X.call('mvx_sparse_conv_output', P, idx_grid, bias, out, stats, din, dout, H, W, cout, sd, pd,
+               (FLAG_RELU if relu else 0) | fz)
     return out, stats
 
 
@@ -1739,9 +1664,8 @@ def sparse_conv_output_tiles(P, idx_grid, dhw, bias, cout, sd, pd, tflag, F=1, o
         out = torch.empty((F * dout, H, W, cout), dtype=torch.float32, device=P.device)
     stats, fz = _acc_f64((F, STATS_REPLICAS, 2, cout), P.device)
     with _timed_bytes('sparse_conv_output', out.numel() * 4 + F * din * H * W * 4):     # dense output written + index grid read
-        X.check(X.lib.mvx_sparse_conv_output_tiles_frames(X.ptr(P), X.ptr(idx_grid), X.ptr(bias), X.ptr(out), X.ptr(stats), din, dout,
-                                                          H, W, cout, sd, pd, FLAG_RELU | FLAG_NO_BG_FILL | fz, F, X.ptr(tflag),
-                                                          X.stream()), 'mvx_sparse_conv_output_tiles_frames')
+        X.call('mvx_sparse_conv_output_tiles_frames', P, idx_grid, bias, out, stats, din, dout, H, W, cout, sd, pd,
+               FLAG_RELU | FLAG_NO_BG_FILL | fz, F, tflag)
     return out, stats
 
 
@@ -1750,8 +1674,7 @@ def sparse_conv_gather_dz(dz, coords, din, sd, pd, desc=None):
     dout = FD // (desc.n_frames if desc is not None else 1)
     V = coords.shape[0]
     G = torch.empty((V, 27 * cout), dtype=torch.float32, device=dz.device)
-    X.check(X.lib.mvx_sparse_conv_gather_dz_frames(X.ptr(dz), X.ptr(coords), V, X.ptr(G), din, dout, H, W, cout, sd, pd,
-                                                   _desc_ref(desc), X.stream()), 'mvx_sparse_conv_gather_dz_frames')
+    X.call('mvx_sparse_conv_gather_dz_frames', dz, coords, V, G, din, dout, H, W, cout, sd, pd, _desc_ref(desc))
     return tag_amax(G, amax_of(dz))                     # G's rows are rows of dz
 
 
@@ -1873,7 +1796,7 @@ def bbox_pairwise(b1, b2, want_iou):
     """b1 (N,4,2), b2 (M,4,2) f32 BEV corners on the GPU -> (N,M) IoU or intersection area."""
     n, m = b1.shape[0], b2.shape[0]
     out = torch.empty((n, m), dtype=torch.float32, device=b1.device)
-    X.check(X.lib.mvx_bbox_pairwise(X.ptr(b1), n, X.ptr(b2), m, int(want_iou), X.ptr(out), X.stream()), 'mvx_bbox_pairwise')
+    X.call('mvx_bbox_pairwise', b1, n, b2, m, int(want_iou), out)
     return out
 
 
@@ -1908,10 +1831,8 @@ def classify_anchors_frames(gts, gt_off, anchor_bevs, nls, nws, neg_thr, pos_thr
     counts = torch.empty((F, 2), dtype=torch.int32, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     ws = workspace(X.lib.mvx_classify_anchors_workspace_bytes(int(gt_off[-1]), A, radius), dev, 'anchors')
-    X.check(X.lib.mvx_classify_anchors_frames(X.ptr(gts), _gt_offsets(gt_off), F, X.ptr(anchor_bevs), L, W, A, X.ptr(nls), X.ptr(nws),
-                                              float(neg_thr), float(pos_thr), int(radius), X.ptr(pos), X.ptr(neg), X.ptr(gi), cap,
-                                              X.ptr(counts), X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
-            'mvx_classify_anchors_frames')
+    X.call('mvx_classify_anchors_frames', gts, _gt_offsets(gt_off), F, anchor_bevs, L, W, A, nls, nws, float(neg_thr),
+           float(pos_thr), int(radius), pos, neg, gi, cap, counts, status, ws, ws.numel())
     return pos, neg, gi, counts, status
 
 
@@ -1930,10 +1851,8 @@ def assign_anchors_frames(gts, gt_off, anchor_bevs, neg_thr, pos_thr, force_thr,
     host = torch.zeros((2 * F + 1 + G,), dtype=torch.int32, device=dev)
     counts, status, best = host[:2 * F], host[2 * F:2 * F + 1], host[2 * F + 1:]
     ws = workspace(X.lib.mvx_assign_anchors_frames_workspace_bytes(G, F, L, W, A), dev, 'anchors')
-    X.check(X.lib.mvx_assign_anchors_frames(X.ptr(gts), _gt_offsets(gt_off), F, X.ptr(anchor_bevs), L, W, A, float(neg_thr), float(pos_thr),
-                                            float(force_thr), int(radius), X.ptr(pos), X.ptr(neg), X.ptr(gi), cap, X.ptr(counts),
-                                            X.ptr(best) if G else None, X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
-            'mvx_assign_anchors_frames')
+    X.call('mvx_assign_anchors_frames', gts, _gt_offsets(gt_off), F, anchor_bevs, L, W, A, float(neg_thr), float(pos_thr),
+           float(force_thr), int(radius), pos, neg, gi, cap, counts, best if G else None, status, ws, ws.numel())
     return pos, neg, gi, host
 
 
@@ -1946,9 +1865,8 @@ def box_point_counts_frames(points6, n_points, boxes, gt_off):
     assert points6.dtype == boxes.dtype == torch.float32 and n_points.dtype == gt_off.dtype == torch.int32
     assert tuple(n_points.shape) == (F,) and tuple(gt_off.shape) == (F + 1,) and (G == 0 or tuple(boxes.shape) == (G, 7))
     counts = torch.empty((G,), dtype=torch.int32, device=points6.device)
-    X.check(X.lib.mvx_box_point_counts_frames(X.ptr(points6), F, cap_points, ld, X.ptr(n_points), X.ptr(boxes) if G else None,
-                                              X.ptr(gt_off), G, X.ptr(counts) if G else None, X.stream()),
-            'mvx_box_point_counts_frames')
+    X.call('mvx_box_point_counts_frames', points6, F, cap_points, ld, n_points, boxes if G else None, gt_off, G,
+           counts if G else None)
     return counts
 
 
@@ -1980,12 +1898,9 @@ def ignore_anchors_frames(pos, neg, gi, counts, anchors, anchor_bevs, gt_off=Non
     assert out.dtype == torch.int32 and out.numel() == 6 * F + 1 and out.is_contiguous()
     nbytes = X.lib.mvx_ignore_anchors_frames_workspace_bytes(F, L, W, A)
     ws = workspace(nbytes, dev, 'ignore')
-    X.check(X.lib.mvx_ignore_anchors_frames(X.ptr(pos), X.ptr(neg), X.ptr(gi), cap, X.ptr(counts), F, X.ptr(gt_off), X.ptr(gt_points),
-                                            int(min_points), X.ptr(anchors), X.ptr(anchor_bevs), L, W, A, X.ptr(rects),
-                                            X.ptr(rect_off), X.ptr(img_from_lidar), X.ptr(ign_quads), X.ptr(ign_off), float(ioa_thr),
-                                            X.ptr(pos_o), X.ptr(neg_o), X.ptr(gi_o), cap_out, X.ptr(out[:2 * F]),
-                                            X.ptr(out[2 * F:6 * F]), X.ptr(out[6 * F:]), X.ptr(ws), ws.numel(), X.stream()),
-            'mvx_ignore_anchors_frames')
+    X.call('mvx_ignore_anchors_frames', pos, neg, gi, cap, counts, F, gt_off, gt_points, int(min_points), anchors, anchor_bevs, L,
+           W, A, rects, rect_off, img_from_lidar, ign_quads, ign_off, float(ioa_thr), pos_o, neg_o, gi_o, cap_out, out[:2 * F],
+           out[2 * F:6 * F], out[6 * F:], ws, ws.numel())
     return pos_o, neg_o, gi_o, out
 
 
@@ -2011,13 +1926,10 @@ def voxel_loss(score, reg, pos_idx, neg_idx, gi, n_pos, n_neg, gts, anchors, A, 
     rs = reg.stride() if reg is not None else (0, 0, 0)
     ds = dscore.stride() if dscore is not None else (0, 0, 0)
     dr = dreg.stride() if dreg is not None else (0, 0, 0)
-    X.check(X.lib.mvx_voxel_loss(_vptr(score), ss[0], ss[1], ss[2], _vptr(reg), rs[0], rs[1], rs[2],
-                                 X.ptr(pos_idx), pos_idx.shape[1] if pos_idx is not None else 0,
-                                 X.ptr(neg_idx), neg_idx.shape[1] if neg_idx is not None else 0, X.ptr(gi), None,
-                                 int(n_pos), int(n_neg), X.ptr(gts), gts.shape[1] if gts is not None else 7,
-                                 X.ptr(anchors), L, W, int(A), float(a), float(b), float(eps),
-                                 _vptr(dscore), ds[0], ds[1], ds[2], _vptr(dreg), dr[0], dr[1], dr[2],
-                                 X.ptr(losses), X.ptr(scratch), X.stream()), 'mvx_voxel_loss')
+    X.call('mvx_voxel_loss', _vptr(score), ss[0], ss[1], ss[2], _vptr(reg), rs[0], rs[1], rs[2], pos_idx,
+           pos_idx.shape[1] if pos_idx is not None else 0, neg_idx, neg_idx.shape[1] if neg_idx is not None else 0, gi, None,
+           int(n_pos), int(n_neg), gts, gts.shape[1] if gts is not None else 7, anchors, L, W, int(A), float(a), float(b),
+           float(eps), _vptr(dscore), ds[0], ds[1], ds[2], _vptr(dreg), dr[0], dr[1], dr[2], losses, scratch)
     return losses, dscore, dreg
 
 
@@ -2037,10 +1949,9 @@ def focal_loss_frames(heads, F, l, w, A, pos_idx, neg_idx, gi, counts, gts, gt_o
     d_heads = torch.empty_like(heads) if want_grads else None
     nbytes = X.lib.mvx_focal_loss_frames_workspace_bytes(int(F), int(l), int(w), int(A))
     ws = workspace(nbytes, dev, 'focal_loss')
-    X.check(X.lib.mvx_focal_loss_frames(X.ptr(heads), int(F), int(l), int(w), int(A), X.ptr(pos_idx), X.ptr(neg_idx), X.ptr(gi),
-                                        gi.shape[1], X.ptr(counts), X.ptr(gts), gts.shape[1], X.ptr(gt_off), X.ptr(anchors),
-                                        float(alpha), float(gamma), float(cls_weight), float(reg_weight), X.ptr(d_heads),
-                                        X.ptr(losses), X.ptr(ws), ws.numel(), X.stream()), 'mvx_focal_loss_frames')
+    X.call('mvx_focal_loss_frames', heads, int(F), int(l), int(w), int(A), pos_idx, neg_idx, gi, gi.shape[1], counts, gts,
+           gts.shape[1], gt_off, anchors, float(alpha), float(gamma), float(cls_weight), float(reg_weight), d_heads, losses, ws,
+           ws.numel())
     return losses, d_heads
 
 
@@ -2083,13 +1994,10 @@ def focal_loss_dir_frames(heads, dir_logits, F, l, w, A, pos_idx, neg_idx, gi, c
         d_heads = d_dir = None
     nbytes = X.lib.mvx_focal_loss_dir_frames_workspace_bytes(int(F), int(l), int(w), int(A), int(ldd))
     ws = workspace(nbytes, dev, 'focal_loss')
-    X.check(X.lib.mvx_focal_loss_dir_frames(_vptr(heads), int(ld), _vptr(dir_logits), int(dir_ld), int(F), int(l), int(w), int(A),
-                                            X.ptr(pos_idx), X.ptr(neg_idx), X.ptr(gi), gi.shape[1], X.ptr(counts), X.ptr(gts),
-                                            gts.shape[1], X.ptr(gt_off), X.ptr(anchors), float(alpha), float(gamma),
-                                            float(cls_weight), float(reg_weight), float(dir_weight), float(dir_offset),
-                                            _vptr(d_heads) if want_grads else None, int(ldd),
-                                            _vptr(d_dir) if want_grads else None, int(d_dir.stride(0)) if want_grads else 0,
-                                            X.ptr(losses), X.ptr(ws), ws.numel(), X.stream()), 'mvx_focal_loss_dir_frames')
+    X.call('mvx_focal_loss_dir_frames', _vptr(heads), int(ld), _vptr(dir_logits), int(dir_ld), int(F), int(l), int(w), int(A),
+           pos_idx, neg_idx, gi, gi.shape[1], counts, gts, gts.shape[1], gt_off, anchors, float(alpha), float(gamma),
+           float(cls_weight), float(reg_weight), float(dir_weight), float(dir_offset), _vptr(d_heads) if want_grads else None,
+           int(ldd), _vptr(d_dir) if want_grads else None, int(d_dir.stride(0)) if want_grads else 0, losses, ws, ws.numel())
     return losses, d_heads, d_dir
 
 
@@ -2128,19 +2036,15 @@ def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, po
     if dir_logits is not None:
         assert dir_logits.shape == (F, l, w, A) and dir_logits.dtype == torch.float32 and dir_logits.device == dev
         ds = dir_logits.stride()
-        X.check(X.lib.mvx_detect_frames_dir(_vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3],
-                                            _vptr(dir_logits), ds[0], ds[1], ds[2], ds[3], float(dir_offset), X.ptr(anchors),
-                                            int(F), int(l), int(w), int(A), float(score_thr), float(iou_thr), int(pre_max),
-                                            int(post_max), DECODE_MODES[decode], X.ptr(boxes), X.ptr(scores), X.ptr(idx),
-                                            X.ptr(meta[0]), X.ptr(meta[1]), X.ptr(meta[2]), X.ptr(dbg[0]), X.ptr(dbg[1]),
-                                            X.ptr(dbg[2]), X.ptr(ws), ws.numel(), X.stream()), 'mvx_detect_frames_dir')
+        X.call('mvx_detect_frames_dir', _vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3],
+               _vptr(dir_logits), ds[0], ds[1], ds[2], ds[3], float(dir_offset), anchors, int(F), int(l), int(w), int(A),
+               float(score_thr), float(iou_thr), int(pre_max), int(post_max), DECODE_MODES[decode], boxes, scores, idx, meta[0],
+               meta[1], meta[2], dbg[0], dbg[1], dbg[2], ws, ws.numel())
         out = (boxes, scores, idx, meta)
         return out + dbg if debug else out
-    X.check(X.lib.mvx_detect_frames(_vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3], X.ptr(anchors),
-                                    int(F), int(l), int(w), int(A), float(score_thr), float(iou_thr), int(pre_max), int(post_max),
-                                    DECODE_MODES[decode], X.ptr(boxes), X.ptr(scores), X.ptr(idx), X.ptr(meta[0]),
-                                    X.ptr(meta[1]), X.ptr(meta[2]), X.ptr(dbg[0]), X.ptr(dbg[1]), X.ptr(dbg[2]), X.ptr(ws),
-                                    ws.numel(), X.stream()), 'mvx_detect_frames')
+    X.call('mvx_detect_frames', _vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3], anchors, int(F),
+           int(l), int(w), int(A), float(score_thr), float(iou_thr), int(pre_max), int(post_max), DECODE_MODES[decode], boxes,
+           scores, idx, meta[0], meta[1], meta[2], dbg[0], dbg[1], dbg[2], ws, ws.numel())
     out = (boxes, scores, idx, meta)
     return out + dbg if debug else out
 
@@ -2157,9 +2061,8 @@ def kitti_eval_overlaps(inp, t):
     dev = t['off'].device
     ov = torch.empty((3, inp.n_pairs), dtype=torch.float64, device=dev)
     dco = torch.empty((inp.n_dc_pairs,), dtype=torch.float64, device=dev)
-    X.check(X.lib.mvx_kitti_eval_overlaps(inp.F, _host_ptr(inp.off), X.ptr(t['off']), X.ptr(t['pair_off']), X.ptr(t['det_rows']),
-                                          X.ptr(t['det_quads']), X.ptr(t['gt_rows']), X.ptr(t['gt_quads']), X.ptr(t['dc_rows']),
-                                          X.ptr(ov), X.ptr(dco), X.stream()), 'mvx_kitti_eval_overlaps')
+    X.call('mvx_kitti_eval_overlaps', inp.F, _host_ptr(inp.off), t['off'], t['pair_off'], t['det_rows'], t['det_quads'],
+           t['gt_rows'], t['gt_quads'], t['dc_rows'], ov, dco)
     return ov, dco
 
 
@@ -2169,10 +2072,8 @@ def kitti_eval_tp_scores(inp, t, ov):
     C = len(inp.keys)
     tp = torch.empty((C, inp.n_slots), dtype=torch.float64, device=dev)
     n_valid = torch.empty((C, inp.F), dtype=torch.int32, device=dev)
-    X.check(X.lib.mvx_kitti_eval_tp_scores(inp.F, _host_ptr(inp.off), X.ptr(t['off']), X.ptr(t['pair_off']), C, _host_ptr(inp.curves),
-                                           _host_ptr(inp.min_overlaps), inp.ignored_gt.shape[0], X.ptr(t['ignored_gt']),
-                                           X.ptr(t['ignored_det']), X.ptr(t['scores']), X.ptr(ov), X.ptr(tp), X.ptr(n_valid),
-                                           X.stream()), 'mvx_kitti_eval_tp_scores')
+    X.call('mvx_kitti_eval_tp_scores', inp.F, _host_ptr(inp.off), t['off'], t['pair_off'], C, _host_ptr(inp.curves),
+           _host_ptr(inp.min_overlaps), inp.ignored_gt.shape[0], t['ignored_gt'], t['ignored_det'], t['scores'], ov, tp, n_valid)
     return tp, n_valid
 
 
@@ -2183,8 +2084,7 @@ def kitti_eval_thresholds(inp, tp_sorted, n_valid):
     thr = torch.empty((C, 41), dtype=torch.float64, device=dev)
     n_thr = torch.empty((C,), dtype=torch.int32, device=dev)
     n_gt = torch.empty((C,), dtype=torch.int32, device=dev)
-    X.check(X.lib.mvx_kitti_eval_thresholds(inp.F, C, inp.n_slots, X.ptr(tp_sorted.contiguous()), X.ptr(n_valid), X.ptr(thr),
-                                            X.ptr(n_thr), X.ptr(n_gt), X.stream()), 'mvx_kitti_eval_thresholds')
+    X.call('mvx_kitti_eval_thresholds', inp.F, C, inp.n_slots, tp_sorted.contiguous(), n_valid, thr, n_thr, n_gt)
     return thr, n_thr, n_gt
 
 
@@ -2195,11 +2095,9 @@ def kitti_eval_counts(inp, t, ov, dco, thr, n_thr):
     totals = torch.empty((C, 41, 3), dtype=torch.int32, device=dev)
     sim = torch.empty((C, 41), dtype=torch.float64, device=dev)
     ws = workspace(X.lib.mvx_kitti_eval_workspace_bytes(inp.F, C), dev, 'kitti_eval')
-    X.check(X.lib.mvx_kitti_eval_counts(inp.F, _host_ptr(inp.off), X.ptr(t['off']), X.ptr(t['pair_off']), C, _host_ptr(inp.curves),
-                                        _host_ptr(inp.min_overlaps), inp.ignored_gt.shape[0], X.ptr(t['ignored_gt']),
-                                        X.ptr(t['ignored_det']), X.ptr(t['scores']), X.ptr(t['det_alpha']), X.ptr(t['gt_alpha']),
-                                        X.ptr(ov), X.ptr(dco), X.ptr(thr), X.ptr(n_thr), X.ptr(totals), X.ptr(sim), X.ptr(ws),
-                                        ws.numel(), X.stream()), 'mvx_kitti_eval_counts')
+    X.call('mvx_kitti_eval_counts', inp.F, _host_ptr(inp.off), t['off'], t['pair_off'], C, _host_ptr(inp.curves),
+           _host_ptr(inp.min_overlaps), inp.ignored_gt.shape[0], t['ignored_gt'], t['ignored_det'], t['scores'], t['det_alpha'],
+           t['gt_alpha'], ov, dco, thr, n_thr, totals, sim, ws, ws.numel())
     return totals, sim
 
 
@@ -2218,9 +2116,8 @@ def gt_paste_ground(points6, n_points, range6, grid_shape=(704, 800)):
     dev = points6.device
     nbytes = X.lib.mvx_gt_paste_workspace_bytes(F, gh, gw)
     zmax = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev)
-    X.check(X.lib.mvx_gt_paste_ground_frames(X.ptr(points6), X.ptr(n_points), F, cap, float(range6[0]), float(range6[1]),
-                                             float(range6[2]), float(range6[3]), float(range6[4]), gh, gw, X.ptr(zmax), nbytes,
-                                             X.stream()), 'mvx_gt_paste_ground_frames')
+    X.call('mvx_gt_paste_ground_frames', points6, n_points, F, cap, float(range6[0]), float(range6[1]), float(range6[2]),
+           float(range6[3]), float(range6[4]), gh, gw, zmax, nbytes)
     return zmax[:F * gh * gw].view(F, gh, gw)
 
 
@@ -2241,11 +2138,9 @@ def gt_paste_place(zmax, range6, box2d, box3d, bev, n_scene, lim, cand, thr, db,
     dbg = (None, None)
     if debug:
         dbg = (torch.empty((F, S, C), dtype=torch.int32, device=dev), torch.empty((F, S, C, 3), dtype=torch.float32, device=dev))
-    X.check(X.lib.mvx_gt_paste_place_frames(X.ptr(zmax), gh, gw, float(range6[0]), float(range6[1]), float(cell), float(z_margin),
-                                            float(iou_thr), X.ptr(box2d), X.ptr(box3d), X.ptr(bev), X.ptr(n_scene), F, cap,
-                                            int(lim), X.ptr(cand), X.ptr(thr), S, C, X.ptr(db.box2d), X.ptr(db.box3d),
-                                            X.ptr(db.bev), db.n, X.ptr(picked), X.ptr(n_out), X.ptr(status), X.ptr(dbg[0]),
-                                            X.ptr(dbg[1]), X.stream()), 'mvx_gt_paste_place_frames')
+    X.call('mvx_gt_paste_place_frames', zmax, gh, gw, float(range6[0]), float(range6[1]), float(cell), float(z_margin),
+           float(iou_thr), box2d, box3d, bev, n_scene, F, cap, int(lim), cand, thr, S, C, db.box2d, db.box3d, db.bev, db.n,
+           picked, n_out, status, dbg[0], dbg[1])
     out = (picked, n_out)
     return out + dbg if debug else out
 
@@ -2254,9 +2149,8 @@ def gt_paste_points(points6, n_points, picked, db, status):
     """Appends the picked objects' rows behind the scene points of every frame (in place); returns the new counts i32 (F,)."""
     F, cap = points6.shape[0], points6.shape[1]
     n_new = torch.empty((F,), dtype=torch.int32, device=points6.device)
-    X.check(X.lib.mvx_gt_paste_points_frames(X.ptr(points6), X.ptr(n_points), X.ptr(n_new), F, cap, X.ptr(picked), picked.shape[1],
-                                             X.ptr(db.points), X.ptr(db.pt_off), db.n, X.ptr(status), X.stream()),
-            'mvx_gt_paste_points_frames')
+    X.call('mvx_gt_paste_points_frames', points6, n_points, n_new, F, cap, picked, picked.shape[1], db.points, db.pt_off, db.n,
+           status)
     return n_new
 
 
@@ -2264,9 +2158,8 @@ def gt_paste_image(img, picked, db):
     """img u8 (F, H, W, 3) in place: every picked object's patch under its mask, later slots over earlier ones."""
     F, H, W = img.shape[0], img.shape[1], img.shape[2]
     assert img.dtype == torch.uint8 and img.shape[3] == 3
-    X.check(X.lib.mvx_gt_paste_image_frames(X.ptr(img), F, H, W, X.ptr(picked), picked.shape[1], X.ptr(db.patch), X.ptr(db.mask),
-                                            X.ptr(db.px_off), X.ptr(db.maskbbox), db.n, int(db.max_patch_px), X.stream()),
-            'mvx_gt_paste_image_frames')
+    X.call('mvx_gt_paste_image_frames', img, F, H, W, picked, picked.shape[1], db.patch, db.mask, db.px_off, db.maskbbox, db.n,
+           int(db.max_patch_px))
     return img
 
 
@@ -2303,9 +2196,8 @@ def geom_place(box3d, n_box, noise, glob, range6, status, iou_thr=0.05):
     out.kept_idx = torch.empty((F, B), dtype=torch.int32, device=dev)
     out.n_kept = torch.empty((F,), dtype=torch.int32, device=dev)
     r = _range6_host(range6)
-    X.check(X.lib.mvx_geom_place_frames(X.ptr(box3d), X.ptr(n_box), F, B, X.ptr(noise), T, X.ptr(glob), float(iou_thr), _host_ptr(r),
-                                        X.ptr(out.trial), X.ptr(out.move), X.ptr(out.box3d), X.ptr(out.bev), X.ptr(out.kept_idx),
-                                        X.ptr(out.n_kept), X.ptr(status), X.stream()), 'mvx_geom_place_frames')
+    X.call('mvx_geom_place_frames', box3d, n_box, F, B, noise, T, glob, float(iou_thr), _host_ptr(r), out.trial, out.move,
+           out.box3d, out.bev, out.kept_idx, out.n_kept, status)
     return out
 
 
@@ -2321,9 +2213,8 @@ def geom_points(points6, n_points, box3d, n_box, placed, glob, range6):
     ws = workspace(X.lib.mvx_geom_workspace_bytes(F, cap), dev, 'geom')
     r = _range6_host(range6)
     with _timed_bytes('geom_points', F * cap * 6 * 4 * 3):
-        X.check(X.lib.mvx_geom_points_frames(X.ptr(points6), X.ptr(n_points), F, cap, X.ptr(box3d), X.ptr(n_box), B,
-                                             X.ptr(placed.trial), X.ptr(placed.move), X.ptr(glob), _host_ptr(r), X.ptr(out),
-                                             X.ptr(n_out), X.ptr(ws), ws.numel(), X.stream()), 'mvx_geom_points_frames')
+        X.call('mvx_geom_points_frames', points6, n_points, F, cap, box3d, n_box, B, placed.trial, placed.move, glob,
+               _host_ptr(r), out, n_out, ws, ws.numel())
     return out, n_out
 
 
@@ -2347,9 +2238,8 @@ def gtdb_match(t, iou_thr=GTDB_IOU_THR):
     flag = torch.empty((n,), dtype=torch.int32, device=dev)
     roi = torch.empty((n, 4), dtype=torch.int32, device=dev)
     px_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
-    X.check(X.lib.mvx_gtdb_match(X.ptr(t.lab_box2d), X.ptr(t.lab_group), X.ptr(t.lab_frame), n, X.ptr(t.ann_box), X.ptr(t.ann_off),
-                                 t.ann_off.numel() - 1, X.ptr(t.im_hw), t.n_frames, float(iou_thr), X.ptr(best), X.ptr(iou),
-                                 X.ptr(flag), X.ptr(roi), X.ptr(px_off), X.stream()), 'mvx_gtdb_match')
+    X.call('mvx_gtdb_match', t.lab_box2d, t.lab_group, t.lab_frame, n, t.ann_box, t.ann_off, t.ann_off.numel() - 1, t.im_hw,
+           t.n_frames, float(iou_thr), best, iou, flag, roi, px_off)
     return best, iou, flag, roi, px_off
 
 
@@ -2362,18 +2252,16 @@ def gtdb_crop_count(t, flag):
     nbytes = X.lib.mvx_gtdb_workspace_bytes(n, int(t.max_frame_points))
     ws = torch.empty((max(int(nbytes), 256),), dtype=torch.uint8, device=dev)
     pt_off = torch.empty((n + 1,), dtype=torch.int64, device=dev)
-    X.check(X.lib.mvx_gtdb_crop_count(X.ptr(t.points), X.ptr(t.pts_off), t.n_frames, int(t.max_frame_points), X.ptr(t.lab_box3d),
-                                      X.ptr(t.lab_cs), X.ptr(t.lab_frame), X.ptr(flag), n, X.ptr(pt_off), X.ptr(ws), ws.numel(),
-                                      X.stream()), 'mvx_gtdb_crop_count')
+    X.call('mvx_gtdb_crop_count', t.points, t.pts_off, t.n_frames, int(t.max_frame_points), t.lab_box3d, t.lab_cs, t.lab_frame,
+           flag, n, pt_off, ws, ws.numel())
     return pt_off, ws
 
 
 def gtdb_crop_write(t, flag, pt_off, ws, n_rows):
     """points f32 (max(n_rows, 1), 4): every object's inside points at pt_off, in file order."""
     out = torch.zeros((max(int(n_rows), 1), 4), dtype=torch.float32, device=t.points.device)
-    X.check(X.lib.mvx_gtdb_crop_write(X.ptr(t.points), X.ptr(t.pts_off), t.n_frames, int(t.max_frame_points), X.ptr(t.lab_box3d),
-                                      X.ptr(t.lab_cs), X.ptr(t.lab_frame), X.ptr(flag), t.n_labels, X.ptr(pt_off), X.ptr(ws),
-                                      ws.numel(), X.ptr(out), out.shape[0], X.stream()), 'mvx_gtdb_crop_write')
+    X.call('mvx_gtdb_crop_write', t.points, t.pts_off, t.n_frames, int(t.max_frame_points), t.lab_box3d, t.lab_cs, t.lab_frame,
+           flag, t.n_labels, pt_off, ws, ws.numel(), out, out.shape[0])
     return out
 
 
@@ -2385,10 +2273,8 @@ def gtdb_raster(t, best, flag, roi, px_off, n_px, max_roi_rows):
     assert t.edges.dtype == torch.float64 and t.edge_poly.dtype == torch.int32 and t.edge_off.dtype == torch.int32
     mask = torch.zeros((max(int(n_px), 1),), dtype=torch.uint8, device=dev)
     patch = torch.zeros((max(int(n_px), 1), 3), dtype=torch.uint8, device=dev)
-    X.check(X.lib.mvx_gtdb_raster(X.ptr(t.images), F, H, W, X.ptr(t.lab_frame), X.ptr(flag), X.ptr(best), X.ptr(roi), X.ptr(px_off),
-                                  t.n_labels, X.ptr(t.edges), X.ptr(t.edge_poly), X.ptr(t.edge_off), t.edge_off.numel() - 1,
-                                  max(1, min(int(max_roi_rows), H)), X.ptr(mask), X.ptr(patch), mask.numel(), X.stream()),
-            'mvx_gtdb_raster')
+    X.call('mvx_gtdb_raster', t.images, F, H, W, t.lab_frame, flag, best, roi, px_off, t.n_labels, t.edges, t.edge_poly,
+           t.edge_off, t.edge_off.numel() - 1, max(1, min(int(max_roi_rows), H)), mask, patch, mask.numel())
     return mask, patch
 
 
@@ -2420,8 +2306,7 @@ def image_prepare(img, min_size=800, max_size=1333):
     oh, ow, ph, pw = prepared_size(H, W, min_size, max_size)
     out = torch.empty((F, ph, pw, 4), dtype=torch.float32, device=img.device)
     with _timed_bytes('image_prepare', out.numel() * 4 + img.numel() * img.element_size()):
-        X.check(X.lib.mvx_image_prepare_frames(X.ptr(img), int(u8), X.ptr(out), F, H, W, oh, ow, ph, pw, X.stream()),
-                'mvx_image_prepare_frames')
+        X.call('mvx_image_prepare_frames', img, int(u8), out, F, H, W, oh, ow, ph, pw)
     return out, (oh, ow)
 
 
@@ -2431,8 +2316,7 @@ def stem_conv7(x4, wpk, bias):
     assert x4.shape[3] == 4 and wpk.numel() == 49 * 3 * 64 and bias.numel() == 64
     out = torch.empty((F, (ph - 1) // 2 + 1, (pw - 1) // 2 + 1, 64), dtype=torch.float32, device=x4.device)
     with _Timed('stem_conv7', 2.0 * out.numel() * 147 if KERNEL_TIMERS is not None else 0):
-        X.check(X.lib.mvx_stem_conv7_frames(X.ptr(x4), X.ptr(wpk), X.ptr(bias), X.ptr(out), F, ph, pw, X.stream()),
-                'mvx_stem_conv7_frames')
+        X.call('mvx_stem_conv7_frames', x4, wpk, bias, out, F, ph, pw)
     return out
 
 
@@ -2440,7 +2324,7 @@ def maxpool3s2(x):
     """Max pool 3x3 / 2 / 1 of (F, h, w, C)."""
     F, h, w, C = x.shape
     out = torch.empty((F, (h - 1) // 2 + 1, (w - 1) // 2 + 1, C), dtype=torch.float32, device=x.device)
-    X.check(X.lib.mvx_maxpool3s2_frames(X.ptr(x), X.ptr(out), F, h, w, C, X.stream()), 'mvx_maxpool3s2_frames')
+    X.call('mvx_maxpool3s2_frames', x, out, F, h, w, C)
     return out
 
 
@@ -2448,7 +2332,7 @@ def add_relu(a, b):
     """ReLU(a + b) of two tensors of the same shape (the bottleneck's skip)."""
     assert a.shape == b.shape
     out = torch.empty_like(a)
-    X.check(X.lib.mvx_add_relu_frames(X.ptr(a), X.ptr(b), X.ptr(out), a.numel(), X.stream()), 'mvx_add_relu_frames')
+    X.call('mvx_add_relu_frames', a, b, out, a.numel())
     return out
 
 
@@ -2456,7 +2340,7 @@ def gather_stride2(x):
     """(F, h, w, C) -> its even (y, x) sites (F, ceil(h / 2), ceil(w / 2), C): the rows a 1x1 stride-2 convolution reads."""
     F, h, w, C = x.shape
     out = torch.empty((F, (h - 1) // 2 + 1, (w - 1) // 2 + 1, C), dtype=torch.float32, device=x.device)
-    X.check(X.lib.mvx_gather_stride2_frames(X.ptr(x), X.ptr(out), F, h, w, C, X.stream()), 'mvx_gather_stride2_frames')
+    X.call('mvx_gather_stride2_frames', x, out, F, h, w, C)
     return out
 
 
@@ -2466,8 +2350,7 @@ def topdown_merge(lateral, top):
     if top.shape != (F, lh // 2, lw // 2, C) or lh % 2 or lw % 2:
         raise X.MvxHipError('topdown_merge: the lateral map %s is not exactly twice the top map %s' % (tuple(lateral.shape), tuple(top.shape)))
     out = torch.empty_like(lateral)
-    X.check(X.lib.mvx_topdown_merge_frames(X.ptr(lateral), X.ptr(top), X.ptr(out), F, lh, lw, top.shape[1], top.shape[2], C,
-                                           X.stream()), 'mvx_topdown_merge_frames')
+    X.call('mvx_topdown_merge_frames', lateral, top, out, F, lh, lw, top.shape[1], top.shape[2], C)
     return out
 
 
@@ -2478,11 +2361,10 @@ def conv2d_forward_plain(x, wpk, bias, F, h, w, cin, cout, flags, relu, split=Fa
     fl = (FLAG_RELU if relu else 0) | flags
     with _Timed('extractor_conv', _conv2d_flops(F, h, w, cin, cout, flags)):
         if split:
-            X.check(X.lib.mvx_conv2d_forward_split_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), None, h, w, cin, cout,
-                                                          fl | split_flags(split), F, X.stream()), 'mvx_conv2d_forward_split_frames')
+            X.call('mvx_conv2d_forward_split_frames', x, wpk, bias, y, None, h, w, cin, cout, fl | split_flags(split), F)
         else:
-            X.check(X.lib.mvx_conv2d_forward_frames(X.ptr(x), X.ptr(wpk), X.ptr(bias), X.ptr(y), None, h, w, cin, cout, fl, None, 0.0,
-                                                    None, X.ptr(_work_counter(x.device)), F, X.stream()), 'mvx_conv2d_forward_frames')
+            X.call('mvx_conv2d_forward_frames', x, wpk, bias, y, None, h, w, cin, cout, fl, None, 0.0, None,
+                   _work_counter(x.device), F)
     return y
 
 
@@ -2502,10 +2384,8 @@ def optim_adamw_step(table, grad_flat, m_flat, v_flat, count, state, lr, beta1, 
     assert state.dtype == torch.float64 and state.numel() == 8 and (count is None or count.dtype == torch.float32)
     ws = workspace(X.lib.mvx_optim_workspace_bytes(n), dev, 'optim')
     with _timed_bytes('optim_adamw', 7 * 4 * n):
-        X.check(X.lib.mvx_optim_adamw_step(X.ptr(table), table.shape[0], X.ptr(grad_flat), X.ptr(m_flat), X.ptr(v_flat), n,
-                                           X.ptr(count), X.ptr(state), float(lr), float(beta1), float(beta2), float(eps),
-                                           float(weight_decay), float(max_norm), 1 if guard else 0, X.ptr(ws), ws.numel(),
-                                           X.stream()), 'mvx_optim_adamw_step')
+        X.call('mvx_optim_adamw_step', table, table.shape[0], grad_flat, m_flat, v_flat, n, count, state, float(lr), float(beta1),
+               float(beta2), float(eps), float(weight_decay), float(max_norm), 1 if guard else 0, ws, ws.numel())
 
 
 # ---------------------------------------------------------------------------------------------
@@ -2541,10 +2421,9 @@ def render_bev_frames(points6, n_points, boxes, n_boxes, colors, x0, y0, res, z0
         raise X.MvxHipError("color_by must be 'height' or 'intensity', not %r" % (color_by,))
     F, cap, ld, Bcap, boxes, n_boxes, colors, out, status, ws = _render_common(points6, n_points, boxes, n_boxes, colors, lut, H, W)
     with _timed_bytes('render_bev', F * (cap * ld * 4 + H * W * 15)):
-        X.check(X.lib.mvx_render_bev_frames(X.ptr(points6), ld, X.ptr(n_points), F, cap, X.ptr(boxes), X.ptr(n_boxes), X.ptr(colors),
-                                            Bcap, float(x0), float(y0), float(res), float(z0), float(z1), int(H), int(W), X.ptr(lut),
-                                            RENDER_COLOR_BY[color_by], int(cmax), int(background) & 0xFFFFFF, int(thickness),
-                                            X.ptr(out), X.ptr(status), X.ptr(ws), ws.numel(), X.stream()), 'mvx_render_bev_frames')
+        X.call('mvx_render_bev_frames', points6, ld, n_points, F, cap, boxes, n_boxes, colors, Bcap, float(x0), float(y0),
+               float(res), float(z0), float(z1), int(H), int(W), lut, RENDER_COLOR_BY[color_by], int(cmax),
+               int(background) & 0xFFFFFF, int(thickness), out, status, ws, ws.numel())
     return out, status
 
 
@@ -2557,9 +2436,7 @@ def render_camera_frames(points6, n_points, boxes, n_boxes, colors, image_from_l
     assert image_from_lidar.dtype == torch.float64 and image_from_lidar.shape == (F, 4, 4)
     assert images is None or (images.dtype == torch.uint8 and images.shape == (F, H, W, 3))
     with _timed_bytes('render_camera', F * (cap * ld * 4 + H * W * (11 + (3 if images is not None else 0)))):
-        X.check(X.lib.mvx_render_camera_frames(X.ptr(points6), ld, X.ptr(n_points), F, cap, X.ptr(boxes), X.ptr(n_boxes),
-                                               X.ptr(colors), Bcap, X.ptr(image_from_lidar), float(z_near), float(depth_max), int(H),
-                                               int(W), X.ptr(lut_depth), int(point_radius), X.ptr(images), 1 if images_bgr else 0,
-                                               int(thickness), X.ptr(out), X.ptr(status), X.ptr(ws), ws.numel(), X.stream()),
-                'mvx_render_camera_frames')
+        X.call('mvx_render_camera_frames', points6, ld, n_points, F, cap, boxes, n_boxes, colors, Bcap, image_from_lidar,
+               float(z_near), float(depth_max), int(H), int(W), lut_depth, int(point_radius), images, 1 if images_bgr else 0,
+               int(thickness), out, status, ws, ws.numel())
     return out, status

@@ -11,20 +11,16 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, 'include', 'mvx_hip.h')
-
-
-def declared_symbols():
-    text = open(HEADER).read()
-    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
-    return sorted(set(re.findall(r'\b(mvx_[a-z0-9_]+)\s*\(', text)))
+HEADER = abi_header.HEADER
 
 
 def test_library_exports_every_declared_symbol():
     from modules import Extension as X
     lib = ctypes.CDLL(X.LIB_PATH)
-    names = declared_symbols()
+    names = sorted(abi_header.declarations())
     assert len(names) >= 30
     for n in names:
         assert hasattr(lib, n), 'libmvx_hip.so lacks %s declared in include/mvx_hip.h' % n
@@ -33,14 +29,30 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_argument_counts_match_header():
+    """Every entry of the prototype table against the header: the same names, and per name the result type and the whole list
+    of argument types (a pointer is c_void_p, ``int`` is int32_t)."""
     from modules import Extension as X
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    for name, (_, args) in X.PROTOTYPES.items():
-        m = re.search(r'\b%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S)
-        assert m, name
-        params = m.group(1).strip()
-        n = 0 if params in ('', 'void') else params.count(',') + 1
-        assert n == len(args), (name, n, len(args))
+    decl = abi_header.declarations()
+    assert set(decl) == set(X.PROTOTYPES), set(decl) ^ set(X.PROTOTYPES)
+    for name, (res, args) in X.PROTOTYPES.items():
+        assert len(decl[name][1]) == len(args), (name, len(decl[name][1]), len(args))
+        assert decl[name][0] is res, (name, decl[name][0], res)
+        assert abi_header.parameter_types(name) == list(args), name
+
+
+def test_every_call_site_names_an_entry_point_that_ends_in_the_stream():
+    """Extension.call appends the stream itself: every entry point _hip.py reaches through it takes ``void *stream`` last."""
+    src = open(os.path.join(REPO, 'mvxnet-makise_amd', 'modules', '_hip.py')).read()
+    names = re.findall(r"X\.call\('(mvx_\w+)'", src)
+    assert names and len(re.findall(r'X\.call\(', src)) == len(names)                      # no call with a computed name
+    from modules import Extension as X
+    decl = abi_header.declarations()
+    for name in sorted(set(names)):
+        assert decl[name][1][-1] == ('stream', ctypes.c_void_p), name
+        assert decl[name][0] is ctypes.c_int32, name                                         # a status for Extension.check
+        fn, pointers = X._LAUNCHES[name]                                                     # the helper's own table agrees
+        assert list(pointers) == [i for i, (_, t) in enumerate(decl[name][1][:-1]) if t is ctypes.c_void_p], name
+        assert fn.argtypes == X.PROTOTYPES[name][1] and fn.restype is ctypes.c_int32, name
 
 
 def test_no_cpu_fallback_and_loud_failure():
@@ -94,12 +106,6 @@ def test_conv_wgrad_workspace_sizes_are_those_of_the_separate_copies():
     assert X.lib.mvx_conv3d_wgrad_bg_workspace_bytes_frames(0, 11, 37, 64, 64, 1) == 0
 
 
-def _header_parameters(name):
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    params = re.search(r'\b%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S).group(1)
-    return [re.search(r'(\w+)\s*$', q).group(1) for q in params.split(',')]
-
-
 # every convolution entry point that launches a gather or a weight gradient: f32 and split, 3-D and 2-D
 CONV_ENTRY_POINTS = (
     'mvx_conv3d_forward', 'mvx_conv3d_forward_bg', 'mvx_conv3d_forward_bg_frames', 'mvx_conv3d_dgrad', 'mvx_conv3d_dgrad_tiles',
@@ -126,7 +132,7 @@ def test_conv_entry_points_reject_bad_geometry_before_any_launch():
                 count=1.0, eps=1e-5, workspace_bytes=1 << 40, stream=None)
     calls = 0
     for name in CONV_ENTRY_POINTS:
-        names = _header_parameters(name)
+        names = abi_header.parameter_names(name)
         assert len(names) == len(X.PROTOTYPES[name][1])
         for param, value, code in CONV_BAD_ARGUMENTS:
             if param not in names or (param == 'dout' and 'forward' not in name):
@@ -207,7 +213,7 @@ def test_rowgemm_entry_points_reject_a_bad_argument_before_any_launch():
                 frames_host=ctypes.addressof(fr), row_kind=5, stream=None)
     calls = 0
     for name, pointers in ROWGEMM_ENTRY_POINTS.items():
-        names = _header_parameters(name)
+        names = abi_header.parameter_names(name)
         assert len(names) == len(X.PROTOTYPES[name][1])
         for param, value in tuple((p, None) for p in pointers) + ROWGEMM_BAD_ARGUMENTS:
             if param not in names or ((param, value) == ('k', 40) and 'pre' not in name):

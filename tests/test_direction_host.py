@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import direction_cases as DC
 import direction_ref as DR
 import focal_cases as C
@@ -221,29 +222,14 @@ def test_new_entry_points_resolve_with_their_prototypes():
     assert X.lib.mvx_focal_loss_dir_frames_workspace_bytes(3, 6, 5, 2, 12) == 0         # narrower than [cls | reg]
 
 
-def _header_parameters(name):
-    """(return type, [(parameter name, ctypes type)]) of a declaration in include/mvx_hip.h."""
-    import os
-    import re
-    header = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'mvx_hip.h')
-    types = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'size_t': ctypes.c_size_t}
-    text = re.sub(r'/\*.*?\*/', '', open(header).read(), flags=re.S)
-    ret, params = re.search(r'(\w+)\s+%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S).groups()
-    out = []
-    for q in params.split(','):
-        q = ' '.join(q.split())
-        out.append((re.search(r'(\w+)$', q).group(1), ctypes.c_void_p if '*' in q else types[q.replace('const ', '').split()[0]]))
-    return ret, out
-
-
 def test_header_matches_the_prototypes_of_the_new_entry_points():
     from modules import Extension as X
     for name in ('mvx_focal_loss_dir_frames_workspace_bytes', 'mvx_focal_loss_dir_frames', 'mvx_detect_frames_dir'):
-        ret, params = _header_parameters(name)
-        assert ret == ('int64_t' if name.endswith('_bytes') else 'int')
+        ret, params = abi_header.declarations()[name]
+        assert ret is (ctypes.c_int64 if name.endswith('_bytes') else ctypes.c_int32)
         assert [t for _, t in params] == list(X.PROTOTYPES[name][1]), name
-    old = [n for n, _ in _header_parameters('mvx_detect_frames')[1]]
-    new = [n for n, _ in _header_parameters('mvx_detect_frames_dir')[1]]
+    old = abi_header.parameter_names('mvx_detect_frames')
+    new = abi_header.parameter_names('mvx_detect_frames_dir')
     assert [n for n in new if n not in old] == ['dir', 'dir_sf', 'dir_sl', 'dir_sw', 'dir_sa', 'dir_offset']
     assert [n for n in new if n in old] == old
 
@@ -253,7 +239,7 @@ def test_loss_entry_rejects_bad_arguments_before_any_launch():
     from modules import Extension as X
     buf = ctypes.create_string_buffer(4096 + 64)
     dummy = (ctypes.addressof(buf) + 63) & ~63
-    names = [n for n, _ in _header_parameters('mvx_focal_loss_dir_frames')[1]]
+    names = abi_header.parameter_names('mvx_focal_loss_dir_frames')
     need = X.lib.mvx_focal_loss_dir_frames_workspace_bytes(2, 6, 5, 2, 20)
     good = dict(heads_ld=20, dir_ld=20, n_frames=2, l=6, w=5, anchors_per_loc=2, cap=8, gt_ld=7, alpha=0.25, gamma=2.0,
                 cls_weight=1.0, reg_weight=2.0, dir_weight=0.2, dir_offset=math.pi / 4, d_heads_ld=20, d_dir_ld=20,

@@ -2,40 +2,28 @@
 per-frame targets, the float64 reference's simplest closed form, and train_like.py's flags."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import focal_cases as C
 import focal_ref as R
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, 'mvxnet-makise_amd')
-HEADER = os.path.join(REPO, 'include', 'mvx_hip.h')
-C_TYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
-
-
-def _header_parameters(name):
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    ret, params = re.search(r'(\w+)\s+%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S).groups()
-    out = []
-    for q in params.split(','):
-        q = ' '.join(q.split())
-        out.append((re.search(r'(\w+)$', q).group(1), ctypes.c_void_p if '*' in q else C_TYPES[q.replace('const ', '').split()[0]]))
-    return ret, out
 
 
 def test_header_matches_the_prototypes():
     from modules import Extension as X
     for name, ret_type in (('mvx_focal_loss_frames_workspace_bytes', ctypes.c_int64), ('mvx_focal_loss_frames', ctypes.c_int32)):
-        ret, params = _header_parameters(name)
+        ret, params = abi_header.declarations()[name]
         assert name in X.PROTOTYPES and hasattr(X.lib, name)
-        assert X.PROTOTYPES[name][0] is ret_type and ret == ('int64_t' if ret_type is ctypes.c_int64 else 'int')
+        assert X.PROTOTYPES[name][0] is ret_type and ret is ret_type
         assert [t for _, t in params] == list(X.PROTOTYPES[name][1]), name
-    names = [n for n, _ in _header_parameters('mvx_focal_loss_frames')[1]]
+    names = abi_header.parameter_names('mvx_focal_loss_frames')
     for n in ('heads', 'n_frames', 'anchors_per_loc', 'pos_idx', 'neg_idx', 'gi', 'cap', 'counts', 'gts', 'gt_ld', 'gt_off', 'anchors',
               'alpha', 'gamma', 'cls_weight', 'reg_weight', 'd_heads', 'losses', 'workspace', 'workspace_bytes', 'stream'):
         assert n in names, n
@@ -59,7 +47,7 @@ def test_entry_rejects_bad_arguments_before_any_launch():
     from modules import Extension as X
     buf = ctypes.create_string_buffer(4096 + 64)
     dummy = (ctypes.addressof(buf) + 63) & ~63
-    names = [n for n, _ in _header_parameters('mvx_focal_loss_frames')[1]]
+    names = abi_header.parameter_names('mvx_focal_loss_frames')
     need = X.lib.mvx_focal_loss_frames_workspace_bytes(2, 6, 5, 2)
     good = dict(n_frames=2, l=6, w=5, anchors_per_loc=2, cap=8, gt_ld=7, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0,
                 workspace_bytes=need, stream=None)

@@ -3,32 +3,16 @@ prototype table and its argument checks, the rule itself (tests/ignore_ref.ignor
 the conditions the GPU fixtures must meet, the label reader, the geometry helpers and the command-line switches."""
 import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import ignore_cases as IC
 import ignore_ref as IR
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CTYPES = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double,
-          'size_t': ctypes.c_size_t, 'int': ctypes.c_int32}
 ENTRIES = ('mvx_box_point_counts_frames', 'mvx_ignore_anchors_frames_workspace_bytes', 'mvx_ignore_anchors_frames')
-
-
-def _header_decl(name):
-    """(result ctype, [(parameter name, ctype)]) of a declaration of include/mvx_hip.h."""
-    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'mvx_hip.h')).read(), flags=re.S)
-    m = re.search(r'(\w+)\s+%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S)
-    out = []
-    for q in m.group(2).split(','):
-        q = ' '.join(q.split())
-        pname = re.search(r'(\w+)\s*$', q).group(1)
-        out.append((pname, ctypes.c_void_p if '*' in q else CTYPES[q.replace('const ', '').split(' ')[0]]))
-    return CTYPES[m.group(1)], out
 
 
 def test_header_matches_the_prototype_table_and_the_abi_is_still_10():
@@ -37,10 +21,11 @@ def test_header_matches_the_prototype_table_and_the_abi_is_still_10():
     lib = ctypes.CDLL(X.LIB_PATH)
     for name in ENTRIES:
         assert hasattr(lib, name) and name in X.PROTOTYPES
-        res, params = _header_decl(name)
+        res, params = abi_header.declarations()[name]
         assert X.PROTOTYPES[name][0] is res, name
         assert X.PROTOTYPES[name][1] == [t for _, t in params], name
-    assert len(_header_decl('mvx_ignore_anchors_frames')[1]) == 30 and len(_header_decl('mvx_box_point_counts_frames')[1]) == 10
+    assert len(abi_header.parameter_names('mvx_ignore_anchors_frames')) == 30
+    assert len(abi_header.parameter_names('mvx_box_point_counts_frames')) == 10
     q = X.lib.mvx_ignore_anchors_frames_workspace_bytes
     assert q(4, 176, 200, 2) >= 4 * 176 * 200 * 2 * 4 + 4 * 16 and q(0, 176, 200, 2) <= 256
     assert q(4, 176, 200, 2) < X.lib.mvx_assign_anchors_frames_workspace_bytes(60, 4, 176, 200, 2)      # a 4-byte map against an 8-byte one
@@ -64,7 +49,7 @@ def test_each_bad_argument_is_refused_before_any_launch():
     dummy = (ctypes.addressof(buf) + 63) & ~63
     calls = 0
     for name in ('mvx_ignore_anchors_frames', 'mvx_box_point_counts_frames'):
-        names = [p for p, _ in _header_decl(name)[1]]
+        names = abi_header.parameter_names(name)
         for param, value in BAD:
             if param not in names:
                 continue
@@ -73,12 +58,12 @@ def test_each_bad_argument_is_refused_before_any_launch():
             calls += 1
     assert calls == 30 + 10
     # every source is optional: with all of them null the check that fails is the (too small) workspace, not they
-    names = [p for p, _ in _header_decl('mvx_ignore_anchors_frames')[1]]
+    names = abi_header.parameter_names('mvx_ignore_anchors_frames')
     absent = ('gt_off', 'gt_points', 'rects', 'rect_off', 'img_from_lidar', 'ign_quads', 'ign_off')
     args = [None if q in absent else 16 if q == 'workspace_bytes' else GOOD[q] if q in GOOD else dummy for q in names]
     assert X.lib.mvx_ignore_anchors_frames(*args) == -1
     # no box at all: nothing to count, nothing touched, no launch
-    names = [p for p, _ in _header_decl('mvx_box_point_counts_frames')[1]]
+    names = abi_header.parameter_names('mvx_box_point_counts_frames')
     args = [0 if q == 'n_boxes_total' else GOOD[q] if q in GOOD else None for q in names]
     assert X.lib.mvx_box_point_counts_frames(*args) == 0
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_header
 import render_cases as C
 import render_ref as R
 
@@ -140,13 +141,6 @@ def test_save_png_round_trip(tmp_path):
     assert [os.path.basename(p) for p in paths] == ['000000_bev.png', '000001_bev.png'] and all(os.path.exists(p) for p in paths)
 
 
-def _header_parameters(name):
-    import re
-    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'mvx_hip.h')).read(), flags=re.S)
-    params = re.search(r'\b%s\s*\(([^;]*?)\)\s*;' % name, text, flags=re.S).group(1)
-    return [re.search(r'(\w+)\s*$', q).group(1) for q in params.split(',')]
-
-
 # one bad argument each -> MVX_EINVAL; a parameter an entry point does not have is skipped for it
 RENDER_BAD_ARGUMENTS = (
     ('points6', None), ('n_points', None), ('boxes', None), ('n_boxes', None), ('colors', None), ('lut', None), ('lut_depth', None),
@@ -170,7 +164,7 @@ def test_render_entry_points_reject_bad_arguments_before_any_launch():
         assert X.lib.mvx_render_workspace_bytes(*bad) == 0
     calls = 0
     for name in ('mvx_render_bev_frames', 'mvx_render_camera_frames'):
-        names = _header_parameters(name)
+        names = abi_header.parameter_names(name)
         assert len(names) == len(X.PROTOTYPES[name][1])
         for param, value in RENDER_BAD_ARGUMENTS:
             if param not in names:
@@ -180,7 +174,7 @@ def test_render_entry_points_reject_bad_arguments_before_any_launch():
             calls += 1
     assert calls == 26 + 25
     # without boxes the three box pointers may be null: the check that fails is the (too small) workspace, not them
-    names = _header_parameters('mvx_render_bev_frames')
+    names = abi_header.parameter_names('mvx_render_bev_frames')
     args = [None if q in ('boxes', 'n_boxes', 'colors') else 0 if q == 'cap_boxes' else 16 if q == 'workspace_bytes' else
             good[q] if q in good else dummy for q in names]
     assert X.lib.mvx_render_bev_frames(*args) == -1
