@@ -561,6 +561,8 @@ int mvx_expand_rows_backward(const float *grad_out, const int32_t *row_map, int3
  *                or NULL: keep cam.z > 0 and 0 <= (u, v) < (imsize_w, imsize_h) - 1e-3;
  *                math_f32 selects the torch-path (f32) arithmetic instead of the numpy-path (f64)
  *   out f32 [F][cap_points][ncol], n_out i32 [F]; src_index (optional) i32 [F][cap_points]
+ *   n_in[f] is clamped to cap_points.  n_out[f] = the number of points of frame f that passed; rows of out
+ *   at and after n_out[f] are not written, nor are those of src_index.
  * mvx_lidar2img: out[i][col_offset + 0..1] = (u, v), or (v, u) = (row, col) when swap_to_row_col
  *   (train.py:33); cam_z (optional) f32 [n] = depth in the camera frame.
  */
@@ -574,7 +576,10 @@ int mvx_crop_points(const float *pcd, const int32_t *n_in, int32_t n_frames, int
  *   crop + cropToSight with the numpy-path (f64) masks of cropdata.py:30-65, then for every kept point the f32
  *   projection of train.py:31-34 (lidar2Img on the torch path, swapped to (row, col)) appended as two columns:
  *   out f32 [F][cap_out][ncol + 2] = [x y z r ... row col], n_out i32 [F].  cam_from_velo / p2: the f64 matrices of the
- *   masks; proj_*: the matrices of the f32 projection (R0_rect @ Tr_velo_to_cam formed in f32, as torch does). */
+ *   masks; proj_*: the matrices of the f32 projection (R0_rect @ Tr_velo_to_cam formed in f32, as torch does).
+ *   The input stride is cap_points, the output stride cap_out.  n_out[f] is the number of points that passed, which
+ *   may exceed cap_out: only the first cap_out of them, in source order, are stored, and the caller sees the overflow
+ *   in the count (every consumer of (out, n_out) takes min(n_out[f], cap_out)). */
 size_t mvx_crop_project_workspace_bytes(int32_t n_frames, int32_t cap_points);
 int mvx_crop_project_points(const float *pcd, const int32_t *n_in, int32_t n_frames, int32_t cap_points, int32_t ncol,
                             const double *range6_host, const double *cam_from_velo_host, const double *p2_host,

@@ -1602,7 +1602,8 @@ def crop_points(pcd, n_in=None, range6=None, bounds_f32=False, cam_from_velo=Non
 
 def crop_project(pcd, n_in, range6, cam_from_velo64, p2_64, imsize_wh, cam_from_velo32, p2_32, cap_out):
     """Raw clouds f32 (F, cap, 4) -> (points6 (F, cap_out, 6) = [x y z r row col], n_out i32 (F,)): crop + cropToSight
-    (numpy-path f64 masks) and the f32 projection of train.py:31-34 in one compaction pass."""
+    (numpy-path f64 masks) and the f32 projection of train.py:31-34 in one compaction pass.  n_out[f] counts the points that
+    passed and may exceed cap_out: only the first cap_out of them are stored."""
     F, cap, ncol = pcd.shape
     dev = pcd.device
     out = torch.empty((F, cap_out, ncol + 2), dtype=torch.float32, device=dev)
