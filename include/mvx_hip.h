@@ -1386,6 +1386,49 @@ int mvx_render_camera_frames(const float *points6, int32_t ld, const int32_t *n_
                              int32_t image_is_bgr, int32_t thickness, uint8_t *out, int32_t *status, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Running BatchNorm statistics (csrc/bn_running.hip; config.yml `bntrack`, nn.BatchNorm*d(track_running_stats=True)).
+ * Every BatchNorm site of the frame-set path hands its consumer mean_inv f32 [n_frames][2][channels] = (mean,
+ * 1 / sqrt(biased var + eps)) per frame; the apply kernels, mvx_bn_background_frames and the fused BEV writer read only that.
+ * Tracking folds these tensors into the modules' buffers, eval mode fills them from the buffers -- each direction for ALL
+ * sites of a step in one launch, one thread per (site, channel), plain vector stores.  The site table is a HOST array that
+ * travels by value in the kernel arguments (like mvx_frames_t): no host synchronisation, nothing to keep alive.  One launch
+ * takes up to MVX_BN_SITES_PER_LAUNCH sites with up to 8 distinct population vectors (the model has 30 sites and 7); a longer
+ * table goes out in further launches.
+ *   mean_inv                    f32 [n_frames][2][channels] on the device (update: read; mean_inv_sites: written)
+ *   running_mean / running_var  f32 [channels], num_batches_tracked i64 [1]: the module's buffers, on the device
+ *   momentum                    the module's bn.momentum, 0..1 (None, the cumulative average, is refused by the caller)
+ *   row_kind, rows              the layout of the site's row matrix and its row count over all frames: the per-frame populations
+ *                               are those of the site's finaliser -- MVX_ROWS_GRID: rows / n_frames; the row layouts (FUSION,
+ *                               VFE, VOXELS, REAL): (voxels of the frame) x t of `frames_host`, the DENSE population the compact
+ *                               rows stand for.  `rows` must match the layout like in every frame-set entry point.
+ * mvx_bn_running_update_sites (training): the reference runs batch 1, one forward per frame, so the fold is n_frames sequential
+ *   PyTorch updates in frame order; for every frame f with bit f of live_mask set and a population n_f > 0:
+ *     rm = (1 - m) rm + m mean_f;   rv = (1 - m) rv + m var_f n_f / (n_f - 1),   var_f = max(0, 1 / inv_f^2 - eps)
+ *   (n_f = 1 folds the mean and leaves rv alone), the whole chain in float64 registers, each buffer element stored once as
+ *   f32; num_batches_tracked += the number of frames folded.  A frame without population (no voxels: the finalisers give it
+ *   mean 0, inverse deviation 1 / sqrt(eps)) folds nothing and is not counted.  frames_host may be NULL when every site is
+ *   MVX_ROWS_GRID; otherwise frames_host->n_frames == n_frames.
+ * mvx_bn_running_mean_inv_sites (eval): mean_inv[f] = (running_mean, 1 / sqrt(running_var + eps)) for every f < n_frames, the
+ *   inverse deviation computed in float64 and rounded once; momentum, rows, row_kind and num_batches_tracked are not read.
+ * MVX_EINVAL before any launch (no buffer is touched): a null table or buffer pointer, channels <= 0, n_frames outside
+ *   1..MVX_MAX_FRAMES, eps < 0, momentum outside 0..1, an inconsistent layout.
+ */
+#define MVX_BN_SITES_PER_LAUNCH 48
+typedef struct {
+    float *mean_inv;
+    float *running_mean;
+    float *running_var;
+    int64_t *num_batches_tracked;
+    int64_t rows;
+    double momentum;
+    int32_t channels;
+    int32_t row_kind;
+} mvx_bn_site_t;
+int mvx_bn_running_update_sites(const mvx_bn_site_t *sites_host, int32_t n_sites, const mvx_frames_t *frames_host,
+                                int32_t n_frames, uint32_t live_mask, double eps, void *stream);
+int mvx_bn_running_mean_inv_sites(const mvx_bn_site_t *sites_host, int32_t n_sites, int32_t n_frames, double eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ grid) -> the frame's boxes after decoding and NMS (modules/detect.py; the refere
 import torch
 from torch import nn
 
+from modules import _hip
 from modules.imhead import ImageHead
 from modules.voxelnet import VoxelNet
 
@@ -61,6 +62,7 @@ class MVXNet(nn.Module):
         real rows + one padded row per voxel instead of all N*T rows -- identical results because
         inside MVXNet all padded rows of a voxel are identical; ``compact=False`` runs the
         reference's dense formulation."""
+        _hip.require_plain_batchnorm('MVXNet.middle')      # bntrack lives on the frame-set path (modules/bn_running.py)
         if not compact:
             return self.backbone.middle(self.point_features(voxels, imgs, calibs, imsize), idx)
         from modules.voxelnet.Pipe import CompactInputFunction
@@ -76,6 +78,7 @@ class MVXNet(nn.Module):
         (SURVEY Q5).  On the GPU the whole forward is then ONE autograd node over the frame-set kernels (modules/whole.py);
         ``compact='modules'`` keeps the same arithmetic on the per-module autograd path (modules.voxelnet / imhead / layers),
         ``compact=False`` is the reference's dense (1,N,T,23) formulation."""
+        _hip.require_plain_batchnorm('MVXNet.forward')      # bntrack lives on the frame-set path (modules/bn_running.py)
         if not compact:
             return self.backbone(self.point_features(voxels, imgs, calibs, imsize), idx)
         if compact != 'modules':
@@ -96,6 +99,7 @@ class MVXNet(nn.Module):
         from modules import detect, whole
         from modules import Extension as X
         import modules.config as cfg
+        _hip.require_plain_batchnorm('MVXNet.detect')      # bntrack lives on the frame-set path (modules/bn_running.py)
         if not whole.supported(self, voxels, idx):
             raise X.MvxHipError('MVXNet.detect runs on the single-node HIP path: f32 contiguous (1,N,T,9) voxels and (N,4) i64 '
                                 'indices on the GPU, the background rewrite and the HIP RPN on, map sides divisible by 8')

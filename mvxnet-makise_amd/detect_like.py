@@ -38,6 +38,9 @@ def parse_args(argv=None):
     ap.add_argument('--decode', choices=['loss', 'reference'], default='loss')
     ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
                     help='a checkpoint of train_like.py --direction (it holds backbone.rpn.dir.weight): the --dir-offset it was trained with')
+    ap.add_argument('--bn-stats', choices=['auto', 'batch'], default='auto',
+                    help='auto: a checkpoint of train_like.py --bn-track (it holds running_mean keys) runs in eval mode on its '
+                         'running statistics; batch: every frame\'s own statistics even then (for comparison)')
     ap.add_argument('--eval', action='store_true', help='score the written files against the split\'s label_2 (KITTI AP on the GPU)')
     ap.add_argument('--classes', nargs='+', default=['Car'], help='classes scored by --eval')
     ap.add_argument('--extractor-weights', default=None,
@@ -49,6 +52,16 @@ def parse_args(argv=None):
 
 def main(args):
     import modules.config as cfg
+    old = cfg.config.get('bntrack', False)
+    try:
+        return _main(args)
+    finally:
+        cfg.config['bntrack'] = old             # a tracked checkpoint switches it on for the run
+
+
+def _main(args):
+    import modules.config as cfg
+    from modules import bn_running as bnr
     from modules import Extension as X
     from modules import pipeline as pl
     from modules.Calc import bbox3d2bev
@@ -74,9 +87,16 @@ def main(args):
     torch.manual_seed(0)
     state = torch.load(args.checkpoint, map_location=device) if args.checkpoint else None
     direction = state is not None and 'backbone.rpn.dir.weight' in state      # written by train_like.py --direction
+    tracked = bnr.checkpoint_tracks(state) and args.bn_stats != 'batch'      # written by train_like.py --bn-track
+    if bnr.checkpoint_tracks(state) and not tracked:
+        state = bnr.strip_running(state)
+    cfg.config['bntrack'] = tracked
     model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
     if state is not None:
         model.load_state_dict(state)
+    if tracked:
+        model.eval()                            # detect_frame_set then normalises with the running statistics
+        print('running BatchNorm statistics of the checkpoint (eval mode; --bn-stats batch: per-frame statistics)')
     fpn_fn = fpn_maps_for
     if args.extractor_weights:
         model.head.extractor.load_weights(args.extractor_weights).to(device)

@@ -220,6 +220,8 @@ PROTOTYPES = {
                                      _i32, _i32, ctypes.c_uint32, _i32, _p, _p, _p, _sz, _p]),
     'mvx_render_camera_frames': (_i32, [_p, _i32, _p, _i32, _i32, _p, _p, _p, _i32, _p, _f64, _f64, _i32, _i32, _p, _i32, _p,
                                         _i32, _i32, _p, _p, _p, _sz, _p]),
+    'mvx_bn_running_update_sites': (_i32, [_p, _i32, _p, _i32, ctypes.c_uint32, _f64, _p]),
+    'mvx_bn_running_mean_inv_sites': (_i32, [_p, _i32, _i32, _f64, _p]),
 }
 
 
@@ -270,6 +272,15 @@ class FramesDesc(ctypes.Structure):
 
     def ref(self):
         return ctypes.byref(self)
+
+
+BN_SITES_PER_LAUNCH = 48      # MVX_BN_SITES_PER_LAUNCH
+
+
+class BnSite(ctypes.Structure):
+    """mvx_bn_site_t of include/mvx_hip.h: one BatchNorm site of the running-statistics table (device addresses as integers)."""
+    _fields_ = [('mean_inv', _p), ('running_mean', _p), ('running_var', _p), ('num_batches_tracked', _p), ('rows', _i64),
+                ('momentum', _f64), ('channels', _i32), ('row_kind', _i32)]
 
 
 def check(status, what):

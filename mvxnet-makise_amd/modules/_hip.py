@@ -441,15 +441,68 @@ def timer_value(v):
     return float(v)
 
 
-def require_plain_batchnorm():
-    """The kernels normalise with (mean, 1/sqrt(var + eps)) of the batch only -- the reference's configuration
-    (config.yml:19-20: bnaffine False, bntrack False; Blocks.py:10,25).  With affine parameters or running statistics
-    switched on, bn.weight / bn.bias would enter the optimizer with permanently zero gradients and the running buffers
-    would never move, silently: refuse instead."""
+def require_no_bnaffine():
+    """The kernels normalise without affine parameters -- the reference's configuration (config.yml:19: bnaffine False;
+    Blocks.py:10,25).  With them switched on, bn.weight / bn.bias would enter the optimizer with permanently zero gradients,
+    silently: refuse instead.  (``bntrack`` is honoured on the frame-set path: modules/bn_running.py.)"""
     import modules.config as cfg
-    if bool(cfg.config.get('bnaffine', False)) or bool(cfg.config.get('bntrack', False)):
-        raise X.MvxHipError('bnaffine / bntrack are not supported by the HIP BatchNorm kernels (batch statistics, no affine '
-                            'parameters, no running buffers: the reference\'s config.yml:19-20); set both to False')
+    if bool(cfg.config.get('bnaffine', False)):
+        raise X.MvxHipError('bnaffine is not supported by the HIP BatchNorm kernels (no affine parameters: the reference\'s '
+                            'config.yml:19); set it to False')
+
+
+def bn_tracking():
+    """config.yml ``bntrack``: the BatchNorm modules carry running statistics (nn.BatchNorm*d(track_running_stats=True))."""
+    import modules.config as cfg
+    return bool(cfg.config.get('bntrack', False))
+
+
+def require_plain_batchnorm(what='this path'):
+    """The per-frame autograd paths (MVXNet.forward, modules/tape.py, modules/whole.py, the stand-alone blocks) normalise with
+    the batch statistics only and never touch a running buffer: with ``bntrack`` the buffers would not move in training and
+    would not be read in eval, silently: refuse instead and name the path that honours it."""
+    require_no_bnaffine()
+    if bn_tracking():
+        raise X.MvxHipError('bntrack: %s normalises with batch statistics only; running statistics are kept and read on the '
+                            'frame-set path (pipeline.train_step_full / train_step_frame_set / train_step_rows_only, '
+                            'detect.detect_frame_set; train_like.py --mode fast)' % what)
+
+
+# ---------------------------------------------------------------------------------------------
+# Running BatchNorm statistics of a step's sites (csrc/bn_running.hip; modules/bn_running.py)
+# ---------------------------------------------------------------------------------------------
+def bn_site_table(sites):
+    """The host table of mvx_bn_site_t from ``(mean_inv (F,2,C), running_mean (C,), running_var (C,), num_batches_tracked i64
+    (), momentum, row kind, rows)`` per site.  The tensors must outlive the launches that read the table."""
+    table = (X.BnSite * len(sites))()
+    for k, (mi, rm, rv, nbt, momentum, kind, rows) in enumerate(sites):
+        C = rm.numel()
+        if momentum is None:
+            raise X.MvxHipError('BatchNorm momentum None (the cumulative average) is not supported by the running-statistics fold')
+        if not (mi.dtype == rm.dtype == rv.dtype == torch.float32 and nbt.dtype == torch.int64 and mi.dim() == 3 and
+                mi.shape[1:] == (2, C) and rv.numel() == C and nbt.numel() == 1 and mi.is_cuda and rm.is_cuda and rv.is_cuda and
+                nbt.is_cuda and mi.is_contiguous() and rm.is_contiguous() and rv.is_contiguous()):
+            raise X.MvxHipError('a BatchNorm site needs mean_inv f32 (F,2,C) and the f32 / i64 running buffers of C channels, '
+                                'contiguous on the device')
+        s = table[k]
+        s.mean_inv, s.running_mean, s.running_var, s.num_batches_tracked = mi.data_ptr(), rm.data_ptr(), rv.data_ptr(), nbt.data_ptr()
+        s.rows, s.momentum, s.channels, s.row_kind = int(rows), float(momentum), C, int(kind)
+    return table
+
+
+def bn_running_update_sites(table, F, eps, desc=None, live_mask=None):
+    """Fold every site's per-frame (mean, inverse deviation) into its running buffers, frame after frame, in one launch
+    (mvx_bn_running_update_sites).  ``desc``: the frame set's descriptor (the row layouts take their populations from it);
+    ``live_mask``: bit f clear = frame f folds nothing (default: every frame)."""
+    mask = (1 << F) - 1 if live_mask is None else int(live_mask)
+    if len(table):
+        X.call('mvx_bn_running_update_sites', table, len(table), _desc_ref(desc), F, mask, float(eps))
+
+
+def bn_running_mean_inv_sites(table, F, eps):
+    """Every site's mean_inv (F,2,C) = (running_mean, 1/sqrt(running_var + eps)) in one launch (mvx_bn_running_mean_inv_sites)."""
+    if len(table):
+        X.call('mvx_bn_running_mean_inv_sites', table, len(table), F, float(eps))
 
 
 def conv_flops(d_out_planes, d_src_planes, H, W, cin, cout, sd, pd, dgrad=False):
@@ -819,8 +872,10 @@ def _conv2d_flops(F, h, w, cin, cout, flags):
     return 2.0 * F * h * w * cin * cout * (2.25 if flags & FLAG_TAPS2 else 9)     # 2x2 window: 9 of the 16 (tap, parity) blocks run
 
 
-def conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, split=False):
-    """y = ReLU(conv(x) + b) -> (y, mean_inv (F,2,cout)): per-frame statistics finalised in the launch (split kernels: behind it)."""
+def conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, split=False, want_mi=True):
+    """y = ReLU(conv(x) + b) -> (y, mean_inv (F,2,cout)): per-frame statistics finalised in the launch (split kernels: behind it).
+    ``want_mi=False`` (an eval forward on running statistics): the split kernels' finaliser launch is left out and mean_inv is
+    not to be read; the sums built into the kernels are formed as ever."""
     dev = x.device
     y = torch.empty((F, h, w, cout), dtype=torch.float32, device=dev)
     stats, fz = _acc_f64((F, STATS_REPLICAS, 2, cout), dev)
@@ -835,7 +890,7 @@ def conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, split=False):
         else:
             X.call('mvx_conv2d_forward_frames', x, wpk, bias, y, stats, h, w, cin, cout, FLAG_RELU | fz | flags, fin, float(eps),
                    mi, _work_counter(dev), F)
-    if split:
+    if split and want_mi:
         X.call('mvx_bn_finalize_frames', stats, float(h * w), float(eps), mi, cout, F)
     return y, mi
 

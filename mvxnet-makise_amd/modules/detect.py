@@ -99,30 +99,40 @@ def _empty(dev):
 def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw):
     """Detections for every frame of ``batch`` (pipeline.FrameBatch): the forward of ``pipeline.train_step_full`` -- the frame
     set through fusion / VFE / CML and the RPN on this library's kernels, per-frame BatchNorm statistics -- then
-    ``postprocess`` (keyword arguments as there).  ``ready``: a prepared frame set as train_step_full takes it (or None).
+    ``postprocess`` (keyword arguments as there).  With ``bntrack`` it follows ``model.training``: a model in eval mode is
+    normalised with its running statistics (modules/bn_running.py: one table launch in front of the first layer, no statistics
+    pass where a layer has a form without), a model in training mode with the frames' own statistics as ever; the buffers are
+    never written here.  ``ready``: a prepared frame set as train_step_full takes it (or None).
     Returns one dict per batch frame; frames without voxels get empty results.  Reads no gradient and writes none; the
-    data-dependent status words are checked like ``pipeline.read_losses``.  ``keep`` (tests): receives 'heads'."""
+    data-dependent status words are checked like ``pipeline.read_losses``.  ``keep`` (tests): receives 'heads', 'geom', the saved
+    state of the forwards ('saved', 'rpn') and, with ``bntrack``, 'bn_sites'."""
+    from modules import bn_running as bnr
     from modules import frames as fr
     from modules import pipeline as pl
     from modules import rpn_frames as rf
     opts = dict(DEFAULTS, **kw)
     dev = batch.device
+    bn_step = bnr.step(model, train_entry=False)
     fs, live, counts, status = pl._take_ready(batch, ready, torch.cuda.current_stream(dev))
     hw = [float(imsize[0]), float(imsize[1])]
     statuses = [status]
     dets = None
-    with pl._step_scope(dev, train=False):
+    with pl._step_scope(dev, train=False), bn_step as bn:
         if fs is not None:
             model.prepack()
             _hip.arena_begin(dev, doubles=1 << 22)
             F = len(live)
             with torch.no_grad():
+                if bn is not None and bn.eval:
+                    bn.fill(model, F)               # every site's (running_mean, 1/sqrt(running_var + eps)): one launch
                 feat, saved = fr.rows_forward(model, fs, [batch.fpn_levels[f] for f in live], hw, statuses)
                 fr.cml_forward(model, fs, feat, saved, statuses, want_bev=False)
                 heads, rs = rf.rpn_forward(model.backbone.rpn, saved.x3, F, saved.D3, saved.H, saved.W, saved.C3)
                 dets = postprocess(heads, anchors, F, rs['h1'], rs['w1'], read=False, **opts)
             if keep is not None:
-                keep.update(heads=heads, geom=(F, rs['h1'], rs['w1']))
+                keep.update(heads=heads, geom=(F, rs['h1'], rs['w1']), saved=saved, rpn=rs)
+                if bn is not None:
+                    keep['bn_sites'] = bn.records(F, fs.desc)
     pl._check_statuses(statuses)
     out = [_empty(dev) for _ in range(batch.n_frames)]
     if dets is not None:

@@ -18,6 +18,7 @@ import torch
 
 import modules.config as cfg
 from modules import _hip
+from modules import bn_running as bnr
 from modules import Extension as X
 from modules.layers.Blocks import conv_background_on, conv_split_math
 
@@ -95,13 +96,20 @@ def _knocked(like=None, shape=None, dtype=torch.float32):
     return torch.empty_like(like) if shape is None else torch.empty(shape, dtype=dtype, device=like.device)
 
 
-def linear_bn(x, w, b, fs, kind, row_w, eps, tag='fusion', foreign=False):
+def linear_bn(x, w, b, fs, kind, row_w, eps, tag='fusion', foreign=False, bn=None):
     """rows -> (y = ReLU(x w^T + b), mean_inv (F,2,N)) with per-frame statistics formed inside the launch, in the arithmetic of
-    _hip.row_split(tag).  ``foreign``: x was not produced by this library (the sampled image features): _hip.foreign_split."""
+    _hip.row_split(tag).  ``foreign``: x was not produced by this library (the sampled image features): _hip.foreign_split.
+    ``bn``: the layer's BatchNorm module (bnr.site); an eval forward on running statistics runs the GEMM without its sums --
+    the same products -- unless x exists as planes of bf16 pieces only (the GEMM on pre-cut operands has its sums built in)."""
     N = w.shape[0]
     if 'lin_fwd' in KNOCKOUT:
         return _knocked(x, (x.shape[0], N)), _knocked(x, (fs.F, 2, N))
-    return _hip.linear_forward_bn_frames(x, w.reshape(N, -1), b, fs.desc, kind, row_w, eps, _hip.row_split(tag), foreign)
+    split = _hip.row_split(tag)
+    if bnr.eval_mode() and not (getattr(x, '_mvx_planes', None) is not None and _hip.precut_ok(split, x.shape[0], x.shape[1], N)):
+        y, _ = _hip.linear_forward(x, w.reshape(N, -1), b, relu=True, want_stats=False, split=split, foreign=foreign)
+        return y, bnr.site(bn, None, kind, x.shape[0])
+    y, mi = _hip.linear_forward_bn_frames(x, w.reshape(N, -1), b, fs.desc, kind, row_w, eps, split, foreign)
+    return y, bnr.site(bn, mi, kind, x.shape[0])
 
 
 def bn_apply(y, mi, fs, kind):
@@ -233,7 +241,7 @@ def rows_forward(model, fs, fpn_levels, imsize, status_sink, imfeat=None):
     head, bb = model.head, model.backbone
     dev = fs.voxels.device
     F, T, Rt, Vt = fs.F, fs.T, fs.Rt, fs.Vt
-    _hip.require_plain_batchnorm()
+    _hip.require_no_bnaffine()
     S = _Saved()
     S.fs = fs
     eps = cfg.eps
@@ -253,9 +261,9 @@ def rows_forward(model, fs, fpn_levels, imsize, status_sink, imfeat=None):
         status_sink.append(_hip.fp16_weight_status(dev))    # fp16x3: the weight-range guard's word (modules/_hip.py guard_fp16_weight)
     # ---- fusion MLP (imhead/Pipe.py:84-104) on [real rows | one shared padded row per frame]
     x = compact
-    for i, (w, b) in enumerate(head.fusion._layers()):
+    for i, ((w, b), bn) in enumerate(zip(head.fusion._layers(), head.fusion._bns())):
         y, mi = linear_bn(x, w, b, fs, X.ROWS_FUSION, fs.fusion_row_w, eps, 'fusion_%dx%d' % (w.shape[0], w[0].numel()),
-                          foreign=(i == 0))
+                          foreign=(i == 0), bn=bn)
         S.fusion.append((x, w, b, y, mi))
         x = bn_apply(y, mi, fs, X.ROWS_FUSION)
     return _vfe_forward(bb, fs, x, S, eps)
@@ -277,12 +285,13 @@ def _vfe_forward(bb, fs, x, S, eps):
     x = rows23
     for vfe in (bb.svfe.vfe1, bb.svfe.vfe2):
         w, b = vfe.fcn.fc.weight, vfe.fcn.fc.bias
-        y, mi = linear_bn(x, _hip.padded_weight(w.reshape(w.shape[0], -1), x.shape[1]), b, fs, X.ROWS_VFE, fs.row_w, eps, 'vfe')
+        y, mi = linear_bn(x, _hip.padded_weight(w.reshape(w.shape[0], -1), x.shape[1]), b, fs, X.ROWS_VFE, fs.row_w, eps, 'vfe',
+                          bn=vfe.fcn.bn)
         out, am = _hip.vfe_bn_max_concat(y, mi, Vt, T, fs)
         S.vfe.append((x, w, b, y, mi, am))
         x = out
     w, b = bb.fcn.fc.weight, bb.fcn.fc.bias
-    y, mi = linear_bn(x, w, b, fs, X.ROWS_VFE, fs.row_w, eps, 'vfe')
+    y, mi = linear_bn(x, w, b, fs, X.ROWS_VFE, fs.row_w, eps, 'vfe', bn=bb.fcn.bn)
     feat, am = _hip.bn_segment_max(y, mi, Vt, T, fs)
     S.head = (x, w, b, y, mi, am)
     return feat, S
@@ -331,7 +340,8 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
     dev = fs.voxels.device
     F, T, Rt, Vt = fs.F, fs.T, fs.Rt, fs.Vt
     eps = cfg.eps
-    _hip.require_plain_batchnorm()
+    _hip.require_no_bnaffine()
+    bn_eval = bnr.eval_mode()         # running statistics: the layers run without their sums where an entry point has that form
     # ---- reindex + conv1 through the voxel-GEMM factorisation (VoxelNet.py:16-22, voxelnet/Pipe.py:36)
     D0, H, W = cfg.voxelshape[2], cfg.voxelshape[0], cfg.voxelshape[1]
     c1, c2, c3 = bb.cml.conv1, bb.cml.conv2, bb.cml.conv3
@@ -353,7 +363,8 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
     else:
         # only the tiles of y1 that hold a site next to a voxel are built: the flags of this layer's output from grid_activity
         y1, stats = _hip.sparse_conv_output_tiles(P, idx_grid, (D0, H, W), b1, cout, c1._sd, c1._pd, ga['layers'][0][2], F, out=y1)
-    mi1 = _hip.bn_finalize(stats, D1 * H * W, eps, F)
+    # (the sums are built into the sparse output kernel: an eval forward leaves them unused and skips their finaliser)
+    mi1 = bnr.site(c1.bn, None if bn_eval else _hip.bn_finalize(stats, D1 * H * W, eps, F), X.ROWS_GRID, F * D1 * H * W)
 
     def dilate(li):
         return ga['layers'][li]
@@ -396,7 +407,8 @@ def cml_forward(model, fs, feat, S, status_sink, want_bev=True):
             y, mi = _knocked(x_in, (F * dout, H, W, co)), _knocked(x_in, (F, 2, co))
         else:
             y, mi = _hip.conv3d_forward_bg(x_in, wpk, b, co, sd, pd, _hip.Background(c_in, mask_in, hflag_in), mask_o, bg_pre,
-                                           finalize_eps=eps, split=split, F=F, bg_taps=True)
+                                           want_stats=not bn_eval, finalize_eps=eps, split=split, F=F, bg_taps=True)
+        mi = bnr.site(m.bn, None if bn_eval else mi, X.ROWS_GRID, F * dout * H * W)
         c_o, ybg_o = background(bg_pre, b, mi, dout, co)         # the background of this layer's output
         if want_bev and li == 1 and co <= 64 and 'bn_apply_cml' not in KNOCKOUT and BEV_FUSED:
             # the last layer's normalised output goes straight into the reference's (F, C * D, H, W) layout

@@ -144,6 +144,10 @@ class ImageFeatureFusion(nn.Module):
                 (self.fcn2.fc.weight, self.fcn2.fc.bias), (self.conv2.conv.weight, self.conv2.conv.bias),
                 (self.fcn3.fc.weight, self.fcn3.fc.bias))
 
+    def _bns(self):
+        """The BatchNorm modules of ``_layers``, in its order."""
+        return (self.fcn1.bn, self.conv1.bn, self.fcn2.bn, self.conv2.bn, self.fcn3.bn)
+
     def forward_rows(self, x2d, row_w=None, count=None):
         """rows (R,768) [+ multiplicities] -> (R,16)."""
         if _hip.split_pieces() == 4 and x2d.is_cuda and x2d.is_contiguous() and _hip.amax_of(x2d) is None:

@@ -4,7 +4,9 @@
 Reference: modules/layers/Blocks.py -- every block is  affine -> ReLU -> BatchNorm  with
 batch statistics in train and eval, biased variance, eps = cfg.eps, no affine, no buffers
 (Blocks.py:10,16; config.yml:19-20).  State-dict keys are unchanged (``fc.weight`` ...), so
-reference checkpoints load.
+reference checkpoints load.  With ``bntrack`` the ``bn`` modules carry torch's running buffers under
+torch's key names; they are kept and read on the frame-set path only (modules/bn_running.py): a
+block called on its own refuses.
 """
 import torch
 from torch import nn
@@ -55,6 +57,7 @@ class FCNFunction(torch.autograd.Function):
 
 def fcn_rows(x2d, weight, bias, row_w=None, count=None, foreign=True):
     count = x2d.shape[0] if count is None else count
+    _hip.require_plain_batchnorm('a row block called on its own (FCN / 1x1 CRB2d)')
     return FCNFunction.apply(x2d, weight, bias, cfg.eps, row_w, float(count), foreign)
 
 
@@ -63,7 +66,7 @@ class FCN(nn.Module):
 
     def __init__(self, cin, cout):
         super().__init__()
-        _hip.require_plain_batchnorm()
+        _hip.require_no_bnaffine()
         self.fc = nn.Linear(cin, cout)
         self.bn = nn.BatchNorm2d(cout, eps=cfg.eps, affine=cfg.bnaffine, track_running_stats=cfg.bntrack)
 
@@ -252,7 +255,7 @@ class CRB3d(nn.Module):
 
     def __init__(self, cin, cout, k, s, p):
         super().__init__()
-        _hip.require_plain_batchnorm()
+        _hip.require_no_bnaffine()
         self.conv = nn.Conv3d(cin, cout, k, s, p)
         self.bn = nn.BatchNorm3d(cout, eps=cfg.eps, affine=cfg.bnaffine, track_running_stats=cfg.bntrack)
         k3, s3, p3 = _triple(k), _triple(s), _triple(p)
@@ -265,6 +268,7 @@ class CRB3d(nn.Module):
         """Fused reindex + this block on sparse voxel rows: the [V x 27*Cout] factorisation (exact, see
         VoxelGemmCRB3dFunction); the dense grid is never built."""
         aux = {} if conv_background_on() else None
+        _hip.require_plain_batchnorm('CRB3d called on its own')
         out = VoxelGemmCRB3dFunction.apply(feat, coords, self.conv.weight, self.conv.bias, tuple(dhw), self._sd,
                                            self._pd, cfg.eps, aux)
         res = _hip.mark_lib(out.permute(3, 0, 1, 2).unsqueeze(0))
@@ -275,6 +279,7 @@ class CRB3d(nn.Module):
     def forward(self, x):
         if x.shape[0] != 1:
             raise NotImplementedError('batch size 1 only (reference VoxelNet.py:19)')
+        _hip.require_plain_batchnorm('CRB3d called on its own')
         # squeeze, not x[0]: the backward of a select allocates zeros and copies the whole gradient
         xc = x.squeeze(0).permute(1, 2, 3, 0).contiguous()  # no-op when already channels-last
         bg_in = getattr(x, '_mvx_background', None) if conv_background_on() else None
@@ -349,7 +354,7 @@ class CRB2d(nn.Module):
 
     def __init__(self, cin, cout, k, s, p):
         super().__init__()
-        _hip.require_plain_batchnorm()
+        _hip.require_no_bnaffine()
         self.conv = nn.Conv2d(cin, cout, k, s, p)
         self.bn = nn.BatchNorm2d(cout, eps=cfg.eps, affine=cfg.bnaffine, track_running_stats=cfg.bntrack)
         self._pointwise = (k == 1 and s == 1 and p == 0)
@@ -359,6 +364,7 @@ class CRB2d(nn.Module):
         object.__setattr__(self, '_pack2d', Block2d._Pack())
 
     def forward(self, x):
+        _hip.require_plain_batchnorm('CRB2d called on its own')
         if self._pointwise and x.is_cuda:
             # (b, c, h, w) -> rows (b*h*w, c); a permuted channels-last input costs no copy
             rows = x.permute(0, 2, 3, 1)
@@ -379,7 +385,7 @@ class DeCRB2d(nn.Module):
 
     def __init__(self, cin, cout, k, s, p):
         super().__init__()
-        _hip.require_plain_batchnorm()
+        _hip.require_no_bnaffine()
         self.deconv = nn.ConvTranspose2d(cin, cout, k, s, p)
         self.bn = nn.BatchNorm2d(cout, eps=cfg.eps, affine=cfg.bnaffine, track_running_stats=cfg.bntrack)
         from modules.layers import Block2d
@@ -388,6 +394,7 @@ class DeCRB2d(nn.Module):
         object.__setattr__(self, '_pack2d', Block2d._Pack())
 
     def forward(self, x):
+        _hip.require_plain_batchnorm('DeCRB2d called on its own')
         if _block2d_on(x, self._kind):
             from modules.layers.Block2d import Block2dFunction
             out = Block2dFunction.apply(x, self.deconv.weight, self.deconv.bias, self._kind, self._stride, self._pack2d)

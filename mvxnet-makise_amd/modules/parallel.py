@@ -2,7 +2,11 @@
 all-reduce (RCCL over xGMI, `nccl` backend; `gloo` on CPU for tests) of a flat fp32 gradient
 bucket per step.  The reference has no distributed code; this is the
 MI355X-native addition of SURVEY section 8e.  Ring all-reduce is per-link bound on xGMI, so the
-whole trainable gradient (<= 29.5 MB) goes out as a single large bucket."""
+whole trainable gradient (<= 29.5 MB) goes out as a single large bucket.
+
+Only gradients travel.  With ``bntrack`` (modules/bn_running.py) every rank folds the statistics of its OWN frames into its own
+running BatchNorm buffers and rank 0's are saved with the checkpoint: there is no buffer all-reduce, and
+``assert_replicas_in_sync`` compares parameters, not buffers."""
 import collections
 import os
 

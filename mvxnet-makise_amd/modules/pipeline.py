@@ -12,6 +12,7 @@ import torch
 
 import modules.config as cfg
 from modules import _hip
+from modules import bn_running as bnr
 from modules import tape
 
 
@@ -465,6 +466,9 @@ def _lane_flat(flat, k):
 def _train_step_frame_set_lanes(model, batch, grad_mid, imsize, ready, prepare_next, keep_mid):
     """train_step_frame_set with SET_LANES > 1 (see SET_LANES)."""
     from modules import frames as fr
+    if _hip.bn_tracking():
+        raise _hip.X.MvxHipError('bntrack: the running statistics are folded frame after frame from ONE frame set; '
+                                 'pipeline.SET_LANES > 1 splits the step into several')
     dev = batch.device
     main = torch.cuda.current_stream(dev)
     if ready is None:
@@ -547,16 +551,19 @@ def train_step_frame_set(model, batch, grad_mid, imsize, ready=None, prepare_nex
     if SET_LANES > 1:
         return _train_step_frame_set_lanes(model, batch, grad_mid, imsize, ready, prepare_next, keep_mid)
     dev = batch.device
+    bn_step = bnr.step(model)                       # bntrack: the step's BatchNorm sites (refuses an eval model here)
     fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev))
     statuses = [status]
     next_ready = None
-    with _step_scope(dev):
+    with _step_scope(dev), bn_step as bn:
         if fs is not None:
             model.prepack()
             _hip.arena_begin(dev, doubles=1 << 21)
             gm = grad_mid if grad_mid.shape[0] == 1 or len(live) == batch.n_frames else grad_mid[live]
             with torch.no_grad():
                 mid, saved = fr.middle_forward(model, fs, [batch.fpn_levels[f] for f in live], imsize, statuses)
+                if bn is not None:
+                    bn.update(fs.F, fs.desc)        # the running buffers: one launch behind the forward
                 fr.middle_backward(model, saved, gm)
             if keep_mid is not None:
                 for k in range(len(live)):
@@ -578,9 +585,10 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
     the frames' FPN maps at the projected points + the fusion MLP (imhead/Pipe.py:23-104), forward and backward."""
     from modules import frames as fr
     dev = batch.device
+    bn_step = bnr.step(model)
     fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev))
     next_ready = None
-    with _step_scope(dev, async_wgrad=True):
+    with _step_scope(dev, async_wgrad=True), bn_step as bn:
         if fs is not None:
             cap_rows = batch.n_frames * (batch.cap_points + 1)
             if 'imfeat' not in state or state['imfeat'].shape[0] < cap_rows:
@@ -595,6 +603,8 @@ def train_step_rows_only(model, batch, state, ready=None, prepare_next=None, wit
                     state['statuses'] = statuses
                 else:
                     feat, saved = fr.rows_forward(model, fs, None, None, [], imfeat=state['imfeat'][:fs.Rt + fs.F])
+                if bn is not None:
+                    bn.update(fs.F, fs.desc)
                 fr.rows_backward(model, saved, state['dfeat'][:fs.Vt])
         if prepare_next is not None:
             next_ready = _prepare_next(dev, prepare_next, lambda: prepare_frame_set(prepare_next))
@@ -816,7 +826,9 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     ``read=False`` leaves the losses on the device (out['losses_dev'] (F,2)) and skips the status read: the caller reads
     them a step later, so the host never waits for the step it has just enqueued.
     ``keep`` (tests): a dict that receives the step's intermediate maps -- 'x3' the normalised CML output, channels-last
-    [F*D3][H][W][C3] (BEV channel c*D3 + d, VoxelNet.py:36), 'heads' (F*h1*w1, 16) = [cls logits | reg], 'geom'."""
+    [F*D3][H][W][C3] (BEV channel c*D3 + d, VoxelNet.py:36), 'heads' (F*h1*w1, 16) = [cls logits | reg], 'geom', 'saved' / 'rpn'
+    the saved state of the two forwards and, with ``bntrack``, 'bn_sites' = (BatchNorm module, mean_inv, per-frame populations)
+    of every site the step folded into the running buffers (modules/bn_running.py)."""
     from modules import frames as fr
     from modules import rpn_frames as rf
     dev = batch.device
@@ -828,13 +840,17 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
         raise _hip.X.MvxHipError('the direction head is trained by FocalLoss(direction=True) on MVXNet(direction=True): the model %s '
                                  'rpn.dir, the criterion is %s' % ('has' if hasattr(model.backbone.rpn, 'dir') else 'has no',
                                                                    type(criterion).__name__ + ('(direction=True)' if getattr(criterion, 'direction', False) else '')))
+    if not rpn_hip and _hip.bn_tracking():
+        raise _hip.X.MvxHipError('bntrack: the torch RPN modules of rpn_hip=False normalise with batch statistics only; the running '
+                                 'statistics are kept on the frame-set RPN (rpn_hip=True)')
+    bn_step = bnr.step(model)
     target_tensors =(x for t in targets if t is not None for x in tuple(t[0]) + tuple(t[1]) + (t[2], t[3])
                       if isinstance(x, torch.Tensor) and x.is_cuda)      # written on the preparation stream too (target_fn)
     fs, live, counts, status = _take_ready(batch, ready, torch.cuda.current_stream(dev), also=target_tensors)
     out = {'loss': [], 'cls': [], 'reg': [], 'voxels': counts, 'live': live}
     hw = [float(imsize[0]), float(imsize[1])]
     statuses = [status]
-    with _step_scope(dev, async_wgrad=True):
+    with _step_scope(dev, async_wgrad=True), bn_step as bn:
         if fs is not None:
             model.prepack()
             _hip.arena_begin(dev, doubles=1 << 22)
@@ -846,12 +862,17 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
                     fr.cml_forward(model, fs, feat, saved, statuses, want_bev=False)
                     rpn = model.backbone.rpn
                     heads, rs = rf.rpn_forward(rpn, saved.x3, F, saved.D3, saved.H, saved.W, saved.C3)
+                    if bn is not None:
+                        bn.update(F, fs.desc)       # the running buffers of all 30 sites: one launch behind the forward
                     if frames_loss:
                         losses, has_reg, d_heads = criterion.heads_loss_frames(heads, F, rs['h1'], rs['w1'], tl, anchors)
                     else:
                         losses, has_reg, d_heads = heads_loss(heads, F, rs['h1'], rs['w1'], tl, criterion, anchors)
                     if keep is not None:
-                        keep.update(x3=saved.x3, heads=heads, geom=(F, saved.D3, saved.H, saved.W, saved.C3, rs['h1'], rs['w1']))
+                        keep.update(x3=saved.x3, heads=heads, geom=(F, saved.D3, saved.H, saved.W, saved.C3, rs['h1'], rs['w1']),
+                                    saved=saved, rpn=rs)
+                        if bn is not None:
+                            keep['bn_sites'] = bn.records(F, fs.desc)
                     g_cl = rf.rpn_backward(rpn, rs, d_heads)
                     fr.rows_backward(model, saved, fr.cml_backward(model, saved, None, g_cl=g_cl))
                 else:

@@ -25,6 +25,7 @@ import torch
 
 import modules.config as cfg
 from modules import _hip
+from modules import bn_running as bnr
 from modules import Extension as X
 
 TAPS2 = _hip.FLAG_TAPS2
@@ -142,9 +143,15 @@ def _desc(F):
 
 
 # The convolution wrappers of _hip in this RPN's arithmetic (_split) and with its gradient targets (_grad_of).
-def _conv(x, wpk, bias, F, h, w, cin, cout, flags, eps):
-    """y = ReLU(conv(x) + b) with per-frame statistics finalised in the launch -> (y, mean_inv (F,2,cout))."""
-    return _hip.conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, _split())
+def _conv(x, wpk, bias, F, h, w, cin, cout, flags, eps, bn=None):
+    """y = ReLU(conv(x) + b) with per-frame statistics finalised in the launch -> (y, mean_inv (F,2,cout)); ``bn``: the layer's
+    BatchNorm module as a site of the step (bnr.site: with running statistics in eval mode the kernel's own sums stay
+    unused); None: a stand-alone block (modules/layers/Block2d.py), batch statistics."""
+    if bn is None:
+        return _hip.conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, _split())
+    ev = bnr.eval_mode()
+    y, mi = _hip.conv2d_forward(x, wpk, bias, F, h, w, cin, cout, flags, eps, _split(), want_mi=not ev)
+    return y, bnr.site(bn, None if ev else mi, X.ROWS_GRID, F * h * w)
 
 
 def _bn_apply(y, mi, F):
@@ -183,7 +190,8 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
     are 20 wide, [cls (2) | reg (14) | dir logits (2) | 0 0] (``head_layout``)."""
     dev = x_cl.device
     eps = cfg.eps
-    _hip.require_plain_batchnorm()
+    _hip.require_no_bnaffine()
+    bn_eval = bnr.eval_mode()
     pk = _packs_of(rpn)
     S = {'F': F, 'geom': (planes, H, W, Cp), 'blocks': []}
     x, h, w, C, pl = x_cl, H, W, Cp, planes
@@ -197,13 +205,13 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
                 h, w = h // 2, w // 2
                 cin = 4 * pl * C
                 wpk = pk.get(('s2', bi), wt, lambda wt=wt, pl=pl: _s2d_weight(wt, pl), False)
-                y, mi = _conv(xs, wpk, b, F, h, w, cin, cout, TAPS2, eps)
+                y, mi = _conv(xs, wpk, b, F, h, w, cin, cout, TAPS2, eps, m.bn)
                 layers.append(dict(kind='s2', x=xs, y=y, mi=mi, m=m, cin=cin, cout=cout, h=h, w=w, planes=pl, cfull=C, bi=bi))
                 pl = 1
             else:
                 cin = C
                 wpk = pk.get(('s1', bi, li), wt, lambda wt=wt: wt, False)
-                y, mi = _conv(x, wpk, b, F, h, w, cin, cout, 0, eps)
+                y, mi = _conv(x, wpk, b, F, h, w, cin, cout, 0, eps, m.bn)
                 layers.append(dict(kind='s1', x=x, y=y, mi=mi, m=m, cin=cin, cout=cout, h=h, w=w, bi=bi, li=li))
             x = _bn_apply(y, mi, F)
             C = cout
@@ -214,7 +222,7 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
     # deconv1: stride-1 transposed convolution = convolution with the flipped kernel, channel axes swapped
     d1 = rpn.deconv1
     wc = pk.get(('d1',), d1.deconv.weight, lambda: d1.deconv.weight.flip(2, 3).transpose(0, 1).contiguous(), False)
-    y, mi = _conv(x1, wc, d1.deconv.bias, F, h1, w1, 128, 256, 0, eps)
+    y, mi = _conv(x1, wc, d1.deconv.bias, F, h1, w1, 128, 256, 0, eps, d1.bn)
     _hip.bn_apply_strided(y, mi, up, rows, 256, 768, 0, F)
     S['d1'] = dict(x=x1, y=y, mi=mi)
     # deconv2 / deconv3: kernel = stride -> row GEMM + normalising pixel shuffle into the concat slice
@@ -225,7 +233,9 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
         w_all = wt.permute(2, 3, 1, 0).reshape(s * s * cout, cin).contiguous()     # row (i*s+j)*Cout + co
         xr = xk.view(F * hk * wk, cin)
         t, _ = _hip.linear_forward(xr, w_all, b.repeat(s * s), relu=True, want_stats=False, split=_hip.row_split('rpn'))
-        mi = _hip.bn_finalize(_hip.row_stats_frames(t, cout, F), hk * wk * s * s, eps, F)
+        # (statistics and finaliser are launches of their own here: an eval forward on running statistics has neither)
+        mi = bnr.site(m.bn, None if bn_eval else _hip.bn_finalize(_hip.row_stats_frames(t, cout, F), hk * wk * s * s, eps, F),
+                      X.ROWS_GRID, F * hk * wk * s * s)
         _hip.d2s_bn_apply(t, mi, up, F, hk, wk, s, cout, 768, off)
         S['dk'].append(dict(x=xr, t=t, mi=mi, m=m, s=s, off=off, h=hk, w=wk, w_all=w_all, cin=cin, cout=cout))
     # heads (Pipe.py:64-65,74): one GEMM, 16 columns

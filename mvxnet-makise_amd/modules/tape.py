@@ -41,6 +41,7 @@ def _call(tape, fn, needs_first, *args):
 def middle_forward(model, voxels, fpn_levels, idx, imsize, prepared, status_sink):
     """Forward of MVXNet.middle (compact rows) for one frame; returns (mid (1,128,H,W), tape)."""
     head, bb = model.head, model.backbone
+    _hip.require_plain_batchnorm('the per-frame executor (modules/tape.py)')
     tape = []
     v = voxels.squeeze(0) if voxels.dim() == 4 else voxels[0]
     n, t, c = v.shape

@@ -110,7 +110,15 @@ def parse_args(argv=None):
     ap.add_argument('--dir-weight', type=float, default=0.2, help='--direction: weight of the direction loss (SECOND\'s value)')
     ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
                     help='--direction: yaw at which the direction bit flips (SECOND\'s pi/4); detect_like.py takes the same value')
+    ap.add_argument('--bn-track', action='store_true',
+                    help='--mode fast: running BatchNorm statistics (config.yml bntrack: True does the same): the checkpoints carry '
+                         'running_mean / running_var / num_batches_tracked, detect_like.py then runs the model in eval mode')
+    ap.add_argument('--bn-momentum', type=float, default=0.1, help='--bn-track: momentum of the running statistics (torch\'s default)')
     args = ap.parse_args(argv)
+    if args.bn_track and args.mode != 'fast':
+        ap.error('--bn-track needs --mode fast: the running statistics are kept on the frame-set path')
+    if not 0.0 <= args.bn_momentum <= 1.0:
+        ap.error('--bn-momentum must lie in 0..1')
     if args.direction and (args.mode != 'fast' or args.loss != 'focal'):
         ap.error('--direction needs --mode fast --loss focal: the direction head is trained by the focal loss of the frame-set '
                  'heads only')
@@ -210,8 +218,21 @@ def fast_chunks(n_frames, frames_per_rank, world):
 
 
 def train(args):
+    """The training loop; ``--bn-track`` switches ``bntrack`` on for its duration (the configuration is restored on return)."""
+    import modules.config as cfg
+    old = cfg.config.get('bntrack', False)
+    if getattr(args, 'bn_track', False):
+        cfg.config['bntrack'] = True
+    try:
+        return _train(args)
+    finally:
+        cfg.config['bntrack'] = old
+
+
+def _train(args):
     check_optimizer_args(args)
     import modules.config as cfg
+    from modules import bn_running as bnr
     from modules import parallel
     from modules.Calc import bbox3d2bev
     from modules.data import Load as load, Preprocessing as pre
@@ -276,7 +297,14 @@ def train(args):
             % (sum(r.shape[0] for r, _ in rows), '' if args.ignore_dontcare else ' (not used)', sum(b.shape[0] for _, b in rows),
                '/'.join(args.ignore_classes) or 'no class', args.min_gt_points))
     torch.manual_seed(0)
+    tracked = bool(cfg.config.get('bntrack', False))
+    if tracked and args.mode != 'fast':
+        raise SystemExit('bntrack needs --mode fast: the running BatchNorm statistics are kept on the frame-set path')
     model = (MVXNet(direction=True) if args.direction else MVXNet()).to(device)
+    if tracked:
+        # every rank folds its own frames into its own buffers and rank 0's are saved: no buffer all-reduce (modules/parallel.py)
+        bnr.set_momentum(model, getattr(args, 'bn_momentum', 0.1))
+        say('bntrack: running BatchNorm statistics, momentum %g' % getattr(args, 'bn_momentum', 0.1))
     if args.loss == 'focal':
         from modules.voxelnet.FocalLoss import FocalLoss
         if args.direction:
@@ -305,7 +333,8 @@ def train(args):
     imsize = torch.Tensor(cfg.imsize).to(device)
     os.makedirs(args.checkpoints, exist_ok=True)
     if args.lastiter > 0:
-        model.load_state_dict(torch.load(os.path.join(args.checkpoints, 'epoch%d.pkl' % args.lastiter), map_location=device))
+        if bnr.load_state(model, torch.load(os.path.join(args.checkpoints, 'epoch%d.pkl' % args.lastiter), map_location=device)):
+            say('bntrack: epoch%d.pkl holds no running statistics: the buffers start at mean 0, variance 1' % args.lastiter)
         opt.load_state_dict(torch.load(os.path.join(args.checkpoints, 'epoch%d_opt.pkl' % args.lastiter), map_location=device))
     tv = have_torchvision()
     fpn_fn = fpn_maps_for

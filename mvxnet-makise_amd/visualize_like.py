@@ -28,6 +28,9 @@ def parse_args(argv=None):
     ap.add_argument('--checkpoint', default=None, help='state dict written by train_like.py: detections from running the model')
     ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
                     help='a checkpoint of train_like.py --direction (it holds backbone.rpn.dir.weight): the --dir-offset it was trained with')
+    ap.add_argument('--bn-stats', choices=['auto', 'batch'], default='auto',
+                    help='auto: a checkpoint of train_like.py --bn-track (it holds running_mean keys) runs in eval mode on its '
+                         'running statistics; batch: every frame\'s own statistics even then')
     ap.add_argument('--split', default='train', help='ImageSets/<split>.txt')
     ap.add_argument('--out', default=None, help='picture directory (default <dataroot>/pictures)')
     ap.add_argument('--view', choices=['bev', 'camera', 'both'], default='both')
@@ -56,6 +59,7 @@ def read_result_boxes(path, calib):
 def _model_detector(args, device, data, names):
     """Frames -> (FrameBatch, per-frame detections) through the model of ``--checkpoint``, as detect_like.py runs it."""
     import modules.config as cfg
+    from modules import bn_running as bnr
     from modules import pipeline as pl
     from modules.Calc import bbox3d2bev
     from modules.data import Preprocessing as pre
@@ -68,8 +72,14 @@ def _model_detector(args, device, data, names):
     torch.manual_seed(0)
     state = torch.load(args.checkpoint, map_location=device)
     direction = 'backbone.rpn.dir.weight' in state                            # written by train_like.py --direction
+    tracked = bnr.checkpoint_tracks(state) and args.bn_stats != 'batch'      # written by train_like.py --bn-track
+    if bnr.checkpoint_tracks(state) and not tracked:
+        state = bnr.strip_running(state)
+    cfg.config['bntrack'] = tracked             # main() restores it
     model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
     model.load_state_dict(state)
+    if tracked:
+        model.eval()                            # detect_frame_set then normalises with the running statistics
     kw = dict(dir_offset=args.dir_offset) if direction else {}
     cap = max(d[0].shape[0] for d in data)
 
@@ -80,6 +90,15 @@ def _model_detector(args, device, data, names):
 
 
 def main(args):
+    import modules.config as cfg
+    old = cfg.config.get('bntrack', False)
+    try:
+        return _main(args)
+    finally:
+        cfg.config['bntrack'] = old             # a tracked checkpoint switches it on for the run
+
+
+def _main(args):
     import modules.config as cfg
     from modules import Extension as X
     from modules import render
