@@ -1077,6 +1077,57 @@ int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t cls_sl, int6
                           float *dbg_corners, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Test-time augmentation, the fusion of the views' detections (csrc/tta.hip).  The reference has none of it.
+ *
+ * A view is a row (phi, s, flip, 0) as Geometry.draw_geometry writes `glob`, applied to the cloud by mvx_geom_points_frames'
+ * global step; the detection step then runs over n_frames * n_views frames, view-major inside a source frame: frame
+ * f * n_views + v is view v of source frame f.
+ *
+ * mvx_tta_fuse_frames: inputs (device) are that step's padded output,
+ *     boxes f32 [n_frames * n_views][post_max][7] xyzlwhr, scores f32 [n_frames * n_views][post_max], counts i32
+ *     [n_frames * n_views] (clamped to 0..post_max), each view's list in its own order, and views f32 [n_views][4].
+ *   1. tta_merge: every box back into the source frame, the inverse of Geometry.transform_boxes, in f64 from the f32 inputs
+ *      and rounded to f32 once: with the flip y <- -y and r <- -r; (x, y) <- ((x, y) @ R(-phi)) / s, z <- z / s,
+ *      (l, w, h) <- (l, w, h) / s, r <- r - phi wrapped into [-pi, pi).  A row that is exactly (0, 1, 0) copies its boxes
+ *      bitwise.  The N = n_views * post_max entries are ordered by score descending, then view, then rank ascending (a total
+ *      order).  BEV corners and bounding circle as mvx_detect_frames forms them.  An entry with a non-finite box or score is
+ *      dropped and sets MVX_TTA_NONFINITE.
+ *   2. tta_mask: for every pair j > i in merged order ONE IoU (bboxOverlap's arithmetic; pairs whose bounding circles cannot
+ *      touch count as IoU 0) gives two bits: sup = IoU > iou_thr, vote = IoU > fuse_iou.  Pairs of the same view are pairs
+ *      like any other.
+ *   3. tta_fuse: entry i is a HEAD iff no earlier head has its sup bit on i; every other entry belongs to the first head that
+ *      suppresses it.  A member votes for its head iff its vote bit with that head is set and no earlier entry of its view
+ *      has voted for that head; the head votes first, for its own view.  With weights w = score and the sums over the voters
+ *      in merged order, in f64: x y z l w h = sum(w q) / sum(w); d_j = r_j - r_head wrapped into [-pi/2, pi/2), with
+ *      full_turn != 0 into [-pi, pi); r = r_head + sum(w d) / sum(w) wrapped into [-pi, pi); rounded to f32 once.  A cluster
+ *      whose only voter is its head (or whose weights do not sum to a positive number) copies the head's box bitwise.  Fused
+ *      score = (sum of the voters' scores) / n_views in f64, rounded once: with n_views = 1 the head's score bitwise.
+ *      Clusters with fewer than min_views voters are dropped; the rest are ordered by fused score descending, then head
+ *      position ascending, and the first out_max are written.
+ *   The heads are exactly the boxes a greedy NMS over the union of the views keeps, in their original poses.  Averaging moves
+ *   them, so IoU <= iou_thr holds for the heads and not strictly for the fused poses.  For car-shaped boxes a fuse_iou above
+ *   roughly 0.26 excludes voters a quarter turn off their head, so the half-turn wrap never sits near its seam.  The callers'
+ *   defaults fuse_iou = 0.5 and min_views = 1 are design choices, not measured optima.
+ *   Outputs (device), per source frame: out_boxes f32 [n_frames][out_max][7], out_scores f32 [n_frames][out_max],
+ *   out_n_views i32 [n_frames][out_max] the voters of the cluster, out_src i32 [n_frames][out_max] = view * post_max + rank of
+ *   the cluster's head, out_counts i32 [n_frames] (the rest padded with 0 / src -1), status i32 [n_frames]
+ *   (MVX_TTA_NONFINITE).
+ *   Limits (MVX_EINVAL before any launch): 1 <= n_frames <= MVX_MAX_FRAMES, 1 <= n_views <= MVX_TTA_MAX_VIEWS,
+ *   n_views * post_max <= MVX_TTA_MAX_BOXES, 1e-3 <= iou_thr <= fuse_iou < 1, 1 <= min_views <= n_views,
+ *   1 <= out_max <= n_views * post_max, non-NULL inputs / outputs, a 256-byte aligned workspace of
+ *   mvx_tta_workspace_bytes(n_frames, n_views, post_max) bytes (0 for sizes outside the limits).  Three launches whatever
+ *   n_frames and n_views are, no float atomics, every sum in a fixed order (bitwise reproducible), no host synchronisation.
+ */
+#define MVX_TTA_MAX_VIEWS 8
+#define MVX_TTA_MAX_BOXES 1024
+#define MVX_TTA_NONFINITE 2
+size_t mvx_tta_workspace_bytes(int32_t n_frames, int32_t n_views, int32_t post_max);
+int mvx_tta_fuse_frames(const float *boxes, const float *scores, const int32_t *counts, const float *views, int32_t n_frames,
+                        int32_t n_views, int32_t post_max, float iou_thr, float fuse_iou, int32_t min_views, int32_t out_max,
+                        int32_t full_turn, float *out_boxes, float *out_scores, int32_t *out_n_views, int32_t *out_src,
+                        int32_t *out_counts, int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI object evaluation (csrc/kitti_eval.hip): AP for 2D bbox, BEV and 3D, plus AOS, in the semantics of the widely used
  * kitti-object-eval-python tool as DESIGN.md section 3.17 states them.  The reference has no evaluation.
  *

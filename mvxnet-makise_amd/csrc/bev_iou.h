@@ -132,6 +132,26 @@ __device__ __forceinline__ float quad_iou(const Polys &w, const float *qa, const
     return inter / (a1 + a2 - inter);
 }
 
+// Order-preserving map of a float to an unsigned key (larger float -> larger key); -0 counts as +0 so equal logits tie
+// (the sort keys of detect_select, tta_merge and tta_fuse).
+__device__ __forceinline__ unsigned order_key(float x) {
+    const unsigned u = x == 0.f ? 0u : __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// BEV quad of a box b = xyzlwhr (Calc.bbox3d2bev), as detect_select and tta_merge form it
+__device__ __forceinline__ void box_quad(const float *b, P2 *q) {
+    // unit-square corners scaled by (l, w), times [[cos, -sin], [sin, cos]] from the right, shifted by (x, y)
+    const float cs = cosf(b[6]), sn = sinf(b[6]);
+    const float ux[4] = {0.5f, -0.5f, -0.5f, 0.5f}, uy[4] = {0.5f, 0.5f, -0.5f, -0.5f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float px = ux[k] * b[3], py = uy[k] * b[4];
+        q[k].x = (px * cs + py * sn) + b[0];
+        q[k].y = (px * -sn + py * cs) + b[1];
+    }
+}
+
 // Bounding circle of a quad (q[0..4) as P2): centre = mean of the corners, radius = largest corner distance from it
 template <class Quad>
 __device__ __forceinline__ void quad_circle(const Quad &q, P2 &c, float &r) {

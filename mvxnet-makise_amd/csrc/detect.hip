@@ -51,12 +51,6 @@ struct Layout {
     __host__ __device__ size_t total(int F) const { return keys + (size_t)F * npad * 4 + 256; }
 };
 
-// Order-preserving map of a float to an unsigned key (larger float -> larger key); -0 counts as +0 so equal logits tie.
-__device__ __forceinline__ unsigned order_key(float x) {
-    const unsigned u = x == 0.f ? 0u : __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ long long head_off(const Head &h, int f, int x, int y, int c) {
@@ -217,16 +211,8 @@ __global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg,
             if (t > PI_BELOW) t -= 2.f * PI;
             b[6] = fmaxf(t, -PI_BELOW);             // [-pi, pi) as real numbers too
         }
-        // unit-square corners scaled by (l, w), times [[cos, -sin], [sin, cos]] from the right, shifted by (x, y)
-        const float cs = cosf(b[6]), sn = sinf(b[6]);
-        const float ux[4] = {0.5f, -0.5f, -0.5f, 0.5f}, uy[4] = {0.5f, 0.5f, -0.5f, -0.5f};
         P2 q[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float px = ux[k] * b[3], py = uy[k] * b[4];
-            q[k].x = (px * cs + py * sn) + b[0];
-            q[k].y = (px * -sn + py * cs) + b[1];
-        }
+        box_quad(b, q);
         P2 c;
         float rad;
         quad_circle(q, c, rad);

@@ -9,6 +9,7 @@ GPU).  The feature maps come from the same stand-in as train_like.py when torchv
     python detect_like.py /tmp/kitti --synthetic 8          # a synthetic tree, an untrained (seeded) model
     python detect_like.py <dataroot> --split val --eval     # then score the files against the split's label_2 (eval_like.py)
     python detect_like.py <dataroot> --render pictures      # and a bird's-eye and a camera picture of every frame (visualize_like.py)
+    python detect_like.py <dataroot> --tta identity flip     # test-time augmentation: the views' detections fused (modules/tta.py)
 """
 import argparse
 import math
@@ -29,7 +30,7 @@ def parse_args(argv=None):
     ap.add_argument('--out', default=None, help='result directory (default <dataroot>/results/data)')
     ap.add_argument('--synthetic', type=int, default=0, help='write a synthetic KITTI tree with this many frames into dataroot first')
     ap.add_argument('--points', type=int, default=20000)
-    ap.add_argument('--frames', type=int, default=4, help='frames per frame set')
+    ap.add_argument('--frames', type=int, default=4, help='frames per frame set (with --tta of V views at most 16 // V)')
     ap.add_argument('--need-crop', action='store_true')
     ap.add_argument('--score-thr', type=float, default=0.05)
     ap.add_argument('--iou-thr', type=float, default=0.01)
@@ -47,7 +48,17 @@ def parse_args(argv=None):
                     help='state dict of the frozen ResNet50-FPN extractor (torchvision key names): images go through the HIP extractor')
     ap.add_argument('--render', default=None, metavar='DIR',
                     help='also write <name>_bev.png and <name>_cam.png of every frame (ground truth green, detections red to yellow)')
+    add_tta_arguments(ap)
     return ap.parse_args(argv)
+
+
+def add_tta_arguments(ap):
+    """The test-time augmentation switches (also of visualize_like.py --checkpoint); ``modules.tta.options`` reads them."""
+    ap.add_argument('--tta', nargs='+', default=None, metavar='NAME',
+                    help='test-time augmentation: fuse the detections of these views (identity, flip, rot+, rot-, flip+rot+, flip+rot-)')
+    ap.add_argument('--tta-rot', type=float, default=math.pi / 8, help='angle of the named rotations of --tta')
+    ap.add_argument('--fuse-iou', type=float, default=0.5, help='--tta: a view votes for a cluster above this BEV IoU with its head')
+    ap.add_argument('--min-views', type=int, default=1, help='--tta: clusters with fewer voting views are dropped')
 
 
 def main(args):
@@ -104,10 +115,14 @@ def _main(args):
     kw = dict(score_thr=args.score_thr, iou_thr=args.iou_thr, pre_max=args.pre_max, post_max=args.post_max, decode=args.decode)
     if direction:
         kw['dir_offset'] = args.dir_offset
+    from modules import tta
+    tta_kw, n_views = tta.options(args)
+    kw.update(tta_kw)
+    per_set = max(1, min(args.frames, X.MAX_FRAMES // n_views))          # F * V frames go through one forward
     cap = max(args.points, max(d[0].shape[0] for d in data))
     t0, n_boxes = time.perf_counter(), 0
-    for lo in range(0, len(data), args.frames):
-        group, gnames = data[lo:lo + args.frames], names[lo:lo + args.frames]
+    for lo in range(0, len(data), per_set):
+        group, gnames = data[lo:lo + per_set], names[lo:lo + per_set]
         batch, _ = pl.batch_from_dataset(group, gnames, device, anchorBevs, fpn_fn, cap_points=cap)
         dets = detect_frame_set(model, batch, anchors, cfg.imsize, **kw)
         for name, d, frame in zip(gnames, dets, group):

@@ -187,6 +187,8 @@ PROTOTYPES = {
                                  _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'mvx_detect_frames_dir': (_i32, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _f32, _p, _i32,
                                      _i32, _i32, _i32, _f32, _f32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'mvx_tta_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'mvx_tta_fuse_frames': (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'mvx_kitti_eval_workspace_bytes': (_sz, [_i32, _i32]),
     'mvx_kitti_eval_overlaps': (_i32, [_i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'mvx_kitti_eval_tp_scores': (_i32, [_i32, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _p, _p, _p, _p]),

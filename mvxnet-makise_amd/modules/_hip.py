@@ -2106,6 +2106,46 @@ def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, po
 
 
 # ---------------------------------------------------------------------------------------------
+# test-time augmentation: fusion of the views' detections (csrc/tta.hip)
+# ---------------------------------------------------------------------------------------------
+TTA_MAX_VIEWS, TTA_MAX_BOXES, TTA_NONFINITE = 8, 1024, 2      # MVX_TTA_*
+
+
+def _arena_bytes(nbytes, dev, tag):
+    """A 256-byte aligned byte buffer: carved from the step's arena while one is open, else the grow-only workspace of ``tag``."""
+    if _ARENA_ON:
+        a = _ARENAS.get(_arena_key(dev))
+        v = a.take((int(nbytes) + 7) // 8) if a is not None else None
+        if v is not None and v.data_ptr() % 256 == 0:
+            return v.view(torch.uint8)
+    return workspace(nbytes, dev, tag)
+
+
+def tta_fuse_frames(boxes, scores, counts, views, F, iou_thr, fuse_iou, min_views, out_max, full_turn):
+    """The detections of V views of F source frames -> one list per source frame, three launches (mvx_tta_fuse_frames).
+    boxes f32 (F*V, post_max, 7), scores f32 (F*V, post_max), counts i32 (F*V,), frame f*V + v being view v of source frame f;
+    views f32 (V, 4) rows (phi, s, flip, 0) on the device.  Returns (boxes (F,out_max,7), scores (F,out_max), n_views i32
+    (F,out_max), src i32 (F,out_max) = view * post_max + rank of the cluster's head, meta i32 (2,F) = (counts, status))."""
+    dev = boxes.device
+    V, post_max = views.shape[0], boxes.shape[1]
+    if not 1 <= V <= TTA_MAX_VIEWS or V * post_max > TTA_MAX_BOXES:
+        raise X.MvxHipError('the fusion takes 1..%d views and at most %d boxes per source frame, not %d x %d'
+                            % (TTA_MAX_VIEWS, TTA_MAX_BOXES, V, post_max))
+    assert boxes.shape == (F * V, post_max, 7) and scores.shape == (F * V, post_max) and counts.shape == (F * V,)
+    assert views.shape == (V, 4) and boxes.dtype == scores.dtype == views.dtype == torch.float32 and counts.dtype == torch.int32
+    out_boxes = torch.empty((F, out_max, 7), dtype=torch.float32, device=dev)
+    out_scores = torch.empty((F, out_max), dtype=torch.float32, device=dev)
+    n_views = torch.empty((F, out_max), dtype=torch.int32, device=dev)
+    src = torch.empty((F, out_max), dtype=torch.int32, device=dev)
+    meta = torch.empty((2, F), dtype=torch.int32, device=dev)           # counts, status
+    nbytes = X.lib.mvx_tta_workspace_bytes(int(F), int(V), int(post_max))
+    ws = _arena_bytes(nbytes, dev, 'tta')
+    X.call('mvx_tta_fuse_frames', boxes, scores, counts, views, int(F), int(V), int(post_max), float(iou_thr), float(fuse_iou),
+           int(min_views), int(out_max), int(bool(full_turn)), out_boxes, out_scores, n_views, src, meta[0], meta[1], ws, int(nbytes))
+    return out_boxes, out_scores, n_views, src, meta
+
+
+# ---------------------------------------------------------------------------------------------
 # KITTI object evaluation (csrc/kitti_eval.hip); ``inp`` is a kitti_eval.EvalInput, ``t`` its device copies
 # ---------------------------------------------------------------------------------------------
 def _host_ptr(a):

@@ -5,6 +5,8 @@ The reference stops at the score / regression maps (its Calc.decodeRegression is
     host read of the counts;
   * ``detect_frame_set``: the forward half of ``pipeline.train_step_full`` (frame sets through fusion / VFE / CML, the RPN on
     this library's kernels) followed by ``postprocess`` -- no parameter, gradient or gradient bucket is touched;
+  * ``detect_frame_set(..., tta=views)``: test-time augmentation -- V views of every frame through the same forward, their
+    lists fused per source frame (modules/tta.py, csrc/tta.hip);
   * ``boxes_lidar_to_camera`` / ``write_kitti_results``: KITTI ``label_2`` lines for the devkit.
 """
 import math
@@ -96,7 +98,7 @@ def _empty(dev):
                 anchor_idx=torch.zeros((0,), dtype=torch.int32, device=dev), n_candidates=0, status=0)
 
 
-def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw):
+def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, tta=None, fuse_iou=0.5, min_views=1, **kw):
     """Detections for every frame of ``batch`` (pipeline.FrameBatch): the forward of ``pipeline.train_step_full`` -- the frame
     set through fusion / VFE / CML and the RPN on this library's kernels, per-frame BatchNorm statistics -- then
     ``postprocess`` (keyword arguments as there).  With ``bntrack`` it follows ``model.training``: a model in eval mode is
@@ -105,7 +107,28 @@ def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw)
     never written here.  ``ready``: a prepared frame set as train_step_full takes it (or None).
     Returns one dict per batch frame; frames without voxels get empty results.  Reads no gradient and writes none; the
     data-dependent status words are checked like ``pipeline.read_losses``.  ``keep`` (tests): receives 'heads', 'geom', the saved
-    state of the forwards ('saved', 'rpn') and, with ``bntrack``, 'bn_sites'."""
+    state of the forwards ('saved', 'rpn') and, with ``bntrack``, 'bn_sites'.
+
+    ``tta`` (default None: nothing below happens, not a launch more): test-time augmentation, views as ``modules.tta.views``
+    takes them.  The batch is expanded to F * V frames (``tta.expand_batch``; F * V <= 16), the same forward and ``postprocess``
+    run over them and ``tta.fuse_views`` (``fuse_iou``, ``min_views`` as there; the full-turn yaw average when the model has the
+    direction head) turns the views' lists into one per source frame.  The dicts keep 'boxes' / 'scores' and gain 'n_views' and
+    'src'; 'anchor_idx' is the cluster head's, 'n_candidates' the sum and 'status' the OR over the frame's views (and the
+    fusion's).  A source frame whose views are all empty gets the empty result.  ``ready`` cannot be combined with it."""
+    if tta is not None:
+        return _detect_tta(model, batch, anchors, imsize, ready, keep, tta, fuse_iou, min_views, kw)
+    dets, live, _ = _detect_dev(model, batch, anchors, imsize, ready, keep, kw)
+    out = [_empty(batch.device) for _ in range(batch.n_frames)]
+    if dets is not None:
+        for f, d in zip(live, unpack(dets)):
+            out[f] = d
+    return out
+
+
+def _detect_dev(model, batch, anchors, imsize, ready, keep, kw, then=None):
+    """The step of ``detect_frame_set`` up to the padded device tensors of ``postprocess(read=False)`` over the live frames:
+    (that dict or None when no frame has a voxel, the live frames' ids, the result of ``then(dets, live)`` -- more launches
+    inside the step's scope, on its arena -- or None).  The status words are checked here."""
     from modules import bn_running as bnr
     from modules import frames as fr
     from modules import pipeline as pl
@@ -116,7 +139,7 @@ def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw)
     fs, live, counts, status = pl._take_ready(batch, ready, torch.cuda.current_stream(dev))
     hw = [float(imsize[0]), float(imsize[1])]
     statuses = [status]
-    dets = None
+    dets = extra = None
     with pl._step_scope(dev, train=False), bn_step as bn:
         if fs is not None:
             model.prepack()
@@ -129,15 +152,63 @@ def detect_frame_set(model, batch, anchors, imsize, ready=None, keep=None, **kw)
                 fr.cml_forward(model, fs, feat, saved, statuses, want_bev=False)
                 heads, rs = rf.rpn_forward(model.backbone.rpn, saved.x3, F, saved.D3, saved.H, saved.W, saved.C3)
                 dets = postprocess(heads, anchors, F, rs['h1'], rs['w1'], read=False, **opts)
+                if then is not None:
+                    extra = then(dets, live)
             if keep is not None:
                 keep.update(heads=heads, geom=(F, rs['h1'], rs['w1']), saved=saved, rpn=rs)
                 if bn is not None:
                     keep['bn_sites'] = bn.records(F, fs.desc)
     pl._check_statuses(statuses)
-    out = [_empty(dev) for _ in range(batch.n_frames)]
-    if dets is not None:
-        for f, d in zip(live, unpack(dets)):
-            out[f] = d
+    return dets, live, extra
+
+
+def pad_frames(dets, live, n_frames):
+    """The padded device dict of the live frames -> that of all ``n_frames`` frames, the others with count 0 and zero rows."""
+    if len(live) == n_frames:
+        return dets
+    dev = dets['boxes'].device
+    at = torch.as_tensor(list(live), dtype=torch.long, device=dev)
+    out = {}
+    for k, fill in (('boxes', 0), ('scores', 0), ('anchor_idx', -1)):
+        t = torch.full((n_frames,) + tuple(dets[k].shape[1:]), fill, dtype=dets[k].dtype, device=dev)
+        t[at] = dets[k]
+        out[k] = t
+    out['meta'] = torch.zeros((3, n_frames), dtype=torch.int32, device=dev)
+    out['meta'][:, at] = dets['meta']
+    return out
+
+
+def _detect_tta(model, batch, anchors, imsize, ready, keep, views, fuse_iou, min_views, kw):
+    from modules import tta
+    if ready is not None:
+        raise X.MvxHipError('detect_frame_set(tta=...) expands the batch itself: a prepared frame set (ready=) cannot go with it')
+    rows = tta.views(views)
+    F, V = batch.n_frames, rows.shape[0]
+    dev = batch.device
+    full_turn = getattr(model.backbone.rpn, 'dir', None) is not None and kw.get('direction') is not False
+
+    def fuse(dets, live):                       # inside the step's scope: the workspace comes from its arena
+        full = pad_frames(dets, live, F * V)
+        return full, tta.fuse_views(full, rows, F, iou_thr=dict(DEFAULTS, **kw)['iou_thr'], fuse_iou=fuse_iou, min_views=min_views,
+                                    full_turn=full_turn, read=False)
+    dets, live, both = _detect_dev(model, tta.expand_batch(batch, rows), anchors, imsize, None, keep, kw, then=fuse)
+    empty = dict(_empty(dev), n_views=torch.zeros((0,), dtype=torch.int32, device=dev),
+                 src=torch.zeros((0,), dtype=torch.int32, device=dev))
+    if dets is None:
+        return [dict(empty) for _ in range(F)]
+    full, fused = both
+    heads_idx = torch.gather(full['anchor_idx'].view(F, -1), 1, fused['src'].clamp_min(0).long())
+    host = torch.cat([fused['meta'].reshape(-1), full['meta'][1:].reshape(-1)]).tolist()      # the one host read
+    counts, status = host[:F], host[F:2 * F]
+    n_cand, st_views = host[2 * F:2 * F + F * V], host[2 * F + F * V:]
+    out = []
+    for f, n in enumerate(counts):              # n = 0 (every view empty): empty slices
+        st = status[f]
+        for v in range(V):
+            st |= st_views[f * V + v]
+        out.append(dict(boxes=fused['boxes'][f, :n], scores=fused['scores'][f, :n], anchor_idx=heads_idx[f, :n],
+                        n_views=fused['n_views'][f, :n], src=fused['src'][f, :n], n_candidates=sum(n_cand[f * V:(f + 1) * V]),
+                        status=st))
     return out
 
 

@@ -38,6 +38,8 @@ def parse_args(argv=None):
     ap.add_argument('--res', type=float, default=0.1, help='metres per pixel of the bird\'s-eye view')
     ap.add_argument('--thickness', type=int, default=1, choices=[1, 2, 3], help='line thickness in pixels')
     ap.add_argument('--synthetic', type=int, default=0, help='write a synthetic KITTI tree with this many frames into dataroot first')
+    from detect_like import add_tta_arguments
+    add_tta_arguments(ap)                        # with --checkpoint: the views' detections fused (modules/tta.py)
     return ap.parse_args(argv)
 
 
@@ -60,6 +62,7 @@ def _model_detector(args, device, data, names):
     """Frames -> (FrameBatch, per-frame detections) through the model of ``--checkpoint``, as detect_like.py runs it."""
     import modules.config as cfg
     from modules import bn_running as bnr
+    from modules import Extension as X
     from modules import pipeline as pl
     from modules.Calc import bbox3d2bev
     from modules.data import Preprocessing as pre
@@ -81,11 +84,15 @@ def _model_detector(args, device, data, names):
     if tracked:
         model.eval()                            # detect_frame_set then normalises with the running statistics
     kw = dict(dir_offset=args.dir_offset) if direction else {}
+    from modules import tta
+    tta_kw, n_views = tta.options(args)
+    kw.update(tta_kw)
     cap = max(d[0].shape[0] for d in data)
 
     def run(group, gnames):
         batch, _ = pl.batch_from_dataset(group, gnames, device, anchor_bevs, fpn_maps_for, cap_points=cap)
         return batch, detect_frame_set(model, batch, anchors, cfg.imsize, **kw)
+    run.per_set = max(1, min(SET, X.MAX_FRAMES // n_views))              # F * V frames go through one forward
     return run
 
 
@@ -117,8 +124,9 @@ def _main(args):
     out_dir = args.out or os.path.join(args.dataroot, 'pictures')
     detector = _model_detector(args, device, data, names) if args.checkpoint else None
     paths, dropped = [], 0
-    for lo in range(0, len(data), SET):
-        group, gnames = data[lo:lo + SET], names[lo:lo + SET]
+    per_set = detector.per_set if detector is not None else SET
+    for lo in range(0, len(data), per_set):
+        group, gnames = data[lo:lo + per_set], names[lo:lo + per_set]
         dets = None
         if detector is not None:
             points, dets = detector(group, gnames)
