@@ -1016,6 +1016,37 @@ int mvx_focal_loss_dir_frames(const float *heads, int32_t heads_ld, const float 
                               float *d_dir, int32_t d_dir_ld, float *losses, void *workspace, int64_t workspace_bytes,
                               void *stream);
 
+/* mvx_focal_loss_iou_frames: mvx_focal_loss_dir_frames with an IoU-aware confidence head (CIA-SSD, AFDetV2, CenterPoint's second
+ * stage): one more launch (the memset plus four, for any F).  The IoU logits and their gradient come as pointer +
+ * row stride exactly like the direction logits: iou[row*iou_ld + a], columns of the head rows (iou = heads + 9A, iou_ld =
+ * heads_ld) or a tensor of their own; d_iou likewise (given exactly when d_heads is; outside the d_heads rows its A columns per
+ * row are zeroed first).  Per pos_idx entry (anchor a, box g, IoU logit x, the anchor's regression row r read as a constant;
+ * entries the regression term skips are skipped, duplicates count every time):
+ *   b = the 'loss' decode of mvx_detect_frames: b0,1 = r0,1 * sqrt(an3^2 + an4^2) + an0,1, b2 = r2 an5 + an2, b3..5 = exp(r3..5)
+ *       an3..5, b6 = r6 + an6 (no direction fold: a rectangle is blind to it);
+ *   I = BEV intersection of the quads of b and g in the f32 arithmetic of the NMS, exactly 0 when their bounding circles
+ *       cannot touch; ih = min(b2 + b5, g2 + g5) - max(b2, g2) (z is the bottom face);
+ *   q = clamp(I ih / (b3 b4 b5 + g3 g4 g5 - I ih), 0, 1): the 3D IoU; 0 when ih <= 0, when a component of b (or g) is not
+ *       finite, or when the quotient is not finite;
+ *   iou_f = iou_weight / max(1, n_pos) * sum (softplus(x) - q x), gradient iou_weight / max(1, n_pos) * (sigmoid(x) - q).
+ * Nothing flows into the regression columns from this term.  The cls, reg and dir terms and their gradient columns are
+ * mvx_focal_loss_dir_frames's bit for bit.  iou_weight >= 0.  losses f32 [n_frames][4] = (cls_f, reg_f, dir_f, iou_f).
+ * q_out (optional) f32 [n_frames][cap]: q of every pos_idx entry, -1 for skipped entries and for the slots beyond the count.
+ * workspace: mvx_focal_loss_iou_frames_workspace_bytes(n_frames, l, w, anchors_per_loc, d_heads_ld, cap) bytes: the direction
+ * entry's plus n_frames * min(ceil(cap / 128), 64) doubles.  The four losses are bitwise reproducible, the gradient whenever
+ * no anchor is listed twice in pos_idx.
+ */
+int64_t mvx_focal_loss_iou_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                                  int32_t d_heads_ld, int64_t cap);
+int mvx_focal_loss_iou_frames(const float *heads, int32_t heads_ld, const float *dir, int32_t dir_ld, const float *iou,
+                              int32_t iou_ld, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                              const int64_t *pos_idx, const int64_t *neg_idx, const int64_t *gi, int64_t cap,
+                              const int32_t *counts, const float *gts, int32_t gt_ld, const int32_t *gt_off,
+                              const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight,
+                              float dir_weight, float dir_offset, float iou_weight, float *d_heads, int32_t d_heads_ld,
+                              float *d_dir, int32_t d_dir_ld, float *d_iou, int32_t d_iou_ld, float *q_out, float *losses,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Detection output (csrc/detect.hip): score selection, top-K, box decoding and rotated BEV NMS for the frames of a step.
  * The reference has none of it (its Calc.decodeRegression is never called).
@@ -1071,6 +1102,22 @@ int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t 
 int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
                           int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *dir, int64_t dir_sf,
                           int64_t dir_sl, int64_t dir_sw, int64_t dir_sa, float dir_offset, const float *anchors,
+                          int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc, float score_thr, float iou_thr,
+                          int32_t pre_max, int32_t post_max, int32_t decode, float *boxes, float *scores, int32_t *anchor_idx,
+                          int32_t *counts, int32_t *n_candidates, int32_t *status, int32_t *dbg_idx, float *dbg_boxes,
+                          float *dbg_corners, void *workspace, size_t workspace_bytes, void *stream);
+/* mvx_detect_frames_iou: mvx_detect_frames_dir plus a fifth head, the IoU logit u of anchor a at iou[f*iou_sf + x*iou_sl +
+ * y*iou_sw + a*iou_sa] (what mvx_focal_loss_iou_frames trains), and iou_alpha = a in [0, 1] (anything else, a NaN included, is
+ * MVX_EINVAL before any launch).  The score becomes cls^(1-a) iou^a, formed from the logits as its logarithm
+ *   s = -((1 - a) softplus(-c) + a softplus(-u)):
+ * an anchor is a candidate when expf(s) >= score_thr (a NaN fails), candidates are ordered by s (ties: lowest anchor index
+ * first) and the score written out is expf(s).  Boxes, direction fold, NMS and outputs are mvx_detect_frames_dir's.  iou = NULL
+ * or iou_alpha = 0 is mvx_detect_frames_dir bit for bit (which calls this); the head is not read then.
+ */
+int mvx_detect_frames_iou(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+                          int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *dir, int64_t dir_sf,
+                          int64_t dir_sl, int64_t dir_sw, int64_t dir_sa, float dir_offset, const float *iou, int64_t iou_sf,
+                          int64_t iou_sl, int64_t iou_sw, int64_t iou_sa, float iou_alpha, const float *anchors,
                           int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc, float score_thr, float iou_thr,
                           int32_t pre_max, int32_t post_max, int32_t decode, float *boxes, float *scores, int32_t *anchor_idx,
                           int32_t *counts, int32_t *n_candidates, int32_t *status, int32_t *dbg_idx, float *dbg_boxes,

@@ -21,11 +21,12 @@ def initWeights(m):
 
 class MVXNet(nn.Module):
 
-    def __init__(self, direction=False):
-        """``direction``: the RPN carries the direction classifier ``backbone.rpn.dir`` (voxelnet/Pipe.py RPN)."""
+    def __init__(self, direction=False, iou=False):
+        """``direction``: the RPN carries the direction classifier ``backbone.rpn.dir`` (voxelnet/Pipe.py RPN); ``iou`` (with
+        ``direction``): and the IoU-aware confidence head ``backbone.rpn.iou``."""
         super().__init__()
         self.head = ImageHead()
-        self.backbone = VoxelNet(direction=direction)
+        self.backbone = VoxelNet(direction=direction, iou=iou)
         self.backbone.apply(initWeights)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -94,7 +95,8 @@ class MVXNet(nn.Module):
         """Boxes of one frame, with forward's inputs (MVXNet.py:21-27) and the anchor grid (h1, w1, 14)
         (Preprocessing.createAnchors): the forward on the single HIP node up to the raw head logits, then
         ``modules.detect.postprocess`` (keyword arguments as there: score_thr, iou_thr, pre_max, post_max, decode).
-        A model with the direction head decodes through it (``direction`` / ``dir_offset`` of postprocess): yaws in [-pi, pi).
+        A model with the direction head decodes through it (``direction`` / ``dir_offset`` of postprocess): yaws in [-pi, pi);
+        one with the IoU head ranks and scores by cls^(1-a) iou^a (``iou_alpha`` of postprocess, default 0.5).
         Returns ``{boxes (n,7) xyzlwhr LiDAR frame, scores (n,), anchor_idx (n,), n_candidates, status}``."""
         from modules import detect, whole
         from modules import Extension as X
@@ -105,4 +107,5 @@ class MVXNet(nn.Module):
                                 'indices on the GPU, the background rewrite and the HIP RPN on, map sides divisible by 8')
         with torch.no_grad():
             heads = whole.forward_heads(self, voxels, imgs, idx, imsize)
+            kw.setdefault('iou', hasattr(self.backbone.rpn, 'iou'))
             return detect.postprocess(heads, anchors, 1, cfg.voxelshape[0] // 2, cfg.voxelshape[1] // 2, **kw)[0]

@@ -19,6 +19,12 @@
 // detect_select folds the decoded yaw t = r6 + an6 into the half turn the bit names,
 //   base = (t - dir_offset) - floor((t - dir_offset) / pi) pi,  t' = base + dir_offset + pi [x > 0],  wrapped into [-pi, pi),
 // before the corners are formed, so the circle, the NMS and the output all see t'.  A null head is mvx_detect_frames.
+//
+// mvx_detect_frames_iou adds a fifth head, the IoU logit u per anchor that mvx_focal_loss_iou_frames trains, and iou_alpha = a
+// in [0, 1]: the score becomes cls^(1-a) iou^a (CIA-SSD, AFDetV2), formed from the logits as its logarithm
+//   s = -((1 - a) softplus(-c) + a softplus(-u)),  softplus(-x) = max(-x, 0) + log1p(exp(-|x|)).
+// detect_keys admits an anchor when expf(s) >= score_thr (a NaN fails) and keys it by order_key(s); detect_select writes expf(s)
+// as the score.  Boxes, direction fold, NMS and outputs are unchanged.  A null head, or a = 0, is mvx_detect_frames_dir.
 #include "bev_iou.h"
 
 namespace {
@@ -57,9 +63,16 @@ __device__ __forceinline__ long long head_off(const Head &h, int f, int x, int y
     return f * h.sf + x * h.sl + y * h.sw + c * h.sc;
 }
 
+__device__ __forceinline__ float softplus_neg(float x) { return fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x))); }      // -log sigmoid(x)
+
+// log of the rectified score cls^(1-a) iou^a from the two logits
+__device__ __forceinline__ float rectified_log(float c, float u, float a) {
+    return -((1.f - a) * softplus_neg(c) + a * softplus_neg(u));
+}
+
 // 1. keys[f][n] for every anchor n = (x*w + y)*A + a; the tail up to npad is 0
-__global__ __launch_bounds__(256) void detect_keys(Head cls, int F, int L, int W, int A, float score_thr, unsigned *__restrict__ keys,
-                                                   long long npad) {
+__global__ __launch_bounds__(256) void detect_keys(Head cls, Head iou, float iou_alpha, int F, int L, int W, int A, float score_thr,
+                                                   unsigned *__restrict__ keys, long long npad) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (long long)F * npad) return;
     const int f = (int)(e / npad);
@@ -68,13 +81,16 @@ __global__ __launch_bounds__(256) void detect_keys(Head cls, int F, int L, int W
     if (n < (long long)L * W * A) {
         const int a = (int)(n % A), cell = (int)(n / A);
         const float logit = cls.p[head_off(cls, f, cell / W, cell % W, a)];
-        if (sigmoid(logit) >= score_thr) k = order_key(logit);      // NaN fails the comparison
+        if (iou.p) {                                                 // the rectified score (kernel-uniform branch)
+            const float s = rectified_log(logit, iou.p[head_off(iou, f, cell / W, cell % W, a)], iou_alpha);
+            if (expf(s) >= score_thr) k = order_key(s);             // NaN fails the comparison
+        } else if (sigmoid(logit) >= score_thr) k = order_key(logit);      // NaN fails the comparison
     }
     keys[e] = k;
 }
 
 // 2. one workgroup per frame
-__global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg, Head dir, float dir_offset,
+__global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg, Head dir, float dir_offset, Head iou, float iou_alpha,
                                                              const float *__restrict__ anchors, int L, int W, int A,
                                                              int decode, Layout lay, unsigned char *__restrict__ ws,
                                                              int *__restrict__ n_candidates, int *__restrict__ status,
@@ -224,7 +240,8 @@ __global__ __launch_bounds__(SEL_THREADS) void detect_select(Head cls, Head reg,
         c_circ[(size_t)i * 4 + 1] = c.y;
         c_circ[(size_t)i * 4 + 2] = rad;
         c_circ[(size_t)i * 4 + 3] = 0.f;
-        c_score[i] = sigmoid(cls.p[head_off(cls, f, x, y, a)]);
+        const float logit = cls.p[head_off(cls, f, x, y, a)];
+        c_score[i] = iou.p ? expf(rectified_log(logit, iou.p[head_off(iou, f, x, y, a)], iou_alpha)) : sigmoid(logit);
         c_idx[i] = n;
         c_ok[i] = ok;
         if (!ok) s_bad = 1;                     // benign race: every writer stores 1
@@ -360,15 +377,18 @@ extern "C" size_t mvx_detect_workspace_bytes(int32_t n_frames, int32_t n_anchors
     return Layout(pre_max > 0 ? pre_max : 0, n_anchors > 0 ? n_anchors : 0, F).total(F);
 }
 
-extern "C" int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+extern "C" int mvx_detect_frames_iou(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
                                      int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *dir,
                                      int64_t dir_sf, int64_t dir_sl, int64_t dir_sw, int64_t dir_sa, float dir_offset,
-                                     const float *anchors, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                     const float *iou, int64_t iou_sf, int64_t iou_sl, int64_t iou_sw, int64_t iou_sa,
+                                     float iou_alpha, const float *anchors, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
                                      float score_thr, float iou_thr, int32_t pre_max, int32_t post_max, int32_t decode, float *boxes,
                                      float *scores, int32_t *anchor_idx, int32_t *counts, int32_t *n_candidates, int32_t *status,
                                      int32_t *dbg_idx, float *dbg_boxes, float *dbg_corners, void *workspace, size_t workspace_bytes,
                                      void *stream) {
     MVX_CHECK_ARG(!dir || dir_offset == dir_offset);
+    MVX_CHECK_ARG(iou_alpha >= 0.f && iou_alpha <= 1.f);      // a NaN fails both
+    if (iou_alpha == 0.f) iou = nullptr;                      // cls^1 iou^0: the plain score and key, bit for bit; the head is not read
     MVX_CHECK_ARG(n_frames >= 1 && n_frames <= MVX_MAX_FRAMES);
     MVX_CHECK_ARG(pre_max >= 1 && pre_max <= MVX_DETECT_MAX_PRE && post_max >= 1 && post_max <= pre_max);
     MVX_CHECK_ARG(iou_thr >= 1e-3f && iou_thr < 1.f && score_thr >= 0.f && score_thr < 1.f);
@@ -384,13 +404,13 @@ extern "C" int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t c
     hipStream_t st = (hipStream_t)stream;
     unsigned char *ws = (unsigned char *)workspace;
     const Head hc = {cls, cls_sf, cls_sl, cls_sw, cls_sa}, hr = {reg, reg_sf, reg_sl, reg_sw, reg_sc};
-    const Head hd = {dir, dir_sf, dir_sl, dir_sw, dir_sa};
+    const Head hd = {dir, dir_sf, dir_sl, dir_sw, dir_sa}, hu = {iou, iou_sf, iou_sl, iou_sw, iou_sa};
     const long long tot = (long long)n_frames * lay.npad;
-    hipLaunchKernelGGL(detect_keys, dim3(mvx_cdiv(tot, 256)), dim3(256), 0, st, hc, n_frames, l, w, anchors_per_loc, score_thr,
-                       (unsigned *)(ws + lay.keys), lay.npad);
+    hipLaunchKernelGGL(detect_keys, dim3(mvx_cdiv(tot, 256)), dim3(256), 0, st, hc, hu, iou_alpha, n_frames, l, w, anchors_per_loc,
+                       score_thr, (unsigned *)(ws + lay.keys), lay.npad);
     MVX_LAUNCH_CHECK();
-    hipLaunchKernelGGL(detect_select, dim3(n_frames), dim3(SEL_THREADS), 0, st, hc, hr, hd, dir_offset, anchors, l, w, anchors_per_loc,
-                       decode, lay, ws, n_candidates, status, dbg_idx, dbg_boxes, dbg_corners);
+    hipLaunchKernelGGL(detect_select, dim3(n_frames), dim3(SEL_THREADS), 0, st, hc, hr, hd, dir_offset, hu, iou_alpha, anchors, l, w,
+                       anchors_per_loc, decode, lay, ws, n_candidates, status, dbg_idx, dbg_boxes, dbg_corners);
     MVX_LAUNCH_CHECK();
     const unsigned nb = (unsigned)lay.NW;
     hipLaunchKernelGGL(detect_mask, dim3(nb * MASK_SPLIT, nb, n_frames), dim3(MASK_THREADS), 0, st, lay, ws, iou_thr);
@@ -398,6 +418,20 @@ extern "C" int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t c
     hipLaunchKernelGGL(detect_scan, dim3(n_frames), dim3(64), 0, st, lay, ws, post_max, boxes, scores, anchor_idx, counts);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
+}
+
+extern "C" int mvx_detect_frames_dir(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,
+                                     int64_t reg_sf, int64_t reg_sl, int64_t reg_sw, int64_t reg_sc, const float *dir,
+                                     int64_t dir_sf, int64_t dir_sl, int64_t dir_sw, int64_t dir_sa, float dir_offset,
+                                     const float *anchors, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                     float score_thr, float iou_thr, int32_t pre_max, int32_t post_max, int32_t decode, float *boxes,
+                                     float *scores, int32_t *anchor_idx, int32_t *counts, int32_t *n_candidates, int32_t *status,
+                                     int32_t *dbg_idx, float *dbg_boxes, float *dbg_corners, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+    return mvx_detect_frames_iou(cls, cls_sf, cls_sl, cls_sw, cls_sa, reg, reg_sf, reg_sl, reg_sw, reg_sc, dir, dir_sf, dir_sl, dir_sw,
+                                 dir_sa, dir_offset, nullptr, 0, 0, 0, 0, 0.f, anchors, n_frames, l, w, anchors_per_loc, score_thr,
+                                 iou_thr, pre_max, post_max, decode, boxes, scores, anchor_idx, counts, n_candidates, status, dbg_idx,
+                                 dbg_boxes, dbg_corners, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mvx_detect_frames(const float *cls, int64_t cls_sf, int64_t cls_sl, int64_t cls_sw, int64_t cls_sa, const float *reg,

@@ -28,7 +28,19 @@
 //   dir_f = dir_weight / max(1, n_pos) * sum (b ? softplus(-x) : softplus(x)),  gradient dir_weight / max(1, n_pos) * (sigmoid(x) - b)
 // The direction logits and their gradient come as pointer + row stride: columns of the head rows (the dense pass zeroes them
 // with the rest of the row) or a tensor of their own (the dense pass zeroes its A columns).  losses is (F,3) = (cls, reg, dir).
-#include "common.h"
+//
+// mvx_focal_loss_iou_frames adds the IoU-aware confidence head (CIA-SSD, AFDetV2) and one launch, focal_iou,
+// between the dense and the list pass.  Per pos_idx entry of anchor a, box g and IoU logit x (entries the regression term skips
+// are skipped, duplicates count every time), with the anchor's regression row r read as a constant:
+//   b = the 'loss' decode of detect_select (diagonal of (an3, an4), expf on the sizes, b6 = r6 + an6, no direction fold)
+//   I = BEV intersection of box_quad(b) and box_quad(g) (bev_iou.h), 0 when circles_apart; ih = min(b2+b5, g2+g5) - max(b2, g2)
+//   q = clamp(I ih / (b3 b4 b5 + g3 g4 g5 - I ih), 0, 1), 0 when ih <= 0, when b is not finite or the quotient is not
+//   iou_f = iou_weight / max(1, n_pos) * sum (softplus(x) - q x),  gradient iou_weight / max(1, n_pos) * (sigmoid(x) - q)
+// Nothing flows into the regression columns.  The clipping keeps POLY_SLOTS P2 per thread in LDS (320 B), so the pass cannot
+// live in the 1024-thread focal_lists (320 KB): 128 threads (40 KB), grid (nq, F), nq = min(ceil(cap / 128), 64), a strided loop
+// over the entries and one f64 partial per workgroup, which focal_lists sums in index order into losses[f][3].  The IoU logits
+// and their gradient come as pointer + row stride like the direction logits.  losses is (F,4) = (cls, reg, dir, iou).
+#include "bev_iou.h"
 
 namespace {
 
@@ -36,6 +48,13 @@ constexpr int DENSE_THREADS = 256;
 constexpr int DENSE_MAX_BLOCKS = 128;      // workgroups (= partial sums) per frame at most
 constexpr int LIST_BLOCKS = 8;             // workgroups per frame of the flag pass
 constexpr int LIST_THREADS = 1024;
+constexpr int IOU_THREADS = 128;           // focal_iou: 40 KB of polygon slots per workgroup
+constexpr int IOU_MAX_BLOCKS = 64;         // its workgroups (= partial sums) per frame at most
+
+inline int iou_blocks(long long cap) {
+    const long long want = (cap + IOU_THREADS - 1) / IOU_THREADS;
+    return (int)(want > IOU_MAX_BLOCKS ? IOU_MAX_BLOCKS : (want < 1 ? 1 : want));
+}
 
 struct Layout {
     long long n_anchors;      // per frame
@@ -103,11 +122,12 @@ __device__ __forceinline__ double block_sum_f64(double v, double *s_part) {
 }
 
 // One thread per float4 of a gradient row (ldd floats); the first float4 of a row holds its A <= 4 logits.  zero / ldz: a
-// direction gradient outside the head rows, whose A columns per row are zeroed here for the list pass to add into.
+// direction gradient outside the head rows, whose A columns per row are zeroed here for the list pass to add into; zero2 /
+// ldz2: the same for an IoU gradient outside the head rows (focal_iou adds into it).
 __global__ void __launch_bounds__(DENSE_THREADS)
 focal_dense(const float *__restrict__ heads, int ld, int rows, int A, const unsigned char *__restrict__ flags, Lists ls, float alpha,
             float gamma, float cls_weight, float *__restrict__ d_heads, int ldd, float *__restrict__ zero, int ldz,
-            double *__restrict__ partials) {
+            float *__restrict__ zero2, int ldz2, double *__restrict__ partials) {
     const int f = blockIdx.y;
     const int cpr = ldd >> 2, cpr_in = ld >> 2;              // float4 pieces per row
     const long long chunks = (long long)rows * cpr;
@@ -153,6 +173,9 @@ focal_dense(const float *__restrict__ heads, int ld, int rows, int A, const unsi
     if (zero)
         for (long long i = (long long)blockIdx.x * DENSE_THREADS + threadIdx.x; i < (long long)rows * A; i += (long long)gridDim.x * DENSE_THREADS)
             zero[((size_t)f * rows + i / A) * ldz + i % A] = 0.f;
+    if (zero2)
+        for (long long i = (long long)blockIdx.x * DENSE_THREADS + threadIdx.x; i < (long long)rows * A; i += (long long)gridDim.x * DENSE_THREADS)
+            zero2[((size_t)f * rows + i / A) * ldz2 + i % A] = 0.f;
     __shared__ double s_part[DENSE_THREADS / 64];
     const double t = block_sum_f64(part, s_part);
     if (threadIdx.x == 0) partials[(size_t)f * gridDim.x + blockIdx.x] = t;
@@ -168,12 +191,95 @@ struct Dir {
 
 constexpr float PI_F = 3.14159265358979323846f;
 
-template <bool DIR>
+// The IoU head of mvx_focal_loss_iou_frames: logits x and their gradient d as pointer + row stride, the optional target output
+// q_out (F,cap), and the f64 partials (F,nq) of focal_iou that focal_lists sums.
+struct Iou {
+    const float *x;
+    float *d;
+    int ldx, ldd;
+    float weight;
+    float *q_out;
+    double *partials;
+    int nq;
+};
+
+// grid (nq, F): a strided loop over the frame's pos_idx entries, one thread per entry at a time
+__global__ void __launch_bounds__(IOU_THREADS)
+focal_iou(const float *__restrict__ heads, int ld, Lists ls, const float *__restrict__ gts, int gt_ld, const int *__restrict__ gt_off,
+          const float *__restrict__ anchors, int L, int W, int A, Iou iou) {
+    __shared__ P2 s_poly[POLY_SLOTS * IOU_THREADS];
+    __shared__ double s_part[IOU_THREADS / 64];
+    const int f = blockIdx.y;
+    const int n_pos = list_count(ls, f, 0);
+    const long long *pos = ls.pos + (size_t)f * 3 * ls.cap, *gi = ls.gi + (size_t)f * ls.cap;
+    const int g_lo = gt_off[f], n_gt = gt_off[f + 1] - g_lo;
+    const size_t cell0 = (size_t)f * L * W;
+    const float scale = iou.weight / (float)(n_pos > 1 ? n_pos : 1);
+    const Polys w = polys_of(s_poly, IOU_THREADS, threadIdx.x);
+    const long long end = iou.q_out ? ls.cap : (long long)n_pos;       // q_out is written for every slot of the list
+    double s_iou = 0.0;
+    for (long long k = (long long)blockIdx.x * IOU_THREADS + threadIdx.x; k < end; k += (long long)gridDim.x * IOU_THREADS) {
+        float q = -1.f;
+        const long long a = k < n_pos ? list_anchor(pos, ls.cap, (int)k, L, W, A) : -1;
+        const long long gk = k < n_pos ? gi[k] : -1;
+        if (a >= 0 && gk >= 0 && gk < n_gt) {
+            const int z = (int)(a % A);
+            const float *g = gts + (size_t)(g_lo + gk) * gt_ld;
+            const float *an = anchors + (size_t)a * 7;
+            const size_t cell = cell0 + (size_t)(a / A);
+            const float *r = heads + cell * ld + A + z * 7;
+            const float d = sqrtf(an[3] * an[3] + an[4] * an[4]);
+            float b[7], gb[7];
+            b[0] = r[0] * d + an[0];
+            b[1] = r[1] * d + an[1];
+            b[2] = r[2] * an[5] + an[2];
+            b[3] = expf(r[3]) * an[3];
+            b[4] = expf(r[4]) * an[4];
+            b[5] = expf(r[5]) * an[5];
+            b[6] = r[6] + an[6];
+            bool ok = true;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                gb[c] = g[c];
+                ok = ok && isfinite(b[c]) && isfinite(gb[c]);
+            }
+            q = 0.f;
+            const float ih = fminf(b[2] + b[5], gb[2] + gb[5]) - fmaxf(b[2], gb[2]);      // z is the bottom face (box3d.h)
+            if (ok && ih > 0.f) {
+                P2 q1[4], q2[4], c1, c2;
+                float r1, r2;
+                box_quad(b, q1);
+                box_quad(gb, q2);
+                quad_circle(q1, c1, r1);
+                quad_circle(q2, c2, r2);
+                if (!circles_apart(c1, r1, c2, r2)) {
+                    load_oriented(w.q1, (const float *)q1);      // the areas are not used: the volumes below are l w h
+                    load_oriented(w.q2, (const float *)q2);
+                    const float inter = quad_intersection(w.q1, w.q2, w.p, w.q);
+                    const float vol = inter * ih;
+                    const float v = vol / (b[3] * b[4] * b[5] + gb[3] * gb[4] * gb[5] - vol);
+                    q = isfinite(v) ? fminf(fmaxf(v, 0.f), 1.f) : 0.f;
+                }
+            }
+            const float x = iou.x[cell * iou.ldx + z];
+            const float e = expf(-fabsf(x));
+            const float l1p = log1pf(e);
+            s_iou += (double)(fmaxf(x, 0.f) + l1p) - (double)q * (double)x;      // softplus(x) - q x
+            const float inv = 1.f / (1.f + e);
+            if (iou.d) atomicAdd(iou.d + cell * iou.ldd + z, scale * ((x >= 0.f ? inv : e * inv) - q));
+        }
+        if (iou.q_out) iou.q_out[(size_t)f * ls.cap + k] = q;
+    }
+    const double t = block_sum_f64(s_iou, s_part);
+    if (threadIdx.x == 0) iou.partials[(size_t)f * gridDim.x + blockIdx.x] = t;
+}
+
+template <bool DIR, bool IOU>
 __global__ void __launch_bounds__(LIST_THREADS)
 focal_lists(const float *__restrict__ heads, int ld, Lists ls, const float *__restrict__ gts, int gt_ld,
             const int *__restrict__ gt_off, const float *__restrict__ anchors, int L, int W, int A, float cls_weight,
             float reg_weight, float *__restrict__ d_heads, int ldd, const double *__restrict__ partials, int nb, Dir dir,
-            float *__restrict__ losses) {
+            Iou iou, float *__restrict__ losses) {
     const int f = blockIdx.x;
     const int n_pos = list_count(ls, f, 0);
     const long long *pos = ls.pos + (size_t)f * 3 * ls.cap, *gi = ls.gi + (size_t)f * ls.cap;
@@ -232,17 +338,25 @@ focal_lists(const float *__restrict__ heads, int ld, Lists ls, const float *__re
     if (threadIdx.x == 0) {
         double tc = 0.0;
         for (int k = 0; k < nb; ++k) tc += s_cls[k];
-        float *out = losses + (DIR ? 3 : 2) * f;
+        float *out = losses + (IOU ? 4 : DIR ? 3 : 2) * f;
         out[0] = (float)((double)cls_weight * tc / (double)(n_pos > 1 ? n_pos : 1));
         out[1] = n_pos > 0 ? (float)((double)reg_weight * tr / (double)(n_pos * 7)) : 0.f;
         if (DIR) out[2] = (float)((double)dir.weight * td / (double)(n_pos > 1 ? n_pos : 1));
+        if (IOU) {                                           // focal_iou's partials of this frame, in index order
+            double ti = 0.0;
+            for (int k = 0; k < iou.nq; ++k) ti += iou.partials[(size_t)f * iou.nq + k];
+            out[3] = (float)((double)iou.weight * ti / (double)(n_pos > 1 ? n_pos : 1));
+        }
     }
 }
 
-// The three launches of both entry points.  dir.x == nullptr: the plain loss, losses (F,2).
+const Iou NO_IOU = {nullptr, nullptr, 0, 0, 0.f, nullptr, nullptr, 0};
+
+// The launches of the three entry points.  dir.x == nullptr: the plain loss, losses (F,2); iou.x: focal_iou as a fourth
+// launch, losses (F,4).
 int focal_launch(const float *heads, int ld, int n_frames, int l, int w, int A, const Lists &ls, const float *gts, int gt_ld,
                  const int *gt_off, const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight, float *d_heads,
-                 int ldd, const Dir &dir, float *losses, const Layout &lay, void *workspace, hipStream_t st) {
+                 int ldd, const Dir &dir, const Iou &iou, float *losses, const Layout &lay, void *workspace, hipStream_t st) {
     unsigned char *ws = (unsigned char *)workspace;
     double *partials = (double *)(ws + lay.partials());
     hipError_t e = hipMemsetAsync(ws, 0, (size_t)lay.flag_bytes, st);
@@ -251,15 +365,23 @@ int focal_launch(const float *heads, int ld, int n_frames, int l, int w, int A, 
     MVX_LAUNCH_CHECK();
     // a direction gradient that is not a column range of the d_heads rows is zeroed by the dense pass too
     const bool inside = dir.d && d_heads && dir.ldd == ldd && dir.d >= d_heads && dir.d + A <= d_heads + ldd;
+    const bool inside_iou = iou.d && d_heads && iou.ldd == ldd && iou.d >= d_heads && iou.d + A <= d_heads + ldd;
     hipLaunchKernelGGL(focal_dense, dim3(lay.nb, n_frames), dim3(DENSE_THREADS), 0, st, heads, ld, l * w, A, ws, ls, alpha, gamma,
-                       cls_weight, d_heads, ldd, dir.d && !inside ? dir.d : nullptr, dir.ldd, partials);
+                       cls_weight, d_heads, ldd, dir.d && !inside ? dir.d : nullptr, dir.ldd, iou.d && !inside_iou ? iou.d : nullptr,
+                       iou.ldd, partials);
     MVX_LAUNCH_CHECK();
-    if (dir.x)
-        hipLaunchKernelGGL(focal_lists<true>, dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off, anchors, l,
-                           w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, losses);
+    if (iou.x) {
+        hipLaunchKernelGGL(focal_iou, dim3(iou.nq, n_frames), dim3(IOU_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off, anchors, l, w,
+                           A, iou);
+        MVX_LAUNCH_CHECK();
+        hipLaunchKernelGGL((focal_lists<true, true>), dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off,
+                           anchors, l, w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, iou, losses);
+    } else if (dir.x)
+        hipLaunchKernelGGL((focal_lists<true, false>), dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off,
+                           anchors, l, w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, iou, losses);
     else
-        hipLaunchKernelGGL(focal_lists<false>, dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off, anchors, l,
-                           w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, losses);
+        hipLaunchKernelGGL((focal_lists<false, false>), dim3(n_frames), dim3(LIST_THREADS), 0, st, heads, ld, ls, gts, gt_ld, gt_off,
+                           anchors, l, w, A, cls_weight, reg_weight, d_heads, ldd, partials, lay.nb, dir, iou, losses);
     MVX_LAUNCH_CHECK();
     return MVX_OK;
 }
@@ -287,7 +409,7 @@ extern "C" int mvx_focal_loss_frames(const float *heads, int32_t n_frames, int32
     const Lists ls = {(const long long *)pos_idx, (const long long *)neg_idx, (const long long *)gi, (long long)cap, counts};
     const Dir none = {nullptr, nullptr, 0, 0, 0.f, 0.f};
     return focal_launch(heads, ld, n_frames, l, w, anchors_per_loc, ls, gts, gt_ld, gt_off, anchors, alpha, gamma, cls_weight,
-                        reg_weight, d_heads, ld, none, losses, lay, workspace, (hipStream_t)stream);
+                        reg_weight, d_heads, ld, none, NO_IOU, losses, lay, workspace, (hipStream_t)stream);
 }
 
 extern "C" int64_t mvx_focal_loss_dir_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
@@ -317,5 +439,42 @@ extern "C" int mvx_focal_loss_dir_frames(const float *heads, int32_t heads_ld, c
     const Lists ls = {(const long long *)pos_idx, (const long long *)neg_idx, (const long long *)gi, (long long)cap, counts};
     const Dir d = {dir, d_dir, dir_ld, d_dir_ld, dir_weight, dir_offset};
     return focal_launch(heads, heads_ld, n_frames, l, w, anchors_per_loc, ls, gts, gt_ld, gt_off, anchors, alpha, gamma, cls_weight,
-                        reg_weight, d_heads, d_heads_ld, d, losses, lay, workspace, (hipStream_t)stream);
+                        reg_weight, d_heads, d_heads_ld, d, NO_IOU, losses, lay, workspace, (hipStream_t)stream);
+}
+
+extern "C" int64_t mvx_focal_loss_iou_frames_workspace_bytes(int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                                             int32_t d_heads_ld, int64_t cap) {
+    const Layout lay(n_frames, l, w, anchors_per_loc, d_heads_ld);
+    return lay.ok && cap >= 1 ? lay.total(n_frames) + (long long)n_frames * iou_blocks(cap) * (long long)sizeof(double) : 0;
+}
+
+extern "C" int mvx_focal_loss_iou_frames(const float *heads, int32_t heads_ld, const float *dir, int32_t dir_ld, const float *iou,
+                                         int32_t iou_ld, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                                         const int64_t *pos_idx, const int64_t *neg_idx, const int64_t *gi, int64_t cap,
+                                         const int32_t *counts, const float *gts, int32_t gt_ld, const int32_t *gt_off,
+                                         const float *anchors, float alpha, float gamma, float cls_weight, float reg_weight,
+                                         float dir_weight, float dir_offset, float iou_weight, float *d_heads, int32_t d_heads_ld,
+                                         float *d_dir, int32_t d_dir_ld, float *d_iou, int32_t d_iou_ld, float *q_out, float *losses,
+                                         void *workspace, int64_t workspace_bytes, void *stream) {
+    const Layout lay(n_frames, l, w, anchors_per_loc, d_heads_ld);
+    MVX_CHECK_ARG(lay.ok);
+    MVX_CHECK_ARG(heads && dir && iou && pos_idx && neg_idx && gi && counts && gts && gt_off && anchors && losses && workspace);
+    MVX_CHECK_ARG(heads_ld >= 8 * anchors_per_loc && heads_ld % 4 == 0 && (long long)n_frames * l * w * heads_ld < (1ll << 31));
+    MVX_CHECK_ARG(dir_ld >= anchors_per_loc && (long long)n_frames * l * w * dir_ld < (1ll << 31));
+    MVX_CHECK_ARG(iou_ld >= anchors_per_loc && (long long)n_frames * l * w * iou_ld < (1ll << 31));
+    MVX_CHECK_ARG((d_heads == nullptr) == (d_dir == nullptr) && (d_heads == nullptr) == (d_iou == nullptr));
+    MVX_CHECK_ARG(!d_dir || (d_dir_ld >= anchors_per_loc && (long long)n_frames * l * w * d_dir_ld < (1ll << 31)));
+    MVX_CHECK_ARG(!d_iou || (d_iou_ld >= anchors_per_loc && (long long)n_frames * l * w * d_iou_ld < (1ll << 31)));
+    MVX_CHECK_ARG(cap >= 1 && cap < (1ll << 31) && gt_ld >= 7 && (!q_out || (long long)n_frames * cap < (1ll << 31)));
+    MVX_CHECK_ARG(alpha >= 0.f && alpha <= 1.f && gamma >= 0.f && dir_weight >= 0.f && dir_offset == dir_offset && iou_weight >= 0.f);
+    const int nq = iou_blocks(cap);
+    MVX_CHECK_ARG(workspace_bytes >= lay.total(n_frames) + (long long)n_frames * nq * (long long)sizeof(double));
+    MVX_CHECK_ARG(((uintptr_t)heads & 15) == 0 && ((uintptr_t)d_heads & 15) == 0 && ((uintptr_t)workspace & 7) == 0);
+    MVX_CHECK_ARG(((uintptr_t)dir & 3) == 0 && ((uintptr_t)d_dir & 3) == 0 && ((uintptr_t)iou & 3) == 0 && ((uintptr_t)d_iou & 3) == 0 &&
+                  ((uintptr_t)q_out & 3) == 0);
+    const Lists ls = {(const long long *)pos_idx, (const long long *)neg_idx, (const long long *)gi, (long long)cap, counts};
+    const Dir d = {dir, d_dir, dir_ld, d_dir_ld, dir_weight, dir_offset};
+    const Iou u = {iou, d_iou, iou_ld, d_iou_ld, iou_weight, q_out, (double *)((unsigned char *)workspace + lay.total(n_frames)), nq};
+    return focal_launch(heads, heads_ld, n_frames, l, w, anchors_per_loc, ls, gts, gt_ld, gt_off, anchors, alpha, gamma, cls_weight,
+                        reg_weight, d_heads, d_heads_ld, d, u, losses, lay, workspace, (hipStream_t)stream);
 }

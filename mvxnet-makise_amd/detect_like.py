@@ -42,6 +42,9 @@ def parse_args(argv=None):
     ap.add_argument('--bn-stats', choices=['auto', 'batch'], default='auto',
                     help='auto: a checkpoint of train_like.py --bn-track (it holds running_mean keys) runs in eval mode on its '
                          'running statistics; batch: every frame\'s own statistics even then (for comparison)')
+    ap.add_argument('--iou-alpha', type=float, default=0.5,
+                    help='a checkpoint of train_like.py --iou-head (it holds backbone.rpn.iou.weight): the scores are '
+                         'cls^(1-a) iou^a with this a in [0, 1] (0 = the plain score; 0.5 is a design choice, not a measured optimum)')
     ap.add_argument('--eval', action='store_true', help='score the written files against the split\'s label_2 (KITTI AP on the GPU)')
     ap.add_argument('--classes', nargs='+', default=['Car'], help='classes scored by --eval')
     ap.add_argument('--extractor-weights', default=None,
@@ -102,7 +105,12 @@ def _main(args):
     if bnr.checkpoint_tracks(state) and not tracked:
         state = bnr.strip_running(state)
     cfg.config['bntrack'] = tracked
-    model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
+    iou_head = state is not None and 'backbone.rpn.iou.weight' in state       # written by train_like.py --iou-head
+    if iou_head:
+        model = MVXNet(direction=True, iou=True).to(device)
+        print('IoU head of the checkpoint: scores rectified with iou_alpha=%g' % args.iou_alpha)
+    else:
+        model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
     if state is not None:
         model.load_state_dict(state)
     if tracked:
@@ -115,6 +123,8 @@ def _main(args):
     kw = dict(score_thr=args.score_thr, iou_thr=args.iou_thr, pre_max=args.pre_max, post_max=args.post_max, decode=args.decode)
     if direction:
         kw['dir_offset'] = args.dir_offset
+    if iou_head:
+        kw['iou_alpha'] = args.iou_alpha
     from modules import tta
     tta_kw, n_views = tta.options(args)
     kw.update(tta_kw)

@@ -2057,6 +2057,65 @@ def focal_loss_dir_frames(heads, dir_logits, F, l, w, A, pos_idx, neg_idx, gi, c
     return losses, d_heads, d_dir
 
 
+def _column_range(cols, heads, A):
+    """Is ``cols`` (rows, A) a column range of the rows of ``heads``?  -> its first column, or None."""
+    off = cols.data_ptr() - heads.data_ptr()
+    if (cols.stride(0) == heads.stride(0) and 0 <= off <= 4 * (heads.shape[1] - A)
+            and cols.untyped_storage().data_ptr() == heads.untyped_storage().data_ptr()):
+        return off // 4
+    return None
+
+
+def focal_loss_iou_frames(heads, dir_logits, iou_logits, F, l, w, A, pos_idx, neg_idx, gi, counts, gts, gt_off, anchors, alpha, gamma,
+                          cls_weight, reg_weight, dir_weight, dir_offset, iou_weight, want_grads=True, want_q=False, d_heads=None,
+                          d_dir=None, d_iou=None):
+    """``focal_loss_dir_frames`` plus the IoU-aware confidence head (csrc/loss_frames.hip): the memset and four
+    launches.  ``iou_logits`` f32 (F*l*w, A) with any row stride and unit column stride, like ``dir_logits``: columns of
+    ``heads`` (``heads[:, 9A:10A]``) or a tensor of its own.  Returns (losses f32 (F,4) = (cls, reg, dir, iou) per frame,
+    d_heads, d_dir, d_iou, q) -- the gradients None without ``want_grads``, d_dir / d_iou column ranges of d_heads when the
+    logits are column ranges of ``heads`` and tensors of their own otherwise; q f32 (F, cap) with ``want_q``: the IoU target of
+    every pos_idx entry, -1 for skipped entries and unused slots (None otherwise).  ``d_heads`` / ``d_dir`` / ``d_iou``
+    (tests): buffers to write instead."""
+    dev = heads.device
+    rows = F * l * w
+    assert heads.dtype == dir_logits.dtype == iou_logits.dtype == torch.float32 and heads.dim() == 2 and heads.shape[0] == rows
+    assert heads.stride(1) == 1 and heads.shape[1] >= 8 * A and (rows == 1 or heads.stride(0) % 4 == 0)
+    assert tuple(dir_logits.shape) == (rows, A) and dir_logits.stride(1) == 1
+    assert tuple(iou_logits.shape) == (rows, A) and iou_logits.stride(1) == 1
+    assert tuple(pos_idx.shape) == tuple(neg_idx.shape) == (F, 3, gi.shape[1]) and tuple(gi.shape) == (F, gi.shape[1])
+    assert pos_idx.dtype == neg_idx.dtype == gi.dtype == torch.int64 and counts.dtype == gt_off.dtype == torch.int32
+    assert tuple(counts.shape) == (F, 2) and tuple(gt_off.shape) == (F + 1,) and gts.dtype == anchors.dtype == torch.float32
+    assert gts.dim() == 2 and gts.shape[0] >= 1 and anchors.numel() == l * w * A * 7
+    ld, cap = heads.stride(0), gi.shape[1]
+    losses = torch.empty((F, 4), dtype=torch.float32, device=dev)
+    q = torch.empty((F, cap), dtype=torch.float32, device=dev) if want_q else None
+    ldd = ld
+    if want_grads:
+        if d_heads is None:
+            d_heads = torch.empty((rows, heads.shape[1]), dtype=torch.float32, device=dev)
+
+        def grad_of(logits, given):
+            if given is not None:
+                return given
+            c0 = _column_range(logits, heads, A)
+            return d_heads[:, c0:c0 + A] if c0 is not None else torch.empty((rows, A), dtype=torch.float32, device=dev)
+        d_dir, d_iou = grad_of(dir_logits, d_dir), grad_of(iou_logits, d_iou)
+        assert d_heads.stride(1) == 1 and d_dir.stride(1) == 1 and tuple(d_dir.shape) == (rows, A)
+        assert d_iou.stride(1) == 1 and tuple(d_iou.shape) == (rows, A)
+        ldd = d_heads.stride(0)
+    else:
+        d_heads = d_dir = d_iou = None
+    nbytes = X.lib.mvx_focal_loss_iou_frames_workspace_bytes(int(F), int(l), int(w), int(A), int(ldd), int(cap))
+    ws = workspace(nbytes, dev, 'focal_loss')
+    X.call('mvx_focal_loss_iou_frames', _vptr(heads), int(ld), _vptr(dir_logits), int(dir_logits.stride(0)), _vptr(iou_logits),
+           int(iou_logits.stride(0)), int(F), int(l), int(w), int(A), pos_idx, neg_idx, gi, cap, counts, gts, gts.shape[1], gt_off,
+           anchors, float(alpha), float(gamma), float(cls_weight), float(reg_weight), float(dir_weight), float(dir_offset),
+           float(iou_weight), _vptr(d_heads) if want_grads else None, int(ldd), _vptr(d_dir) if want_grads else None,
+           int(d_dir.stride(0)) if want_grads else 0, _vptr(d_iou) if want_grads else None,
+           int(d_iou.stride(0)) if want_grads else 0, q, losses, ws, ws.numel())
+    return losses, d_heads, d_dir, d_iou, q
+
+
 # ---------------------------------------------------------------------------------------------
 # detection output (csrc/detect.hip)
 # ---------------------------------------------------------------------------------------------
@@ -2064,14 +2123,16 @@ DECODE_MODES = {'loss': 0, 'reference': 1}
 
 
 def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, post_max, decode='loss', debug=False, dir_logits=None,
-                  dir_offset=math.pi / 4):
+                  dir_offset=math.pi / 4, iou_logits=None, iou_alpha=0.5):
     """Selection, decoding and rotated BEV NMS of F frames in four launches.  ``cls`` / ``reg``: f32 views (F, l, w, A) and
     (F, l, w, 7A) with arbitrary element strides (the frame-set heads or NCHW maps, read in place); anchors f32 [l][w][A][7]
     contiguous on the device.  Returns (boxes (F,post_max,7), scores (F,post_max), anchor_idx i32 (F,post_max), meta i32 (3,F) =
     (kept count, candidates above score_thr, status)) on the device, plus (candidate anchor indices i32 (F,pre_max), decoded
     boxes (F,pre_max,7), corners (F,pre_max,4,2)) with ``debug``.  ``dir_logits``: f32 view (F, l, w, A) of the direction head:
     the decoded yaw is folded into the half turn its sign names, around ``dir_offset``, and wrapped into [-pi, pi)
-    (mvx_detect_frames_dir); None is the plain decode (mvx_detect_frames)."""
+    (mvx_detect_frames_dir); None is the plain decode (mvx_detect_frames).  ``iou_logits``: f32 view (F, l, w, A) of the IoU head:
+    candidates are admitted, ordered and scored by cls^(1-a) iou^a with a = ``iou_alpha`` in [0, 1] (mvx_detect_frames_iou,
+    DESIGN.md 3.35); None leaves the score sigmoid(cls)."""
     if decode not in DECODE_MODES:
         raise X.MvxHipError("decode must be 'loss' or 'reference', not %r" % (decode,))
     dev = cls.device
@@ -2089,6 +2150,17 @@ def detect_frames(cls, reg, anchors, F, l, w, A, score_thr, iou_thr, pre_max, po
     nbytes = X.lib.mvx_detect_workspace_bytes(F, l * w * A, pre_max)
     ws = workspace(nbytes, dev, 'detect')
     cs, rs = cls.stride(), reg.stride()
+    if iou_logits is not None:
+        assert iou_logits.shape == (F, l, w, A) and iou_logits.dtype == torch.float32 and iou_logits.device == dev
+        assert dir_logits is None or (dir_logits.shape == (F, l, w, A) and dir_logits.dtype == torch.float32 and dir_logits.device == dev)
+        ds, us = dir_logits.stride() if dir_logits is not None else (0, 0, 0, 0), iou_logits.stride()
+        X.call('mvx_detect_frames_iou', _vptr(cls), cs[0], cs[1], cs[2], cs[3], _vptr(reg), rs[0], rs[1], rs[2], rs[3],
+               _vptr(dir_logits) if dir_logits is not None else None, ds[0], ds[1], ds[2], ds[3], float(dir_offset),
+               _vptr(iou_logits), us[0], us[1], us[2], us[3], float(iou_alpha), anchors, int(F), int(l), int(w), int(A),
+               float(score_thr), float(iou_thr), int(pre_max), int(post_max), DECODE_MODES[decode], boxes, scores, idx, meta[0],
+               meta[1], meta[2], dbg[0], dbg[1], dbg[2], ws, ws.numel())
+        out = (boxes, scores, idx, meta)
+        return out + dbg if debug else out
     if dir_logits is not None:
         assert dir_logits.shape == (F, l, w, A) and dir_logits.dtype == torch.float32 and dir_logits.device == dev
         ds = dir_logits.stride()

@@ -30,23 +30,29 @@ def _anchors_dev(anchors, h1, w1, dev):
 
 
 def _views(heads_or_maps, F, h1, w1):
-    """(cls (F,h1,w1,A), reg (F,h1,w1,7A), dir (F,h1,w1,A) or None) views of the channels-last heads (F*h1*w1, 16), of the
-    direction model's (F*h1*w1, 20) = [cls | reg | dir | 0 0] (rpn_frames.head_layout), or of NCHW maps (cls, reg[, dir])."""
+    """(cls (F,h1,w1,A), reg (F,h1,w1,7A), dir (F,h1,w1,A) or None, iou (F,h1,w1,A) or None) views of the channels-last heads
+    (F*h1*w1, 16), of the direction model's (F*h1*w1, 20) = [cls | reg | dir | 0 0] (rpn_frames.head_layout), or of NCHW maps
+    (cls, reg[, dir[, iou]]).  The last entry of a heads tensor is columns 9A..10A when the rows are that wide: whether they are
+    IoU logits or padding the caller knows (``postprocess(iou=)``), the width does not tell."""
     if isinstance(heads_or_maps, (tuple, list)):
         cls, reg = heads_or_maps[:2]
         assert cls.dim() == 4 and cls.shape[0] == F and cls.shape[2:] == (h1, w1), tuple(cls.shape)
         assert reg.shape == (F, 7 * cls.shape[1], h1, w1), tuple(reg.shape)
         dirm = heads_or_maps[2] if len(heads_or_maps) > 2 else None
         assert dirm is None or dirm.shape == cls.shape, tuple(dirm.shape)
-        return cls.permute(0, 2, 3, 1), reg.permute(0, 2, 3, 1), None if dirm is None else dirm.permute(0, 2, 3, 1)
+        ioum = heads_or_maps[3] if len(heads_or_maps) > 3 else None
+        assert ioum is None or ioum.shape == cls.shape, tuple(ioum.shape)
+        return (cls.permute(0, 2, 3, 1), reg.permute(0, 2, 3, 1), None if dirm is None else dirm.permute(0, 2, 3, 1),
+                None if ioum is None else ioum.permute(0, 2, 3, 1))
     from modules import rpn_frames as rf
     v = heads_or_maps.view(F, h1, w1, -1)
     A, has_dir = rf.head_layout(v.shape[-1])
-    return v[..., :A], v[..., A:8 * A], v[..., 8 * A:9 * A] if has_dir else None
+    return (v[..., :A], v[..., A:8 * A], v[..., 8 * A:9 * A] if has_dir else None,
+            v[..., 9 * A:10 * A] if has_dir and v.shape[-1] >= 10 * A else None)
 
 
 def postprocess(heads_or_maps, anchors, F, h1, w1, *, score_thr=0.05, iou_thr=0.01, pre_max=1000, post_max=100, decode='loss',
-                read=True, debug=False, direction=None, dir_offset=math.pi / 4):
+                read=True, debug=False, direction=None, dir_offset=math.pi / 4, iou=None, iou_alpha=0.5):
     """Boxes of F frames from the raw head output, read in place: the frame-set heads (F*h1*w1, 16) = [cls logits | reg] of
     ``rpn_frames.rpn_forward``, or NCHW maps ``(cls logits (F,2,h1,w1), reg (F,14,h1,w1))``.  ``anchors`` (h1, w1, 14) =
     [l][w][A][7] (Preprocessing.createAnchors), on the host or the device.
@@ -60,12 +66,27 @@ def postprocess(heads_or_maps, anchors, F, h1, w1, *, score_thr=0.05, iou_thr=0.
     NMS.  None (default) = when the heads carry direction columns (the 20-wide rows of a direction model, or a third map);
     True without them is an error, False ignores them.
 
+    ``iou``: admit, rank and score the anchors by cls^(1-a) iou^a, a = ``iou_alpha`` in [0, 1], with the IoU logits of the head
+    that ``FocalLoss(iou=True)`` trains -- columns 9A..10A of the rows of an IoU model
+    (``MVXNet(direction=True, iou=True)``), or a fourth map.  With a heads tensor None means off: a 20-wide row does not tell
+    whether its last two columns are IoU logits or the direction model's padding, so ``detect_frame_set`` / ``MVXNet.detect``
+    pass ``hasattr(rpn, 'iou')``; with maps None means "a fourth map is there".  True without the columns is an error.
+    ``iou_alpha = 0.5`` is a design choice taken over from those detectors' papers, not an optimum measured here; 0 is the plain score.
+
     Returns a list of F dicts ``{boxes (n,7) xyzlwhr, scores (n,), anchor_idx (n,) i32, n_candidates, status}`` (device
     tensors) after ONE device->host read; ``read=False`` returns the padded device tensors instead
     ``{boxes (F,post_max,7), scores, anchor_idx, meta i32 (3,F) = (counts, n_candidates, status)}`` for a caller that
     pipelines (``unpack`` reads them later).  ``debug`` adds the sorted candidates ('cand_idx', 'cand_boxes',
     'cand_corners', padded to pre_max) to the device dict."""
-    cls, reg, dirv = _views(heads_or_maps, F, h1, w1)
+    cls, reg, dirv, iouv = _views(heads_or_maps, F, h1, w1)
+    if iou is None:
+        iou = iouv is not None and isinstance(heads_or_maps, (tuple, list))
+    if iou and iouv is None:
+        raise X.MvxHipError('postprocess(iou=True) needs heads with IoU columns (MVXNet(direction=True, iou=True)) or a fourth map')
+    if iou and iouv.dtype != torch.float32:
+        raise X.MvxHipError('postprocess reads f32 head outputs')
+    if iou and not 0.0 <= float(iou_alpha) <= 1.0:
+        raise X.MvxHipError('iou_alpha must lie in [0, 1], not %r' % (iou_alpha,))
     if direction is None:
         direction = dirv is not None
     if direction and dirv is None:
@@ -79,7 +100,8 @@ def postprocess(heads_or_maps, anchors, F, h1, w1, *, score_thr=0.05, iou_thr=0.
     if anc.shape[2] != A:
         raise X.MvxHipError('anchors hold %d orientations per cell, the heads %d' % (anc.shape[2], A))
     res = _hip.detect_frames(cls, reg, anc, F, h1, w1, A, score_thr, iou_thr, pre_max, post_max, decode, debug=debug,
-                             dir_logits=dirv if direction else None, dir_offset=dir_offset)
+                             dir_logits=dirv if direction else None, dir_offset=dir_offset, iou_logits=iouv if iou else None,
+                             iou_alpha=iou_alpha)
     out = dict(boxes=res[0], scores=res[1], anchor_idx=res[2], meta=res[3])
     if debug:
         out.update(cand_idx=res[4], cand_boxes=res[5], cand_corners=res[6])
@@ -134,6 +156,7 @@ def _detect_dev(model, batch, anchors, imsize, ready, keep, kw, then=None):
     from modules import pipeline as pl
     from modules import rpn_frames as rf
     opts = dict(DEFAULTS, **kw)
+    opts.setdefault('iou', hasattr(model.backbone.rpn, 'iou'))
     dev = batch.device
     bn_step = bnr.step(model, train_entry=False)
     fs, live, counts, status = pl._take_ready(batch, ready, torch.cuda.current_stream(dev))

@@ -820,7 +820,9 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     raw head output, in place of the per-frame VoxelLoss; it needs ``rpn_hip=True``.  With ``FocalLoss(direction=True)`` on a
     model with the direction head (``MVXNet(direction=True)``) the losses are (F,3) and out['dir'] holds the direction loss of
     every frame with a positive, out['loss'] includes it; a direction criterion on a model without ``rpn.dir``, or any other
-    criterion on a model with it, raises MvxHipError before anything is launched.
+    criterion on a model with it, raises MvxHipError before anything is launched.  ``FocalLoss(direction=True, iou=True)`` on
+    ``MVXNet(direction=True, iou=True)`` likewise: losses (F,4), out['iou'] the IoU loss of every frame with a positive, included
+    in out['loss']; an IoU criterion on a model without ``rpn.iou``, or a criterion without it on a model with it, raises.
     ``prepare_next`` = (next batch, callable returning its targets): voxelized, mapped and target-assigned on the
     preparation stream after this step has been enqueued; returned as out['next'] = (ready, targets) for the next call.
     ``read=False`` leaves the losses on the device (out['losses_dev'] (F,2)) and skips the status read: the caller reads
@@ -840,6 +842,11 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
         raise _hip.X.MvxHipError('the direction head is trained by FocalLoss(direction=True) on MVXNet(direction=True): the model %s '
                                  'rpn.dir, the criterion is %s' % ('has' if hasattr(model.backbone.rpn, 'dir') else 'has no',
                                                                    type(criterion).__name__ + ('(direction=True)' if getattr(criterion, 'direction', False) else '')))
+    if bool(getattr(criterion, 'iou', False)) != hasattr(model.backbone.rpn, 'iou'):
+        raise _hip.X.MvxHipError('the IoU head is trained by FocalLoss(direction=True, iou=True) on MVXNet(direction=True, iou=True): '
+                                 'the model %s rpn.iou, the criterion is %s'
+                                 % ('has' if hasattr(model.backbone.rpn, 'iou') else 'has no',
+                                    type(criterion).__name__ + ('(iou=True)' if getattr(criterion, 'iou', False) else '')))
     if not rpn_hip and _hip.bn_tracking():
         raise _hip.X.MvxHipError('bntrack: the torch RPN modules of rpn_hip=False normalise with batch statistics only; the running '
                                  'statistics are kept on the frame-set RPN (rpn_hip=True)')
@@ -914,6 +921,17 @@ def read_losses(out):
         return out
     _check_statuses(out['statuses'])
     vals = out['losses_dev'].tolist()
+    if vals and len(vals[0]) == 4:                  # an IoU criterion: (cls, reg, dir, iou) per frame
+        out.setdefault('dir', [])
+        out.setdefault('iou', [])
+        for (c, r, d, u), hr in zip(vals, out['has_reg']):
+            out['cls'].append(c)
+            if hr:
+                out['reg'].append(r)
+                out['dir'].append(d)
+                out['iou'].append(u)
+            out['loss'].append(c + r + d + u if hr else c)
+        return out
     if vals and len(vals[0]) == 3:                  # a direction criterion: (cls, reg, dir) per frame
         out.setdefault('dir', [])
         for (c, r, d), hr in zip(vals, out['has_reg']):

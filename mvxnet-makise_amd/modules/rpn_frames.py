@@ -17,7 +17,8 @@ every CRB2d / DeCRB2d = conv -> ReLU -> BatchNorm with per-frame batch statistic
     its channel slice of the 768-channel concat buffer by one pass (csrc/rpn.hip);
   * the two heads: one row GEMM with 16 output columns; with the optional direction head (``RPN(direction=True)``) the same
     GEMM with 20: [cls 2 | reg 14 | dir 2 | two zero columns], so that rows stay multiples of 16 bytes and the 768-channel
-    concat buffer is read once.
+    concat buffer is read once; the IoU head (``RPN(direction=True, iou=True)``) puts its two logits where the zero columns
+    stand: [cls 2 | reg 14 | dir 2 | iou 2].
 Maps are channels-last [F][h][w][c].  Parameter gradients are ADDED into the existing .grad buffers, weight-gradient
 kernels run on the side stream.
 """
@@ -187,7 +188,8 @@ def _d2s(xs, F, planes, h, w, C):
 def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
     """x_cl: the normalised CML output, channels-last planes [F*planes][H][W][Cp] (BEV channel c*planes + d).
     Returns (heads (F*H/2*W/2, 16) = [cls logits (2) | reg (14)] per BEV cell, saved state); with a direction head the rows
-    are 20 wide, [cls (2) | reg (14) | dir logits (2) | 0 0] (``head_layout``)."""
+    are 20 wide, [cls (2) | reg (14) | dir logits (2) | 0 0] (``head_layout``), and with the IoU head on top of it
+    [cls (2) | reg (14) | dir logits (2) | iou logits (2)]: the width does not tell the two apart, the model does."""
     dev = x_cl.device
     eps = cfg.eps
     _hip.require_no_bnaffine()
@@ -243,10 +245,14 @@ def rpn_forward(rpn, x_cl, F, planes, H, W, Cp):
     if dirh is None:
         w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768)]).contiguous()
         b_heads = torch.cat([rpn.cls.bias, rpn.reg.bias])
-    else:                                           # + the direction logits and two zero rows: 20 columns
+    elif getattr(rpn, 'iou', None) is None:         # + the direction logits and two zero rows: 20 columns
         w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768), dirh.weight.view(2, 768),
                              torch.zeros((2, 768), dtype=torch.float32, device=dev)]).contiguous()
         b_heads = torch.cat([rpn.cls.bias, rpn.reg.bias, dirh.bias, torch.zeros((2,), dtype=torch.float32, device=dev)])
+    else:                                           # the IoU logits where the zero rows stand: the same 20 columns
+        w_heads = torch.cat([rpn.cls.weight.view(2, 768), rpn.reg.weight.view(14, 768), dirh.weight.view(2, 768),
+                             rpn.iou.weight.view(2, 768)]).contiguous()
+        b_heads = torch.cat([rpn.cls.bias, rpn.reg.bias, dirh.bias, rpn.iou.bias])
     heads, _ = _hip.linear_forward(up, w_heads, b_heads, relu=False, want_stats=False)
     S.update(up=up, w_heads=w_heads, h1=h1, w1=w1)
     return heads, S
@@ -306,6 +312,9 @@ def rpn_backward(rpn, S, d_heads):
         if w_heads.shape[0] == 20:                  # the direction head (its two pad columns of d_heads are zero)
             _grad_of(rpn.dir.weight).view(2, 768).add_(dwh[16:18])
             _grad_of(rpn.dir.bias).add_(db[16:18])
+            if getattr(rpn, 'iou', None) is not None:      # the IoU head: columns 18..19 are its logits, not padding
+                _grad_of(rpn.iou.weight).view(2, 768).add_(dwh[18:20])
+                _grad_of(rpn.iou.bias).add_(db[18:20])
     g_up, _ = _hip.linear_forward(d_heads, w_heads, None, relu=False, want_stats=False, w_transposed=True)      # (rows, 768)
     g_up = _mut('heads_dgrad', g_up)
     # deconv2 / deconv3

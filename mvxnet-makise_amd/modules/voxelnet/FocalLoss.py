@@ -19,6 +19,16 @@ have saturated to 0 or 1 in f32 cannot be computed -- so it is used through ``he
 and the decode (modules/detect.py) folds the regressed yaw into the half turn the logit names.  ``dir_weight=0.2`` and
 ``dir_offset=pi/4`` are the values of SECOND's and mmdetection3d's KITTI configurations: design choices taken over from
 there, not optima measured on this model.
+
+``iou=True`` (with ``direction=True``) trains the IoU-aware confidence head of CIA-SSD / AFDetV2 on a model
+built with ``MVXNet(direction=True, iou=True)``.  Per ``pi`` entry, with x the anchor's IoU logit and the anchor's regression
+row read as a constant (nothing flows into the regression from this term):
+
+    q       = 3D IoU of the box the regression currently decodes (modules/detect.py, decode='loss') with its ground truth
+    iouLoss = iou_weight / max(1, len(pi)) * sum (-q log sigmoid(x) - (1 - q) log(1 - sigmoid(x)))
+
+and the decode ranks and scores by sigmoid(cls)^(1-a) sigmoid(x)^a.  ``iou_weight=1.0`` (and the decode's ``iou_alpha=0.5``)
+are design choices in the range those papers use, not optima measured on this model.
 """
 import collections
 import math
@@ -43,10 +53,15 @@ def _on_device(x):
 
 class FocalLoss(nn.Module):
 
-    def __init__(self, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0, direction=False, dir_weight=0.2, dir_offset=math.pi / 4):
+    def __init__(self, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0, direction=False, dir_weight=0.2, dir_offset=math.pi / 4,
+                 iou=False, iou_weight=1.0):
         super().__init__()
+        if iou and not direction:
+            raise X.MvxHipError('FocalLoss(iou=True) needs direction=True: the IoU logits take the two pad columns of the direction '
+                                'model\'s head rows')
         self.alpha, self.gamma, self.cls_weight, self.reg_weight = alpha, gamma, cls_weight, reg_weight
         self.direction, self.dir_weight, self.dir_offset = bool(direction), dir_weight, dir_offset
+        self.iou, self.iou_weight = bool(iou), iou_weight
 
     def forward(self, pi, ni, gi, gts, score, reg, anchors, anchorsPerLoc):
         raise NotImplementedError('FocalLoss needs the logits of the heads, not their probabilities (a focal loss from '
@@ -108,7 +123,9 @@ class FocalLoss(nn.Module):
         loss", d_heads) -- the triple of pipeline.heads_loss.  With ``direction`` the rows are those of a direction model,
         [cls | reg | dir logits | zeros] (rpn_frames.head_layout), losses is (F,3) = (clsLoss, regLoss or 0, dirLoss) and
         d_heads carries the direction gradient in its columns, zeros in the pad columns.  A criterion and rows that do not
-        match raise MvxHipError before anything is launched."""
+        match raise MvxHipError before anything is launched.  With ``iou`` the rows are those of an IoU model, [cls | reg | dir
+        logits | iou logits] (columns 9A..10A), losses is (F,4) = (clsLoss, regLoss or 0, dirLoss, iouLoss) and d_heads carries
+        the IoU gradient in those columns."""
         from modules import rpn_frames as rf
         if not heads.is_cuda:
             raise X.MvxHipError('FocalLoss runs on the GPU (no CPU fallback)')
@@ -123,6 +140,15 @@ class FocalLoss(nn.Module):
         if not anc.is_cuda:
             from modules import Calc
             anc = Calc._anchors_on(anchors, dev)
+        if self.iou:
+            if heads.shape[1] < 10 * A:
+                raise X.MvxHipError('FocalLoss(iou=True) reads the IoU logits from columns %d..%d of the head rows; these are %d '
+                                    'wide' % (9 * A, 10 * A, heads.shape[1]))
+            losses, d_heads = _hip.focal_loss_iou_frames(heads, heads[:, 8 * A:9 * A], heads[:, 9 * A:10 * A], F, h1, w1, A,
+                                                         packed.pos_idx, packed.neg_idx, packed.gi, packed.counts, packed.gts,
+                                                         packed.gt_off, anc, self.alpha, self.gamma, self.cls_weight, self.reg_weight,
+                                                         self.dir_weight, self.dir_offset, self.iou_weight, want_grads=want_grads)[:2]
+            return losses, has_reg, d_heads
         if self.direction:
             losses, d_heads, _ = _hip.focal_loss_dir_frames(heads, heads[:, 8 * A:9 * A], F, h1, w1, A, packed.pos_idx, packed.neg_idx,
                                                             packed.gi, packed.counts, packed.gts, packed.gt_off, anc, self.alpha,

@@ -179,9 +179,15 @@ class RPN(nn.Module):
     ``direction=True`` adds a third head ``dir``, one logit per anchor: the two-way direction classifier of SECOND /
     PointPillars that says which half turn of the box is meant (voxelnet/FocalLoss.py).  It is trained on the
     frame-set path only; ``forward`` / ``forward_cl`` / ``forward_torch`` return (score, reg) for both kinds of model.  Without
-    it the module tree and the state dict are the reference's."""
+    it the module tree and the state dict are the reference's.
 
-    def __init__(self, direction=False):
+    ``iou=True`` (with ``direction=True``) adds a fourth head ``iou``, one logit per anchor: the IoU-aware confidence of
+    CIA-SSD / AFDetV2, trained to predict the 3D IoU of the decoded box with its ground truth and multiplied into the score
+    at inference (voxelnet/FocalLoss.py, modules/detect.py).  Its two logits take the two pad columns of the
+    direction model's 20-wide head rows, which is why it needs the direction head.  Trained on the frame-set path only, like
+    ``dir``."""
+
+    def __init__(self, direction=False, iou=False):
         super().__init__()
         self.blk1 = nn.Sequential(CRB2d(128, 128, 3, 2, 1), *[CRB2d(128, 128, 3, 1, 1) for _ in range(3)])
         self.blk2 = nn.Sequential(CRB2d(128, 128, 3, 2, 1), *[CRB2d(128, 128, 3, 1, 1) for _ in range(5)])
@@ -191,8 +197,14 @@ class RPN(nn.Module):
         self.deconv3 = DeCRB2d(256, 256, 4, 4, 0)
         self.cls = nn.Conv2d(768, 2, 1, 1, 0)
         self.reg = nn.Conv2d(768, 14, 1, 1, 0)
+        if iou and not direction:
+            from modules.Extension import MvxHipError
+            raise MvxHipError('RPN(iou=True) needs direction=True: the IoU logits take the two pad columns of the direction '
+                              'model\'s 20-wide head rows (every IoU-aware detector this follows has the direction head)')
         if direction:
             self.dir = nn.Conv2d(768, 2, 1, 1, 0)
+        if iou:
+            self.iou = nn.Conv2d(768, 2, 1, 1, 0)
 
     def _hip_ok(self, x, H, W):
         return bool(cfg.config.get('rpn_hip', True)) and x.is_cuda and x.dtype == torch.float32 and H % 8 == 0 and W % 8 == 0

@@ -43,12 +43,12 @@ class BEVFunction(torch.autograd.Function):
 
 class VoxelNet(nn.Module):
 
-    def __init__(self, direction=False):
+    def __init__(self, direction=False, iou=False):
         super().__init__()
         self.svfe = Pipe.SVFE(cfg.samplenum)
         self.fcn = Pipe.FCN(128, 128)
         self.cml = Pipe.CML()
-        self.rpn = Pipe.RPN(direction=direction)
+        self.rpn = Pipe.RPN(direction=direction, iou=iou)
         self.sparse_first_layer = True     # exact input-sparse evaluation of reindex + cml.conv1
         self.restricted_backward = True    # tile-restricted backward inside the CML chain (exact; see middle_cl)
 

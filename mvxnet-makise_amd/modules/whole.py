@@ -142,7 +142,8 @@ def _all_params(model):
 
 def forward_heads(model, voxels, imgs, idx, imsize):
     """The single node's raw output: heads (H/2 * W/2, 16) = [cls logits (2) | reg (14)] per BEV cell (20 wide with the
-    direction head: rpn_frames.head_layout).  The data-dependent
+    direction head: rpn_frames.head_layout; columns 18..19 are the IoU logits when ``hasattr(model.backbone.rpn, 'iou')``,
+    which is what a caller passes to ``detect.postprocess(iou=)``).  The data-dependent
     status words of the sampling / scatter kernels stand for the reference's assert (imhead/Pipe.py:71); they are collected
     on the model and read without stalling the training stream (take_status), at once for a no-grad call."""
     hw = _imsize_hw(imsize)

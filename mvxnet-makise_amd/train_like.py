@@ -30,6 +30,10 @@ direction classifier per anchor (``backbone.rpn.dir``), the angle is regressed t
 decode of detect_like.py folds the yaw back with the classifier's bit.  ``--dir-weight`` / ``--dir-offset`` are FocalLoss's;
 pass the same ``--dir-offset`` to detect_like.py / visualize_like.py (the checkpoint is the bare state dict).
 
+``--iou-head`` (with ``--direction``; ``--iou-weight``, default 1.0) adds the IoU-aware confidence head of CIA-SSD / AFDetV2
+(``backbone.rpn.iou``): one logit per anchor trained to predict the 3D IoU of the decoded box with its ground truth, which
+detect_like.py multiplies into the score (``--iou-alpha`` there).
+
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
                 frames), RPN + VoxelLoss per frame (per-frame BatchNorm statistics, as B reference forwards), one AdamW
@@ -110,6 +114,11 @@ def parse_args(argv=None):
     ap.add_argument('--dir-weight', type=float, default=0.2, help='--direction: weight of the direction loss (SECOND\'s value)')
     ap.add_argument('--dir-offset', type=float, default=math.pi / 4,
                     help='--direction: yaw at which the direction bit flips (SECOND\'s pi/4); detect_like.py takes the same value')
+    ap.add_argument('--iou-head', action='store_true',
+                    help='--direction: an IoU-aware confidence logit per anchor (MVXNet(direction=True, iou=True), '
+                         'FocalLoss(direction=True, iou=True)); detect_like.py rectifies the scores with it')
+    ap.add_argument('--iou-weight', type=float, default=1.0,
+                    help='--iou-head: weight of the IoU loss (a design choice, not an optimum measured here)')
     ap.add_argument('--bn-track', action='store_true',
                     help='--mode fast: running BatchNorm statistics (config.yml bntrack: True does the same): the checkpoints carry '
                          'running_mean / running_var / num_batches_tracked, detect_like.py then runs the model in eval mode')
@@ -119,6 +128,10 @@ def parse_args(argv=None):
         ap.error('--bn-track needs --mode fast: the running statistics are kept on the frame-set path')
     if not 0.0 <= args.bn_momentum <= 1.0:
         ap.error('--bn-momentum must lie in 0..1')
+    if args.iou_head and not args.direction:
+        ap.error('--iou-head needs --direction: the IoU logits take the two pad columns of the direction model\'s head rows')
+    if args.iou_weight < 0:
+        ap.error('--iou-weight must not be negative')
     if args.direction and (args.mode != 'fast' or args.loss != 'focal'):
         ap.error('--direction needs --mode fast --loss focal: the direction head is trained by the focal loss of the frame-set '
                  'heads only')
@@ -300,14 +313,20 @@ def _train(args):
     tracked = bool(cfg.config.get('bntrack', False))
     if tracked and args.mode != 'fast':
         raise SystemExit('bntrack needs --mode fast: the running BatchNorm statistics are kept on the frame-set path')
-    model = (MVXNet(direction=True) if args.direction else MVXNet()).to(device)
+    if args.iou_head:
+        model = MVXNet(direction=True, iou=True).to(device)
+    else:
+        model = (MVXNet(direction=True) if args.direction else MVXNet()).to(device)
     if tracked:
         # every rank folds its own frames into its own buffers and rank 0's are saved: no buffer all-reduce (modules/parallel.py)
         bnr.set_momentum(model, getattr(args, 'bn_momentum', 0.1))
         say('bntrack: running BatchNorm statistics, momentum %g' % getattr(args, 'bn_momentum', 0.1))
     if args.loss == 'focal':
         from modules.voxelnet.FocalLoss import FocalLoss
-        if args.direction:
+        if args.iou_head:
+            criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight, direction=True,
+                                  dir_weight=args.dir_weight, dir_offset=args.dir_offset, iou=True, iou_weight=args.iou_weight)
+        elif args.direction:
             criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight, direction=True,
                                   dir_weight=args.dir_weight, dir_offset=args.dir_offset)
         else:
@@ -316,6 +335,8 @@ def _train(args):
             % (criterion.alpha, criterion.gamma, criterion.cls_weight, criterion.reg_weight))
         if args.direction:
             say('direction head: dir_weight=%g, dir_offset=%g, sine angle loss' % (criterion.dir_weight, criterion.dir_offset))
+        if args.iou_head:
+            say('IoU head: iou_weight=%g' % criterion.iou_weight)
     else:
         criterion = VoxelLoss()
         say('criterion: VoxelLoss(a=%g, b=%g)' % (criterion.a, criterion.b))
@@ -372,8 +393,8 @@ def _train(args):
     for epoch in range(args.numepochs):
         random.Random(epoch + args.lastiter).shuffle(trainDataSet)
         mine = trainDataSet
-        clsLossSum = regLossSum = dirLossSum = 0.0
-        clsCnt = regCnt = dirCnt = 0
+        clsLossSum = regLossSum = dirLossSum = iouLossSum = 0.0
+        clsCnt = regCnt = dirCnt = iouCnt = 0
         if args.mode == 'module':
             for i, data in enumerate(mine):
                 voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo, geo, assigner)
@@ -451,7 +472,7 @@ def _train(args):
                                                   # the step it has just enqueued
 
             def account(p):
-                nonlocal clsLossSum, clsCnt, regLossSum, regCnt, dirLossSum, dirCnt
+                nonlocal clsLossSum, clsCnt, regLossSum, regCnt, dirLossSum, dirCnt, iouLossSum, iouCnt
                 if p is None:
                     return
                 pl.read_losses(p)
@@ -462,6 +483,8 @@ def _train(args):
                 regCnt += len(p['reg'])
                 dirLossSum += sum(p.get('dir', ()))
                 dirCnt += len(p.get('dir', ()))
+                iouLossSum += sum(p.get('iou', ()))
+                iouCnt += len(p.get('iou', ()))
 
             t_epoch = time.perf_counter()
             frames_epoch = 0
@@ -489,9 +512,10 @@ def _train(args):
                 pending = out
                 frames_epoch += hi - lo
                 steps_done += 1
-                say('Epoch%d %d/%d  average classification loss %.6f, average regression loss %.6f%s'
+                say('Epoch%d %d/%d  average classification loss %.6f, average regression loss %.6f%s%s'
                     % (epoch + args.lastiter + 1, hi, len(trainDataSet), clsLossSum / max(1, clsCnt), regLossSum / max(1, regCnt),
-                       ', average direction loss %.6f' % (dirLossSum / max(1, dirCnt)) if args.direction else ''))
+                       ', average direction loss %.6f' % (dirLossSum / max(1, dirCnt)) if args.direction else '',
+                       ', average IoU loss %.6f' % (iouLossSum / max(1, iouCnt)) if args.iou_head else ''))
                 if args.steps and steps_done >= args.steps:
                     break
             account(pending)

@@ -31,6 +31,8 @@ def parse_args(argv=None):
     ap.add_argument('--bn-stats', choices=['auto', 'batch'], default='auto',
                     help='auto: a checkpoint of train_like.py --bn-track (it holds running_mean keys) runs in eval mode on its '
                          'running statistics; batch: every frame\'s own statistics even then')
+    ap.add_argument('--iou-alpha', type=float, default=0.5,
+                    help='a checkpoint of train_like.py --iou-head (it holds backbone.rpn.iou.weight): scores are cls^(1-a) iou^a')
     ap.add_argument('--split', default='train', help='ImageSets/<split>.txt')
     ap.add_argument('--out', default=None, help='picture directory (default <dataroot>/pictures)')
     ap.add_argument('--view', choices=['bev', 'camera', 'both'], default='both')
@@ -79,11 +81,14 @@ def _model_detector(args, device, data, names):
     if bnr.checkpoint_tracks(state) and not tracked:
         state = bnr.strip_running(state)
     cfg.config['bntrack'] = tracked             # main() restores it
-    model = (MVXNet(direction=True) if direction else MVXNet()).to(device)
+    iou_head = 'backbone.rpn.iou.weight' in state                             # written by train_like.py --iou-head
+    model = (MVXNet(direction=True, iou=True) if iou_head else MVXNet(direction=True) if direction else MVXNet()).to(device)
     model.load_state_dict(state)
     if tracked:
         model.eval()                            # detect_frame_set then normalises with the running statistics
     kw = dict(dir_offset=args.dir_offset) if direction else {}
+    if iou_head:
+        kw['iou_alpha'] = args.iou_alpha
     from modules import tta
     tta_kw, n_views = tta.options(args)
     kw.update(tta_kw)
