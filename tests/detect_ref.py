@@ -1,5 +1,6 @@
-"""Host reference of the detection output for tests/test_detect_gpu.py: candidate order and selection in numpy, decoding in
-float64, greedy NMS on the C oracle's rotated IoU (oracle/mvx_oracle.py, read only)."""
+"""Host reference of the detection output for tests/test_detect_gpu.py and tests/test_detect_direct_gpu.py: candidate order and
+selection in numpy, decoding in float64, greedy NMS on the C oracle's rotated IoU (oracle/mvx_oracle.py, read only), over the
+whole IoU table (``greedy_nms``) or over the pairs that can touch (``greedy_nms_near``, for thousands of boxes)."""
 import numpy as np
 import torch
 
@@ -72,4 +73,52 @@ def greedy_nms(quads, iou_thr, post_max):
         if len(keep) == post_max:
             break
         removed[i + 1:] |= iou[i, i + 1:] > iou_thr
+    return keep
+
+
+def near_pairs(quads):
+    """The IoU table of ``greedy_nms`` without its empty part: per box i (the partners j, IoU(i, j) from the C oracle) for the
+    pairs whose float64 bounding circles (centre = mean corner, radius = farthest corner) come within 10 % + 1 cm of touching,
+    dist <= 1.1 (r_i + r_j) + 0.01.  Every other pair is disjoint, IoU 0 -- below any iou_thr >= 1e-3, where the oracle itself
+    gives rounding noise of ~1e-6.  The centres are bucketed into square cells as wide as the largest such distance, and the
+    oracle is called per cell against its 3 x 3 neighbourhood."""
+    q = np.ascontiguousarray(quads, np.float32)
+    n = q.shape[0]
+    q64 = q.astype(np.float64)
+    c = q64.mean(1)
+    r = np.sqrt(((q64 - c[:, None]) ** 2).sum(2)).max(1)
+    cell = 2.2 * r.max() + 0.01
+    ij = np.floor((c - c.min(0)) / cell).astype(np.int64)
+    cells = {}
+    for k, key in enumerate(map(tuple, ij)):
+        cells.setdefault(key, []).append(k)
+    cols, ious = [None] * n, [None] * n
+    for (cx, cy), rows in cells.items():
+        rows = np.array(rows)
+        part = np.array([k for dx in (-1, 0, 1) for dy in (-1, 0, 1) for k in cells.get((cx + dx, cy + dy), ())])
+        iou = O.bbox_pairwise(q[rows], q[part], True)
+        dist = np.sqrt(((c[rows][:, None] - c[part][None]) ** 2).sum(2))
+        near = (dist <= 1.1 * (r[rows][:, None] + r[part][None]) + 0.01) & (rows[:, None] != part[None])
+        for a, i in enumerate(rows):
+            cols[i], ious[i] = part[near[a]], iou[a, near[a]]
+    return cols, ious
+
+
+def greedy_nms_near(quads, iou_thr, post_max, pairs=None):
+    """``greedy_nms`` from the IoUs of ``near_pairs`` alone (iou_thr >= 1e-3): the same kept positions without the K x K table."""
+    assert iou_thr >= 1e-3
+    K = quads.shape[0]
+    if K == 0:
+        return []
+    cols, ious = near_pairs(quads) if pairs is None else pairs
+    removed = np.zeros(K, bool)
+    keep = []
+    for i in range(K):
+        if removed[i]:
+            continue
+        keep.append(i)
+        if len(keep) == post_max:
+            break
+        hit = cols[i][(ious[i] > iou_thr) & (cols[i] > i)]
+        removed[hit] = True
     return keep
