@@ -1047,6 +1047,33 @@ int mvx_focal_loss_iou_frames(const float *heads, int32_t heads_ld, const float 
                               float *d_dir, int32_t d_dir_ld, float *d_iou, int32_t d_iou_ld, float *q_out, float *losses,
                               void *workspace, int64_t workspace_bytes, void *stream);
 
+/* mvx_box_iou_loss_frames: the rotated 3D IoU regression loss 1 - IoU3D (Zhou et al., 3DV 2019; SE-SSD's ODIoU, mmdetection3d's
+ * RotatedIoU3DLoss; csrc/box_iou_loss.hip) with its analytic gradient, for the frames of a step in ONE launch:
+ * no workspace, no host read.  heads (rows of heads_ld >= 8A floats, a multiple of 4, base 16-byte aligned), the lists, boxes
+ * and anchors are mvx_focal_loss_dir_frames's; neg_idx is not needed.  Per pos_idx entry of frame f (anchor a, box g, the
+ * anchor's regression row r; an entry outside the grid or with gi outside the frame's boxes is skipped, duplicates count every
+ * time):
+ *   b  = the 'loss' decode of mvx_detect_frames (see mvx_focal_loss_iou_frames), g = the ground-truth row, z the bottom face;
+ *   ih = min(b2 + b5, g2 + g5) - max(b2, g2);
+ *   I  = BEV intersection area of the two rectangles (clockwise yaw: a corner (px, py) of the box lies at
+ *        (px c + py s, -px s + py c) + (x, y)), by an exact convex clip in the predicted box's own frame;
+ *   V = I ih, U = b3 b4 b5 + g3 g4 g5 - V, q = clamp(V / U, 0, 1); q = 0 with a zero gradient when ih <= 0, when a component of
+ *   b or g is not finite, or when the rectangles do not overlap.
+ *   out f32 [n_frames][2] = (weight / max(1, n_pos) * sum (1 - q), mean q over the entries taken or 0), sums in f64 in a fixed
+ *   order: bitwise reproducible.
+ *   d_heads (optional) rows of d_heads_ld floats (>= 8A, base 4-byte aligned): d(term)/d(r) is ADDED (float atomicAdd) into
+ *   the anchor's seven regression columns, nothing else is touched; bitwise reproducible when no anchor is listed twice.
+ *   loss_add (optional): the frame's term is added to loss_add[f * loss_add_ld] (column 1 of the focal losses).
+ *   q_out (optional) f32 [n_frames][cap]: q per pos_idx slot, -1 for skipped entries and for the slots beyond the count.
+ * MVX_EINVAL before any launch: a NULL required pointer, n_frames, anchors_per_loc or cap outside their ranges, gt_ld < 7, a
+ * row stride below 8A (heads_ld also not a multiple of 4) or rows beyond 2^31 floats, weight < 0 or NaN, loss_add_ld < 1 with
+ * loss_add, a misaligned pointer.
+ */
+int mvx_box_iou_loss_frames(const float *heads, int32_t heads_ld, int32_t n_frames, int32_t l, int32_t w, int32_t anchors_per_loc,
+                            const int64_t *pos_idx, const int64_t *gi, int64_t cap, const int32_t *counts, const float *gts,
+                            int32_t gt_ld, const int32_t *gt_off, const float *anchors, float weight, float *d_heads,
+                            int32_t d_heads_ld, float *loss_add, int32_t loss_add_ld, float *out, float *q_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Detection output (csrc/detect.hip): score selection, top-K, box decoding and rotated BEV NMS for the frames of a step.
  * The reference has none of it (its Calc.decodeRegression is never called).

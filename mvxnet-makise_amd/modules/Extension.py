@@ -185,6 +185,8 @@ PROTOTYPES = {
     'mvx_focal_loss_iou_frames_workspace_bytes': (_i64, [_i32, _i32, _i32, _i32, _i32, _i64]),
     'mvx_focal_loss_iou_frames': (_i32, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i64, _p, _p, _i32, _p, _p,
                                          _f32, _f32, _f32, _f32, _f32, _f32, _f32, _p, _i32, _p, _i32, _p, _i32, _p, _p, _p, _i64, _p]),
+    'mvx_box_iou_loss_frames': (_i32, [_p, _i32, _i32, _i32, _i32, _i32, _p, _p, _i64, _p, _p, _i32, _p, _p, _f32, _p, _i32, _p, _i32, _p,
+                                       _p, _p]),
     'mvx_detect_workspace_bytes': (_sz, [_i32, _i32, _i32]),
     'mvx_detect_frames': (_i32, [_p, _i64, _i64, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p, _i32, _i32, _i32, _i32, _f32, _f32, _i32,
                                  _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),

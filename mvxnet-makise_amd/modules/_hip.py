@@ -2116,6 +2116,49 @@ def focal_loss_iou_frames(heads, dir_logits, iou_logits, F, l, w, A, pos_idx, ne
     return losses, d_heads, d_dir, d_iou, q
 
 
+def box_iou_loss_frames(heads, F, l, w, A, pos_idx, gi, counts, gts, gt_off, anchors, weight=1.0, want_grads=True, want_q=False,
+                        d_heads=None, loss_add=None):
+    """The rotated 3D IoU regression loss ``1 - IoU3D`` of all frames of a step and its analytic gradient in ONE launch, without a
+    workspace or a host read (csrc/box_iou_loss.hip).  ``heads`` f32 (F*l*w, >= 8A) with a row stride that is a
+    multiple of 4 and unit column stride, the rows ``focal_loss_dir_frames`` reads; lists, boxes and anchors as there (neg_idx
+    is not needed).  Per pos_idx entry that is not skipped: q = the 3D IoU of the box the anchor's regression row decodes
+    ('loss' decode) with its ground truth, 0 with a zero gradient when they do not overlap or a component is not finite.
+    Returns (out f32 (F,2) = (weight / max(1, n_pos) * sum (1 - q), mean q over the entries taken or 0) per frame, d_heads, q):
+
+      * ``want_grads``: the gradient is ADDED into the seven regression columns of the listed anchors of ``d_heads`` (f32, rows of
+        any stride >= 8A) -- the tensor the focal call has just written -- and nothing else of it is touched; without a
+        ``d_heads`` a zeroed one shaped like ``heads`` is made.  ``want_grads=False``: forward only, d_heads is returned as given.
+      * ``loss_add``: f32 view (F,) or (F,1) of any stride, e.g. ``losses[:, 1:2]`` of the focal losses: the frame's term is added
+        to it on the device.
+      * ``want_q``: q f32 (F, cap), -1 for skipped entries and unused slots (None otherwise).
+    ``weight = 0`` leaves ``d_heads`` and ``loss_add`` untouched."""
+    dev = heads.device
+    rows = F * l * w
+    assert heads.dtype == torch.float32 and heads.dim() == 2 and heads.shape[0] == rows
+    assert heads.stride(1) == 1 and heads.shape[1] >= 8 * A and (rows == 1 or heads.stride(0) % 4 == 0)
+    assert tuple(pos_idx.shape) == (F, 3, gi.shape[1]) and tuple(gi.shape) == (F, gi.shape[1])
+    assert pos_idx.dtype == gi.dtype == torch.int64 and counts.dtype == gt_off.dtype == torch.int32
+    assert pos_idx.is_contiguous() and gi.is_contiguous() and counts.is_contiguous() and gts.is_contiguous()
+    assert tuple(counts.shape) == (F, 2) and tuple(gt_off.shape) == (F + 1,) and gts.dtype == anchors.dtype == torch.float32
+    assert gts.dim() == 2 and gts.shape[0] >= 1 and anchors.numel() == l * w * A * 7
+    cap = gi.shape[1]
+    out = torch.empty((F, 2), dtype=torch.float32, device=dev)
+    q = torch.empty((F, cap), dtype=torch.float32, device=dev) if want_q else None
+    if want_grads:
+        if d_heads is None:
+            d_heads = torch.zeros((rows, heads.shape[1]), dtype=torch.float32, device=dev)
+        assert d_heads.dtype == torch.float32 and d_heads.dim() == 2 and d_heads.shape[0] == rows and d_heads.shape[1] >= 8 * A
+        assert d_heads.stride(1) == 1 and d_heads.device == dev
+    add_ld = 0
+    if loss_add is not None:
+        assert loss_add.dtype == torch.float32 and loss_add.device == dev and loss_add.shape[0] == F and loss_add.numel() == F
+        add_ld = loss_add.stride(0) if F > 1 else 1
+    X.call('mvx_box_iou_loss_frames', _vptr(heads), int(heads.stride(0)), int(F), int(l), int(w), int(A), pos_idx, gi, cap, counts,
+           gts, gts.shape[1], gt_off, anchors, float(weight), _vptr(d_heads) if want_grads else None,
+           int(d_heads.stride(0)) if want_grads else 0, _vptr(loss_add), int(add_ld), out, q)
+    return out, d_heads, q
+
+
 # ---------------------------------------------------------------------------------------------
 # detection output (csrc/detect.hip)
 # ---------------------------------------------------------------------------------------------

@@ -823,6 +823,8 @@ def train_step_full(model, batch, targets, criterion, anchors, imsize, ready=Non
     criterion on a model with it, raises MvxHipError before anything is launched.  ``FocalLoss(direction=True, iou=True)`` on
     ``MVXNet(direction=True, iou=True)`` likewise: losses (F,4), out['iou'] the IoU loss of every frame with a positive, included
     in out['loss']; an IoU criterion on a model without ``rpn.iou``, or a criterion without it on a model with it, raises.
+    With ``FocalLoss(iou_loss=True)`` (any of the three models) out['reg'] includes the rotated IoU term and the
+    criterion keeps the step's (term, mean IoU of the positives) per frame on the device as ``criterion.last_box_iou``.
     ``prepare_next`` = (next batch, callable returning its targets): voxelized, mapped and target-assigned on the
     preparation stream after this step has been enqueued; returned as out['next'] = (ready, targets) for the next call.
     ``read=False`` leaves the losses on the device (out['losses_dev'] (F,2)) and skips the status read: the caller reads

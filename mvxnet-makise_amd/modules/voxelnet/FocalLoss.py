@@ -29,6 +29,15 @@ row read as a constant (nothing flows into the regression from this term):
 
 and the decode ranks and scores by sigmoid(cls)^(1-a) sigmoid(x)^a.  ``iou_weight=1.0`` (and the decode's ``iou_alpha=0.5``)
 are design choices in the range those papers use, not optima measured on this model.
+
+``iou_loss=True`` (with every combination of ``direction`` and ``iou``) adds the rotated 3D IoU regression loss of
+Zhou et al. (3DV 2019; SE-SSD's ODIoU, mmdetection3d's RotatedIoU3DLoss) to regLoss, with its analytic gradient flowing into the
+seven regression columns.  Per ``pi`` entry, with q as above but differentiated:
+
+    regLoss += iou_loss_weight / max(1, len(pi)) * sum (1 - q)
+
+SmoothL1 stays in the sum: ``1 - q`` alone has no gradient for a positive that does not overlap its box, and forced positives
+start at an IoU of 0.1.  ``iou_loss_weight=1.0`` is a design choice, not an optimum measured on this model.
 """
 import collections
 import math
@@ -54,7 +63,7 @@ def _on_device(x):
 class FocalLoss(nn.Module):
 
     def __init__(self, alpha=0.25, gamma=2.0, cls_weight=1.0, reg_weight=2.0, direction=False, dir_weight=0.2, dir_offset=math.pi / 4,
-                 iou=False, iou_weight=1.0):
+                 iou=False, iou_weight=1.0, iou_loss=False, iou_loss_weight=1.0):
         super().__init__()
         if iou and not direction:
             raise X.MvxHipError('FocalLoss(iou=True) needs direction=True: the IoU logits take the two pad columns of the direction '
@@ -62,6 +71,10 @@ class FocalLoss(nn.Module):
         self.alpha, self.gamma, self.cls_weight, self.reg_weight = alpha, gamma, cls_weight, reg_weight
         self.direction, self.dir_weight, self.dir_offset = bool(direction), dir_weight, dir_offset
         self.iou, self.iou_weight = bool(iou), iou_weight
+        if not iou_loss_weight >= 0:
+            raise X.MvxHipError('FocalLoss(iou_loss_weight=%r) must not be negative' % (iou_loss_weight,))
+        self.iou_loss, self.iou_loss_weight = bool(iou_loss), iou_loss_weight
+        self.last_box_iou = None           # (F,2) on the device = (the IoU term, mean IoU of the positives) of the last call
 
     def forward(self, pi, ni, gi, gts, score, reg, anchors, anchorsPerLoc):
         raise NotImplementedError('FocalLoss needs the logits of the heads, not their probabilities (a focal loss from '
@@ -125,7 +138,9 @@ class FocalLoss(nn.Module):
         d_heads carries the direction gradient in its columns, zeros in the pad columns.  A criterion and rows that do not
         match raise MvxHipError before anything is launched.  With ``iou`` the rows are those of an IoU model, [cls | reg | dir
         logits | iou logits] (columns 9A..10A), losses is (F,4) = (clsLoss, regLoss or 0, dirLoss, iouLoss) and d_heads carries
-        the IoU gradient in those columns."""
+        the IoU gradient in those columns.  With ``iou_loss`` the regression loss (column 1) includes the rotated IoU term and
+        d_heads its gradient in the regression columns; the widths and meanings are otherwise unchanged, and ``last_box_iou``
+        keeps the (F,2) device tensor (term, mean IoU of the frame's positives) of this call (no host read)."""
         from modules import rpn_frames as rf
         if not heads.is_cuda:
             raise X.MvxHipError('FocalLoss runs on the GPU (no CPU fallback)')
@@ -148,14 +163,18 @@ class FocalLoss(nn.Module):
                                                          packed.pos_idx, packed.neg_idx, packed.gi, packed.counts, packed.gts,
                                                          packed.gt_off, anc, self.alpha, self.gamma, self.cls_weight, self.reg_weight,
                                                          self.dir_weight, self.dir_offset, self.iou_weight, want_grads=want_grads)[:2]
-            return losses, has_reg, d_heads
-        if self.direction:
+        elif self.direction:
             losses, d_heads, _ = _hip.focal_loss_dir_frames(heads, heads[:, 8 * A:9 * A], F, h1, w1, A, packed.pos_idx, packed.neg_idx,
                                                             packed.gi, packed.counts, packed.gts, packed.gt_off, anc, self.alpha,
                                                             self.gamma, self.cls_weight, self.reg_weight, self.dir_weight,
                                                             self.dir_offset, want_grads=want_grads)
-            return losses, has_reg, d_heads
-        losses, d_heads = _hip.focal_loss_frames(heads, F, h1, w1, A, packed.pos_idx, packed.neg_idx, packed.gi, packed.counts,
-                                                 packed.gts, packed.gt_off, anc, self.alpha, self.gamma, self.cls_weight,
-                                                 self.reg_weight, want_grads=want_grads)
+        else:
+            losses, d_heads = _hip.focal_loss_frames(heads, F, h1, w1, A, packed.pos_idx, packed.neg_idx, packed.gi, packed.counts,
+                                                     packed.gts, packed.gt_off, anc, self.alpha, self.gamma, self.cls_weight,
+                                                     self.reg_weight, want_grads=want_grads)
+        if self.iou_loss:
+            # behind the focal call, on the d_heads it has just written: the term goes into column 1 of the losses on the device
+            self.last_box_iou = _hip.box_iou_loss_frames(heads, F, h1, w1, A, packed.pos_idx, packed.gi, packed.counts, packed.gts,
+                                                         packed.gt_off, anc, self.iou_loss_weight, want_grads=want_grads,
+                                                         d_heads=d_heads, loss_add=losses[:, 1:2])[0]
         return losses, has_reg, d_heads

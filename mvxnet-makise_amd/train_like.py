@@ -34,6 +34,10 @@ pass the same ``--dir-offset`` to detect_like.py / visualize_like.py (the checkp
 (``backbone.rpn.iou``): one logit per anchor trained to predict the 3D IoU of the decoded box with its ground truth, which
 detect_like.py multiplies into the score (``--iou-alpha`` there).
 
+``--iou-loss`` (--mode fast --loss focal only; ``--iou-loss-weight``, default 1.0; with or without the two heads above) adds the
+rotated 3D IoU regression loss ``1 - IoU3D`` of every positive to the regression loss, its analytic gradient flowing into the
+seven regression columns (csrc/box_iou_loss.hip).  The loop prints the epoch's mean IoU of the positives.
+
 --mode module : the reference's own interface, one frame at a time: ``model(voxel, img, idx, [calib], imsize)``.
 --mode fast   : B frames per step through the frame-set executor (modules/frames.py: one launch per layer for all
                 frames), RPN + VoxelLoss per frame (per-frame BatchNorm statistics, as B reference forwards), one AdamW
@@ -119,6 +123,11 @@ def parse_args(argv=None):
                          'FocalLoss(direction=True, iou=True)); detect_like.py rectifies the scores with it')
     ap.add_argument('--iou-weight', type=float, default=1.0,
                     help='--iou-head: weight of the IoU loss (a design choice, not an optimum measured here)')
+    ap.add_argument('--iou-loss', action='store_true',
+                    help='--mode fast --loss focal: add the rotated 3D IoU regression loss 1 - IoU3D, with its analytic gradient, to '
+                         'the regression loss (FocalLoss(iou_loss=True)); with or without --direction / --iou-head')
+    ap.add_argument('--iou-loss-weight', type=float, default=1.0,
+                    help='--iou-loss: weight of the term (a design choice, not an optimum measured here)')
     ap.add_argument('--bn-track', action='store_true',
                     help='--mode fast: running BatchNorm statistics (config.yml bntrack: True does the same): the checkpoints carry '
                          'running_mean / running_var / num_batches_tracked, detect_like.py then runs the model in eval mode')
@@ -132,6 +141,10 @@ def parse_args(argv=None):
         ap.error('--iou-head needs --direction: the IoU logits take the two pad columns of the direction model\'s head rows')
     if args.iou_weight < 0:
         ap.error('--iou-weight must not be negative')
+    if args.iou_loss and (args.mode != 'fast' or args.loss != 'focal'):
+        ap.error('--iou-loss needs --mode fast --loss focal: the term is computed on the frame-set heads behind the focal loss')
+    if not args.iou_loss_weight >= 0:
+        ap.error('--iou-loss-weight must not be negative')
     if args.direction and (args.mode != 'fast' or args.loss != 'focal'):
         ap.error('--direction needs --mode fast --loss focal: the direction head is trained by the focal loss of the frame-set '
                  'heads only')
@@ -323,20 +336,23 @@ def _train(args):
         say('bntrack: running BatchNorm statistics, momentum %g' % getattr(args, 'bn_momentum', 0.1))
     if args.loss == 'focal':
         from modules.voxelnet.FocalLoss import FocalLoss
+        box = dict(iou_loss=True, iou_loss_weight=args.iou_loss_weight) if args.iou_loss else {}
         if args.iou_head:
             criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight, direction=True,
-                                  dir_weight=args.dir_weight, dir_offset=args.dir_offset, iou=True, iou_weight=args.iou_weight)
+                                  dir_weight=args.dir_weight, dir_offset=args.dir_offset, iou=True, iou_weight=args.iou_weight, **box)
         elif args.direction:
             criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight, direction=True,
-                                  dir_weight=args.dir_weight, dir_offset=args.dir_offset)
+                                  dir_weight=args.dir_weight, dir_offset=args.dir_offset, **box)
         else:
-            criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight)
+            criterion = FocalLoss(alpha=args.focal_alpha, gamma=args.focal_gamma, reg_weight=args.focal_reg_weight, **box)
         say('criterion: FocalLoss(alpha=%g, gamma=%g, cls_weight=%g, reg_weight=%g)'
             % (criterion.alpha, criterion.gamma, criterion.cls_weight, criterion.reg_weight))
         if args.direction:
             say('direction head: dir_weight=%g, dir_offset=%g, sine angle loss' % (criterion.dir_weight, criterion.dir_offset))
         if args.iou_head:
             say('IoU head: iou_weight=%g' % criterion.iou_weight)
+        if args.iou_loss:
+            say('rotated IoU regression loss: iou_loss_weight=%g, added to the regression loss' % criterion.iou_loss_weight)
     else:
         criterion = VoxelLoss()
         say('criterion: VoxelLoss(a=%g, b=%g)' % (criterion.a, criterion.b))
@@ -395,6 +411,7 @@ def _train(args):
         mine = trainDataSet
         clsLossSum = regLossSum = dirLossSum = iouLossSum = 0.0
         clsCnt = regCnt = dirCnt = iouCnt = 0
+        boxIouSum, boxIouCnt = 0.0, 0              # --iou-loss: mean IoU of the positives, per frame that has one
         if args.mode == 'module':
             for i, data in enumerate(mine):
                 voxel, idx, img, gt, gtbev, pi, ni, gi, calibCpu = cputask(data, anchorBevs, cfg, gtwithinfo, geo, assigner)
@@ -472,10 +489,15 @@ def _train(args):
                                                   # the step it has just enqueued
 
             def account(p):
-                nonlocal clsLossSum, clsCnt, regLossSum, regCnt, dirLossSum, dirCnt, iouLossSum, iouCnt
+                nonlocal clsLossSum, clsCnt, regLossSum, regCnt, dirLossSum, dirCnt, iouLossSum, iouCnt, boxIouSum, boxIouCnt
                 if p is None:
                     return
                 pl.read_losses(p)
+                if p.get('box_iou') is not None:          # read with the losses, a step later
+                    for (_, mean_q), hr in zip(p['box_iou'].tolist(), p['has_reg']):
+                        if hr:
+                            boxIouSum += mean_q
+                            boxIouCnt += 1
                 losses.extend(p['loss'])
                 clsLossSum += sum(p['cls'])
                 clsCnt += len(p['cls'])
@@ -496,6 +518,8 @@ def _train(args):
                 if batch is not None:
                     out = pl.train_step_full(model, batch, targets, criterion, anchors, cfg.imsize, read=False)
                     used = len(out['live'])
+                    if args.iou_loss and 'losses_dev' in out:
+                        out['box_iou'] = criterion.last_box_iou
                     if used < batch.n_frames:
                         say('Epoch%d step %d: %d frame(s) without a voxel skipped' % (epoch + args.lastiter + 1, gstep, batch.n_frames - used))
                 forwardTime += time.perf_counter() - st
@@ -529,6 +553,9 @@ def _train(args):
             say('Epoch%d: %d frames in %.2f s = %.1f frames/s (all ranks, %s)'
                 % (epoch + args.lastiter + 1, frames_epoch, loop_s, frames_epoch / max(loop_s, 1e-9),
                    'prefetch thread' if args.prefetch else 'batches prepared inside the step'))
+            if args.iou_loss:
+                say('Epoch%d: mean 3D IoU of the positives with their boxes %.4f (over %d frame(s) with a positive)'
+                    % (epoch + args.lastiter + 1, boxIouSum / max(1, boxIouCnt), boxIouCnt))
         if assigner is not None:
             say('Epoch%d targets: %d boxes, %d with only a forced positive, %d with none'
                 % (epoch + args.lastiter + 1, assign_stats['boxes'], assign_stats['forced_only'], assign_stats['none']))
